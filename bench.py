@@ -15,10 +15,18 @@ coordination (barrier, max-over-ranks) uses torch.distributed's gloo backend on 
 host: the engine's HIP runtime is /opt/rocm's, and initialising torch's bundled HIP
 runtime in the same process as well would put two HIP/HSA runtimes in one process.
 
-Extra JSON fields: `roofline` (FP32 compute roof of the propagation kernel, measured
-with HIP events on the kernel's stream; HBM traffic from the committed rocprofv3 PMC
-pass when one exists for this config) and `cpu_baseline` (the CPU oracle on a bounded
-row-band sample of the same view, rank 0, N = 1 only).
+A plain run sets up, warms up, times `--steps` steps and prints the result line
+(`--dump-outputs DIR` also writes the last timed step's planes and costs as .npy).
+Its `roofline` field (FP32 compute roof of the propagation kernel) comes from the HIP
+events the engine records on the kernel's stream during the timed steps, HBM traffic
+from the committed rocprofv3 PMC pass when one exists for this config.
+
+`--full` adds every measurement that takes runs of its own, reported beside `value`,
+never in it: the other math mode, per-map latency with the D2H, the PCIe-inclusive
+rate, the clock probe, `cpu_baseline` (the CPU oracle on a bounded row-band sample of
+the same view, rank 0, N = 1 only), the 2000x1000 variant, the end-to-end schedule
+and, with N > 1, the RCCL depth exchange and band split.  Without it those fields
+are null.
 """
 from __future__ import annotations
 
@@ -105,6 +113,14 @@ def parse():
     ap.add_argument("--math", choices=["exact", "fast"], default="fast",
                     help="engine arithmetic (acmmp_set_math): fast = the reference's --use_fast_math arithmetic "
                          "(tolerance parity, tests/test_gpu_fastmath.py); exact = bit-identical to the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement (the other math mode, per-map "
+                         "latency and PCIe-inclusive rate, clock probe, CPU baseline, 2000x1000 variant, end-to-end "
+                         "schedule, multi-rank RCCL legs); without it only the headline figure is measured and the "
+                         "--no-* options below have nothing to switch off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (planes, costs; float32, a NaN cost "
+                         "written as -1) as DIR/<name>.npy")
     ap.add_argument("--no-other-mode", action="store_true", help="skip timing the other math mode beside `value`")
     ap.add_argument("--cpu-seconds", type=float, default=25.0,
                     help="target length of the CPU-baseline sample (the probe rows sit at the equator, the "
@@ -128,10 +144,15 @@ def parse():
                     help="launch/rendezvous check: ranks join the gloo group, agree on the world and exit without "
                          "touching a GPU (the CPU test of `--gpus N`)")
     a = ap.parse_args()
-    if a.timed_only:
+    if a.timed_only or not a.full:
         a.no_other_mode = a.no_cpu_baseline = a.no_variant = a.no_pipeline = True
+    if not a.full:
+        a.no_clock = True
+    a.extras = a.full and not a.timed_only      # the latency, PCIe and multi-rank legs after the timed steps
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.dump_outputs and a.mode != "patchmatch":
+        ap.error("--dump-outputs writes the patchmatch mode's outputs")
     pipe = a.mode == "pipeline"        # BASELINE.json configs[3] shape vs the headline metric's
     for k, head, pl in (("width", 2000, 3200), ("height", 1500, 2133), ("n_src", 4, 20), ("model", "sphere", "pinhole")):
         if getattr(a, k) is None:
@@ -143,6 +164,31 @@ def make_scene(args, rank: int):
     if args.model == "sphere":
         return scene.sphere_scene(args.width, args.height, n_src=args.n_src, seed=args.seed + 7919 * rank)
     return scene.pinhole_scene(args.width, args.height, n_src=args.n_src, seed=args.seed + 7919 * rank)
+
+
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files of all ranks together
+DUMP_NAN_COST = -1.0             # --dump-outputs: what a non-finite cost is written as
+
+
+def dump_outputs(path: str, planes, costs, rank: int, world: int):
+    """--dump-outputs: the planes (H x W x 4: normal, depth) and costs (H x W) the last timed step left, as a
+    caller of run_patchmatch + download receives them, float32 .npy.  Outputs above the byte budget are cut to
+    a fixed sample of pixels (seeded, sorted, the same pixels in both files and in every run of one shape).
+    The files hold finite numbers only, so that two dumps can be subtracted: a NaN cost (the reference's 0/0
+    costs of the SPHERE band, SURVEY.md §0.5, which the engine reproduces) is written as DUMP_NAN_COST, below
+    every real cost (an NCC cost lies in [0, 2], the geometric term adds to it), and a non-finite plane
+    component as 0 (no valid normal or depth)."""
+    os.makedirs(path, exist_ok=True)
+    planes = np.where(np.isfinite(planes), planes, np.float32(0.0)).astype(np.float32)
+    costs = np.where(np.isfinite(costs), costs, np.float32(DUMP_NAN_COST)).astype(np.float32)
+    budget = DUMP_BUDGET_BYTES // world
+    if planes.nbytes + costs.nbytes > budget:
+        npix = costs.size
+        idx = np.sort(np.random.default_rng(0).choice(npix, size=budget // 20, replace=False))
+        planes, costs = planes.reshape(npix, 4)[idx], costs.reshape(npix)[idx]
+    tag = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(path, f"planes{tag}.npy"), planes)
+    np.save(os.path.join(path, f"costs{tag}.npy"), costs)
 
 
 def end_to_end(args, sc, device):
@@ -613,6 +659,11 @@ def main():
     elapsed = time.perf_counter() - t0
     t_max = allmax(elapsed)
 
+    # what the last timed step left (`quality` below; a --full run's latency legs overwrite it first)
+    planes, costs = ctx.download()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, planes, costs, rank, world)
+
     # which GPU, and the clock it holds under a VALU-dense load right after the timed region (the chip's DVFS
     # give-back differs from device to device, MI355X_MICROARCH.md; k_eval_nb's time follows that clock):
     # reported so two records of the same build on different boxes can be put side by side per GHz
@@ -665,9 +716,8 @@ def main():
                  "note": "exact = bit-identical to the CPU oracle; fast = tolerance parity (DESIGN.md §2.4)"}
         ctx.set_math(args.math)
 
-    planes, costs = ctx.download()
     d2h_ms = pcie_ms = None
-    if not args.timed_only:
+    if args.extras:
         # per-map latency as the reference's RunPatchMatch ends (ACMMP.cu:1553-1554): run + D2H of planes
         # and costs into caller-owned host buffers (inputs resident, as for `value`)
         lat = []
@@ -763,11 +813,11 @@ def main():
     exch = None
     abandoned = False
     deadline = float(os.environ.get("ACMMP_BENCH_EXTRA_S", "180"))
-    if world > 1 and ndev and world <= ndev and not args.timed_only and os.environ.get("ACMMP_BENCH_EXCHANGE", "1") != "0":
+    if world > 1 and ndev and world <= ndev and args.extras and os.environ.get("ACMMP_BENCH_EXCHANGE", "1") != "0":
         exch, abandoned = guarded(depth_exchange, deadline, args, ctx, rank, world, local_rank % ndev, dist, allmax)
     # the single-view latency mode: one view's rows split over the GPUs
     bsplit = None
-    if (world > 1 and ndev and world <= ndev and not args.timed_only and not abandoned
+    if (world > 1 and ndev and world <= ndev and args.extras and not abandoned
             and os.environ.get("ACMMP_BENCH_BAND", "1") != "0"):
         bsplit, abandoned = guarded(band_split, deadline, args, rank, world, local_rank % ndev, dist, allmax)
 

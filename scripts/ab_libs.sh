@@ -14,12 +14,12 @@ rm -f $OUT/base.npz $OUT/cand.npz
 for cfg in "$@"; do
   for rep in 1 2; do
     for lib in $LIBS; do
-      ACMMP_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-variant --no-pipeline --no-other-mode $cfg > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 1; }
+      ACMMP_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-variant --no-pipeline --no-other-mode $cfg > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 1; }
       python -c "import json,os;d=json.load(open('$OUT/b.json'));print(os.path.basename('$lib'), '$cfg', d['value'], d['ms_per_step'], d['clock']['ghz'], d['roofline']['half_sweep_kernels_ms'])" | tee -a $OUT/ab.txt
     done
   done
 done
 timeout -k 10 200 python scripts/planar_timing.py 2000 1500 sphere > $OUT/planar_sphere.json || exit 1
-timeout -k 10 400 python bench.py --no-cpu-baseline --no-variant --no-other-mode > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-variant --no-other-mode > $OUT/bench.json 2> $OUT/bench.err || exit 1
 python -c "import json;d=json.load(open('$OUT/bench.json'));print(d['value'], json.dumps(d['end_to_end']['stages_s']))"
 echo AB_DONE

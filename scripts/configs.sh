@@ -20,7 +20,7 @@ if [ "$2" != "no-pmc" ]; then
   bash scripts/pmc.sh $OUT/pmc_c3 "$C3 --steps 1 --warmup 1 --timed-only" || exit 1
   python scripts/pmc_summary.py $OUT/pmc_c3 --json $OUT/pmc_c3.json --width 3200 --height 1600 --n-src 15 --model sphere > $OUT/pmc_c3_summary.txt || exit 1
 fi
-run c2_patchmatch 300 python bench.py $C2 --no-cpu-baseline --no-variant --no-pipeline --pmc $OUT/pmc_c2.json
-run c3_patchmatch 400 python bench.py $C3 --steps 3 --warmup 1 --no-cpu-baseline --no-variant --no-pipeline --pmc $OUT/pmc_c3.json
+run c2_patchmatch 300 python bench.py $C2 --full --no-cpu-baseline --no-variant --no-pipeline --pmc $OUT/pmc_c2.json
+run c3_patchmatch 400 python bench.py $C3 --full --steps 3 --warmup 1 --no-cpu-baseline --no-variant --no-pipeline --pmc $OUT/pmc_c3.json
 run c2_pipeline 500 python -u scripts/pipeline_bench.py --model pinhole --width 1600 --height 1200 --views 49 --n-src 10 --math fast
 echo CONFIGS_DONE
