@@ -162,3 +162,25 @@ def near_surface_planes(sc, px, py, k, seed, spread=0.2, depth_jitter=0.02):
             depth = float(sc.gt_depth[py[q], px[q]]) * rng.uniform(1 - depth_jitter, 1 + depth_jitter)
             out[q, h] = [*nrm, -float(nrm @ (d * depth))]
     return out.astype(np.float32)
+
+
+# ---- pixel sets of the small-shape fast-mode instance matrix (tests/fastmath_support.py) -------------------
+
+def interior_pixels(W, H, n, seed, margin=6):
+    """n random pixels at least `margin` pixels inside the image."""
+    rng = np.random.default_rng(seed)
+    return rng.integers(margin, W - margin, n).astype(np.int32), rng.integers(margin, H - margin, n).astype(np.int32)
+
+
+def border_pixels(W, H, n, seed, margin=6):
+    """The four corners, then random pixels of the `margin`-wide frame (px < margin, px >= W - margin,
+    py < margin or py >= H - margin): the reference patch's reads are clamped there."""
+    rng = np.random.default_rng(seed)
+    ys, xs = np.mgrid[0:H, 0:W]
+    frame = (xs < margin) | (xs >= W - margin) | (ys < margin) | (ys >= H - margin)
+    corner = ((xs == 0) | (xs == W - 1)) & ((ys == 0) | (ys == H - 1))
+    cand = np.nonzero((frame & ~corner).ravel())[0]
+    pick = rng.choice(cand, size=n - 4, replace=False)
+    px = np.concatenate([[0, W - 1, 0, W - 1], pick % W])
+    py = np.concatenate([[0, 0, H - 1, H - 1], pick // W])
+    return px.astype(np.int32), py.astype(np.int32)

@@ -19,6 +19,15 @@ bit-identical, so it is held to the gates DESIGN.md §2.4 states, measured in pr
       fast departs from exact by > 1e-4 no more often than exact departs from float64, + 5 points.
       (c) No systematic accuracy loss: the fraction of queries where fast is farther from float64 than
       exact by > 1e-4 is at most the converse fraction + 3 points.
+      Here T1 runs at the workload's shapes (binary16 texels, V in {4, 10, 15, 20, 32}, interior pixels).  The
+      same gates (fastmath_support.t1_gates, one function) hold every other instance at small shapes in
+      tests/test_gpu_fast_instances.py: pinhole 96x64 and SPHERE 128x64, V in {1, 2, 3, 5, 9} (view chunks of
+      1 and 2, partial last chunks), binary16 and fp32 texels, on interior, border, source-edge and wild-plane
+      queries, per set -- acmmp_debug_ncc and the fast pinhole homogeneous k_eval_nb / k_eval_ref hooks against
+      float64, every other hook (SPHERE nb / ref, pinhole per-sample nb / ref, the exact hooks against the
+      oracle, the fast k_init's costs against the debug hook's) bit for bit.  What stays statistical only: the
+      half-sweep same-plane floors of T2, measured and gated at the large shapes alone, and the pass gates'
+      seeds 72-75, which are the seeds the floors were measured on (in-sample).
   T2  After RandomInitialization every plane is identical (same RNG draws) and costs agree within 1e-3
       for >= 99.5% (pinhole) / 99% (SPHERE) of pixels; after one black half-sweep >= 99.5% (pinhole) /
       98.5% (SPHERE) of pixels hold the same plane, and the flips are near ties: their median cost gap
@@ -44,6 +53,7 @@ import os
 import numpy as np
 import pytest
 
+import fastmath_support as fs
 import np_interp as ni
 import np_reference as npr
 from acmmp import capi, scene, types
@@ -105,22 +115,10 @@ def check_t1(ctx, sc, p, n, seed, sphere):
     e = ctx.debug_ncc(px, py, planes)
     ref = np.array([[npr.bilateral_ncc(sc.images, sc.cameras, p, v, int(px[k]), int(py[k]),
                                        planes[k].astype(np.float64)) for v in range(1, V + 1)] for k in range(n)])
-    # (a) a cost of 2.0 is the reference's "no match" (centre outside, weight sum < 1e-6, variance
-    # < 1e-5) or a clamped NCC; its thresholds are discontinuities the binary32 noise can cross, so the
-    # fast mode may flip a query's class no more often than the exact mode's own class differs from
-    # float64's, and never by more than 1% of the queries
-    agree_fe = np.mean((f >= 2.0) == (e >= 2.0))
-    agree_ef = np.mean((e >= 2.0) == (ref >= 2.0))
-    assert agree_fe >= min(agree_ef, 0.999) - 0.002 and agree_fe >= 0.99, (agree_fe, agree_ef)
-    valid = (e < 2.0) & (f < 2.0) & (ref < 2.0)
-    assert valid.mean() > 0.3
-    df, de, dfe = np.abs(f - ref)[valid], np.abs(e - ref)[valid], np.abs(f - e)[valid]
-    if sphere:                                                                        # (b)
-        assert np.mean(dfe <= 1e-4) >= np.mean(de <= 1e-4) - 0.05, (np.mean(dfe <= 1e-4), np.mean(de <= 1e-4))
-    else:
-        assert np.mean(dfe <= 1e-4) >= 0.995, np.mean(dfe <= 1e-4)
-    fast_worse, exact_worse = np.mean(df > de + 1e-4), np.mean(de > df + 1e-4)        # (c)
-    assert fast_worse <= exact_worse + 0.03, (fast_worse, exact_worse)
+    # T1's gates (a)-(c), stated once for this file and the small-shape instance matrix
+    # (tests/test_gpu_fast_instances.py): fastmath_support.t1_gates
+    fr = fs.t1_gates(f, e, ref, sphere)
+    assert fr["valid_frac"] > 0.3
 
 
 def check_t2(ctx, setup, seed, sphere, init=True, hs_min=None, gap_max=1e-4):
