@@ -111,7 +111,8 @@ EXPORTS = [
     "acmmp_band_begin", "acmmp_band_sweep", "acmmp_band_sweeps_left", "acmmp_band_halo_ranges",
     "acmmp_band_copy_rows", "acmmp_band_get_rows", "acmmp_band_set_rows", "acmmp_band_end",
     "acmmp_fusion_create", "acmmp_fusion_set_view", "acmmp_fusion_run", "acmmp_fusion_last_error",
-    "acmmp_fusion_destroy", "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
+    "acmmp_fusion_destroy", "acmmp_fusion_run_scene", "acmmp_fusion_scene_points", "acmmp_fusion_reset_used",
+    "acmmp_fusion_download_used", "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
 
@@ -199,6 +200,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_run.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     L.acmmp_fusion_last_error.argtypes = [vp]
     L.acmmp_fusion_destroy.argtypes = [vp]
+    L.acmmp_fusion_run_scene.argtypes = [vp, i32, vp, vp, vp, i32, vp, C.POINTER(C.c_int64)]
+    L.acmmp_fusion_scene_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
+    L.acmmp_fusion_reset_used.argtypes = [vp]
+    L.acmmp_fusion_download_used.argtypes = [vp, i32, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -828,6 +833,9 @@ class Comm:
 
 # ---- GPU fusion (RunFusionCuda / SimpleFusionKernel, ACMMP.cu:1662-2105) ---------------------------
 
+FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
+
+
 class Fusion:
     """Depth-map fusion on one GPU.  cams: CAMERA_DTYPE array, each rescaled to its depth map."""
 
@@ -860,6 +868,51 @@ class Fusion:
         self._check(self.L.acmmp_fusion_run(self.h, ref, srcs.size, _p(srcs), _p(out), n.value, C.byref(n)),
                     "fusion_run")
         return out[:n.value]
+
+    def run_scene(self, refs, src_lists, unique: bool = False):
+        """Fuse the reference views `refs` in that order, view k against src_lists[k] (-1 = missing, at most
+        32), in one device-resident pass; the result stays on the GPU until the next run_scene (read it with
+        scene_points).  unique: the duplicate-free mode (ACMMP_FUSE_UNIQUE, include/acmmp.h) -- a depth sample
+        contributes to the points of one reference view only, across calls until reset_used().
+        Returns (total points, per-view counts)."""
+        refs = np.ascontiguousarray(refs, np.int32).reshape(-1)
+        if len(src_lists) != refs.size:
+            raise ValueError("one source list per reference view")
+        n_src = np.array([len(s) for s in src_lists], np.int32)
+        srcs = np.full((max(refs.size, 1), 32), -1, np.int32)
+        for k, s in enumerate(src_lists):
+            srcs[k, :min(len(s), 32)] = np.asarray(s, np.int32).reshape(-1)[:32]     # (> 32 is refused below)
+        counts = np.zeros(max(refs.size, 1), np.int32)
+        total = C.c_int64(0)
+        self._check(self.L.acmmp_fusion_run_scene(self.h, refs.size, _p(refs), _p(n_src), _p(srcs),
+                                                  FUSE_UNIQUE if unique else 0, _p(counts), C.byref(total)),
+                    "fusion_run_scene")
+        self.scene_total = int(total.value)
+        return self.scene_total, counts[:refs.size].copy()
+
+    def scene_points(self, first: int, n: int, provenance: bool = False):
+        """Points [first, first + n) of the last run_scene: (n, 9) float32, and with provenance also the
+        position of each point's view in `refs`, its pixel r*W + c (int32) and its consistent-source mask
+        (uint32, bit j = src_lists[k][j])."""
+        pts = host_empty((n, 9), np.float32)
+        if not provenance:
+            self._check(self.L.acmmp_fusion_scene_points(self.h, first, n, _p(pts), None, None, None), "fusion_scene_points")
+            return pts
+        ref, pix, mask = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
+        self._check(self.L.acmmp_fusion_scene_points(self.h, first, n, _p(pts), _p(ref), _p(pix), _p(mask)),
+                    "fusion_scene_points")
+        return pts, ref, pix, mask
+
+    def reset_used(self):
+        """Clear every view's used mask (the duplicate-free mode starts over)."""
+        self._check(self.L.acmmp_fusion_reset_used(self.h), "fusion_reset_used")
+
+    def used(self, view: int) -> np.ndarray:
+        """View's used mask, (H, W) uint8 (test hook)."""
+        H, W = int(self.cams[view]["height"]), int(self.cams[view]["width"])
+        m = np.empty((H, W), np.uint8)
+        self._check(self.L.acmmp_fusion_download_used(self.h, view, _p(m)), "fusion_download_used")
+        return m
 
     def close(self):
         if self.h:

@@ -173,11 +173,12 @@ def scale_schedule(problems: list, max_num_downscale: int) -> list:
     return out
 
 
-def write_ply(path: str, points: np.ndarray) -> None:
-    """StoreColorPlyFileBinaryPointCloud (ACMMP.cpp:481-534).  points: (n, 9) float32 rows
-    x y z nx ny nz c0 c1 c2 as SimpleFusionKernel stores them (c0 = the texture's .z channel);
-    the writer emits red = (char)(int)c2, green = (char)(int)c1, blue = (char)(int)c0 and zeroes
-    coordinates that are not finite (the FLT_MAX tests of :508-512, including the z >= -FLT_MAX quirk)."""
+_PLY_RECORD = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                        ("r", "u1"), ("g", "u1"), ("b", "u1")])
+
+
+def _ply_records(points: np.ndarray) -> np.ndarray:
+    """(n, 9) float32 fused points -> the PLY's vertex records (the per-vertex rules of write_ply)."""
     p = np.ascontiguousarray(points, np.float32).reshape(-1, 9)
     n = p.shape[0]
     X = p[:, 0:3].copy()
@@ -185,8 +186,7 @@ def write_ply(path: str, points: np.ndarray) -> None:
     bad = ~((X[:, 0] < fmax) & (X[:, 0] > -fmax)) | ~((X[:, 1] < fmax) & (X[:, 1] > -fmax)) | \
         ~((X[:, 2] < fmax) & (X[:, 2] >= -fmax))
     X[bad] = 0.0
-    rec = np.zeros(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
-                             ("r", "u1"), ("g", "u1"), ("b", "u1")])
+    rec = np.zeros(n, dtype=_PLY_RECORD)
     rec["x"], rec["y"], rec["z"] = X[:, 0], X[:, 1], X[:, 2]
     rec["nx"], rec["ny"], rec["nz"] = p[:, 3], p[:, 4], p[:, 5]
 
@@ -195,14 +195,59 @@ def write_ply(path: str, points: np.ndarray) -> None:
             iv = np.where(np.isfinite(v), np.trunc(v), 0).astype(np.int64)
         return (iv & 0xFF).astype(np.uint8)
     rec["r"], rec["g"], rec["b"] = to_char(p[:, 8]), to_char(p[:, 7]), to_char(p[:, 6])
-    header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {n}\n"
-              "property float x\nproperty float y\nproperty float z\n"
-              "property float nx\nproperty float ny\nproperty float nz\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
-    with open(path, "wb") as f:
-        f.write(header.encode("ascii"))
-        f.write(rec.tobytes())
+    return rec
+
+
+class PlyWriter:
+    """write_ply in pieces: the header with the vertex count known up front, then the points in any
+    number of write() calls, so a cloud never has to exist as one array.  The bytes are write_ply's.
+    close() (or leaving the `with` block without an exception) checks that exactly n_points were written."""
+
+    def __init__(self, path: str, n_points: int):
+        self.n, self.written = int(n_points), 0
+        header = ("ply\nformat binary_little_endian 1.0\n"
+                  f"element vertex {self.n}\n"
+                  "property float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+        self.f = open(path, "wb")
+        self.f.write(header.encode("ascii"))
+
+    def write(self, points: np.ndarray) -> None:
+        rec = _ply_records(points)
+        if self.written + rec.shape[0] > self.n:
+            raise ValueError(f"more than the {self.n} points the header announced")
+        self.f.write(rec.tobytes())
+        self.written += rec.shape[0]
+
+    def close(self) -> None:
+        if self.f is None:
+            return
+        self.f.close()
+        self.f = None
+        if self.written != self.n:
+            raise ValueError(f"{self.written} points written, the header announced {self.n}")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self.f is not None:
+            self.f.close()
+            self.f = None
+        return False
+
+
+def write_ply(path: str, points: np.ndarray) -> None:
+    """StoreColorPlyFileBinaryPointCloud (ACMMP.cpp:481-534).  points: (n, 9) float32 rows
+    x y z nx ny nz c0 c1 c2 as SimpleFusionKernel stores them (c0 = the texture's .z channel);
+    the writer emits red = (char)(int)c2, green = (char)(int)c1, blue = (char)(int)c0 and zeroes
+    coordinates that are not finite (the FLT_MAX tests of :508-512, including the z >= -FLT_MAX quirk)."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 9)
+    with PlyWriter(path, p.shape[0]) as w:
+        w.write(p)
 
 
 def read_ply(path: str) -> np.ndarray:

@@ -787,10 +787,19 @@ class Pipeline:
             self._upload_views(e, images, cams)
 
     # -- RunFusionCuda (ACMMP.cu:1817-2105), after the last pass
-    def run_fusion(self, fusion_factory=None, ply_path: str | None = None):
+    def run_fusion(self, fusion_factory=None, ply_path: str | None = None, unique: bool = False,
+                   chunk_points: int = 1 << 22, max_host_points: int | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
-        Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set."""
+        Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
+
+        A fusion object with run_scene (capi.Fusion) fuses the whole scene in one device-resident pass; the
+        cloud then comes to the host chunk_points at a time and the PLY is written piece by piece.  unique=False
+        is the reference's cloud (every view emits every point it sees: the same PLY bytes and self.fused as
+        the per-view path); unique=True is the duplicate-free mode of acmmp_fusion_run_scene (a depth sample
+        contributes to one reference view's points only, views in problem order).  A cloud of more than
+        max_host_points points (None: no limit) is only streamed to the PLY: self.fused and the return
+        value are then None.  A fusion object without run_scene is driven view by view (plain mode only)."""
         if self.world > 1:
             views = [p.ref_image_id for p in self.problems]
             owners = {self.problems[i].ref_image_id: self.owner(i) for i in range(len(self.problems))}
@@ -808,17 +817,33 @@ class Pipeline:
         for k in range(len(cams)):
             fu.set_view(k, depths[k], normals[k], colours[k])
         index = {p.ref_image_id: k for k, p in enumerate(self.problems)}
-        pts = []
-        for k, p in enumerate(self.problems):
-            srcs = [index.get(s, -1) for s in p.src_image_ids][:32]            # ACMMP.cu:2010-2023
-            pts.append(fu.run(k, srcs))
-        if hasattr(fu, "close"):
-            fu.close()
-        points = np.concatenate(pts, 0) if pts else np.zeros((0, 9), np.float32)
+        src_lists = [[index.get(s, -1) for s in p.src_image_ids][:32] for p in self.problems]   # ACMMP.cu:2010-2023
         path = ply_path or (os.path.join(self.out_folder, "ACMMP", "ACMM_model_cuda_5.ply") if self.out_folder else None)
         if path:
             os.makedirs(os.path.dirname(path), exist_ok=True)
-            io.write_ply(path, points)
+        if hasattr(fu, "run_scene"):
+            total, _ = fu.run_scene(list(range(len(self.problems))), src_lists, unique=unique)
+            keep = max_host_points is None or total <= max_host_points
+            points = np.zeros((total, 9), np.float32) if keep else None
+            writer = io.PlyWriter(path, total) if path else None
+            step = max(1, int(chunk_points))
+            for first in range(0, total, step):
+                part = fu.scene_points(first, min(step, total - first))
+                if writer:
+                    writer.write(part)
+                if keep:
+                    points[first:first + part.shape[0]] = part
+            if writer:
+                writer.close()
+        else:
+            if unique:
+                raise ValueError("unique fusion needs a fusion object with run_scene (capi.Fusion)")
+            pts = [fu.run(k, srcs) for k, srcs in enumerate(src_lists)]
+            points = np.concatenate(pts, 0) if pts else np.zeros((0, 9), np.float32)
+            if path:
+                io.write_ply(path, points)
+        if hasattr(fu, "close"):
+            fu.close()
         self.fused = points
         return points
 
@@ -910,6 +935,9 @@ def main(argv=None):
                     help="engine arithmetic (default: exact, bit-identical to the oracle)")
     ap.add_argument("--no-dmb", action="store_true", help="keep results in memory only")
     ap.add_argument("--no-fusion", action="store_true", help="skip RunFusionCuda")
+    ap.add_argument("--unique-fusion", action="store_true",
+                    help="duplicate-free cloud: a depth sample contributes to one reference view's points only "
+                         "(default: the reference's cloud, every view emits every point it sees)")
     a = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = int(os.environ.get("LOCAL_RANK", "0"))
@@ -923,7 +951,8 @@ def main(argv=None):
                     log=lambda *m: print(*m, flush=True), math=a.math).run()
     n_points = None
     if not a.no_fusion:
-        pts = pipe.run_fusion(ply_path=os.path.join(a.dense_folder, "ACMMP", "ACMM_model_cuda_5.ply"))
+        pts = pipe.run_fusion(ply_path=os.path.join(a.dense_folder, "ACMMP", "ACMM_model_cuda_5.ply"),
+                              unique=a.unique_fusion)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     print(json.dumps({"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -162,11 +162,14 @@ struct KParams {
 // Per-half-sweep output buffers of the colour being updated.
 // One view of the fusion set (device pointers): depth (W x H), normals (3 floats per pixel, world
 // frame as normals.dmb holds them), colour as the reference's float RGBA texture (4 per pixel, /255).
+// used: one byte per pixel, 1 = the depth sample already contributed to a point of an earlier reference
+// view of a duplicate-free scene pass (acmmp_fusion_run_scene with ACMMP_FUSE_UNIQUE); other passes ignore it.
 struct FuseView {
     const float* depth;
     const float* normal;
     const float* rgba;
     int W, H;
+    uint8_t* used;
 };
 
 struct SweepOut {
@@ -206,6 +209,19 @@ hipError_t launch_fuse(int model, const DevCam* cams, const FuseView* views, int
 // block_counts: valid pixels per 256-pixel chunk (written by launch_fuse); block_offsets: their prefix.
 hipError_t launch_fuse_compact(int W, int H, const float* out_dense, const int* flags, const int* block_offsets,
                                float* out, hipStream_t s);
+// One reference view of a whole-scene pass, all in stream order with no host step: SimpleFusionKernel with
+// the per-pixel consistent-source mask (unique: depths read through the views' used masks), the chunk
+// counts, their exclusive scan into block_offsets, *view_count = the view's points, *view_base = *running,
+// *running += *view_count, and (unique) the marking of every contributing sample.  src_mask is P-sized scratch.
+hipError_t launch_fuse_scene(int model, bool unique, const DevCam* cams, const FuseView* views, int ref, int W, int H,
+                             const int* srcs, int n_src, float* out_dense, int* flags, uint32_t* src_mask,
+                             int* block_counts, int* block_offsets, int* view_count, unsigned long long* running,
+                             unsigned long long* view_base, hipStream_t s);
+// Points and provenance of that view to the scene buffers at *view_base; nothing is written at or past `cap` points.
+hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const int* flags, const uint32_t* src_mask,
+                                     const int* block_offsets, const unsigned long long* view_base, int ref_pos,
+                                     unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
+                                     hipStream_t s);
 hipError_t launch_export_depth(const float4* planes, long long P, float* dst, hipStream_t s);
 hipError_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s);  // bytes % 4 == 0
 hipError_t launch_jbu(const float* ref, int W, int H, const float* coarse, int sw, int sh, int imagescale,

@@ -5,8 +5,14 @@
 // reference view SimpleFusionKernel (`k_fuse`) and an in-order compaction of the valid pixels -- the
 // order RunFusionCuda's host loop collects them in (ACMMP.cu:2064-2071).  Everything stays in HBM; only
 // the fused points come back.
+//
+// acmmp_fusion_run_scene is the same for a whole list of reference views in one call: the chunk prefix sum
+// runs on the device, the points and their provenance (view, pixel, consistent-source mask) stay in HBM until
+// acmmp_fusion_scene_points copies a range out, the count is 64-bit, and ACMMP_FUSE_UNIQUE keeps per-view
+// `used` masks so that a depth sample contributes to the points of one reference view only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -30,6 +36,22 @@ struct acmmp_fusion {
     int* d_offsets = nullptr;
     float* d_out = nullptr;
     size_t cap_P = 0, cap_out = 0;
+    // whole-scene pass: the resident result of the last acmmp_fusion_run_scene ...
+    float* s_pts = nullptr;                      // 9 floats per point
+    int* s_ref = nullptr;                        // position in the run's reference list
+    int* s_pix = nullptr;                        // r * W + c
+    uint32_t* s_mask = nullptr;                  // consistent sources
+    size_t s_cap = 0;                            // points allocated
+    unsigned long long s_total = 0;              // points held
+    // ... and its scratch
+    uint32_t* d_smask = nullptr;                 // per pixel, cap_smask pixels
+    size_t cap_smask = 0;
+    int* d_scene_srcs = nullptr;                 // 32 per reference view
+    int* d_view_counts = nullptr;                // per reference view
+    unsigned long long* d_view_base = nullptr;   // per reference view: scene offset of its first point
+    size_t cap_refs = 0;
+    unsigned long long* d_running = nullptr;     // running scene offset
+    int* h_count = nullptr;                      // pinned: the one word the host reads per view
     std::string err;
 };
 
@@ -84,11 +106,12 @@ acmmp_status acmmp_fusion_create(int device, int n_views, const acmmp_camera* ca
     f->n = n_views;
     f->cams.resize(n_views);
     for (int i = 0; i < n_views; ++i) f->cams[i] = make_devcam(cams[i]);
-    f->views.assign(n_views, FuseView{nullptr, nullptr, nullptr, 0, 0});
+    f->views.assign(n_views, FuseView{nullptr, nullptr, nullptr, 0, 0, nullptr});
     acmmp_status s = ACMMP_OK;
     if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
         alloc(f->d_cams, n_views) != hipSuccess || alloc(f->d_views, n_views) != hipSuccess ||
-        alloc(f->d_srcs, 32) != hipSuccess ||
+        alloc(f->d_srcs, 32) != hipSuccess || alloc(f->d_running, 1) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&f->h_count), sizeof(int), hipHostMallocDefault) != hipSuccess ||
         hipMemcpy(f->d_cams, f->cams.data(), sizeof(DevCam) * n_views, hipMemcpyHostToDevice) != hipSuccess)
         s = ACMMP_ERR_HIP;
     if (s != ACMMP_OK) { acmmp_fusion_destroy(f); return s; }
@@ -103,6 +126,11 @@ void acmmp_fusion_destroy(acmmp_fusion* f) {
     for (FuseView& v : f->views) { (void)fre(v.depth); (void)fre(v.normal); (void)fre(v.rgba); }
     (void)fre(f->d_cams); (void)fre(f->d_views); (void)fre(f->d_srcs); (void)fre(f->d_dense);
     (void)fre(f->d_flags); (void)fre(f->d_counts); (void)fre(f->d_offsets); (void)fre(f->d_out);
+    for (FuseView& v : f->views) (void)fre(v.used);
+    (void)fre(f->s_pts); (void)fre(f->s_ref); (void)fre(f->s_pix); (void)fre(f->s_mask);
+    (void)fre(f->d_smask); (void)fre(f->d_scene_srcs); (void)fre(f->d_view_counts); (void)fre(f->d_view_base);
+    (void)fre(f->d_running);
+    if (f->h_count) (void)hipHostFree(f->h_count);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }
@@ -129,11 +157,14 @@ acmmp_status acmmp_fusion_set_view(acmmp_fusion* f, int view, const float* depth
     float* d = nullptr;
     float* nrm = nullptr;
     float* col = nullptr;
-    (void)fre(v.depth); (void)fre(v.normal); (void)fre(v.rgba);
+    uint8_t* usd = nullptr;
+    (void)fre(v.depth); (void)fre(v.normal); (void)fre(v.rgba); (void)fre(v.used);
     F_HIP(f, alloc(d, P));
     F_HIP(f, alloc(nrm, 3 * P));
     F_HIP(f, alloc(col, 4 * P));
-    v = FuseView{d, nrm, col, W, H};
+    F_HIP(f, alloc(usd, P));
+    v = FuseView{d, nrm, col, W, H, usd};
+    F_HIP(f, hipMemset(usd, 0, P));                 // a newly set view has no used sample
     F_HIP(f, hipMemcpy(d, depth, sizeof(float) * P, hipMemcpyHostToDevice));
     F_HIP(f, hipMemcpy(nrm, normals, sizeof(float) * 3 * P, hipMemcpyHostToDevice));
     F_HIP(f, hipMemcpy(col, rgba.data(), sizeof(float) * 4 * P, hipMemcpyHostToDevice));
@@ -183,6 +214,208 @@ acmmp_status acmmp_fusion_run(acmmp_fusion* f, int ref, int n_src, const int* sr
     F_HIP(f, launch_fuse_compact(W, H, f->d_dense, f->d_flags, f->d_offsets, f->d_out, s));
     F_HIP(f, hipMemcpyAsync(points, f->d_out, sizeof(float) * 9 * total, hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The four arrays of a scene result.
+struct SceneBuf {
+    float* pts = nullptr;
+    int* ref = nullptr;
+    int* pix = nullptr;
+    uint32_t* mask = nullptr;
+    size_t cap = 0;
+    void release() { (void)fre(pts); (void)fre(ref); (void)fre(pix); (void)fre(mask); cap = 0; }
+};
+
+// b := arrays of at least `need` points (geometric growth) holding b's first `live` points.  b is unchanged
+// when an allocation fails.
+acmmp_status scene_grow(acmmp_fusion* f, SceneBuf& b, size_t need, size_t live, hipStream_t s) {
+    SceneBuf nb;
+    nb.cap = std::max(need, 2 * b.cap);
+    if (alloc(nb.pts, 9 * nb.cap) != hipSuccess || alloc(nb.ref, nb.cap) != hipSuccess ||
+        alloc(nb.pix, nb.cap) != hipSuccess || alloc(nb.mask, nb.cap) != hipSuccess) {
+        (void)hipGetLastError();
+        nb.release();
+        return ffail(f, ACMMP_ERR_OUT_OF_MEMORY, "scene buffer of " + std::to_string(need) + " points");
+    }
+    hipError_t e = hipSuccess;
+    if (live > 0) {
+        e = hipMemcpyAsync(nb.pts, b.pts, sizeof(float) * 9 * live, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nb.ref, b.ref, sizeof(int) * live, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nb.pix, b.pix, sizeof(int) * live, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nb.mask, b.mask, sizeof(uint32_t) * live, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        nb.release();
+        return ffail(f, ACMMP_ERR_HIP, std::string("scene buffer copy: ") + hipGetErrorString(e));
+    }
+    b.release();
+    b = nb;
+    return ACMMP_OK;
+}
+
+// The views of a scene run, fused in order into `out` (see acmmp_fusion_run_scene); counts[k] per view.
+acmmp_status scene_views(acmmp_fusion* f, int n_refs, const int* refs, const int* n_src, bool unique, SceneBuf& out,
+                         std::vector<int>& counts, unsigned long long& total) {
+    hipStream_t s = f->stream;
+    F_HIP(f, hipMemsetAsync(f->d_running, 0, sizeof(unsigned long long), s));
+    total = 0;
+    for (int k = 0; k < n_refs; ++k) {
+        const int ref = refs[k];
+        const int W = f->cams[ref].W, H = f->cams[ref].H;
+        F_HIP(f, launch_fuse_scene(f->model, unique, f->d_cams, f->d_views, ref, W, H, f->d_scene_srcs + 32 * k, n_src[k],
+                                   f->d_dense, f->d_flags, f->d_smask, f->d_counts, f->d_offsets, f->d_view_counts + k,
+                                   f->d_running, f->d_view_base + k, s));
+        // the one host wait of the view: its 4-byte count, to size the output before anything is written there
+        F_HIP(f, hipMemcpyAsync(f->h_count, f->d_view_counts + k, sizeof(int), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        const int c = *f->h_count;
+        counts[k] = c;
+        if (c > 0) {
+            if (total + static_cast<unsigned long long>(c) > out.cap) {
+                const acmmp_status st = scene_grow(f, out, static_cast<size_t>(total) + c, static_cast<size_t>(total), s);
+                if (st != ACMMP_OK) return st;
+            }
+            F_HIP(f, launch_fuse_scatter_scene(W, H, f->d_dense, f->d_flags, f->d_smask, f->d_offsets, f->d_view_base + k, k,
+                                               out.cap, out.pts, out.ref, out.pix, out.mask, s));
+        }
+        total += static_cast<unsigned long long>(c);
+    }
+    F_HIP(f, hipStreamSynchronize(s));
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs, const int* n_src, const int* src_views,
+                                    int flags, int* counts, int64_t* n_points) {
+    if (!f || !n_points || n_refs < 0 || (n_refs > 0 && (!refs || !n_src || !src_views)) ||
+        (flags & ~ACMMP_FUSE_UNIQUE) != 0)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    const bool unique = (flags & ACMMP_FUSE_UNIQUE) != 0;
+    size_t maxP = 0;
+    for (int k = 0; k < n_refs; ++k) {
+        if (refs[k] < 0 || refs[k] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "reference index out of range");
+        if (n_src[k] < 0 || n_src[k] > 32) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "more than 32 source views");
+        if (!f->views[refs[k]].depth) return ffail(f, ACMMP_ERR_STATE, "set_view first for every view used");
+        for (int j = 0; j < n_src[k]; ++j) {
+            const int v = src_views[32 * k + j];
+            if (v >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source index out of range");
+            if (v >= 0 && !f->views[v].depth) return ffail(f, ACMMP_ERR_STATE, "set_view first for every view used");
+        }
+        maxP = std::max(maxP, static_cast<size_t>(f->cams[refs[k]].W) * f->cams[refs[k]].H);
+    }
+    F_HIP(f, hipSetDevice(f->device));
+    // scratch (no part of the object's visible state)
+    const size_t nblk = (maxP + 255) / 256;
+    if (f->cap_P < maxP) {
+        f->cap_P = 0;
+        F_HIP(f, alloc(f->d_dense, 9 * maxP));
+        F_HIP(f, alloc(f->d_flags, maxP));
+        F_HIP(f, alloc(f->d_counts, nblk));
+        F_HIP(f, alloc(f->d_offsets, nblk));
+        f->cap_P = maxP;
+    }
+    if (f->cap_smask < maxP) {
+        f->cap_smask = 0;
+        F_HIP(f, alloc(f->d_smask, maxP));
+        f->cap_smask = maxP;
+    }
+    if (f->cap_refs < static_cast<size_t>(n_refs)) {
+        f->cap_refs = 0;
+        F_HIP(f, alloc(f->d_scene_srcs, 32 * static_cast<size_t>(n_refs)));
+        F_HIP(f, alloc(f->d_view_counts, static_cast<size_t>(n_refs)));
+        F_HIP(f, alloc(f->d_view_base, static_cast<size_t>(n_refs)));
+        f->cap_refs = static_cast<size_t>(n_refs);
+    }
+    std::vector<int> srcs(32 * static_cast<size_t>(n_refs), -1);
+    for (int k = 0; k < n_refs; ++k)
+        for (int j = 0; j < n_src[k]; ++j) srcs[32 * static_cast<size_t>(k) + j] = src_views[32 * k + j];
+    hipStream_t s = f->stream;
+    if (n_refs > 0)
+        F_HIP(f, hipMemcpyAsync(f->d_scene_srcs, srcs.data(), sizeof(int) * srcs.size(), hipMemcpyHostToDevice, s));
+    // unique: the used masks as they are now, to put back if the run fails part-way
+    std::vector<uint8_t*> saved(unique ? f->n : 0, nullptr);
+    auto drop_saved = [&]() { for (uint8_t*& p : saved) (void)fre(p); };
+    for (size_t v = 0; v < saved.size(); ++v) {
+        if (!f->views[v].used) continue;
+        const size_t P = static_cast<size_t>(f->views[v].W) * f->views[v].H;
+        hipError_t e = alloc(saved[v], P);
+        if (e == hipSuccess) e = hipMemcpyAsync(saved[v], f->views[v].used, P, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s);
+            drop_saved();
+            return ffail(f, e == hipErrorOutOfMemory ? ACMMP_ERR_OUT_OF_MEMORY : ACMMP_ERR_HIP,
+                         std::string("used-mask snapshot: ") + hipGetErrorString(e));
+        }
+    }
+    // the new result is built beside the previous one and replaces it only when the whole run succeeded
+    SceneBuf out;
+    std::vector<int> view_counts(n_refs, 0);
+    unsigned long long total = 0;
+    const acmmp_status st = scene_views(f, n_refs, refs, n_src, unique, out, view_counts, total);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipStreamSynchronize(s);
+        for (size_t v = 0; v < saved.size(); ++v)
+            if (saved[v])
+                (void)hipMemcpyAsync(f->views[v].used, saved[v], static_cast<size_t>(f->views[v].W) * f->views[v].H,
+                                     hipMemcpyDeviceToDevice, s);
+        (void)hipStreamSynchronize(s);
+        drop_saved();
+        out.release();
+        f->err = why;
+        return st;
+    }
+    drop_saved();
+    (void)fre(f->s_pts); (void)fre(f->s_ref); (void)fre(f->s_pix); (void)fre(f->s_mask);
+    f->s_pts = out.pts; f->s_ref = out.ref; f->s_pix = out.pix; f->s_mask = out.mask;
+    f->s_cap = out.cap;
+    f->s_total = total;
+    if (counts) std::copy(view_counts.begin(), view_counts.end(), counts);
+    *n_points = static_cast<int64_t>(total);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_scene_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* ref_index,
+                                       int32_t* pixel, uint32_t* src_mask) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (static_cast<unsigned long long>(first) > f->s_total || static_cast<unsigned long long>(n) > f->s_total - first)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the scene result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    if (points) F_HIP(f, hipMemcpy(points, f->s_pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
+    if (ref_index) F_HIP(f, hipMemcpy(ref_index, f->s_ref + a, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (pixel) F_HIP(f, hipMemcpy(pixel, f->s_pix + a, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (src_mask) F_HIP(f, hipMemcpy(src_mask, f->s_mask + a, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_reset_used(acmmp_fusion* f) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    F_HIP(f, hipSetDevice(f->device));
+    for (const FuseView& v : f->views)
+        if (v.used) F_HIP(f, hipMemsetAsync(v.used, 0, static_cast<size_t>(v.W) * v.H, f->stream));
+    F_HIP(f, hipStreamSynchronize(f->stream));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_download_used(acmmp_fusion* f, int view, uint8_t* mask) {
+    if (!f || !mask) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "null argument");
+    if (view < 0 || view >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
+    const size_t P = static_cast<size_t>(f->cams[view].W) * f->cams[view].H;
+    if (!f->views[view].used) { std::memset(mask, 0, P); return ACMMP_OK; }   // never set: nothing used
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, hipMemcpy(mask, f->views[view].used, P, hipMemcpyDeviceToHost));
     return ACMMP_OK;
 }
 

@@ -3689,9 +3689,17 @@ __device__ __forceinline__ float4 fuse_colour(const float* rgba, int W, int H, i
 // reprojects within 1 px, 1% depth and 0.149 rad of normal; >= 3 consistent (the reference
 // included) -> averaged point, normal and colour.  out: 9 floats per pixel (x y z nx ny nz c0 c1 c2,
 // c0 = 255 * texture .z as the reference stores it).
-template <int MODEL>
-__global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
-                       const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags) {
+//
+// Two compile-time variants serve the whole-scene pass (acmmp_fusion_run_scene): PROV also writes, per
+// pixel, the mask of consistent sources (bit j = srcs[j]); UNIQUE reads every depth through the views'
+// `used` byte masks -- a used pixel reads as depth 0, so a used reference pixel is skipped and a used
+// source sample is skipped, with the arithmetic, the thresholds and the order of the sums untouched.
+// k_fuse<MODEL> is the reference-equal kernel of acmmp_fusion_run (neither variant), k_fuse_scene the
+// kernel of the scene pass.
+template <int MODEL, bool PROV, bool UNIQUE>
+__device__ __forceinline__ void fuse_pixel(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref,
+                                           int W, int H, const int* __restrict__ srcs, int n_src, float* __restrict__ out,
+                                           int* __restrict__ flags, uint32_t* __restrict__ src_mask) {
     const int c = blockIdx.x * 16 + (threadIdx.x & 15);
     const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
     const bool inside = c < W && r < H;
@@ -3700,7 +3708,9 @@ __global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restri
     if (inside) {
         const DevCam& rc = cams[ref];
         const FuseView rv = views[ref];
-        const float ref_depth = rv.depth[idx];
+        float ref_depth = rv.depth[idx];
+        if constexpr (UNIQUE) { if (rv.used[idx]) ref_depth = 0.0f; }
+        uint32_t consistent = 0;
         if (!(ref_depth <= 0.0f)) {
             const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), ref_depth);
             const float rn0 = rv.normal[3 * idx], rn1 = rv.normal[3 * idx + 1], rn2 = rv.normal[3 * idx + 2];
@@ -3719,7 +3729,8 @@ __global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restri
                 const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
                 if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;
                 const long long sidx = static_cast<long long>(src_r) * sv.W + src_c;
-                const float sd = sv.depth[sidx];
+                float sd = sv.depth[sidx];
+                if constexpr (UNIQUE) { if (sv.used[sidx]) sd = 0.0f; }
                 if (sd <= 0.0f) continue;
                 const float3 Xs = world_point<MODEL>(sc, static_cast<float>(src_c), static_cast<float>(src_r), sd);
                 float qx, qy, qd;
@@ -3738,6 +3749,7 @@ __global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restri
                     cs1 = fmaf(scol.y, 255.0f, cs1);
                     cs2 = fmaf(scol.x, 255.0f, cs2);
                     ++n;
+                    if constexpr (PROV) consistent |= 1u << j;
                 }
             }
             if (n >= 3) {
@@ -3753,6 +3765,52 @@ __global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restri
             }
         }
         flags[idx] = valid;
+        if constexpr (PROV) src_mask[idx] = valid ? consistent : 0u;
+    }
+}
+
+template <int MODEL>
+__global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                       const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags) {
+    fuse_pixel<MODEL, false, false>(cams, views, ref, W, H, srcs, n_src, out, flags, nullptr);
+}
+
+template <int MODEL, bool UNIQUE>
+__global__ void k_fuse_scene(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                             const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags,
+                             uint32_t* __restrict__ src_mask) {
+    fuse_pixel<MODEL, true, UNIQUE>(cams, views, ref, W, H, srcs, n_src, out, flags, src_mask);
+}
+
+// After a unique-mode k_fuse_scene of view `ref`, before the next view's: every sample that contributed
+// to an emitted point is marked used -- the reference pixel, and for each consistent source j the pixel
+// (src_c, src_r) k_fuse sampled, recomputed by the same device functions from the same depth (an emitted
+// pixel was not used when k_fuse read it, so the raw depth is what it saw).  Plain byte stores of 1: lanes
+// that hit the same byte store the same value.
+template <int MODEL>
+__global__ void k_fuse_mark(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                            const int* __restrict__ srcs, int n_src, const int* __restrict__ flags,
+                            const uint32_t* __restrict__ src_mask) {
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (c >= W || r >= H) return;
+    const long long idx = static_cast<long long>(r) * W + c;
+    if (!flags[idx]) return;
+    const DevCam& rc = cams[ref];
+    const FuseView rv = views[ref];
+    const uint32_t m = src_mask[idx];
+    const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), rv.depth[idx]);
+    rv.used[idx] = 1;
+    for (int j = 0; j < n_src; ++j) {
+        if (!((m >> j) & 1u)) continue;
+        const int si = srcs[j];
+        const DevCam& sc = cams[si];
+        const FuseView sv = views[si];
+        float px, py, pd;
+        project<MODEL, const DevCam, true>(sc, X, px, py, pd);
+        const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
+        if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;   // (never: the bit says it was inside)
+        sv.used[static_cast<long long>(src_r) * sv.W + src_c] = 1;
     }
 }
 
@@ -3785,6 +3843,79 @@ __global__ void k_fuse_scatter(const float* __restrict__ dense, const int* __res
     }
 }
 
+// Exclusive scan of the chunk counts of one view (each 0..256) and the scene bookkeeping, one workgroup
+// of 1024 lanes walking the chunks in tiles of 1024 with a running carry.  Within a wave the prefix is
+// built bit plane by bit plane from ballots: popcount(ballot(bit b of count) below my lane) << b, summed
+// over the 9 planes; the 16 wave totals meet in LDS.  Lane 0 then publishes the view's point count, takes
+// the 64-bit running scene offset as this view's base and advances it.
+__global__ __launch_bounds__(1024) void k_fuse_scan(const int* __restrict__ counts, int n_chunks, int* __restrict__ offsets,
+                                                    int* __restrict__ view_count, unsigned long long* __restrict__ running,
+                                                    unsigned long long* __restrict__ view_base) {
+    __shared__ int wave_tot[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int carry = 0;
+    for (int t0 = 0; t0 < n_chunks; t0 += 1024) {
+        const int i = t0 + static_cast<int>(threadIdx.x);
+        const int v = i < n_chunks ? counts[i] : 0;
+        int excl = 0, tot = 0;
+#pragma unroll
+        for (int b = 0; b < 9; ++b) {
+            const unsigned long long m = __ballot((v >> b) & 1);
+            excl += __popcll(m & below) << b;
+            tot += __popcll(m) << b;
+        }
+        if (lane == 0) wave_tot[wave] = tot;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int x = wave_tot[w];
+            all += x;
+            if (w < wave) before += x;
+        }
+        if (i < n_chunks) offsets[i] = carry + before + excl;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *view_count = carry;
+        const unsigned long long t = *running;
+        *view_base = t;
+        *running = t + static_cast<unsigned long long>(carry);
+    }
+}
+
+// k_fuse_scatter into the scene buffers at *view_base + offsets[chunk] + rank: the point and its provenance
+// (position of the view in the run's reference list, pixel r*W + c, consistent-source mask).  Nothing is
+// written at or beyond `cap` points.
+__global__ void k_fuse_scatter_scene(const float* __restrict__ dense, const int* __restrict__ flags,
+                                     const uint32_t* __restrict__ src_mask, long long P, const int* __restrict__ offsets,
+                                     const unsigned long long* __restrict__ view_base, int ref_pos, unsigned long long cap,
+                                     float* __restrict__ out, int* __restrict__ out_ref, int* __restrict__ out_pix,
+                                     uint32_t* __restrict__ out_mask) {
+    __shared__ int wave_tot[4];
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    const int f = i < P ? flags[i] : 0;
+    const unsigned long long b = __ballot(f);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(b);
+    __syncthreads();
+    int base = offsets[blockIdx.x];
+    for (int w = 0; w < wave; ++w) base += wave_tot[w];
+    const unsigned long long pos = *view_base + static_cast<unsigned long long>(base + below);
+    if (f && pos < cap) {
+        float* o = out + 9ull * pos;
+        const float* d = dense + 9 * i;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = d[k];
+        out_ref[pos] = ref_pos;
+        out_pix[pos] = static_cast<int>(i);
+        out_mask[pos] = src_mask[i];
+    }
+}
+
 __global__ void k_export_depth(const float4* __restrict__ planes, long long P, float* __restrict__ dst) {
     const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i < P) dst[i] = planes[i].w;
@@ -3804,6 +3935,40 @@ hipError_t launch_fuse_compact(int W, int H, const float* out_dense, const int* 
                                float* out, hipStream_t s) {
     const long long P = static_cast<long long>(W) * H;
     k_fuse_scatter<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, P, block_offsets, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_scene(int model, bool unique, const DevCam* cams, const FuseView* views, int ref, int W, int H,
+                             const int* srcs, int n_src, float* out_dense, int* flags, uint32_t* src_mask,
+                             int* block_counts, int* block_offsets, int* view_count, unsigned long long* running,
+                             unsigned long long* view_base, hipStream_t s) {
+    dim3 grd(cdiv(W, 16), cdiv(H, 16));
+    if (model == kSphere) {
+        if (unique) k_fuse_scene<kSphere, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+        else k_fuse_scene<kSphere, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+    } else {
+        if (unique) k_fuse_scene<kPinhole, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+        else k_fuse_scene<kPinhole, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+    }
+    const long long P = static_cast<long long>(W) * H;
+    const int n_chunks = static_cast<int>((P + 255) / 256);
+    k_fuse_count<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(flags, P, block_counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(block_counts, n_chunks, block_offsets, view_count, running, view_base);
+    if (unique) {
+        if (model == kSphere) k_fuse_mark<kSphere><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
+        else k_fuse_mark<kPinhole><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const int* flags, const uint32_t* src_mask,
+                                     const int* block_offsets, const unsigned long long* view_base, int ref_pos,
+                                     unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
+                                     hipStream_t s) {
+    const long long P = static_cast<long long>(W) * H;
+    k_fuse_scatter_scene<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, src_mask, P, block_offsets,
+                                                                               view_base, ref_pos, cap, out, out_ref,
+                                                                               out_pix, out_mask);
     return hipGetLastError();
 }
 

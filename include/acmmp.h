@@ -333,6 +333,47 @@ acmmp_status acmmp_fusion_run(acmmp_fusion *f, int ref, int n_src, const int *sr
 const char *acmmp_fusion_last_error(const acmmp_fusion *f);
 void acmmp_fusion_destroy(acmmp_fusion *f);
 
+/* ---- whole-scene fusion (no reference counterpart: RunFusionCuda collects every view's points on the
+ * host, ACMMP.cu:2064-2071) -------------------------------------------------------------------------
+ * acmmp_fusion_run_scene fuses the reference views refs[0 .. n_refs) in that order in one call; view k
+ * against src_views[32*k .. 32*k + n_src[k]) (indices into the set, -1 = missing, n_src[k] <= 32).  The
+ * result stays in HBM, in the fusion object, until the next successful run replaces it: the points (9 floats
+ * each, as acmmp_fusion_run) and per point its provenance -- the position k of its view in `refs`, its pixel
+ * r*W + c in that view, and a source mask whose bit j says that src_views[32*k + j] was consistent.
+ * counts[k] (may be NULL) = points of view k; *n_points = their 64-bit sum.  The chunk prefix sum runs on the
+ * device; the host waits once per view, for that view's 4-byte count (the output buffer grows from it before
+ * anything is written there; a growth, geometric, also waits for the device copy into the larger buffer),
+ * and once at the end of the call.  No point crosses to the host before acmmp_fusion_scene_points.
+ *
+ * flags = 0, plain: the result is the concatenation of acmmp_fusion_run(refs[k], ...) over k, bit for bit
+ * and in that order (every view emits every surface point it sees consistently: a point seen by V views
+ * appears about V times).  The used masks are neither read nor written.
+ *
+ * flags = ACMMP_FUSE_UNIQUE, duplicate-free: every view carries a byte mask `used`, cleared by
+ * acmmp_fusion_create, by acmmp_fusion_set_view of that view and by acmmp_fusion_reset_used.  View k is fused
+ * exactly as above on depth maps in which every used pixel reads as depth 0 (a used reference pixel is
+ * skipped, a used source sample is skipped; arithmetic, thresholds and the order of the sums are unchanged).
+ * It sees the marks of the earlier views of the run and of earlier runs, never those of its own pixels.
+ * After view k, for each point it emitted, its reference pixel is marked, and for each set source bit the
+ * source pixel that was sampled.  So a depth sample that contributed to a point of an earlier reference view
+ * contributes to no point of a later one.  Marks persist across calls until reset.
+ *
+ * Any error -- an out-of-memory part-way included -- leaves the object as it was before the call: the used
+ * masks and the previous result are unchanged (the new result is built beside the previous one, so both are
+ * held until the run ends). */
+#define ACMMP_FUSE_UNIQUE 1
+acmmp_status acmmp_fusion_run_scene(acmmp_fusion *f, int n_refs, const int *refs, const int *n_src,
+                                    const int *src_views, int flags, int *counts, int64_t *n_points);
+/* Points [first, first + n) of the scene result to host arrays, any of which may be NULL: points n x 9
+ * floats, ref_index / pixel n int32, src_mask n uint32.  A caller streams a cloud larger than it wants to
+ * hold by asking for one range after another. */
+acmmp_status acmmp_fusion_scene_points(acmmp_fusion *f, int64_t first, int64_t n, float *points,
+                                       int32_t *ref_index, int32_t *pixel, uint32_t *src_mask);
+/* Clears every view's used mask. */
+acmmp_status acmmp_fusion_reset_used(acmmp_fusion *f);
+/* Test hook: view's used mask, H x W bytes (all 0 for a view that was never set). */
+acmmp_status acmmp_fusion_download_used(acmmp_fusion *f, int view, uint8_t *mask);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
