@@ -112,7 +112,8 @@ EXPORTS = [
     "acmmp_band_copy_rows", "acmmp_band_get_rows", "acmmp_band_set_rows", "acmmp_band_end",
     "acmmp_fusion_create", "acmmp_fusion_set_view", "acmmp_fusion_run", "acmmp_fusion_last_error",
     "acmmp_fusion_destroy", "acmmp_fusion_run_scene", "acmmp_fusion_scene_points", "acmmp_fusion_reset_used",
-    "acmmp_fusion_download_used", "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
+    "acmmp_fusion_download_used", "acmmp_fusion_voxelize", "acmmp_fusion_voxel_points", "acmmp_fusion_voxel_table",
+    "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
 
@@ -204,6 +205,9 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_scene_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.acmmp_fusion_reset_used.argtypes = [vp]
     L.acmmp_fusion_download_used.argtypes = [vp, i32, vp]
+    L.acmmp_fusion_voxelize.argtypes = [vp, C.c_float, vp, i32, vp, vp, vp, vp]
+    L.acmmp_fusion_voxel_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    L.acmmp_fusion_voxel_table.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -913,6 +917,36 @@ class Fusion:
         m = np.empty((H, W), np.uint8)
         self._check(self.L.acmmp_fusion_download_used(self.h, view, _p(m)), "fusion_download_used")
         return m
+
+    def voxelize(self, size: float, origin=None, min_points: int = 1):
+        """Reduce the resident scene result to one point per occupied cell of a grid of `size` (centroid, mean
+        normal, mean colour, point count; integer accumulation, so bit-reproducible: acmmp_fusion_voxelize,
+        include/acmmp.h).  origin None: the component-wise minimum of the cloud.  Cells of fewer than min_points
+        points are dropped.  The result stays on the GPU (read it with voxel_points) until the next voxelize or
+        run_scene.  Returns (voxels, {"n_occupied", "n_rejected", "origin"})."""
+        o = None if origin is None else np.ascontiguousarray(origin, np.float32).reshape(3)
+        out = np.zeros(3, np.int64)
+        used = np.zeros(3, np.float32)
+        self._check(self.L.acmmp_fusion_voxelize(self.h, float(size), None if o is None else _p(o), int(min_points),
+                                                 _p(out[0:1]), _p(out[1:2]), _p(out[2:3]), _p(used)), "fusion_voxelize")
+        return int(out[0]), {"n_occupied": int(out[1]), "n_rejected": int(out[2]), "origin": used}
+
+    def voxel_points(self, first: int, n: int, counts: bool = False):
+        """Voxels [first, first + n) of the last voxelize, in order of first appearance in the scene cloud:
+        (n, 9) float32, and with counts also the points per voxel (int32)."""
+        pts = host_empty((max(n, 0), 9), np.float32)          # (a negative n is refused below)
+        cnt = np.empty(max(n, 0), np.int32) if counts else None
+        self._check(self.L.acmmp_fusion_voxel_points(self.h, first, n, _p(pts), None if cnt is None else _p(cnt)),
+                    "fusion_voxel_points")
+        return (pts, cnt) if counts else pts
+
+    def voxel_table(self, force_slots: int = 0):
+        """Test hook: sets the hash-table size of the next voxelize (0 = automatic) and returns the last
+        successful run's {"slots", "occupied", "max_probe", "wrapped"}."""
+        st = np.zeros(4, np.int64)
+        self._check(self.L.acmmp_fusion_voxel_table(self.h, int(force_slots), _p(st[0:1]), _p(st[1:2]), _p(st[2:3]),
+                                                    _p(st[3:4])), "fusion_voxel_table")
+        return {"slots": int(st[0]), "occupied": int(st[1]), "max_probe": int(st[2]), "wrapped": int(st[3])}
 
     def close(self):
         if self.h:

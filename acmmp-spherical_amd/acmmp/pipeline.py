@@ -788,7 +788,8 @@ class Pipeline:
 
     # -- RunFusionCuda (ACMMP.cu:1817-2105), after the last pass
     def run_fusion(self, fusion_factory=None, ply_path: str | None = None, unique: bool = False,
-                   chunk_points: int = 1 << 22, max_host_points: int | None = None):
+                   chunk_points: int = 1 << 22, max_host_points: int | None = None,
+                   voxel_size: float | None = None, voxel_min_points: int = 1):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -799,7 +800,15 @@ class Pipeline:
         the per-view path); unique=True is the duplicate-free mode of acmmp_fusion_run_scene (a depth sample
         contributes to one reference view's points only, views in problem order).  A cloud of more than
         max_host_points points (None: no limit) is only streamed to the PLY: self.fused and the return
-        value are then None.  A fusion object without run_scene is driven view by view (plain mode only)."""
+        value are then None.  A fusion object without run_scene is driven view by view (plain mode only).
+
+        voxel_size: the scene cloud (plain or unique, as asked) is reduced on the device to one point per
+        occupied cell of a grid of that size -- centroid, mean normal, mean colour; cells of fewer than
+        voxel_min_points points are dropped (acmmp_fusion_voxelize, include/acmmp.h) -- and that cloud, bounded
+        by the scene's surface and not by the number of views, is what is streamed to the PLY, kept in self.fused
+        and held to max_host_points.  self.fusion_info then tells the scene's points, the voxels and the
+        rejected points.  It needs a fusion object with voxelize (capi.Fusion)."""
+        self.fusion_info = None
         if self.world > 1:
             views = [p.ref_image_id for p in self.problems]
             owners = {self.problems[i].ref_image_id: self.owner(i) for i in range(len(self.problems))}
@@ -821,14 +830,25 @@ class Pipeline:
         path = ply_path or (os.path.join(self.out_folder, "ACMMP", "ACMM_model_cuda_5.ply") if self.out_folder else None)
         if path:
             os.makedirs(os.path.dirname(path), exist_ok=True)
+        if voxel_size is not None and not (hasattr(fu, "run_scene") and hasattr(fu, "voxelize")):
+            raise ValueError("voxel fusion needs a fusion object with run_scene and voxelize (capi.Fusion)")
         if hasattr(fu, "run_scene"):
             total, _ = fu.run_scene(list(range(len(self.problems))), src_lists, unique=unique)
+            read = fu.scene_points
+            if voxel_size is not None:
+                scene_total = total
+                total, info = fu.voxelize(voxel_size, min_points=voxel_min_points)
+                read = fu.voxel_points
+                self.fusion_info = {"scene_points": int(scene_total), "voxels": int(total),
+                                    "rejected": int(info["n_rejected"]), "occupied": int(info["n_occupied"]),
+                                    "origin": [float(x) for x in info["origin"]], "voxel_size": float(voxel_size),
+                                    "min_points": int(voxel_min_points)}
             keep = max_host_points is None or total <= max_host_points
             points = np.zeros((total, 9), np.float32) if keep else None
             writer = io.PlyWriter(path, total) if path else None
             step = max(1, int(chunk_points))
             for first in range(0, total, step):
-                part = fu.scene_points(first, min(step, total - first))
+                part = read(first, min(step, total - first))
                 if writer:
                     writer.write(part)
                 if keep:
@@ -917,14 +937,9 @@ def write_dense_folder(folder: str, ds: Dataset, pairs=None, quality: int = 95):
     io.write_pair_list(folder, pairs)
 
 
-def main(argv=None):
-    """`python -m acmmp.pipeline DENSE_FOLDER` -- the reference's `ACMMP dense_folder` (main.cpp:369-489):
-    the multi-scale schedule, then RunFusionCuda into ACMMP/ACMM_model_cuda_5.ply.
-    Under torchrun (WORLD_SIZE > 1) every rank drives GPU LOCAL_RANK, views are sharded and the
-    depth maps are exchanged over RCCL between passes (snapshot order)."""
+def arg_parser():
+    """The command line of `python -m acmmp.pipeline`."""
     import argparse
-    import json
-    import time
     ap = argparse.ArgumentParser()
     ap.add_argument("dense_folder")
     ap.add_argument("--seed", type=int, default=1234)
@@ -938,7 +953,22 @@ def main(argv=None):
     ap.add_argument("--unique-fusion", action="store_true",
                     help="duplicate-free cloud: a depth sample contributes to one reference view's points only "
                          "(default: the reference's cloud, every view emits every point it sees)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="reduce the fused cloud on the GPU to one point per occupied cell of a grid of this size "
+                         "(centroid, mean normal, mean colour) and write that cloud")
+    ap.add_argument("--voxel-min-points", type=int, default=1,
+                    help="with --voxel-size: drop cells of fewer points than this")
+    return ap
+
+
+def main(argv=None):
+    """`python -m acmmp.pipeline DENSE_FOLDER` -- the reference's `ACMMP dense_folder` (main.cpp:369-489):
+    the multi-scale schedule, then RunFusionCuda into ACMMP/ACMM_model_cuda_5.ply.
+    Under torchrun (WORLD_SIZE > 1) every rank drives GPU LOCAL_RANK, views are sharded and the
+    depth maps are exchanged over RCCL between passes (snapshot order)."""
+    import json
+    import time
+    a = arg_parser().parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device = int(os.environ.get("LOCAL_RANK", "0"))
     order = a.order or ("reference" if world == 1 else "snapshot")
@@ -952,12 +982,14 @@ def main(argv=None):
     n_points = None
     if not a.no_fusion:
         pts = pipe.run_fusion(ply_path=os.path.join(a.dense_folder, "ACMMP", "ACMM_model_cuda_5.ply"),
-                              unique=a.unique_fusion)
+                              unique=a.unique_fusion, voxel_size=a.voxel_size, voxel_min_points=a.voxel_min_points)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
-    print(json.dumps({"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),
-                      "passes": [p.name for p in pipe.passes], "fused_points": n_points,
-                      "seconds": round(dt, 3)}), flush=True)
+    line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),
+            "passes": [p.name for p in pipe.passes], "fused_points": n_points, "seconds": round(dt, 3)}
+    if getattr(pipe, "fusion_info", None):
+        line["fusion_info"] = pipe.fusion_info
+    print(json.dumps(line), flush=True)
     exchange.close()
     return 0
 

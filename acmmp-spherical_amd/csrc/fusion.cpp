@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -52,6 +53,21 @@ struct acmmp_fusion {
     size_t cap_refs = 0;
     unsigned long long* d_running = nullptr;     // running scene offset
     int* h_count = nullptr;                      // pinned: the one word the host reads per view
+    bool s_have = false;                         // a run_scene has succeeded
+    // voxel-grid reduction of the scene result (acmmp_fusion_voxelize): its resident result ...
+    float* v_pts = nullptr;                      // 9 floats per voxel
+    int32_t* v_cnt = nullptr;                    // points per voxel
+    unsigned long long v_total = 0;              // voxels held
+    long long v_force_slots = 0;                 // test hook: table size of the next run, 0 = automatic
+    long long v_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful run
+    // ... and its scratch, kept between runs and dropped with the scene result it was sized for
+    VoxTable v_tab = {nullptr, nullptr, nullptr, nullptr, 0, 0};
+    int* v_flags = nullptr;                      // per point of a segment
+    int* v_counts = nullptr;                     // per 256-point chunk of a segment
+    int* v_offsets = nullptr;
+    size_t v_cap_seg = 0;
+    unsigned long long* v_words = nullptr;       // kVoxWords run words, then the segment base, then 3 minima (as 2 words)
+    int* v_seg_count = nullptr;
     std::string err;
 };
 
@@ -130,6 +146,9 @@ void acmmp_fusion_destroy(acmmp_fusion* f) {
     (void)fre(f->s_pts); (void)fre(f->s_ref); (void)fre(f->s_pix); (void)fre(f->s_mask);
     (void)fre(f->d_smask); (void)fre(f->d_scene_srcs); (void)fre(f->d_view_counts); (void)fre(f->d_view_base);
     (void)fre(f->d_running);
+    (void)fre(f->v_pts); (void)fre(f->v_cnt); (void)fre(f->v_tab.keys); (void)fre(f->v_tab.first); (void)fre(f->v_tab.oid);
+    (void)fre(f->v_tab.cnt); (void)fre(f->v_flags); (void)fre(f->v_counts); (void)fre(f->v_offsets); (void)fre(f->v_words);
+    (void)fre(f->v_seg_count);
     if (f->h_count) (void)hipHostFree(f->h_count);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
@@ -220,6 +239,13 @@ acmmp_status acmmp_fusion_run(acmmp_fusion* f, int ref, int n_src, const int* sr
 }  // extern "C"
 
 namespace {
+
+void voxel_scratch_release(acmmp_fusion* f) {
+    (void)fre(f->v_tab.keys); (void)fre(f->v_tab.first); (void)fre(f->v_tab.oid); (void)fre(f->v_tab.cnt);
+    f->v_tab.slots = 0;
+    (void)fre(f->v_flags); (void)fre(f->v_counts); (void)fre(f->v_offsets);
+    f->v_cap_seg = 0;
+}
 
 // The four arrays of a scene result.
 struct SceneBuf {
@@ -380,6 +406,11 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
     f->s_pts = out.pts; f->s_ref = out.ref; f->s_pix = out.pix; f->s_mask = out.mask;
     f->s_cap = out.cap;
     f->s_total = total;
+    f->s_have = true;
+    // the voxel result described the previous scene: it goes, with the scratch sized for that scene
+    (void)fre(f->v_pts); (void)fre(f->v_cnt);
+    f->v_total = 0;
+    voxel_scratch_release(f);
     if (counts) std::copy(view_counts.begin(), view_counts.end(), counts);
     *n_points = static_cast<int64_t>(total);
     return ACMMP_OK;
@@ -416,6 +447,204 @@ acmmp_status acmmp_fusion_download_used(acmmp_fusion* f, int view, uint8_t* mask
     if (!f->views[view].used) { std::memset(mask, 0, P); return ACMMP_OK; }   // never set: nothing used
     F_HIP(f, hipSetDevice(f->device));
     F_HIP(f, hipMemcpy(mask, f->views[view].used, P, hipMemcpyDeviceToHost));
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- voxel-grid reduction of the resident scene result (include/acmmp.h; kernels: k_voxel_*) --------------
+
+namespace {
+
+// Points per compaction segment: the scan's chunk offsets are 32-bit.  ACMMP_VOXEL_SEGMENT_POINTS (a multiple of
+// 256, tests) makes a small scene take the multi-segment path.
+unsigned long long voxel_segment_points() {
+    const unsigned long long dflt = 1ull << 30;
+    const char* e = std::getenv("ACMMP_VOXEL_SEGMENT_POINTS");
+    if (!e || !*e) return dflt;
+    const long long v = std::atoll(e);
+    return (v >= 256 && v % 256 == 0 && static_cast<unsigned long long>(v) <= dflt) ? static_cast<unsigned long long>(v) : dflt;
+}
+
+bool finite32(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, 4);
+    return (b & 0x7f800000u) != 0x7f800000u;
+}
+
+// The new result of a voxel run, swapped in only when the whole run succeeded.
+struct VoxelOut {
+    float* pts = nullptr;
+    int32_t* cnt = nullptr;
+    unsigned long long* sums = nullptr;      // scratch: 9 int64 per kept voxel
+    unsigned long long* vslot = nullptr;     // scratch: table slot per kept voxel
+    void release() { (void)fre(pts); (void)fre(cnt); (void)fre(sums); (void)fre(vslot); }
+};
+
+acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_points, unsigned long long slots,
+                       int log2_slots, VoxelOut& out, unsigned long long words[kVoxWords]) {
+    hipStream_t s = f->stream;
+    const unsigned long long N = f->s_total, seg = voxel_segment_points();
+    const size_t seg_pts = static_cast<size_t>(std::min(N, seg)), seg_chunks = (seg_pts + 255) / 256;
+    // scratch
+    if (!f->v_words) F_HIP(f, alloc(f->v_words, kVoxWords + 3));
+    if (!f->v_seg_count) F_HIP(f, alloc(f->v_seg_count, 1));
+    if (f->v_tab.slots != slots) {
+        f->v_tab.slots = 0;
+        F_HIP(f, alloc(f->v_tab.keys, slots));
+        F_HIP(f, alloc(f->v_tab.first, slots));
+        F_HIP(f, alloc(f->v_tab.oid, slots));
+        F_HIP(f, alloc(f->v_tab.cnt, slots));
+        f->v_tab.slots = slots;
+    }
+    f->v_tab.log2_slots = log2_slots;
+    if (f->v_cap_seg < seg_pts) {
+        f->v_cap_seg = 0;
+        F_HIP(f, alloc(f->v_flags, seg_pts));
+        F_HIP(f, alloc(f->v_counts, seg_chunks));
+        F_HIP(f, alloc(f->v_offsets, seg_chunks));
+        f->v_cap_seg = seg_pts;
+    }
+    const VoxTable t = f->v_tab;
+    unsigned long long* st = f->v_words;
+    unsigned long long* seg_base = f->v_words + kVoxWords;
+    uint32_t* mn = reinterpret_cast<uint32_t*>(f->v_words + kVoxWords + 1);
+    F_HIP(f, hipMemsetAsync(st, 0, sizeof(unsigned long long) * (kVoxWords + 1), s));
+    auto segments = [&](auto&& fn) -> hipError_t {
+        for (unsigned long long i0 = 0; i0 < N; i0 += seg) {
+            const hipError_t e = fn(i0, static_cast<int>(std::min(seg, N - i0)));
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    if (find_origin) {
+        uint32_t h_mn[3];
+        F_HIP(f, hipMemsetAsync(mn, 0xff, sizeof(uint32_t) * 4, s));
+        F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_min(f->s_pts, i0, n, mn, s); }));
+        F_HIP(f, hipMemcpyAsync(h_mn, mn, sizeof(h_mn), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        // no point passed the finiteness test: the origin is (0, 0, 0), and every point is rejected below
+        const bool any = h_mn[0] != 0xffffffffu;
+        g.ox = any ? vox_decode_ordered(h_mn[0]) : 0.0f;
+        g.oy = any ? vox_decode_ordered(h_mn[1]) : 0.0f;
+        g.oz = any ? vox_decode_ordered(h_mn[2]) : 0.0f;
+    }
+    // insert pass, then the table's counts
+    F_HIP(f, hipMemsetAsync(t.keys, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(t.first, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(t.oid, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(t.cnt, 0, sizeof(uint32_t) * slots, s));
+    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_insert(f->s_pts, i0, n, g, t, st, s); }));
+    F_HIP(f, launch_voxel_stats(t, min_points, st, s));
+    F_HIP(f, hipMemcpyAsync(words, st, sizeof(unsigned long long) * kVoxWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (words[kVoxErr]) return ffail(f, ACMMP_ERR_HIP, "voxel table: a probe sequence covered every slot");
+    const unsigned long long kept = words[kVoxKept];
+    F_HIP(f, alloc(out.pts, 9 * static_cast<size_t>(kept)));
+    F_HIP(f, alloc(out.cnt, static_cast<size_t>(kept)));
+    F_HIP(f, alloc(out.sums, 9 * static_cast<size_t>(kept)));
+    F_HIP(f, alloc(out.vslot, static_cast<size_t>(kept)));
+    if (kept == 0) return ACMMP_OK;
+    // compaction in order of first appearance, the sums, the means
+    F_HIP(f, hipMemsetAsync(f->d_running, 0, sizeof(unsigned long long), s));
+    F_HIP(f, hipMemsetAsync(out.sums, 0, sizeof(unsigned long long) * 9 * kept, s));
+    F_HIP(f, hipMemsetAsync(out.vslot, 0xff, sizeof(unsigned long long) * kept, s));
+    F_HIP(f, segments([&](unsigned long long i0, int n) {
+        return launch_voxel_compact(f->s_pts, i0, n, g, t, min_points, f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count,
+                                    f->d_running, seg_base, kept, out.vslot, st, s);
+    }));
+    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->s_pts, i0, n, g, t, out.sums, st, s); }));
+    F_HIP(f, launch_voxel_finalise(kept, out.vslot, t, out.sums, g, out.pts, out.cnt, s));
+    unsigned long long end[2] = {0, 0};                                  // error word, voxels compacted
+    F_HIP(f, hipMemcpyAsync(&end[0], st + kVoxErr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipMemcpyAsync(&end[1], f->d_running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (end[0] || end[1] != kept)
+        return ffail(f, ACMMP_ERR_HIP, "voxel table: lookup failed (flags " + std::to_string(end[0]) + ", compacted " +
+                                           std::to_string(end[1]) + " of " + std::to_string(kept) + ")");
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const float* origin, int min_points,
+                                   int64_t* n_voxels, int64_t* n_occupied, int64_t* n_rejected, float* origin_used) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (!finite32(voxel_size) || !(voxel_size > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "voxel size must be finite and > 0");
+    if (min_points < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_points must be at least 1");
+    if (origin && !(finite32(origin[0]) && finite32(origin[1]) && finite32(origin[2])))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "origin must be finite");
+    if (!f->s_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no scene result: acmmp_fusion_run_scene first");
+    const unsigned long long N = f->s_total;
+    unsigned long long slots = 1024;
+    if (f->v_force_slots != 0) {
+        const long long v = f->v_force_slots;
+        if (v < 64 || (v & (v - 1)) != 0 || static_cast<unsigned long long>(v) <= N)
+            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "forced table size must be a power of two >= 64 and > the scene's points");
+        slots = static_cast<unsigned long long>(v);
+    } else {
+        if (N > (1ull << 61)) return ffail(f, ACMMP_ERR_UNSUPPORTED, "scene too large for the voxel table");
+        while (slots < 2 * N) slots <<= 1;
+    }
+    int log2_slots = 0;
+    while ((1ull << log2_slots) < slots) ++log2_slots;
+    F_HIP(f, hipSetDevice(f->device));
+    VoxGrid g;
+    g.ox = origin ? origin[0] : 0.0f;
+    g.oy = origin ? origin[1] : 0.0f;
+    g.oz = origin ? origin[2] : 0.0f;
+    g.size = voxel_size;
+    g.inv = 1.0f / voxel_size;
+    VoxelOut out;
+    unsigned long long words[kVoxWords] = {0};
+    if (N > 0) {
+        const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, log2_slots, out, words);
+        if (st != ACMMP_OK) {
+            const std::string why = f->err;
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(f->stream);
+            out.release();
+            f->err = why;
+            return st;
+        }
+    }
+    (void)fre(out.sums); (void)fre(out.vslot);
+    (void)fre(f->v_pts); (void)fre(f->v_cnt);
+    f->v_pts = out.pts; f->v_cnt = out.cnt;
+    f->v_total = words[kVoxKept];
+    f->v_stats[0] = static_cast<long long>(slots);
+    f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
+    f->v_stats[2] = static_cast<long long>(words[kVoxMaxProbe]);
+    f->v_stats[3] = static_cast<long long>(words[kVoxWrapped]);
+    if (n_voxels) *n_voxels = static_cast<int64_t>(words[kVoxKept]);
+    if (n_occupied) *n_occupied = static_cast<int64_t>(words[kVoxOccupied]);
+    if (n_rejected) *n_rejected = static_cast<int64_t>(words[kVoxRejected]);
+    if (origin_used) { origin_used[0] = g.ox; origin_used[1] = g.oy; origin_used[2] = g.oz; }
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_voxel_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (static_cast<unsigned long long>(first) > f->v_total || static_cast<unsigned long long>(n) > f->v_total - first)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the voxel result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    if (points) F_HIP(f, hipMemcpy(points, f->v_pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
+    if (counts) F_HIP(f, hipMemcpy(counts, f->v_cnt + a, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_voxel_table(acmmp_fusion* f, int64_t force_slots, int64_t* slots, int64_t* occupied,
+                                      int64_t* max_probe, int64_t* wrapped) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->v_force_slots = force_slots;                   // checked against the scene by the next voxelize
+    if (slots) *slots = f->v_stats[0];
+    if (occupied) *occupied = f->v_stats[1];
+    if (max_probe) *max_probe = f->v_stats[2];
+    if (wrapped) *wrapped = f->v_stats[3];
     return ACMMP_OK;
 }
 

@@ -3972,6 +3972,296 @@ hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ voxel-grid reduction of the scene cloud
+//
+// acmmp_fusion_voxelize (include/acmmp.h).  Everything a result depends on is an integer: the
+// cell index, the 16.16 fixed-point channels and their 64-bit sums, the count and the smallest scene index of
+// a cell.  Integer adds and minima commute, so the order in which the atomics land is invisible; the only
+// racy thing is which slot of the hash table a cell gets, and no output depends on it.
+
+constexpr unsigned long long kVoxEmpty = ~0ull;
+
+__device__ __forceinline__ bool vox_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// step 1: all nine finite, normal and colour within 2^20
+__device__ __forceinline__ bool vox_load(const float* __restrict__ p, float v[9]) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        v[k] = p[k];
+        ok = ok && !vox_nonfinite(v[k]);
+    }
+#pragma unroll
+    for (int k = 3; k < 9; ++k) ok = ok && fabsf(v[k]) <= 1048576.0f;
+    return ok;
+}
+
+// step 2: the cell of (x, y, z) and the position inside it, frac[a] = t - floorf(t) (exact); false = outside
+// the 2^21 cells per axis (a NaN index, from 0 * inf with a denormal size, is outside too)
+__device__ __forceinline__ bool vox_cell(const float v[9], const VoxGrid& g, unsigned long long& key, float frac[3]) {
+    const float o[3] = {g.ox, g.oy, g.oz};
+    key = 0;
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float t = (v[a] - o[a]) * g.inv;
+        const float c = floorf(t);
+        const bool in = c >= 0.0f && c < 2097152.0f;
+        ok = ok && in;
+        key |= (in ? static_cast<unsigned long long>(c) : 0ull) << (21 * a);
+        frac[a] = t - c;
+    }
+    return ok;
+}
+
+__device__ __forceinline__ unsigned long long vox_home(unsigned long long key, int log2_slots) {
+    unsigned long long z = key + 0x9e3779b97f4a7c15ull;       // splitmix64's finaliser
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z >> (64 - log2_slots);
+}
+
+// The slot of a key that is in the table (after the insert pass); at most `slots` steps.
+__device__ __forceinline__ bool vox_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        const unsigned long long k = t.keys[s];
+        if (k == key) { slot = s; return true; }
+        if (k == kVoxEmpty) return false;
+        s = (s + 1ull) & mask;
+    }
+    return false;
+}
+
+__device__ __forceinline__ uint32_t vox_ordered(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_min(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                   uint32_t* __restrict__ mn) {
+    __shared__ uint32_t blk[3];
+    if (threadIdx.x < 3) blk[threadIdx.x] = 0xffffffffu;
+    __syncthreads();
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    uint32_t m[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    if (i < n) {
+        float v[9];
+        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v)) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) m[a] = vox_ordered(v[a]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[a] = min(m[a], static_cast<uint32_t>(__shfl_xor(static_cast<int>(m[a]), d)));
+        if ((threadIdx.x & 63) == 0 && m[a] != 0xffffffffu) atomicMin(&blk[a], m[a]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && blk[threadIdx.x] != 0xffffffffu) atomicMin(&mn[threadIdx.x], blk[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_insert(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                      const VoxGrid g, const VoxTable t, unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
+    bool ok = false;
+    unsigned long long key = 0;
+    if (i < n) {
+        float v[9], frac[3];
+        ok = vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac);
+    }
+    const int rejected = __syncthreads_count(i < n && !ok);
+    if (threadIdx.x == 0 && rejected) atomicAdd(&st[kVoxRejected], static_cast<unsigned long long>(rejected));
+    if (!ok) return;
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    bool found = false;
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        // a slot's key changes once, from empty: a plain read that shows a key is final, one that shows
+        // empty (stale or not) is settled by the CAS
+        unsigned long long k = t.keys[s];
+        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
+        if (k == kVoxEmpty || k == key) { found = true; break; }
+        s = (s + 1ull) & mask;
+    }
+    if (!found) { atomicOr(&st[kVoxErr], 1ull); return; }
+    atomicAdd(&t.cnt[s], 1u);
+    atomicMin(&t.first[s], idx);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_stats(const VoxTable t, int min_points, unsigned long long* __restrict__ st) {
+    unsigned long long occ = 0, kept = 0, wrapped = 0, far = 0;
+    const unsigned long long mask = t.slots - 1ull;
+    for (unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x; s < t.slots;
+         s += static_cast<unsigned long long>(gridDim.x) * 256) {
+        const unsigned long long k = t.keys[s];
+        if (k == kVoxEmpty) continue;
+        const unsigned long long h = vox_home(k, t.log2_slots);
+        ++occ;
+        kept += t.cnt[s] >= static_cast<uint32_t>(min_points) ? 1ull : 0ull;
+        wrapped += s < h ? 1ull : 0ull;
+        far = max(far, ((s - h) & mask) + 1ull);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        occ += __shfl_xor(occ, d);
+        kept += __shfl_xor(kept, d);
+        wrapped += __shfl_xor(wrapped, d);
+        far = max(far, static_cast<unsigned long long>(__shfl_xor(far, d)));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (occ) atomicAdd(&st[kVoxOccupied], occ);
+        if (kept) atomicAdd(&st[kVoxKept], kept);
+        if (wrapped) atomicAdd(&st[kVoxWrapped], wrapped);
+        if (far) atomicMax(&st[kVoxMaxProbe], far);
+    }
+}
+
+// flags[i] = point i0 + i is the first point of a voxel that is kept; counts[chunk] as k_fuse_count
+__global__ __launch_bounds__(256) void k_voxel_mark(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                    const VoxGrid g, const VoxTable t, int min_points,
+                                                    int* __restrict__ flags, int* __restrict__ counts,
+                                                    unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
+    int f = 0;
+    if (i < n) {
+        float v[9], frac[3];
+        unsigned long long key, s;
+        if (vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac)) {
+            if (vox_find(t, key, s)) f = (t.first[s] == idx && t.cnt[s] >= static_cast<uint32_t>(min_points)) ? 1 : 0;
+            else atomicOr(&st[kVoxErr], 2ull);
+        }
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// the flagged points of each chunk in order: output id = *seg_base + offsets[chunk] + rank
+__global__ __launch_bounds__(256) void k_voxel_scatter(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                       const VoxGrid g, const VoxTable t, const int* __restrict__ flags,
+                                                       const int* __restrict__ offsets,
+                                                       const unsigned long long* __restrict__ seg_base, unsigned long long cap,
+                                                       unsigned long long* __restrict__ vslot,
+                                                       unsigned long long* __restrict__ st) {
+    __shared__ int wave_tot[4];
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const unsigned long long b = __ballot(f);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(b);
+    __syncthreads();
+    int base = offsets[blockIdx.x];
+    for (int w = 0; w < wave; ++w) base += wave_tot[w];
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(base + below);
+    if (f && pos < cap) {
+        float v[9], frac[3];
+        unsigned long long key, s;
+        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac) &&
+            vox_find(t, key, s)) {
+            t.oid[s] = pos;
+            vslot[pos] = s;
+        } else {
+            atomicOr(&st[kVoxErr], 4ull);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_voxel_accumulate(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                          const VoxGrid g, const VoxTable t,
+                                                          unsigned long long* __restrict__ sums,
+                                                          unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (i >= n) return;
+    float v[9], frac[3];
+    unsigned long long key, s;
+    if (!(vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac))) return;
+    if (!vox_find(t, key, s)) { atomicOr(&st[kVoxErr], 8ull); return; }
+    const unsigned long long o = t.oid[s];
+    if (o == kVoxEmpty) return;                      // fewer than min_points
+    unsigned long long* acc = sums + 9ull * o;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        // step 3: 16.16 fixed point, round half to even; the product by a power of two is exact
+        const float q = rintf((k < 3 ? frac[k] : v[k]) * 65536.0f);
+        atomicAdd(&acc[k], static_cast<unsigned long long>(static_cast<long long>(q)));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_voxel_finalise(unsigned long long nv, const unsigned long long* __restrict__ vslot,
+                                                        const VoxTable t, const unsigned long long* __restrict__ sums,
+                                                        const VoxGrid g, float* __restrict__ out,
+                                                        int32_t* __restrict__ out_cnt) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const unsigned long long s = vslot[v];
+    if (s >= t.slots) return;                        // an id the compaction did not fill (the host reports it)
+    const unsigned long long key = t.keys[s];
+    const uint32_t n = t.cnt[s];
+    const double div = static_cast<double>(n) * 65536.0;
+    const double o[3] = {static_cast<double>(g.ox), static_cast<double>(g.oy), static_cast<double>(g.oz)};
+    const unsigned long long* acc = sums + 9ull * v;
+    float* dst = out + 9ull * v;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double mean = static_cast<double>(static_cast<long long>(acc[k])) / div;
+        if (k < 3) {
+            const double cell = static_cast<double>((key >> (21 * k)) & 0x1fffffull);
+            dst[k] = static_cast<float>(o[k] + (cell + mean) * static_cast<double>(g.size));
+        } else {
+            dst[k] = static_cast<float>(mean);
+        }
+    }
+    out_cnt[v] = static_cast<int32_t>(n);
+}
+
+hipError_t launch_voxel_min(const float* pts, unsigned long long i0, int n, uint32_t* mn, hipStream_t s) {
+    k_voxel_min<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, mn);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_insert(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
+                               unsigned long long* st, hipStream_t s) {
+    k_voxel_insert<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st, hipStream_t s) {
+    const unsigned long long blocks = std::min<unsigned long long>((t.slots + 255ull) / 256ull, 4096ull);
+    k_voxel_stats<<<static_cast<unsigned>(blocks), 256, 0, s>>>(t, min_points, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
+                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
+                                unsigned long long* st, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_voxel_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, min_points, flags, counts, st);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_voxel_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, flags, offsets, seg_base, cap, vslot, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
+                                   unsigned long long* sums, unsigned long long* st, hipStream_t s) {
+    k_voxel_accumulate<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, sums, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long* vslot, VoxTable t,
+                                 const unsigned long long* sums, VoxGrid g, float* out, int32_t* out_cnt, hipStream_t s) {
+    if (nv == 0) return hipSuccess;
+    k_voxel_finalise<<<static_cast<unsigned>((nv + 255ull) / 256ull), 256, 0, s>>>(nv, vslot, t, sums, g, out, out_cnt);
+    return hipGetLastError();
+}
+
 // A plain copy of n 16-byte words on the compute queue (the state export / restart of a geom pass: at HBM
 // rate, where a device-to-device hipMemcpyAsync of the same 38 MB measured ~9 ms inside the pipeline's
 // overlapped passes)

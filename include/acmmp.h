@@ -374,6 +374,48 @@ acmmp_status acmmp_fusion_reset_used(acmmp_fusion *f);
 /* Test hook: view's used mask, H x W bytes (all 0 for a view that was never set). */
 acmmp_status acmmp_fusion_download_used(acmmp_fusion *f, int view, uint8_t *mask);
 
+/* ---- voxel-grid reduction of the scene result (no reference counterpart) -----------------------------
+ * acmmp_fusion_voxelize reduces the resident scene result, points 0 .. N in their order, to one point per
+ * occupied cell of a grid of `voxel_size` (finite, > 0): centroid, mean normal, mean colour and the number of
+ * points.  The scene result is left untouched; the voxel result stays in HBM beside it until the next
+ * successful voxelize replaces it or the next successful acmmp_fusion_run_scene discards it.
+ *
+ * The result is defined in integers, so that it is bit-reproducible and the same whatever order the device's
+ * atomics land in.  With inv = 1.0f / voxel_size and plain IEEE float32 arithmetic (no contraction):
+ *  1. a point is rejected when one of its nine floats is not finite or a normal / colour component exceeds
+ *     2^20 in magnitude;
+ *  2. per axis t = (x - o) * inv, g = floorf(t); the point is rejected too unless 0 <= g < 2^21 on every axis;
+ *     its cell is key = gx | gy << 21 | gz << 42;
+ *  3. per axis q = (int64) rintf((t - g) * 65536.0f), and q = (int64) rintf(v * 65536.0f) for each of the six
+ *     normal and colour components v (round half to even; both products are exact);
+ *  4. per cell: n = its points (at most 2^31 - 1), S = the nine int64 sums of q (wrapping), first = the
+ *     smallest scene index among its points;
+ *  5. a cell with n >= min_points (>= 1) gives, in float64 rounded once to float32,
+ *     position = (float)((double)o + ((double)g + (double)S / ((double)n * 65536.0)) * (double)voxel_size) and
+ *     normal, colour = (float)((double)S / ((double)n * 65536.0)) (normals are a plain mean, not renormalised);
+ *  6. the kept cells are listed in ascending order of `first`: their order of first appearance in the scene.
+ * origin = NULL takes for o the component-wise minimum of x, y, z over the points that pass step 1 (-0 orders
+ * below +0), or (0, 0, 0) when there is none.
+ *
+ * *n_voxels = kept cells, *n_occupied = cells before the min_points cut, *n_rejected = rejected points,
+ * origin_used[3] = o; any of the four may be NULL.  An empty scene gives 0 voxels.  ACMMP_ERR_INVALID_ARGUMENT:
+ * a size that is not finite and > 0, min_points < 1, a non-finite origin, no scene result.  Any error -- an
+ * out-of-memory part-way included -- leaves the previous voxel result and the scene result as they were.
+ * Device memory while it runs: a hash table of 28 bytes per slot, with the smallest power of two
+ * >= max(2 N, 1024) slots, and 72 bytes of sums per kept cell; the result holds 40 bytes per kept cell. */
+acmmp_status acmmp_fusion_voxelize(acmmp_fusion *f, float voxel_size, const float *origin, int min_points,
+                                   int64_t *n_voxels, int64_t *n_occupied, int64_t *n_rejected, float *origin_used);
+/* Voxels [first, first + n) of the voxel result to host arrays, either of which may be NULL: points n x 9
+ * floats (as the scene's), counts n int32.  Ranges as acmmp_fusion_scene_points. */
+acmmp_status acmmp_fusion_voxel_points(acmmp_fusion *f, int64_t first, int64_t n, float *points, int32_t *counts);
+/* Test hook.  force_slots = 0: automatic table size; otherwise the size of the next voxelize's table, a power of
+ * two >= 64 and > the scene's point count then (so it is never full), else that voxelize returns
+ * ACMMP_ERR_INVALID_ARGUMENT.  The outputs (any may be NULL) describe the last successful voxelize: slots,
+ * occupied slots, the longest probe distance + 1 (depends on the order of arrival: informational) and the
+ * number of cells stored at a slot index below their home slot (independent of it). */
+acmmp_status acmmp_fusion_voxel_table(acmmp_fusion *f, int64_t force_slots, int64_t *slots, int64_t *occupied,
+                                      int64_t *max_probe, int64_t *wrapped);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
