@@ -143,7 +143,7 @@ ACMMP_HD float det_atan2_special(float y, float x) {
 // atan2: branch-free main path for finite non-zero arguments; the rare special arguments are
 // re-evaluated by det_atan2_special in a branch that a wave only takes when one of its lanes needs it.
 // t = min(|x|,|y|) / max(|x|,|y|) computed by the caller (the kernels' projection divides with
-// div_proj, kernels.hip).
+// div_proj, camera_dev.h).
 ACMMP_HD float det_atan2_ratio(float y, float x, float t) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float z = t * t;

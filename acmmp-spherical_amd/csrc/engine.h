@@ -160,24 +160,15 @@ struct KParams {
 };
 
 // Per-half-sweep output buffers of the colour being updated.
-// One view of the fusion set (device pointers): depth (W x H), normals (3 floats per pixel, world
-// frame as normals.dmb holds them), colour as the reference's float RGBA texture (4 per pixel, /255).
-// used: one byte per pixel, 1 = the depth sample already contributed to a point of an earlier reference
-// view of a duplicate-free scene pass (acmmp_fusion_run_scene with ACMMP_FUSE_UNIQUE); other passes ignore it.
-struct FuseView {
-    const float* depth;
-    const float* normal;
-    const float* rgba;
-    int W, H;
-    uint8_t* used;
-};
-
 struct SweepOut {
     float4* plane;
     float* cost;
 };
 
-// Host-side launchers (kernels.hip).
+// Grid size of a launch: ceil(a / b).
+inline int cdiv(long long a, int b) { return static_cast<int>((a + b - 1) / b); }
+
+// Host-side launchers (kernels.hip; the fusion and voxel launchers are declared in fusion.h).
 hipError_t launch_ray_tables(const KParams& kp, float4* dirs, float2* sph_row, float2* sph_col, hipStream_t s);
 hipError_t launch_spatial_table(const KParams& kp, float* spatial, hipStream_t s);
 hipError_t launch_init(const KParams& kp, hipStream_t s);
@@ -202,79 +193,11 @@ acmmp_status band_buffers(acmmp_ctx* c, int colour, BandBuffers* out);
 // The context's device and engine stream (every kernel and copy of the context is queued there).
 acmmp_status engine_stream(acmmp_ctx* c, int* device, hipStream_t* stream);
 
-// SimpleFusionKernel (ACMMP.cu:1662-1814) for reference view `ref` + compaction in pixel order:
-// out_dense/flags are P-sized scratch, block_counts ceil(P/256) ints.
-hipError_t launch_fuse(int model, const DevCam* cams, const FuseView* views, int ref, int W, int H, const int* srcs,
-                       int n_src, float* out_dense, int* flags, int* block_counts, hipStream_t s);
-// block_counts: valid pixels per 256-pixel chunk (written by launch_fuse); block_offsets: their prefix.
-hipError_t launch_fuse_compact(int W, int H, const float* out_dense, const int* flags, const int* block_offsets,
-                               float* out, hipStream_t s);
-// One reference view of a whole-scene pass, all in stream order with no host step: SimpleFusionKernel with
-// the per-pixel consistent-source mask (unique: depths read through the views' used masks), the chunk
-// counts, their exclusive scan into block_offsets, *view_count = the view's points, *view_base = *running,
-// *running += *view_count, and (unique) the marking of every contributing sample.  src_mask is P-sized scratch.
-hipError_t launch_fuse_scene(int model, bool unique, const DevCam* cams, const FuseView* views, int ref, int W, int H,
-                             const int* srcs, int n_src, float* out_dense, int* flags, uint32_t* src_mask,
-                             int* block_counts, int* block_offsets, int* view_count, unsigned long long* running,
-                             unsigned long long* view_base, hipStream_t s);
-// Points and provenance of that view to the scene buffers at *view_base; nothing is written at or past `cap` points.
-hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const int* flags, const uint32_t* src_mask,
-                                     const int* block_offsets, const unsigned long long* view_base, int ref_pos,
-                                     unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
-                                     hipStream_t s);
-
-// Voxel-grid reduction of a scene cloud (acmmp_fusion_voxelize, include/acmmp.h).  Every launcher
-// covers points [i0, i0 + n) of `pts` (9 floats each, n <= 2^30: one segment), one lane per point.
-struct VoxGrid {
-    float ox, oy, oz;          // origin
-    float inv;                 // 1.0f / size, computed on the host
-    float size;
-};
-// The hash table: open addressing with linear probing over `slots` = 2^log2_slots cells.  keys (~0 = empty),
-// first (smallest scene index) and oid (output id of a kept voxel, ~0 = none) start as all-ones bytes, cnt as 0.
-struct VoxTable {
-    unsigned long long* keys;
-    unsigned long long* first;
-    unsigned long long* oid;
-    uint32_t* cnt;
-    unsigned long long slots;
-    int log2_slots;
-};
-// Device words of a voxel run (all zero before it).
-enum { kVoxErr = 0, kVoxRejected = 1, kVoxOccupied = 2, kVoxKept = 3, kVoxWrapped = 4, kVoxMaxProbe = 5, kVoxWords = 8 };
-// mn[3] (pre-set to all-ones) := min over the points that pass the finiteness / magnitude test of ordered(x), (y), (z),
-// ordered(f) being the order-preserving map of float bits to unsigned (vox_decode_ordered inverts it).
-hipError_t launch_voxel_min(const float* pts, unsigned long long i0, int n, uint32_t* mn, hipStream_t s);
-inline float vox_decode_ordered(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u;
-    float f;
-    __builtin_memcpy(&f, &b, 4);
-    return f;
-}
-// Insert pass: key, slot (CAS on keys), cnt += 1, first = min(first, index); st[kVoxRejected] += rejected points,
-// st[kVoxErr] |= 1 when a probe sequence walked the whole table.
-hipError_t launch_voxel_insert(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
-                               unsigned long long* st, hipStream_t s);
-// Over the slots: st[kVoxOccupied], st[kVoxKept] (cnt >= min_points), st[kVoxWrapped] (stored below the home slot),
-// st[kVoxMaxProbe] (largest distance from the home slot + 1).
-hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st, hipStream_t s);
-// Compaction of one segment, in stream order: flags[i] = point i0 + i is the first of a kept voxel, the chunk
-// counts, their scan (k_fuse_scan: *seg_base = *running, *running += the segment's count), then per flagged
-// point oid[slot] = *seg_base + rank and vslot[that id] = slot; nothing is written at or past `cap` ids.
-hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
-                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
-                                unsigned long long* st, hipStream_t s);
-// sums[9 * oid + k] += the point's quantised channel k (64-bit integer adds), for points of kept voxels.
-hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
-                                   unsigned long long* sums, unsigned long long* st, hipStream_t s);
-// out[9 * v ..] and out_cnt[v] of voxels [0, nv) from their sums, in float64 rounded once to float32.
-hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long* vslot, VoxTable t,
-                                 const unsigned long long* sums, VoxGrid g, float* out, int32_t* out_cnt, hipStream_t s);
-hipError_t launch_export_depth(const float4* planes, long long P, float* dst, hipStream_t s);
-hipError_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s);  // bytes % 4 == 0
 hipError_t launch_jbu(const float* ref, int W, int H, const float* coarse, int sw, int sh, int imagescale,
                       float* out, hipStream_t s);
+// Launchers of aux_kernels.hip (with planar.h's).
+hipError_t launch_export_depth(const float4* planes, long long P, float* dst, hipStream_t s);
+hipError_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s);  // bytes % 4 == 0
 // Diagnostic clock probe (acmmp_clock_probe): per workgroup, shader cycles and 100 MHz ticks around a
 // VALU-dense loop of `iters` steps on `rnd` (65536 floats); stamps may be null (warm-up launches).
 struct ClockStamp {

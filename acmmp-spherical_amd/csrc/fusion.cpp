@@ -19,55 +19,76 @@
 #include <vector>
 
 #include "acmmp.h"
-#include "engine.h"
+#include "devbuf.h"
+#include "fusion.h"
 
 using namespace acmmp;
+
+namespace {
+
+// The buffers of one view of the fusion set; FuseView holds their addresses for the device.
+struct ViewBuf {
+    DevBuf<float> depth, normal, rgba;
+    DevBuf<uint8_t> used;
+};
+
+// The four arrays of a scene result.
+struct SceneBuf {
+    DevBuf<float> pts;                           // 9 floats per point
+    DevBuf<int> ref;                             // position in the run's reference list
+    DevBuf<int> pix;                             // r * W + c
+    DevBuf<uint32_t> mask;                       // consistent sources
+    size_t cap = 0;                              // points allocated
+};
+
+// The arrays of the voxel hash table; VoxTable holds their addresses for the device.
+struct VoxTableBuf {
+    DevBuf<unsigned long long> keys, first, oid;
+    DevBuf<uint32_t> cnt;
+    unsigned long long slots = 0;
+};
+
+}  // namespace
 
 struct acmmp_fusion {
     int device = 0, model = 0, n = 0;
     hipStream_t stream = nullptr;
     std::vector<DevCam> cams;
-    std::vector<FuseView> views;                 // device pointers
-    DevCam* d_cams = nullptr;
-    FuseView* d_views = nullptr;
-    int* d_srcs = nullptr;
-    float* d_dense = nullptr;
-    int* d_flags = nullptr;
-    int* d_counts = nullptr;
-    int* d_offsets = nullptr;
-    float* d_out = nullptr;
+    std::vector<ViewBuf> view_bufs;
+    std::vector<FuseView> views;                 // view_bufs' addresses, as d_views holds them
+    DevBuf<DevCam> d_cams;
+    DevBuf<FuseView> d_views;
+    DevBuf<int> d_srcs;
+    DevBuf<float> d_dense;
+    DevBuf<int> d_flags, d_counts, d_offsets;
+    DevBuf<float> d_out;
     size_t cap_P = 0, cap_out = 0;
     // whole-scene pass: the resident result of the last acmmp_fusion_run_scene ...
-    float* s_pts = nullptr;                      // 9 floats per point
-    int* s_ref = nullptr;                        // position in the run's reference list
-    int* s_pix = nullptr;                        // r * W + c
-    uint32_t* s_mask = nullptr;                  // consistent sources
-    size_t s_cap = 0;                            // points allocated
+    SceneBuf scene;
     unsigned long long s_total = 0;              // points held
     // ... and its scratch
-    uint32_t* d_smask = nullptr;                 // per pixel, cap_smask pixels
+    DevBuf<uint32_t> d_smask;                    // per pixel, cap_smask pixels
     size_t cap_smask = 0;
-    int* d_scene_srcs = nullptr;                 // 32 per reference view
-    int* d_view_counts = nullptr;                // per reference view
-    unsigned long long* d_view_base = nullptr;   // per reference view: scene offset of its first point
+    DevBuf<int> d_scene_srcs;                    // 32 per reference view
+    DevBuf<int> d_view_counts;                   // per reference view
+    DevBuf<unsigned long long> d_view_base;      // per reference view: scene offset of its first point
     size_t cap_refs = 0;
-    unsigned long long* d_running = nullptr;     // running scene offset
-    int* h_count = nullptr;                      // pinned: the one word the host reads per view
+    DevBuf<unsigned long long> d_running;        // running scene offset
+    PinnedBuf<int> h_count;                      // the one word the host reads per view
     bool s_have = false;                         // a run_scene has succeeded
     // voxel-grid reduction of the scene result (acmmp_fusion_voxelize): its resident result ...
-    float* v_pts = nullptr;                      // 9 floats per voxel
-    int32_t* v_cnt = nullptr;                    // points per voxel
+    DevBuf<float> v_pts;                         // 9 floats per voxel
+    DevBuf<int32_t> v_cnt;                       // points per voxel
     unsigned long long v_total = 0;              // voxels held
     long long v_force_slots = 0;                 // test hook: table size of the next run, 0 = automatic
     long long v_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful run
     // ... and its scratch, kept between runs and dropped with the scene result it was sized for
-    VoxTable v_tab = {nullptr, nullptr, nullptr, nullptr, 0, 0};
-    int* v_flags = nullptr;                      // per point of a segment
-    int* v_counts = nullptr;                     // per 256-point chunk of a segment
-    int* v_offsets = nullptr;
+    VoxTableBuf v_tab;
+    DevBuf<int> v_flags;                         // per point of a segment
+    DevBuf<int> v_counts, v_offsets;             // per 256-point chunk of a segment
     size_t v_cap_seg = 0;
-    unsigned long long* v_words = nullptr;       // kVoxWords run words, then the segment base, then 3 minima (as 2 words)
-    int* v_seg_count = nullptr;
+    DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the segment base, then 3 minima (as 2 words)
+    DevBuf<int> v_seg_count;
     std::string err;
 };
 
@@ -86,19 +107,8 @@ acmmp_status ffail(acmmp_fusion* f, acmmp_status s, const std::string& m) {
                          std::string(#expr) + ": " + hipGetErrorString(e_));                     \
     } while (0)
 
-template <typename T>
-hipError_t fre(T*& p) {
-    hipError_t e = hipSuccess;
-    if (p) e = hipFree(const_cast<void*>(static_cast<const void*>(p)));
-    p = nullptr;
-    return e;
-}
-
-template <typename T>
-hipError_t alloc(T*& p, size_t count) {
-    (void)fre(p);
-    return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * (count ? count : 1));
-}
+template <typename T, bool PINNED>
+hipError_t alloc(DevBuf<T, PINNED>& b, size_t count) { return b.alloc(count); }
 
 }  // namespace
 
@@ -122,12 +132,13 @@ acmmp_status acmmp_fusion_create(int device, int n_views, const acmmp_camera* ca
     f->n = n_views;
     f->cams.resize(n_views);
     for (int i = 0; i < n_views; ++i) f->cams[i] = make_devcam(cams[i]);
+    f->view_bufs.resize(n_views);
     f->views.assign(n_views, FuseView{nullptr, nullptr, nullptr, 0, 0, nullptr});
     acmmp_status s = ACMMP_OK;
     if (hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess ||
         alloc(f->d_cams, n_views) != hipSuccess || alloc(f->d_views, n_views) != hipSuccess ||
         alloc(f->d_srcs, 32) != hipSuccess || alloc(f->d_running, 1) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&f->h_count), sizeof(int), hipHostMallocDefault) != hipSuccess ||
+        alloc(f->h_count, 1) != hipSuccess ||
         hipMemcpy(f->d_cams, f->cams.data(), sizeof(DevCam) * n_views, hipMemcpyHostToDevice) != hipSuccess)
         s = ACMMP_ERR_HIP;
     if (s != ACMMP_OK) { acmmp_fusion_destroy(f); return s; }
@@ -138,20 +149,11 @@ acmmp_status acmmp_fusion_create(int device, int n_views, const acmmp_camera* ca
 void acmmp_fusion_destroy(acmmp_fusion* f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    for (FuseView& v : f->views) { (void)fre(v.depth); (void)fre(v.normal); (void)fre(v.rgba); }
-    (void)fre(f->d_cams); (void)fre(f->d_views); (void)fre(f->d_srcs); (void)fre(f->d_dense);
-    (void)fre(f->d_flags); (void)fre(f->d_counts); (void)fre(f->d_offsets); (void)fre(f->d_out);
-    for (FuseView& v : f->views) (void)fre(v.used);
-    (void)fre(f->s_pts); (void)fre(f->s_ref); (void)fre(f->s_pix); (void)fre(f->s_mask);
-    (void)fre(f->d_smask); (void)fre(f->d_scene_srcs); (void)fre(f->d_view_counts); (void)fre(f->d_view_base);
-    (void)fre(f->d_running);
-    (void)fre(f->v_pts); (void)fre(f->v_cnt); (void)fre(f->v_tab.keys); (void)fre(f->v_tab.first); (void)fre(f->v_tab.oid);
-    (void)fre(f->v_tab.cnt); (void)fre(f->v_flags); (void)fre(f->v_counts); (void)fre(f->v_offsets); (void)fre(f->v_words);
-    (void)fre(f->v_seg_count);
-    if (f->h_count) (void)hipHostFree(f->h_count);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;
+    if (f->stream) {
+        (void)hipStreamSynchronize(f->stream);
+        (void)hipStreamDestroy(f->stream);
+    }
+    delete f;                                      // the buffers free themselves, on this device
 }
 
 const char* acmmp_fusion_last_error(const acmmp_fusion* f) { return f ? f->err.c_str() : ""; }
@@ -172,22 +174,23 @@ acmmp_status acmmp_fusion_set_view(acmmp_fusion* f, int view, const float* depth
         rgba[4 * i + 2] = static_cast<float>(bgr[3 * i + 0]) * s;
         rgba[4 * i + 3] = 255.0f * s;
     }
-    FuseView& v = f->views[view];
-    float* d = nullptr;
-    float* nrm = nullptr;
-    float* col = nullptr;
-    uint8_t* usd = nullptr;
-    (void)fre(v.depth); (void)fre(v.normal); (void)fre(v.rgba); (void)fre(v.used);
+    // the new buffers are built beside the view's present ones and installed only when every step succeeded;
+    // on a failure they free themselves and the view, host and device copy, is as it was
+    DevBuf<float> d, nrm, col;
+    DevBuf<uint8_t> usd;
     F_HIP(f, alloc(d, P));
     F_HIP(f, alloc(nrm, 3 * P));
     F_HIP(f, alloc(col, 4 * P));
     F_HIP(f, alloc(usd, P));
-    v = FuseView{d, nrm, col, W, H, usd};
+    const FuseView v{d, nrm, col, W, H, usd};
     F_HIP(f, hipMemset(usd, 0, P));                 // a newly set view has no used sample
     F_HIP(f, hipMemcpy(d, depth, sizeof(float) * P, hipMemcpyHostToDevice));
     F_HIP(f, hipMemcpy(nrm, normals, sizeof(float) * 3 * P, hipMemcpyHostToDevice));
     F_HIP(f, hipMemcpy(col, rgba.data(), sizeof(float) * 4 * P, hipMemcpyHostToDevice));
     F_HIP(f, hipMemcpy(f->d_views + view, &v, sizeof(FuseView), hipMemcpyHostToDevice));
+    f->views[view] = v;
+    ViewBuf& b = f->view_bufs[view];
+    b.depth = std::move(d); b.normal = std::move(nrm); b.rgba = std::move(col); b.used = std::move(usd);
     return ACMMP_OK;
 }
 
@@ -241,21 +244,10 @@ acmmp_status acmmp_fusion_run(acmmp_fusion* f, int ref, int n_src, const int* sr
 namespace {
 
 void voxel_scratch_release(acmmp_fusion* f) {
-    (void)fre(f->v_tab.keys); (void)fre(f->v_tab.first); (void)fre(f->v_tab.oid); (void)fre(f->v_tab.cnt);
-    f->v_tab.slots = 0;
-    (void)fre(f->v_flags); (void)fre(f->v_counts); (void)fre(f->v_offsets);
+    f->v_tab = VoxTableBuf();
+    f->v_flags.reset(); f->v_counts.reset(); f->v_offsets.reset();
     f->v_cap_seg = 0;
 }
-
-// The four arrays of a scene result.
-struct SceneBuf {
-    float* pts = nullptr;
-    int* ref = nullptr;
-    int* pix = nullptr;
-    uint32_t* mask = nullptr;
-    size_t cap = 0;
-    void release() { (void)fre(pts); (void)fre(ref); (void)fre(pix); (void)fre(mask); cap = 0; }
-};
 
 // b := arrays of at least `need` points (geometric growth) holding b's first `live` points.  b is unchanged
 // when an allocation fails.
@@ -265,7 +257,6 @@ acmmp_status scene_grow(acmmp_fusion* f, SceneBuf& b, size_t need, size_t live, 
     if (alloc(nb.pts, 9 * nb.cap) != hipSuccess || alloc(nb.ref, nb.cap) != hipSuccess ||
         alloc(nb.pix, nb.cap) != hipSuccess || alloc(nb.mask, nb.cap) != hipSuccess) {
         (void)hipGetLastError();
-        nb.release();
         return ffail(f, ACMMP_ERR_OUT_OF_MEMORY, "scene buffer of " + std::to_string(need) + " points");
     }
     hipError_t e = hipSuccess;
@@ -276,12 +267,8 @@ acmmp_status scene_grow(acmmp_fusion* f, SceneBuf& b, size_t need, size_t live, 
         if (e == hipSuccess) e = hipMemcpyAsync(nb.mask, b.mask, sizeof(uint32_t) * live, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    if (e != hipSuccess) {
-        nb.release();
-        return ffail(f, ACMMP_ERR_HIP, std::string("scene buffer copy: ") + hipGetErrorString(e));
-    }
-    b.release();
-    b = nb;
+    if (e != hipSuccess) return ffail(f, ACMMP_ERR_HIP, std::string("scene buffer copy: ") + hipGetErrorString(e));
+    b = std::move(nb);
     return ACMMP_OK;
 }
 
@@ -368,8 +355,7 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
     if (n_refs > 0)
         F_HIP(f, hipMemcpyAsync(f->d_scene_srcs, srcs.data(), sizeof(int) * srcs.size(), hipMemcpyHostToDevice, s));
     // unique: the used masks as they are now, to put back if the run fails part-way
-    std::vector<uint8_t*> saved(unique ? f->n : 0, nullptr);
-    auto drop_saved = [&]() { for (uint8_t*& p : saved) (void)fre(p); };
+    std::vector<DevBuf<uint8_t>> saved(unique ? f->n : 0);
     for (size_t v = 0; v < saved.size(); ++v) {
         if (!f->views[v].used) continue;
         const size_t P = static_cast<size_t>(f->views[v].W) * f->views[v].H;
@@ -378,7 +364,6 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
         if (e != hipSuccess) {
             (void)hipGetLastError();
             (void)hipStreamSynchronize(s);
-            drop_saved();
             return ffail(f, e == hipErrorOutOfMemory ? ACMMP_ERR_OUT_OF_MEMORY : ACMMP_ERR_HIP,
                          std::string("used-mask snapshot: ") + hipGetErrorString(e));
         }
@@ -396,19 +381,14 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
                 (void)hipMemcpyAsync(f->views[v].used, saved[v], static_cast<size_t>(f->views[v].W) * f->views[v].H,
                                      hipMemcpyDeviceToDevice, s);
         (void)hipStreamSynchronize(s);
-        drop_saved();
-        out.release();
         f->err = why;
         return st;
     }
-    drop_saved();
-    (void)fre(f->s_pts); (void)fre(f->s_ref); (void)fre(f->s_pix); (void)fre(f->s_mask);
-    f->s_pts = out.pts; f->s_ref = out.ref; f->s_pix = out.pix; f->s_mask = out.mask;
-    f->s_cap = out.cap;
+    f->scene = std::move(out);
     f->s_total = total;
     f->s_have = true;
     // the voxel result described the previous scene: it goes, with the scratch sized for that scene
-    (void)fre(f->v_pts); (void)fre(f->v_cnt);
+    f->v_pts.reset(); f->v_cnt.reset();
     f->v_total = 0;
     voxel_scratch_release(f);
     if (counts) std::copy(view_counts.begin(), view_counts.end(), counts);
@@ -424,10 +404,10 @@ acmmp_status acmmp_fusion_scene_points(acmmp_fusion* f, int64_t first, int64_t n
     if (n == 0) return ACMMP_OK;
     F_HIP(f, hipSetDevice(f->device));
     const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    if (points) F_HIP(f, hipMemcpy(points, f->s_pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
-    if (ref_index) F_HIP(f, hipMemcpy(ref_index, f->s_ref + a, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (pixel) F_HIP(f, hipMemcpy(pixel, f->s_pix + a, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (src_mask) F_HIP(f, hipMemcpy(src_mask, f->s_mask + a, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    if (points) F_HIP(f, hipMemcpy(points, f->scene.pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
+    if (ref_index) F_HIP(f, hipMemcpy(ref_index, f->scene.ref + a, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (pixel) F_HIP(f, hipMemcpy(pixel, f->scene.pix + a, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (src_mask) F_HIP(f, hipMemcpy(src_mask, f->scene.mask + a, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
     return ACMMP_OK;
 }
 
@@ -474,11 +454,10 @@ bool finite32(float x) {
 
 // The new result of a voxel run, swapped in only when the whole run succeeded.
 struct VoxelOut {
-    float* pts = nullptr;
-    int32_t* cnt = nullptr;
-    unsigned long long* sums = nullptr;      // scratch: 9 int64 per kept voxel
-    unsigned long long* vslot = nullptr;     // scratch: table slot per kept voxel
-    void release() { (void)fre(pts); (void)fre(cnt); (void)fre(sums); (void)fre(vslot); }
+    DevBuf<float> pts;
+    DevBuf<int32_t> cnt;
+    DevBuf<unsigned long long> sums;         // scratch: 9 int64 per kept voxel
+    DevBuf<unsigned long long> vslot;        // scratch: table slot per kept voxel
 };
 
 acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_points, unsigned long long slots,
@@ -497,7 +476,6 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
         F_HIP(f, alloc(f->v_tab.cnt, slots));
         f->v_tab.slots = slots;
     }
-    f->v_tab.log2_slots = log2_slots;
     if (f->v_cap_seg < seg_pts) {
         f->v_cap_seg = 0;
         F_HIP(f, alloc(f->v_flags, seg_pts));
@@ -505,7 +483,7 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
         F_HIP(f, alloc(f->v_offsets, seg_chunks));
         f->v_cap_seg = seg_pts;
     }
-    const VoxTable t = f->v_tab;
+    const VoxTable t = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, slots, log2_slots};
     unsigned long long* st = f->v_words;
     unsigned long long* seg_base = f->v_words + kVoxWords;
     uint32_t* mn = reinterpret_cast<uint32_t*>(f->v_words + kVoxWords + 1);
@@ -520,7 +498,7 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
     if (find_origin) {
         uint32_t h_mn[3];
         F_HIP(f, hipMemsetAsync(mn, 0xff, sizeof(uint32_t) * 4, s));
-        F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_min(f->s_pts, i0, n, mn, s); }));
+        F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_min(f->scene.pts, i0, n, mn, s); }));
         F_HIP(f, hipMemcpyAsync(h_mn, mn, sizeof(h_mn), hipMemcpyDeviceToHost, s));
         F_HIP(f, hipStreamSynchronize(s));
         // no point passed the finiteness test: the origin is (0, 0, 0), and every point is rejected below
@@ -534,7 +512,7 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
     F_HIP(f, hipMemsetAsync(t.first, 0xff, sizeof(unsigned long long) * slots, s));
     F_HIP(f, hipMemsetAsync(t.oid, 0xff, sizeof(unsigned long long) * slots, s));
     F_HIP(f, hipMemsetAsync(t.cnt, 0, sizeof(uint32_t) * slots, s));
-    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_insert(f->s_pts, i0, n, g, t, st, s); }));
+    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_insert(f->scene.pts, i0, n, g, t, st, s); }));
     F_HIP(f, launch_voxel_stats(t, min_points, st, s));
     F_HIP(f, hipMemcpyAsync(words, st, sizeof(unsigned long long) * kVoxWords, hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
@@ -550,10 +528,10 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
     F_HIP(f, hipMemsetAsync(out.sums, 0, sizeof(unsigned long long) * 9 * kept, s));
     F_HIP(f, hipMemsetAsync(out.vslot, 0xff, sizeof(unsigned long long) * kept, s));
     F_HIP(f, segments([&](unsigned long long i0, int n) {
-        return launch_voxel_compact(f->s_pts, i0, n, g, t, min_points, f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count,
+        return launch_voxel_compact(f->scene.pts, i0, n, g, t, min_points, f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count,
                                     f->d_running, seg_base, kept, out.vslot, st, s);
     }));
-    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->s_pts, i0, n, g, t, out.sums, st, s); }));
+    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->scene.pts, i0, n, g, t, out.sums, st, s); }));
     F_HIP(f, launch_voxel_finalise(kept, out.vslot, t, out.sums, g, out.pts, out.cnt, s));
     unsigned long long end[2] = {0, 0};                                  // error word, voxels compacted
     F_HIP(f, hipMemcpyAsync(&end[0], st + kVoxErr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -605,14 +583,13 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
             const std::string why = f->err;
             (void)hipGetLastError();
             (void)hipStreamSynchronize(f->stream);
-            out.release();
             f->err = why;
             return st;
         }
     }
-    (void)fre(out.sums); (void)fre(out.vslot);
-    (void)fre(f->v_pts); (void)fre(f->v_cnt);
-    f->v_pts = out.pts; f->v_cnt = out.cnt;
+    out.sums.reset(); out.vslot.reset();
+    f->v_pts = std::move(out.pts);
+    f->v_cnt = std::move(out.cnt);
     f->v_total = words[kVoxKept];
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);

@@ -1,0 +1,596 @@
+// fusion_kernels.hip -- gfx950 kernels of the depth-map fusion (SimpleFusionKernel, ACMMP.cu:1662-1814, its
+// whole-scene pass and their in-order compaction) and of the voxel-grid reduction of the fused scene cloud
+// (DESIGN.md §8), with their host launchers (fusion.h).  One translation unit, compiled once.
+#include <algorithm>
+
+#include "camera_dev.h"
+#include "detmath.h"
+#include "fusion.h"
+
+namespace acmmp {
+
+// ------------------------------------------------------------------ kernel: fusion
+
+// tex2D<float4>(linear filter, unnormalised (c, r)) at an integer texel index WITHOUT the +0.5
+// (ACMMP.cu:1690, 1768): the footprint is texels (c-1, c) x (r-1, r), both weights 0.5, clamped
+// (wrap is undefined for unnormalised coordinates and acts as clamp).  fp32 fused lerps.
+__device__ __forceinline__ float4 fuse_colour(const float* rgba, int W, int H, int c, int r) {
+    const int x0 = c - 1 < 0 ? 0 : c - 1, x1 = c > W - 1 ? W - 1 : c;
+    const int y0 = r - 1 < 0 ? 0 : r - 1, y1 = r > H - 1 ? H - 1 : r;
+    const float4 t00 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y0) * W + x0];
+    const float4 t10 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y0) * W + x1];
+    const float4 t01 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y1) * W + x0];
+    const float4 t11 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y1) * W + x1];
+    auto lerp = [](float a, float b) { return fmaf(0.5f, b - a, a); };
+    const float4 top = make_float4(lerp(t00.x, t10.x), lerp(t00.y, t10.y), lerp(t00.z, t10.z), lerp(t00.w, t10.w));
+    const float4 bot = make_float4(lerp(t01.x, t11.x), lerp(t01.y, t11.y), lerp(t01.z, t11.z), lerp(t01.w, t11.w));
+    return make_float4(lerp(top.x, bot.x), lerp(top.y, bot.y), lerp(top.z, bot.z), lerp(top.w, bot.w));
+}
+
+// SimpleFusionKernel, ACMMP.cu:1662-1814: per reference pixel, the source views whose depth
+// reprojects within 1 px, 1% depth and 0.149 rad of normal; >= 3 consistent (the reference
+// included) -> averaged point, normal and colour.  out: 9 floats per pixel (x y z nx ny nz c0 c1 c2,
+// c0 = 255 * texture .z as the reference stores it).
+//
+// Two compile-time variants serve the whole-scene pass (acmmp_fusion_run_scene): PROV also writes, per
+// pixel, the mask of consistent sources (bit j = srcs[j]); UNIQUE reads every depth through the views'
+// `used` byte masks -- a used pixel reads as depth 0, so a used reference pixel is skipped and a used
+// source sample is skipped, with the arithmetic, the thresholds and the order of the sums untouched.
+// k_fuse<MODEL> is the reference-equal kernel of acmmp_fusion_run (neither variant), k_fuse_scene the
+// kernel of the scene pass.
+template <int MODEL, bool PROV, bool UNIQUE>
+__device__ __forceinline__ void fuse_pixel(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref,
+                                           int W, int H, const int* __restrict__ srcs, int n_src, float* __restrict__ out,
+                                           int* __restrict__ flags, uint32_t* __restrict__ src_mask) {
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
+    const bool inside = c < W && r < H;
+    int valid = 0;
+    const long long idx = static_cast<long long>(r) * W + c;
+    if (inside) {
+        const DevCam& rc = cams[ref];
+        const FuseView rv = views[ref];
+        float ref_depth = rv.depth[idx];
+        if constexpr (UNIQUE) { if (rv.used[idx]) ref_depth = 0.0f; }
+        uint32_t consistent = 0;
+        if (!(ref_depth <= 0.0f)) {
+            const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), ref_depth);
+            const float rn0 = rv.normal[3 * idx], rn1 = rv.normal[3 * idx + 1], rn2 = rv.normal[3 * idx + 2];
+            const float4 rcol = fuse_colour(rv.rgba, W, H, c, r);
+            float ps0 = X.x, ps1 = X.y, ps2 = X.z;
+            float ns0 = rn0, ns1 = rn1, ns2 = rn2;
+            float cs0 = rcol.z * 255.0f, cs1 = rcol.y * 255.0f, cs2 = rcol.x * 255.0f;
+            int n = 1;
+            for (int j = 0; j < n_src; ++j) {
+                const int si = srcs[j];
+                if (si < 0) continue;
+                const DevCam& sc = cams[si];
+                const FuseView sv = views[si];
+                float px, py, pd;
+                project<MODEL, const DevCam, true>(sc, X, px, py, pd);
+                const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
+                if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;
+                const long long sidx = static_cast<long long>(src_r) * sv.W + src_c;
+                float sd = sv.depth[sidx];
+                if constexpr (UNIQUE) { if (sv.used[sidx]) sd = 0.0f; }
+                if (sd <= 0.0f) continue;
+                const float3 Xs = world_point<MODEL>(sc, static_cast<float>(src_c), static_cast<float>(src_r), sd);
+                float qx, qy, qd;
+                project<MODEL, const DevCam, true>(rc, Xs, qx, qy, qd);
+                const float err = det_hypot(static_cast<float>(c) - qx, static_cast<float>(r) - qy);
+                const float rel = fabsf(pd - sd) / sd;
+                const float sn0 = sv.normal[3 * sidx], sn1 = sv.normal[3 * sidx + 1], sn2 = sv.normal[3 * sidx + 2];
+                float dp = dot3(rn0, rn1, rn2, sn0, sn1, sn2);
+                dp = fmaxf(-1.0f, fminf(1.0f, dp));
+                const float ang = det_acos(dp);
+                if (err < 1.0f && rel < 0.01f && ang < 0.149f) {
+                    ps0 += Xs.x; ps1 += Xs.y; ps2 += Xs.z;
+                    ns0 += sn0; ns1 += sn1; ns2 += sn2;
+                    const float4 scol = fuse_colour(sv.rgba, sv.W, sv.H, src_c, src_r);
+                    cs0 = fmaf(scol.z, 255.0f, cs0);
+                    cs1 = fmaf(scol.y, 255.0f, cs1);
+                    cs2 = fmaf(scol.x, 255.0f, cs2);
+                    ++n;
+                    if constexpr (PROV) consistent |= 1u << j;
+                }
+            }
+            if (n >= 3) {
+                const float fn = static_cast<float>(n);
+                float* o = out + 9 * idx;
+                o[0] = ps0 / fn; o[1] = ps1 / fn; o[2] = ps2 / fn;
+                float a0 = ns0 / fn, a1 = ns1 / fn, a2 = ns2 / fn;
+                const float len = det_hypot(det_hypot(a0, a1), a2);
+                if (len > 0.0f) { a0 /= len; a1 /= len; a2 /= len; }
+                o[3] = a0; o[4] = a1; o[5] = a2;
+                o[6] = cs0 / fn; o[7] = cs1 / fn; o[8] = cs2 / fn;
+                valid = 1;
+            }
+        }
+        flags[idx] = valid;
+        if constexpr (PROV) src_mask[idx] = valid ? consistent : 0u;
+    }
+}
+
+template <int MODEL>
+__global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                       const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags) {
+    fuse_pixel<MODEL, false, false>(cams, views, ref, W, H, srcs, n_src, out, flags, nullptr);
+}
+
+template <int MODEL, bool UNIQUE>
+__global__ void k_fuse_scene(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                             const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags,
+                             uint32_t* __restrict__ src_mask) {
+    fuse_pixel<MODEL, true, UNIQUE>(cams, views, ref, W, H, srcs, n_src, out, flags, src_mask);
+}
+
+// After a unique-mode k_fuse_scene of view `ref`, before the next view's: every sample that contributed
+// to an emitted point is marked used -- the reference pixel, and for each consistent source j the pixel
+// (src_c, src_r) k_fuse sampled, recomputed by the same device functions from the same depth (an emitted
+// pixel was not used when k_fuse read it, so the raw depth is what it saw).  Plain byte stores of 1: lanes
+// that hit the same byte store the same value.
+template <int MODEL>
+__global__ void k_fuse_mark(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
+                            const int* __restrict__ srcs, int n_src, const int* __restrict__ flags,
+                            const uint32_t* __restrict__ src_mask) {
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (c >= W || r >= H) return;
+    const long long idx = static_cast<long long>(r) * W + c;
+    if (!flags[idx]) return;
+    const DevCam& rc = cams[ref];
+    const FuseView rv = views[ref];
+    const uint32_t m = src_mask[idx];
+    const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), rv.depth[idx]);
+    rv.used[idx] = 1;
+    for (int j = 0; j < n_src; ++j) {
+        if (!((m >> j) & 1u)) continue;
+        const int si = srcs[j];
+        const DevCam& sc = cams[si];
+        const FuseView sv = views[si];
+        float px, py, pd;
+        project<MODEL, const DevCam, true>(sc, X, px, py, pd);
+        const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
+        if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;   // (never: the bit says it was inside)
+        sv.used[static_cast<long long>(src_r) * sv.W + src_c] = 1;
+    }
+}
+
+// counts of valid pixels per 256-pixel chunk of the row-major image
+__global__ void k_fuse_count(const int* __restrict__ flags, long long P, int* __restrict__ counts) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    const int f = i < P ? flags[i] : 0;
+    const int n = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = n;
+}
+
+// Output position of a lane within its 256-lane chunk (one workgroup): offsets[chunk] + the flagged lanes
+// before it.  Within a wave the rank is the popcount of the ballot below the lane; the four wave totals meet
+// in LDS.  Every lane of the workgroup calls it.
+__device__ __forceinline__ int chunk_rank(int f, const int* __restrict__ offsets) {
+    __shared__ int wave_tot[4];
+    const unsigned long long b = __ballot(f);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = __popcll(b & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(b);
+    __syncthreads();
+    int base = offsets[blockIdx.x];
+    for (int w = 0; w < wave; ++w) base += wave_tot[w];
+    return base + below;
+}
+
+// scatter the valid pixels of each chunk to offsets[chunk] + rank within the chunk (pixel order)
+__global__ void k_fuse_scatter(const float* __restrict__ dense, const int* __restrict__ flags, long long P,
+                               const int* __restrict__ offsets, float* __restrict__ out) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    const int f = i < P ? flags[i] : 0;
+    const int pos = chunk_rank(f, offsets);
+    if (f) {
+        float* o = out + 9ll * pos;
+        const float* d = dense + 9 * i;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = d[k];
+    }
+}
+
+// Exclusive scan of the chunk counts of one view (each 0..256) and the scene bookkeeping, one workgroup
+// of 1024 lanes walking the chunks in tiles of 1024 with a running carry.  Within a wave the prefix is
+// built bit plane by bit plane from ballots: popcount(ballot(bit b of count) below my lane) << b, summed
+// over the 9 planes; the 16 wave totals meet in LDS.  Lane 0 then publishes the view's point count, takes
+// the 64-bit running scene offset as this view's base and advances it.
+__global__ __launch_bounds__(1024) void k_fuse_scan(const int* __restrict__ counts, int n_chunks, int* __restrict__ offsets,
+                                                    int* __restrict__ view_count, unsigned long long* __restrict__ running,
+                                                    unsigned long long* __restrict__ view_base) {
+    __shared__ int wave_tot[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int carry = 0;
+    for (int t0 = 0; t0 < n_chunks; t0 += 1024) {
+        const int i = t0 + static_cast<int>(threadIdx.x);
+        const int v = i < n_chunks ? counts[i] : 0;
+        int excl = 0, tot = 0;
+#pragma unroll
+        for (int b = 0; b < 9; ++b) {
+            const unsigned long long m = __ballot((v >> b) & 1);
+            excl += __popcll(m & below) << b;
+            tot += __popcll(m) << b;
+        }
+        if (lane == 0) wave_tot[wave] = tot;
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int x = wave_tot[w];
+            all += x;
+            if (w < wave) before += x;
+        }
+        if (i < n_chunks) offsets[i] = carry + before + excl;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        *view_count = carry;
+        const unsigned long long t = *running;
+        *view_base = t;
+        *running = t + static_cast<unsigned long long>(carry);
+    }
+}
+
+// k_fuse_scatter into the scene buffers at *view_base + offsets[chunk] + rank: the point and its provenance
+// (position of the view in the run's reference list, pixel r*W + c, consistent-source mask).  Nothing is
+// written at or beyond `cap` points.
+__global__ void k_fuse_scatter_scene(const float* __restrict__ dense, const int* __restrict__ flags,
+                                     const uint32_t* __restrict__ src_mask, long long P, const int* __restrict__ offsets,
+                                     const unsigned long long* __restrict__ view_base, int ref_pos, unsigned long long cap,
+                                     float* __restrict__ out, int* __restrict__ out_ref, int* __restrict__ out_pix,
+                                     uint32_t* __restrict__ out_mask) {
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    const int f = i < P ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *view_base + static_cast<unsigned long long>(rank);
+    if (f && pos < cap) {
+        float* o = out + 9ull * pos;
+        const float* d = dense + 9 * i;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[k] = d[k];
+        out_ref[pos] = ref_pos;
+        out_pix[pos] = static_cast<int>(i);
+        out_mask[pos] = src_mask[i];
+    }
+}
+
+hipError_t launch_fuse(int model, const DevCam* cams, const FuseView* views, int ref, int W, int H, const int* srcs,
+                       int n_src, float* out_dense, int* flags, int* block_counts, hipStream_t s) {
+    dim3 grd(cdiv(W, 16), cdiv(H, 16));
+    if (model == kSphere) k_fuse<kSphere><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags);
+    else k_fuse<kPinhole><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags);
+    const long long P = static_cast<long long>(W) * H;
+    k_fuse_count<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(flags, P, block_counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_compact(int W, int H, const float* out_dense, const int* flags, const int* block_offsets,
+                               float* out, hipStream_t s) {
+    const long long P = static_cast<long long>(W) * H;
+    k_fuse_scatter<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, P, block_offsets, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_scene(int model, bool unique, const DevCam* cams, const FuseView* views, int ref, int W, int H,
+                             const int* srcs, int n_src, float* out_dense, int* flags, uint32_t* src_mask,
+                             int* block_counts, int* block_offsets, int* view_count, unsigned long long* running,
+                             unsigned long long* view_base, hipStream_t s) {
+    dim3 grd(cdiv(W, 16), cdiv(H, 16));
+    if (model == kSphere) {
+        if (unique) k_fuse_scene<kSphere, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+        else k_fuse_scene<kSphere, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+    } else {
+        if (unique) k_fuse_scene<kPinhole, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+        else k_fuse_scene<kPinhole, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
+    }
+    const long long P = static_cast<long long>(W) * H;
+    const int n_chunks = static_cast<int>((P + 255) / 256);
+    k_fuse_count<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(flags, P, block_counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(block_counts, n_chunks, block_offsets, view_count, running, view_base);
+    if (unique) {
+        if (model == kSphere) k_fuse_mark<kSphere><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
+        else k_fuse_mark<kPinhole><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const int* flags, const uint32_t* src_mask,
+                                     const int* block_offsets, const unsigned long long* view_base, int ref_pos,
+                                     unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
+                                     hipStream_t s) {
+    const long long P = static_cast<long long>(W) * H;
+    k_fuse_scatter_scene<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, src_mask, P, block_offsets,
+                                                                               view_base, ref_pos, cap, out, out_ref,
+                                                                               out_pix, out_mask);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ voxel-grid reduction of the scene cloud
+//
+// acmmp_fusion_voxelize (include/acmmp.h).  Everything a result depends on is an integer: the
+// cell index, the 16.16 fixed-point channels and their 64-bit sums, the count and the smallest scene index of
+// a cell.  Integer adds and minima commute, so the order in which the atomics land is invisible; the only
+// racy thing is which slot of the hash table a cell gets, and no output depends on it.
+
+constexpr unsigned long long kVoxEmpty = ~0ull;
+
+__device__ __forceinline__ bool vox_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// step 1: all nine finite, normal and colour within 2^20
+__device__ __forceinline__ bool vox_load(const float* __restrict__ p, float v[9]) {
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        v[k] = p[k];
+        ok = ok && !vox_nonfinite(v[k]);
+    }
+#pragma unroll
+    for (int k = 3; k < 9; ++k) ok = ok && fabsf(v[k]) <= 1048576.0f;
+    return ok;
+}
+
+// step 2: the cell of (x, y, z) and the position inside it, frac[a] = t - floorf(t) (exact); false = outside
+// the 2^21 cells per axis (a NaN index, from 0 * inf with a denormal size, is outside too)
+__device__ __forceinline__ bool vox_cell(const float v[9], const VoxGrid& g, unsigned long long& key, float frac[3]) {
+    const float o[3] = {g.ox, g.oy, g.oz};
+    key = 0;
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float t = (v[a] - o[a]) * g.inv;
+        const float c = floorf(t);
+        const bool in = c >= 0.0f && c < 2097152.0f;
+        ok = ok && in;
+        key |= (in ? static_cast<unsigned long long>(c) : 0ull) << (21 * a);
+        frac[a] = t - c;
+    }
+    return ok;
+}
+
+__device__ __forceinline__ unsigned long long vox_home(unsigned long long key, int log2_slots) {
+    unsigned long long z = key + 0x9e3779b97f4a7c15ull;       // splitmix64's finaliser
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z >> (64 - log2_slots);
+}
+
+// The slot of a key that is in the table (after the insert pass); at most `slots` steps.
+__device__ __forceinline__ bool vox_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        const unsigned long long k = t.keys[s];
+        if (k == key) { slot = s; return true; }
+        if (k == kVoxEmpty) return false;
+        s = (s + 1ull) & mask;
+    }
+    return false;
+}
+
+__device__ __forceinline__ uint32_t vox_ordered(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_min(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                   uint32_t* __restrict__ mn) {
+    __shared__ uint32_t blk[3];
+    if (threadIdx.x < 3) blk[threadIdx.x] = 0xffffffffu;
+    __syncthreads();
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    uint32_t m[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    if (i < n) {
+        float v[9];
+        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v)) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) m[a] = vox_ordered(v[a]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[a] = min(m[a], static_cast<uint32_t>(__shfl_xor(static_cast<int>(m[a]), d)));
+        if ((threadIdx.x & 63) == 0 && m[a] != 0xffffffffu) atomicMin(&blk[a], m[a]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && blk[threadIdx.x] != 0xffffffffu) atomicMin(&mn[threadIdx.x], blk[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_insert(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                      const VoxGrid g, const VoxTable t, unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
+    bool ok = false;
+    unsigned long long key = 0;
+    if (i < n) {
+        float v[9], frac[3];
+        ok = vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac);
+    }
+    const int rejected = __syncthreads_count(i < n && !ok);
+    if (threadIdx.x == 0 && rejected) atomicAdd(&st[kVoxRejected], static_cast<unsigned long long>(rejected));
+    if (!ok) return;
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    bool found = false;
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        // a slot's key changes once, from empty: a plain read that shows a key is final, one that shows
+        // empty (stale or not) is settled by the CAS
+        unsigned long long k = t.keys[s];
+        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
+        if (k == kVoxEmpty || k == key) { found = true; break; }
+        s = (s + 1ull) & mask;
+    }
+    if (!found) { atomicOr(&st[kVoxErr], 1ull); return; }
+    atomicAdd(&t.cnt[s], 1u);
+    atomicMin(&t.first[s], idx);
+}
+
+__global__ __launch_bounds__(256) void k_voxel_stats(const VoxTable t, int min_points, unsigned long long* __restrict__ st) {
+    unsigned long long occ = 0, kept = 0, wrapped = 0, far = 0;
+    const unsigned long long mask = t.slots - 1ull;
+    for (unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x; s < t.slots;
+         s += static_cast<unsigned long long>(gridDim.x) * 256) {
+        const unsigned long long k = t.keys[s];
+        if (k == kVoxEmpty) continue;
+        const unsigned long long h = vox_home(k, t.log2_slots);
+        ++occ;
+        kept += t.cnt[s] >= static_cast<uint32_t>(min_points) ? 1ull : 0ull;
+        wrapped += s < h ? 1ull : 0ull;
+        far = max(far, ((s - h) & mask) + 1ull);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        occ += __shfl_xor(occ, d);
+        kept += __shfl_xor(kept, d);
+        wrapped += __shfl_xor(wrapped, d);
+        far = max(far, static_cast<unsigned long long>(__shfl_xor(far, d)));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (occ) atomicAdd(&st[kVoxOccupied], occ);
+        if (kept) atomicAdd(&st[kVoxKept], kept);
+        if (wrapped) atomicAdd(&st[kVoxWrapped], wrapped);
+        if (far) atomicMax(&st[kVoxMaxProbe], far);
+    }
+}
+
+// flags[i] = point i0 + i is the first point of a voxel that is kept; counts[chunk] as k_fuse_count
+__global__ __launch_bounds__(256) void k_voxel_mark(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                    const VoxGrid g, const VoxTable t, int min_points,
+                                                    int* __restrict__ flags, int* __restrict__ counts,
+                                                    unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
+    int f = 0;
+    if (i < n) {
+        float v[9], frac[3];
+        unsigned long long key, s;
+        if (vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac)) {
+            if (vox_find(t, key, s)) f = (t.first[s] == idx && t.cnt[s] >= static_cast<uint32_t>(min_points)) ? 1 : 0;
+            else atomicOr(&st[kVoxErr], 2ull);
+        }
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// the flagged points of each chunk in order: output id = *seg_base + offsets[chunk] + rank
+__global__ __launch_bounds__(256) void k_voxel_scatter(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                       const VoxGrid g, const VoxTable t, const int* __restrict__ flags,
+                                                       const int* __restrict__ offsets,
+                                                       const unsigned long long* __restrict__ seg_base, unsigned long long cap,
+                                                       unsigned long long* __restrict__ vslot,
+                                                       unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    if (f && pos < cap) {
+        float v[9], frac[3];
+        unsigned long long key, s;
+        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac) &&
+            vox_find(t, key, s)) {
+            t.oid[s] = pos;
+            vslot[pos] = s;
+        } else {
+            atomicOr(&st[kVoxErr], 4ull);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_voxel_accumulate(const float* __restrict__ pts, unsigned long long i0, int n,
+                                                          const VoxGrid g, const VoxTable t,
+                                                          unsigned long long* __restrict__ sums,
+                                                          unsigned long long* __restrict__ st) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (i >= n) return;
+    float v[9], frac[3];
+    unsigned long long key, s;
+    if (!(vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac))) return;
+    if (!vox_find(t, key, s)) { atomicOr(&st[kVoxErr], 8ull); return; }
+    const unsigned long long o = t.oid[s];
+    if (o == kVoxEmpty) return;                      // fewer than min_points
+    unsigned long long* acc = sums + 9ull * o;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        // step 3: 16.16 fixed point, round half to even; the product by a power of two is exact
+        const float q = rintf((k < 3 ? frac[k] : v[k]) * 65536.0f);
+        atomicAdd(&acc[k], static_cast<unsigned long long>(static_cast<long long>(q)));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_voxel_finalise(unsigned long long nv, const unsigned long long* __restrict__ vslot,
+                                                        const VoxTable t, const unsigned long long* __restrict__ sums,
+                                                        const VoxGrid g, float* __restrict__ out,
+                                                        int32_t* __restrict__ out_cnt) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const unsigned long long s = vslot[v];
+    if (s >= t.slots) return;                        // an id the compaction did not fill (the host reports it)
+    const unsigned long long key = t.keys[s];
+    const uint32_t n = t.cnt[s];
+    const double div = static_cast<double>(n) * 65536.0;
+    const double o[3] = {static_cast<double>(g.ox), static_cast<double>(g.oy), static_cast<double>(g.oz)};
+    const unsigned long long* acc = sums + 9ull * v;
+    float* dst = out + 9ull * v;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double mean = static_cast<double>(static_cast<long long>(acc[k])) / div;
+        if (k < 3) {
+            const double cell = static_cast<double>((key >> (21 * k)) & 0x1fffffull);
+            dst[k] = static_cast<float>(o[k] + (cell + mean) * static_cast<double>(g.size));
+        } else {
+            dst[k] = static_cast<float>(mean);
+        }
+    }
+    out_cnt[v] = static_cast<int32_t>(n);
+}
+
+hipError_t launch_voxel_min(const float* pts, unsigned long long i0, int n, uint32_t* mn, hipStream_t s) {
+    k_voxel_min<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, mn);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_insert(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
+                               unsigned long long* st, hipStream_t s) {
+    k_voxel_insert<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st, hipStream_t s) {
+    const unsigned long long blocks = std::min<unsigned long long>((t.slots + 255ull) / 256ull, 4096ull);
+    k_voxel_stats<<<static_cast<unsigned>(blocks), 256, 0, s>>>(t, min_points, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
+                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
+                                unsigned long long* st, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_voxel_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, min_points, flags, counts, st);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_voxel_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, flags, offsets, seg_base, cap, vslot, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
+                                   unsigned long long* sums, unsigned long long* st, hipStream_t s) {
+    k_voxel_accumulate<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, sums, st);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long* vslot, VoxTable t,
+                                 const unsigned long long* sums, VoxGrid g, float* out, int32_t* out_cnt, hipStream_t s) {
+    if (nv == 0) return hipSuccess;
+    k_voxel_finalise<<<static_cast<unsigned>((nv + 255ull) / 256ull), 256, 0, s>>>(nv, vslot, t, sums, g, out, out_cnt);
+    return hipGetLastError();
+}
+
+}  // namespace acmmp

@@ -19,13 +19,14 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "camera_dev.h"
 #include "detmath.h"
 #include "engine.h"
-#include "planar.h"
 
 // Translation-unit split: build.py compiles this file once per ACMMP_TU value (0..kTUs-1), in
 // parallel, and every kernel instance and host launcher lands in exactly one of those objects.  With
-// ACMMP_TU unset the whole file is one unit.
+// ACMMP_TU unset the whole file is one unit.  The fusion and voxel kernels (fusion_kernels.hip) and the
+// planar-prior, copy, clock-probe and checksum kernels (aux_kernels.hip) are units of their own.
 #ifndef ACMMP_TU
 #define ACMMP_TU -1
 #endif
@@ -73,74 +74,12 @@ struct Rng {
     }
 };
 
-// ------------------------------------------------------------------ camera model
-
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-    const float inv = det_rsqrt(dot3(x, y, z, x, y, z));
-    x *= inv; y *= inv; z *= inv;
-}
-
-// PixelToDir, ACMMP.cu:119-134
-__device__ __forceinline__ float3 pixel_to_dir(const DevCam& c, int px, int py) {
-    float3 d;
-    if (c.model == kPinhole) {
-        d.x = (static_cast<float>(px) - c.K[2]) / c.K[0];
-        d.y = (static_cast<float>(py) - c.K[5]) / c.K[4];
-        d.z = 1.f;
-        normalize3(d.x, d.y, d.z);
-    } else {
-        const float lon = (static_cast<float>(px) - c.cx) / static_cast<float>(c.W) * 2.0f * kCudartPiF;
-        const float lat = -(static_cast<float>(py) - c.cy) / static_cast<float>(c.H) * kCudartPiF;
-        float sl, cl, sa, ca;
-        det_sincos(lon, &sl, &cl);
-        det_sincos(lat, &sa, &ca);
-        d.x = ca * sl;
-        d.y = -sa;
-        d.z = ca * cl;
-    }
-    return d;
-}
-
-template <typename Cam>
-__device__ __forceinline__ float3 rotate_to_world(Cam& c, float x, float y, float z) {
-    float3 r;
-    r.x = dot3(c.R[0], c.R[3], c.R[6], x, y, z) + c.C[0];
-    r.y = dot3(c.R[1], c.R[4], c.R[7], x, y, z) + c.C[1];
-    r.z = dot3(c.R[2], c.R[5], c.R[8], x, y, z) + c.C[2];
-    return r;
-}
-
-// Get3DPointonWorld_cu (ACMMP.cu:565-600) at arbitrary float coordinates.
-template <int MODEL>
-__device__ __forceinline__ float3 world_point(const DevCam& c, float x, float y, float depth) {
-    if (MODEL == kSphere) {
-        const float lon = (x - c.cx) / static_cast<float>(c.W) * 2.0f * kCudartPiF;
-        const float lat = -(y - c.cy) / static_cast<float>(c.H) * kCudartPiF;
-        float sl, cl, sa, ca;
-        det_sincos(lon, &sl, &cl);
-        det_sincos(lat, &sa, &ca);
-        return rotate_to_world(c, (ca * sl) * depth, (-sa) * depth, (ca * cl) * depth);
-    } else {
-        return rotate_to_world(c, (depth * (x - c.K[2])) * c.inv_fx, (depth * (y - c.K[5])) * c.inv_fy, depth);
-    }
-}
-
-// The same at an integer reference pixel whose ray `d` is already known (SPHERE's
-// camera-frame point is ray * depth exactly as Get3DPointonWorld_cu rounds it).
-template <int MODEL, typename Cam>
-__device__ __forceinline__ float3 world_point_ray(Cam& c, int x, int y, float depth, float4 d) {
-    if (MODEL == kSphere) {
-        return rotate_to_world(c, d.x * depth, d.y * depth, d.z * depth);
-    } else {
-        return rotate_to_world(c, (depth * (static_cast<float>(x) - c.K[2])) * c.inv_fx,
-                               (depth * (static_cast<float>(y) - c.K[5])) * c.inv_fy, depth);
-    }
-}
+// ------------------------------------------------------------------ camera model (the exact one: camera_dev.h)
 
 // Single-instruction helpers with the hardware's own semantics (inline asm, so the compiler neither
 // canonicalises operands nor widens them): v_cvt_i32_f32 truncates, saturates and maps NaN to 0
 // (= f2i_sat); v_med3_i32 clamps; v_mad_u32_u24 multiplies 24-bit operands.  None of them may read a
-// transcendental's result directly (see max_abs below); scripts/hazard_scan.py checks the built code.
+// transcendental's result directly (see max_abs, camera_dev.h); scripts/hazard_scan.py checks the built code.
 __device__ __forceinline__ int cvt_i32(float x) {
     int r;
     asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(x));
@@ -161,113 +100,10 @@ __device__ __forceinline__ unsigned mad_u24(unsigned a, unsigned b, unsigned c) 
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
     return r;
 }
-// |a| vs |b| for the atan2 range reductions.  gfx950 wants one wait state between a VALU transcendental
-// (v_sqrt, v_rcp, ...) and the first instruction reading its result; the compiler's hazard recognizer inserts
-// it for the instructions it can see, not for inline asm.  Round 6 found an inline-asm v_max_f32 scheduled
-// directly after the v_sqrt of hypot(x, z): it read a half-written register (wrong costs in lane groups 0-3 of
-// every 8 in k_eval_ref's instances, found by a paired-sample loop whose schedule put the two together; the
-// round-5 tree had the pair in its V = 1 k_eval_ref instances only).  So:
-//   max_abs / min_abs      the builtins (general operands; never signalling NaNs, so no canonicalisation)
-//   max_abs_nt / min_abs_nt inline asm, operands never a transcendental's result (the rigid transform's fmas)
-//   max_abs_h / min_abs_h  inline asm behind an s_nop 0, for the hypot operand
-// The asm forms keep the scheduler's round-5 order in the fast SPHERE projections: both pairs on the builtins
-// measured k_eval_nb 1.444 ms against 1.428 ms this way (profiles/r06_ab8_hazard_ab.txt).
-// scripts/hazard_scan.py checks the device assembly for (transcendental, immediate reader) pairs.
-__device__ __forceinline__ float max_abs(float a, float b) { return __builtin_fmaxf(fabsf(a), fabsf(b)); }
-__device__ __forceinline__ float min_abs(float a, float b) { return __builtin_fminf(fabsf(a), fabsf(b)); }
-__device__ __forceinline__ float max_abs_nt(float a, float b) {
-    float r;
-    asm("v_max_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float min_abs_nt(float a, float b) {
-    float r;
-    asm("v_min_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float max_abs_h(float a, float b) {
-    float r;
-    asm("s_nop 0\n\tv_max_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float min_abs_h(float a, float b) {
-    float r;
-    asm("s_nop 0\n\tv_min_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 __device__ __forceinline__ float clamp0(float x, float hi) {        // fminf(fmaxf(x, 0), hi), hi uniform
     float r;
     asm("v_max_f32_e32 %0, 0, %1\n\tv_min_f32_e32 %0, %2, %0" : "=&v"(r) : "v"(x), "s"(hi));
     return r;
-}
-
-// sqrtf for the SPHERE projection: LLVM's IEEE f32 sqrt lowering (v_sqrt_f32, then the +-1 ulp
-// fma fix-up) without its small-argument rescale and its +-0/inf class select.  Bit-identical to
-// sqrtf for every x >= 2^-96, +inf and NaN; for smaller x the result is still < 1e-6 and the
-// projection replaces it by the principal point (d < 1e-6 select), and the depth it returns is
-// unused by every caller, so outputs never differ.
-__device__ __forceinline__ float sqrt_proj(float x) {
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float sdn = __builtin_bit_cast(float, __builtin_bit_cast(int, s) - 1);
-    const float sup = __builtin_bit_cast(float, __builtin_bit_cast(int, s) + 1);
-    const float r = fmaf(-sdn, s, x) <= 0.0f ? sdn : s;
-    return fmaf(-sup, s, x) > 0.0f ? sup : r;
-}
-
-// a / b for the SPHERE projection: LLVM's IEEE f32 division sequence (v_rcp_f32, one Newton step
-// on the reciprocal, two residual corrections, the last one fused) without v_div_scale's exponent
-// pre-scaling and v_div_fixup's special-case pass.  Bit-identical to a / b whenever |b| lies in
-// [2^-125, 2^125] and |a| >= 2^-102 or a == 0 (the sign of a zero quotient may differ); the two
-// projection callers (ty / d and the atan2 ratio min / max) only leave that range for a point
-// closer than 2^-102 to the camera centre (replaced by the principal point) or a quotient below
-// 2^-80, whose contribution to the pixel coordinate is absorbed by cx / cy.
-__device__ __forceinline__ float div_proj(float a, float b) {
-    float y = __builtin_amdgcn_rcpf(b);
-    y = fmaf(fmaf(-b, y, 1.0f), y, y);
-    float q = a * y;
-    q = fmaf(fmaf(-b, q, a), y, q);
-    return fmaf(fmaf(-b, q, a), y, q);
-}
-
-__device__ __forceinline__ float atan2_proj(float y, float x) {
-    return det_atan2_ratio(y, x, div_proj(min_abs(x, y), max_abs(x, y)));
-}
-
-// det_asin with its large-argument square root through sqrt_proj: there z = (1 - |x|) / 2 is 0, NaN,
-// negative (|x| > 1 by rounding) or >= 2^-25 (1 - |x| is exact and at least 2^-24), where sqrt_proj
-// equals sqrtf bit for bit.
-__device__ __forceinline__ float asin_proj(float x) {
-    // straight-line: one polynomial on selected arguments (no divergent branch, so the compiler can
-    // interleave the views of a chunk; r01_v25 A/B +0.5%)
-    const float a = fabsf(x);
-    const bool small = a <= 0.5f;
-    const float zl = (1.0f - a) * 0.5f;
-    const float c = det_asin_core(small ? a : sqrt_proj(zl), small ? a * a : zl);
-    return copysignf(small ? c : fmaf(-2.0f, c, kPio2Hi) + kPio2Lo, x);
-}
-
-// ProjectonCamera_cu, ACMMP.cu:602-644 (Cam: DevCam in any address space)
-template <int MODEL, typename Cam, bool EXACT_DEPTH = false>
-__device__ __forceinline__ void project(Cam& c, float3 P, float& ox, float& oy, float& depth) {
-    const float tx = dot3(c.R[0], c.R[1], c.R[2], P.x, P.y, P.z) + c.t[0];
-    const float ty = dot3(c.R[3], c.R[4], c.R[5], P.x, P.y, P.z) + c.t[1];
-    const float tz = dot3(c.R[6], c.R[7], c.R[8], P.x, P.y, P.z) + c.t[2];
-    if (MODEL == kSphere) {
-        // sqrt_proj differs from sqrtf only below 2^-96, where the point is replaced by the principal
-        // point; callers that use the returned depth (fusion) ask for the IEEE square root
-        const float d = EXACT_DEPTH ? sqrtf(dot3(tx, ty, tz, tx, ty, tz)) : sqrt_proj(dot3(tx, ty, tz, tx, ty, tz));
-        depth = d;
-        const float neg_lat = asin_proj(EXACT_DEPTH ? ty / d : div_proj(ty, d));
-        const float lon = EXACT_DEPTH ? det_atan2(tx, tz) : atan2_proj(tx, tz);
-        ox = fmaf(lon * kInv2Pi, c.Wf, c.cx);
-        oy = fmaf(neg_lat * kInvPi, c.Hf, c.cy);
-        if (d < 1e-6f) { ox = c.cx; oy = c.cy; }        // (:618-622) selected, not branched around
-    } else {
-        depth = tz;
-        const float inv = 1.0f / tz;
-        ox = dot3(c.K[0], c.K[1], c.K[2], tx, ty, tz) * inv;
-        oy = dot3(c.K[3], c.K[4], c.K[5], tx, ty, tz) * inv;
-    }
 }
 
 // ComputeDepthfromPlaneHypothesis, ACMMP.cu:187-193
@@ -3136,8 +2972,6 @@ __global__ void k_debug(const KParams kp, int which, int n, const int* __restric
 
 // ------------------------------------------------------------------ host launchers
 
-static inline int cdiv(long long a, int b) { return static_cast<int>((a + b - 1) / b); }
-
 #if ACMMP_IN_TU(0)
 hipError_t launch_to_f16_pairs(const float* src, int W, int H, uint32_t* dst, int* inexact, hipStream_t s) {
     const long long n = static_cast<long long>(W + 2) * (H + 1);
@@ -3561,826 +3395,12 @@ hipError_t launch_post(const KParams& kp, int do_post, hipStream_t s) {
     return hipGetLastError();
 }
 
-
-// ------------------------------------------------------------------ kernels: planar prior (device half)
-//
-// ProcessProblem's triangle rasterisation and prior-depth mask (main.cpp:138-181) with the triangles,
-// planes and steps the host computed (planar.h).  One thread per (triangle, p step): the p values are
-// the reference's running float sums 0, step, 2 step, ... (recomputed by the same additions), the q
-// loop runs as in the reference; the reference overwrites labels in triangle order, so a pixel keeps
-// the largest label that reaches it -- atomicMax gives that whatever the schedule.  Same float and
-// double arithmetic as the reference's C++ (no contraction): the same pixels, bit for bit.
-__global__ __launch_bounds__(256) void k_planar_raster(const PlanarDev pd, uint32_t* mask) {
-    const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (t >= pd.n_steps) return;
-    int lo = 0, hi = pd.n_tri - 1;                       // triangle k with first[k] <= t < first[k + 1]
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pd.first[mid] <= t) lo = mid;
-        else hi = mid - 1;
-    }
-    const int k = lo;
-    const long long i = t - pd.first[k];
-    const float step = pd.step[k];
-    float p = 0.f;
-    for (long long a = 0; a < i; ++a) p += step;
-    const int* tr = pd.tri + 6 * static_cast<long long>(k);
-    const uint32_t label = static_cast<uint32_t>(k) + 1u;
-    const double rest = 1.0 - static_cast<double>(p);
-    for (float q = 0.f; static_cast<double>(q) < rest; q += step) {
-        const double w3 = rest - static_cast<double>(q);
-        const int x = static_cast<int>(static_cast<double>(p * static_cast<float>(tr[0]) + q * static_cast<float>(tr[2])) +
-                                       w3 * static_cast<double>(tr[4]));
-        const int y = static_cast<int>(static_cast<double>(p * static_cast<float>(tr[1]) + q * static_cast<float>(tr[3])) +
-                                       w3 * static_cast<double>(tr[5]));
-        if (x >= 0 && x < pd.W && y >= 0 && y < pd.H) atomicMax(mask + static_cast<long long>(y) * pd.W + x, label);
-    }
-}
-
-// GetDepthFromPlaneParam (ACMMP.cpp:991-1011) per labelled pixel; out-of-range prior depths drop the
-// label (main.cpp:168-180); CudaPlanarPriorInitialization's expansion (ACMMP.cpp:855-862).
-__global__ __launch_bounds__(256) void k_planar_mask(const PlanarDev pd, uint32_t* mask, float4* prior) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
-    if (i >= pd.W) return;
-    const long long c = static_cast<long long>(j) * pd.W + i;
-    uint32_t l = mask[c];
-    float4 pl = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (l > 0) {
-        pl = pd.plane[l - 1];
-        float d;
-        if (pd.model == kSphere) {
-            const float2 lat = pd.row_trig[j], lon = pd.col_trig[i];
-            const float dx = lat.y * lon.x, dy = -lat.x, dz = lat.y * lon.y;
-            const float denom = pl.x * dx + pl.y * dy + pl.z * dz;
-            d = (fabsf(denom) < 1e-6f) ? 1e6f : (-pl.w / denom);
-        } else {
-            d = -pl.w * pd.K0 / ((static_cast<float>(i) - pd.K2) * pl.x +
-                                 (pd.K0 / pd.K4) * (static_cast<float>(j) - pd.K5) * pl.y + pd.K0 * pl.z);
-        }
-        if (!(d <= pd.depth_max && d >= pd.depth_min)) {
-            l = 0;
-            pl = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    mask[c] = l;
-    prior[c] = pl;
-}
-
-hipError_t launch_planar_raster(const PlanarDev& pd, uint32_t* mask, hipStream_t s) {
-    if (pd.n_steps > 0) k_planar_raster<<<static_cast<unsigned>(cdiv(pd.n_steps, 256)), 256, 0, s>>>(pd, mask);
-    return hipGetLastError();
-}
-
-hipError_t launch_planar_mask(const PlanarDev& pd, uint32_t* mask, float4* prior, hipStream_t s) {
-    k_planar_mask<<<dim3(cdiv(pd.W, 256), pd.H), 256, 0, s>>>(pd, mask, prior);
-    return hipGetLastError();
-}
-
-// GetSupportPoints (ACMMP.cpp:904-929) on the context's last RunPatchMatch output: one thread per 5x5
-// block, scanned column by column with the reference's strict '>' (the first minimum-cost pixel, costs
-// 2.0 and above skipped), kept when the minimum is < 0.1.  out[strip * bh + block row] = (kept, x, y,
-// depth bits) -- the reference's point order is strip-major, block rows within a strip.
-__global__ __launch_bounds__(256) void k_support_points(const float* __restrict__ costs, const float4* __restrict__ planes,
-                                                        int W, int H, int bh, int4* __restrict__ out) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int bw = (W + 4) / 5;
-    if (t >= bw * bh) return;
-    const int strip = t / bh, rb = t - strip * bh;
-    const int col = strip * 5, row = rb * 5;
-    const int cb = min(W, col + 5), rbe = min(H, row + 5);
-    float min_cost = 2.0f;
-    int tx = 0, ty = 0;
-    for (int c = col; c < cb; ++c)
-        for (int r = row; r < rbe; ++r) {
-            const float v = costs[static_cast<long long>(r) * W + c];
-            if (v < 2.0f && min_cost > v) { tx = c; ty = r; min_cost = v; }
-        }
-    const bool keep = min_cost < 0.1f;
-    const float d = keep ? planes[static_cast<long long>(ty) * W + tx].w : 0.0f;
-    out[t] = make_int4(keep ? 1 : 0, tx, ty, __float_as_int(d));
-}
-
-hipError_t launch_support_points(const float* costs, const float4* planes, int W, int H, int4* out, hipStream_t s) {
-    const int bh = (H + 4) / 5, n = ((W + 4) / 5) * bh;
-    k_support_points<<<cdiv(n, 256), 256, 0, s>>>(costs, planes, W, H, bh, out);
-    return hipGetLastError();
-}
-
-
-// ------------------------------------------------------------------ kernel: fusion
-
-// tex2D<float4>(linear filter, unnormalised (c, r)) at an integer texel index WITHOUT the +0.5
-// (ACMMP.cu:1690, 1768): the footprint is texels (c-1, c) x (r-1, r), both weights 0.5, clamped
-// (wrap is undefined for unnormalised coordinates and acts as clamp).  fp32 fused lerps.
-__device__ __forceinline__ float4 fuse_colour(const float* rgba, int W, int H, int c, int r) {
-    const int x0 = c - 1 < 0 ? 0 : c - 1, x1 = c > W - 1 ? W - 1 : c;
-    const int y0 = r - 1 < 0 ? 0 : r - 1, y1 = r > H - 1 ? H - 1 : r;
-    const float4 t00 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y0) * W + x0];
-    const float4 t10 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y0) * W + x1];
-    const float4 t01 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y1) * W + x0];
-    const float4 t11 = reinterpret_cast<const float4*>(rgba)[static_cast<long long>(y1) * W + x1];
-    auto lerp = [](float a, float b) { return fmaf(0.5f, b - a, a); };
-    const float4 top = make_float4(lerp(t00.x, t10.x), lerp(t00.y, t10.y), lerp(t00.z, t10.z), lerp(t00.w, t10.w));
-    const float4 bot = make_float4(lerp(t01.x, t11.x), lerp(t01.y, t11.y), lerp(t01.z, t11.z), lerp(t01.w, t11.w));
-    return make_float4(lerp(top.x, bot.x), lerp(top.y, bot.y), lerp(top.z, bot.z), lerp(top.w, bot.w));
-}
-
-// SimpleFusionKernel, ACMMP.cu:1662-1814: per reference pixel, the source views whose depth
-// reprojects within 1 px, 1% depth and 0.149 rad of normal; >= 3 consistent (the reference
-// included) -> averaged point, normal and colour.  out: 9 floats per pixel (x y z nx ny nz c0 c1 c2,
-// c0 = 255 * texture .z as the reference stores it).
-//
-// Two compile-time variants serve the whole-scene pass (acmmp_fusion_run_scene): PROV also writes, per
-// pixel, the mask of consistent sources (bit j = srcs[j]); UNIQUE reads every depth through the views'
-// `used` byte masks -- a used pixel reads as depth 0, so a used reference pixel is skipped and a used
-// source sample is skipped, with the arithmetic, the thresholds and the order of the sums untouched.
-// k_fuse<MODEL> is the reference-equal kernel of acmmp_fusion_run (neither variant), k_fuse_scene the
-// kernel of the scene pass.
-template <int MODEL, bool PROV, bool UNIQUE>
-__device__ __forceinline__ void fuse_pixel(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref,
-                                           int W, int H, const int* __restrict__ srcs, int n_src, float* __restrict__ out,
-                                           int* __restrict__ flags, uint32_t* __restrict__ src_mask) {
-    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
-    const bool inside = c < W && r < H;
-    int valid = 0;
-    const long long idx = static_cast<long long>(r) * W + c;
-    if (inside) {
-        const DevCam& rc = cams[ref];
-        const FuseView rv = views[ref];
-        float ref_depth = rv.depth[idx];
-        if constexpr (UNIQUE) { if (rv.used[idx]) ref_depth = 0.0f; }
-        uint32_t consistent = 0;
-        if (!(ref_depth <= 0.0f)) {
-            const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), ref_depth);
-            const float rn0 = rv.normal[3 * idx], rn1 = rv.normal[3 * idx + 1], rn2 = rv.normal[3 * idx + 2];
-            const float4 rcol = fuse_colour(rv.rgba, W, H, c, r);
-            float ps0 = X.x, ps1 = X.y, ps2 = X.z;
-            float ns0 = rn0, ns1 = rn1, ns2 = rn2;
-            float cs0 = rcol.z * 255.0f, cs1 = rcol.y * 255.0f, cs2 = rcol.x * 255.0f;
-            int n = 1;
-            for (int j = 0; j < n_src; ++j) {
-                const int si = srcs[j];
-                if (si < 0) continue;
-                const DevCam& sc = cams[si];
-                const FuseView sv = views[si];
-                float px, py, pd;
-                project<MODEL, const DevCam, true>(sc, X, px, py, pd);
-                const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
-                if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;
-                const long long sidx = static_cast<long long>(src_r) * sv.W + src_c;
-                float sd = sv.depth[sidx];
-                if constexpr (UNIQUE) { if (sv.used[sidx]) sd = 0.0f; }
-                if (sd <= 0.0f) continue;
-                const float3 Xs = world_point<MODEL>(sc, static_cast<float>(src_c), static_cast<float>(src_r), sd);
-                float qx, qy, qd;
-                project<MODEL, const DevCam, true>(rc, Xs, qx, qy, qd);
-                const float err = det_hypot(static_cast<float>(c) - qx, static_cast<float>(r) - qy);
-                const float rel = fabsf(pd - sd) / sd;
-                const float sn0 = sv.normal[3 * sidx], sn1 = sv.normal[3 * sidx + 1], sn2 = sv.normal[3 * sidx + 2];
-                float dp = dot3(rn0, rn1, rn2, sn0, sn1, sn2);
-                dp = fmaxf(-1.0f, fminf(1.0f, dp));
-                const float ang = det_acos(dp);
-                if (err < 1.0f && rel < 0.01f && ang < 0.149f) {
-                    ps0 += Xs.x; ps1 += Xs.y; ps2 += Xs.z;
-                    ns0 += sn0; ns1 += sn1; ns2 += sn2;
-                    const float4 scol = fuse_colour(sv.rgba, sv.W, sv.H, src_c, src_r);
-                    cs0 = fmaf(scol.z, 255.0f, cs0);
-                    cs1 = fmaf(scol.y, 255.0f, cs1);
-                    cs2 = fmaf(scol.x, 255.0f, cs2);
-                    ++n;
-                    if constexpr (PROV) consistent |= 1u << j;
-                }
-            }
-            if (n >= 3) {
-                const float fn = static_cast<float>(n);
-                float* o = out + 9 * idx;
-                o[0] = ps0 / fn; o[1] = ps1 / fn; o[2] = ps2 / fn;
-                float a0 = ns0 / fn, a1 = ns1 / fn, a2 = ns2 / fn;
-                const float len = det_hypot(det_hypot(a0, a1), a2);
-                if (len > 0.0f) { a0 /= len; a1 /= len; a2 /= len; }
-                o[3] = a0; o[4] = a1; o[5] = a2;
-                o[6] = cs0 / fn; o[7] = cs1 / fn; o[8] = cs2 / fn;
-                valid = 1;
-            }
-        }
-        flags[idx] = valid;
-        if constexpr (PROV) src_mask[idx] = valid ? consistent : 0u;
-    }
-}
-
-template <int MODEL>
-__global__ void k_fuse(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
-                       const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags) {
-    fuse_pixel<MODEL, false, false>(cams, views, ref, W, H, srcs, n_src, out, flags, nullptr);
-}
-
-template <int MODEL, bool UNIQUE>
-__global__ void k_fuse_scene(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
-                             const int* __restrict__ srcs, int n_src, float* __restrict__ out, int* __restrict__ flags,
-                             uint32_t* __restrict__ src_mask) {
-    fuse_pixel<MODEL, true, UNIQUE>(cams, views, ref, W, H, srcs, n_src, out, flags, src_mask);
-}
-
-// After a unique-mode k_fuse_scene of view `ref`, before the next view's: every sample that contributed
-// to an emitted point is marked used -- the reference pixel, and for each consistent source j the pixel
-// (src_c, src_r) k_fuse sampled, recomputed by the same device functions from the same depth (an emitted
-// pixel was not used when k_fuse read it, so the raw depth is what it saw).  Plain byte stores of 1: lanes
-// that hit the same byte store the same value.
-template <int MODEL>
-__global__ void k_fuse_mark(const DevCam* __restrict__ cams, const FuseView* __restrict__ views, int ref, int W, int H,
-                            const int* __restrict__ srcs, int n_src, const int* __restrict__ flags,
-                            const uint32_t* __restrict__ src_mask) {
-    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
-    const int r = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (c >= W || r >= H) return;
-    const long long idx = static_cast<long long>(r) * W + c;
-    if (!flags[idx]) return;
-    const DevCam& rc = cams[ref];
-    const FuseView rv = views[ref];
-    const uint32_t m = src_mask[idx];
-    const float3 X = world_point<MODEL>(rc, static_cast<float>(c), static_cast<float>(r), rv.depth[idx]);
-    rv.used[idx] = 1;
-    for (int j = 0; j < n_src; ++j) {
-        if (!((m >> j) & 1u)) continue;
-        const int si = srcs[j];
-        const DevCam& sc = cams[si];
-        const FuseView sv = views[si];
-        float px, py, pd;
-        project<MODEL, const DevCam, true>(sc, X, px, py, pd);
-        const int src_c = f2i_sat(px + 0.5f), src_r = f2i_sat(py + 0.5f);
-        if (src_c < 0 || src_c >= sc.W || src_r < 0 || src_r >= sc.H) continue;   // (never: the bit says it was inside)
-        sv.used[static_cast<long long>(src_r) * sv.W + src_c] = 1;
-    }
-}
-
-// counts of valid pixels per 256-pixel chunk of the row-major image
-__global__ void k_fuse_count(const int* __restrict__ flags, long long P, int* __restrict__ counts) {
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const int f = i < P ? flags[i] : 0;
-    const int n = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = n;
-}
-
-// scatter the valid pixels of each chunk to offsets[chunk] + rank within the chunk (pixel order)
-__global__ void k_fuse_scatter(const float* __restrict__ dense, const int* __restrict__ flags, long long P,
-                               const int* __restrict__ offsets, float* __restrict__ out) {
-    __shared__ int wave_tot[4];
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const int f = i < P ? flags[i] : 0;
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(b);
-    __syncthreads();
-    int base = offsets[blockIdx.x];
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    if (f) {
-        float* o = out + 9ll * (base + below);
-        const float* d = dense + 9 * i;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) o[k] = d[k];
-    }
-}
-
-// Exclusive scan of the chunk counts of one view (each 0..256) and the scene bookkeeping, one workgroup
-// of 1024 lanes walking the chunks in tiles of 1024 with a running carry.  Within a wave the prefix is
-// built bit plane by bit plane from ballots: popcount(ballot(bit b of count) below my lane) << b, summed
-// over the 9 planes; the 16 wave totals meet in LDS.  Lane 0 then publishes the view's point count, takes
-// the 64-bit running scene offset as this view's base and advances it.
-__global__ __launch_bounds__(1024) void k_fuse_scan(const int* __restrict__ counts, int n_chunks, int* __restrict__ offsets,
-                                                    int* __restrict__ view_count, unsigned long long* __restrict__ running,
-                                                    unsigned long long* __restrict__ view_base) {
-    __shared__ int wave_tot[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int carry = 0;
-    for (int t0 = 0; t0 < n_chunks; t0 += 1024) {
-        const int i = t0 + static_cast<int>(threadIdx.x);
-        const int v = i < n_chunks ? counts[i] : 0;
-        int excl = 0, tot = 0;
-#pragma unroll
-        for (int b = 0; b < 9; ++b) {
-            const unsigned long long m = __ballot((v >> b) & 1);
-            excl += __popcll(m & below) << b;
-            tot += __popcll(m) << b;
-        }
-        if (lane == 0) wave_tot[wave] = tot;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-            const int x = wave_tot[w];
-            all += x;
-            if (w < wave) before += x;
-        }
-        if (i < n_chunks) offsets[i] = carry + before + excl;
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *view_count = carry;
-        const unsigned long long t = *running;
-        *view_base = t;
-        *running = t + static_cast<unsigned long long>(carry);
-    }
-}
-
-// k_fuse_scatter into the scene buffers at *view_base + offsets[chunk] + rank: the point and its provenance
-// (position of the view in the run's reference list, pixel r*W + c, consistent-source mask).  Nothing is
-// written at or beyond `cap` points.
-__global__ void k_fuse_scatter_scene(const float* __restrict__ dense, const int* __restrict__ flags,
-                                     const uint32_t* __restrict__ src_mask, long long P, const int* __restrict__ offsets,
-                                     const unsigned long long* __restrict__ view_base, int ref_pos, unsigned long long cap,
-                                     float* __restrict__ out, int* __restrict__ out_ref, int* __restrict__ out_pix,
-                                     uint32_t* __restrict__ out_mask) {
-    __shared__ int wave_tot[4];
-    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
-    const int f = i < P ? flags[i] : 0;
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(b);
-    __syncthreads();
-    int base = offsets[blockIdx.x];
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    const unsigned long long pos = *view_base + static_cast<unsigned long long>(base + below);
-    if (f && pos < cap) {
-        float* o = out + 9ull * pos;
-        const float* d = dense + 9 * i;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) o[k] = d[k];
-        out_ref[pos] = ref_pos;
-        out_pix[pos] = static_cast<int>(i);
-        out_mask[pos] = src_mask[i];
-    }
-}
-
-__global__ void k_export_depth(const float4* __restrict__ planes, long long P, float* __restrict__ dst) {
-    const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i < P) dst[i] = planes[i].w;
-}
-
-hipError_t launch_fuse(int model, const DevCam* cams, const FuseView* views, int ref, int W, int H, const int* srcs,
-                       int n_src, float* out_dense, int* flags, int* block_counts, hipStream_t s) {
-    dim3 grd(cdiv(W, 16), cdiv(H, 16));
-    if (model == kSphere) k_fuse<kSphere><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags);
-    else k_fuse<kPinhole><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags);
-    const long long P = static_cast<long long>(W) * H;
-    k_fuse_count<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(flags, P, block_counts);
-    return hipGetLastError();
-}
-
-hipError_t launch_fuse_compact(int W, int H, const float* out_dense, const int* flags, const int* block_offsets,
-                               float* out, hipStream_t s) {
-    const long long P = static_cast<long long>(W) * H;
-    k_fuse_scatter<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, P, block_offsets, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_fuse_scene(int model, bool unique, const DevCam* cams, const FuseView* views, int ref, int W, int H,
-                             const int* srcs, int n_src, float* out_dense, int* flags, uint32_t* src_mask,
-                             int* block_counts, int* block_offsets, int* view_count, unsigned long long* running,
-                             unsigned long long* view_base, hipStream_t s) {
-    dim3 grd(cdiv(W, 16), cdiv(H, 16));
-    if (model == kSphere) {
-        if (unique) k_fuse_scene<kSphere, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
-        else k_fuse_scene<kSphere, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
-    } else {
-        if (unique) k_fuse_scene<kPinhole, true><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
-        else k_fuse_scene<kPinhole, false><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, out_dense, flags, src_mask);
-    }
-    const long long P = static_cast<long long>(W) * H;
-    const int n_chunks = static_cast<int>((P + 255) / 256);
-    k_fuse_count<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(flags, P, block_counts);
-    k_fuse_scan<<<1, 1024, 0, s>>>(block_counts, n_chunks, block_offsets, view_count, running, view_base);
-    if (unique) {
-        if (model == kSphere) k_fuse_mark<kSphere><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
-        else k_fuse_mark<kPinhole><<<grd, 256, 0, s>>>(cams, views, ref, W, H, srcs, n_src, flags, src_mask);
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const int* flags, const uint32_t* src_mask,
-                                     const int* block_offsets, const unsigned long long* view_base, int ref_pos,
-                                     unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
-                                     hipStream_t s) {
-    const long long P = static_cast<long long>(W) * H;
-    k_fuse_scatter_scene<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(out_dense, flags, src_mask, P, block_offsets,
-                                                                               view_base, ref_pos, cap, out, out_ref,
-                                                                               out_pix, out_mask);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ voxel-grid reduction of the scene cloud
-//
-// acmmp_fusion_voxelize (include/acmmp.h).  Everything a result depends on is an integer: the
-// cell index, the 16.16 fixed-point channels and their 64-bit sums, the count and the smallest scene index of
-// a cell.  Integer adds and minima commute, so the order in which the atomics land is invisible; the only
-// racy thing is which slot of the hash table a cell gets, and no output depends on it.
-
-constexpr unsigned long long kVoxEmpty = ~0ull;
-
-__device__ __forceinline__ bool vox_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// step 1: all nine finite, normal and colour within 2^20
-__device__ __forceinline__ bool vox_load(const float* __restrict__ p, float v[9]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        v[k] = p[k];
-        ok = ok && !vox_nonfinite(v[k]);
-    }
-#pragma unroll
-    for (int k = 3; k < 9; ++k) ok = ok && fabsf(v[k]) <= 1048576.0f;
-    return ok;
-}
-
-// step 2: the cell of (x, y, z) and the position inside it, frac[a] = t - floorf(t) (exact); false = outside
-// the 2^21 cells per axis (a NaN index, from 0 * inf with a denormal size, is outside too)
-__device__ __forceinline__ bool vox_cell(const float v[9], const VoxGrid& g, unsigned long long& key, float frac[3]) {
-    const float o[3] = {g.ox, g.oy, g.oz};
-    key = 0;
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float t = (v[a] - o[a]) * g.inv;
-        const float c = floorf(t);
-        const bool in = c >= 0.0f && c < 2097152.0f;
-        ok = ok && in;
-        key |= (in ? static_cast<unsigned long long>(c) : 0ull) << (21 * a);
-        frac[a] = t - c;
-    }
-    return ok;
-}
-
-__device__ __forceinline__ unsigned long long vox_home(unsigned long long key, int log2_slots) {
-    unsigned long long z = key + 0x9e3779b97f4a7c15ull;       // splitmix64's finaliser
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    z ^= z >> 31;
-    return z >> (64 - log2_slots);
-}
-
-// The slot of a key that is in the table (after the insert pass); at most `slots` steps.
-__device__ __forceinline__ bool vox_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        const unsigned long long k = t.keys[s];
-        if (k == key) { slot = s; return true; }
-        if (k == kVoxEmpty) return false;
-        s = (s + 1ull) & mask;
-    }
-    return false;
-}
-
-__device__ __forceinline__ uint32_t vox_ordered(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__global__ __launch_bounds__(256) void k_voxel_min(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                   uint32_t* __restrict__ mn) {
-    __shared__ uint32_t blk[3];
-    if (threadIdx.x < 3) blk[threadIdx.x] = 0xffffffffu;
-    __syncthreads();
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    uint32_t m[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
-    if (i < n) {
-        float v[9];
-        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v)) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) m[a] = vox_ordered(v[a]);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m[a] = min(m[a], static_cast<uint32_t>(__shfl_xor(static_cast<int>(m[a]), d)));
-        if ((threadIdx.x & 63) == 0 && m[a] != 0xffffffffu) atomicMin(&blk[a], m[a]);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && blk[threadIdx.x] != 0xffffffffu) atomicMin(&mn[threadIdx.x], blk[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void k_voxel_insert(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                      const VoxGrid g, const VoxTable t, unsigned long long* __restrict__ st) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
-    bool ok = false;
-    unsigned long long key = 0;
-    if (i < n) {
-        float v[9], frac[3];
-        ok = vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac);
-    }
-    const int rejected = __syncthreads_count(i < n && !ok);
-    if (threadIdx.x == 0 && rejected) atomicAdd(&st[kVoxRejected], static_cast<unsigned long long>(rejected));
-    if (!ok) return;
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    bool found = false;
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        // a slot's key changes once, from empty: a plain read that shows a key is final, one that shows
-        // empty (stale or not) is settled by the CAS
-        unsigned long long k = t.keys[s];
-        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
-        if (k == kVoxEmpty || k == key) { found = true; break; }
-        s = (s + 1ull) & mask;
-    }
-    if (!found) { atomicOr(&st[kVoxErr], 1ull); return; }
-    atomicAdd(&t.cnt[s], 1u);
-    atomicMin(&t.first[s], idx);
-}
-
-__global__ __launch_bounds__(256) void k_voxel_stats(const VoxTable t, int min_points, unsigned long long* __restrict__ st) {
-    unsigned long long occ = 0, kept = 0, wrapped = 0, far = 0;
-    const unsigned long long mask = t.slots - 1ull;
-    for (unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x; s < t.slots;
-         s += static_cast<unsigned long long>(gridDim.x) * 256) {
-        const unsigned long long k = t.keys[s];
-        if (k == kVoxEmpty) continue;
-        const unsigned long long h = vox_home(k, t.log2_slots);
-        ++occ;
-        kept += t.cnt[s] >= static_cast<uint32_t>(min_points) ? 1ull : 0ull;
-        wrapped += s < h ? 1ull : 0ull;
-        far = max(far, ((s - h) & mask) + 1ull);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        occ += __shfl_xor(occ, d);
-        kept += __shfl_xor(kept, d);
-        wrapped += __shfl_xor(wrapped, d);
-        far = max(far, static_cast<unsigned long long>(__shfl_xor(far, d)));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (occ) atomicAdd(&st[kVoxOccupied], occ);
-        if (kept) atomicAdd(&st[kVoxKept], kept);
-        if (wrapped) atomicAdd(&st[kVoxWrapped], wrapped);
-        if (far) atomicMax(&st[kVoxMaxProbe], far);
-    }
-}
-
-// flags[i] = point i0 + i is the first point of a voxel that is kept; counts[chunk] as k_fuse_count
-__global__ __launch_bounds__(256) void k_voxel_mark(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                    const VoxGrid g, const VoxTable t, int min_points,
-                                                    int* __restrict__ flags, int* __restrict__ counts,
-                                                    unsigned long long* __restrict__ st) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
-    int f = 0;
-    if (i < n) {
-        float v[9], frac[3];
-        unsigned long long key, s;
-        if (vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac)) {
-            if (vox_find(t, key, s)) f = (t.first[s] == idx && t.cnt[s] >= static_cast<uint32_t>(min_points)) ? 1 : 0;
-            else atomicOr(&st[kVoxErr], 2ull);
-        }
-        flags[i] = f;
-    }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// the flagged points of each chunk in order: output id = *seg_base + offsets[chunk] + rank
-__global__ __launch_bounds__(256) void k_voxel_scatter(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                       const VoxGrid g, const VoxTable t, const int* __restrict__ flags,
-                                                       const int* __restrict__ offsets,
-                                                       const unsigned long long* __restrict__ seg_base, unsigned long long cap,
-                                                       unsigned long long* __restrict__ vslot,
-                                                       unsigned long long* __restrict__ st) {
-    __shared__ int wave_tot[4];
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const unsigned long long b = __ballot(f);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int below = __popcll(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(b);
-    __syncthreads();
-    int base = offsets[blockIdx.x];
-    for (int w = 0; w < wave; ++w) base += wave_tot[w];
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(base + below);
-    if (f && pos < cap) {
-        float v[9], frac[3];
-        unsigned long long key, s;
-        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac) &&
-            vox_find(t, key, s)) {
-            t.oid[s] = pos;
-            vslot[pos] = s;
-        } else {
-            atomicOr(&st[kVoxErr], 4ull);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_voxel_accumulate(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                          const VoxGrid g, const VoxTable t,
-                                                          unsigned long long* __restrict__ sums,
-                                                          unsigned long long* __restrict__ st) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    if (i >= n) return;
-    float v[9], frac[3];
-    unsigned long long key, s;
-    if (!(vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac))) return;
-    if (!vox_find(t, key, s)) { atomicOr(&st[kVoxErr], 8ull); return; }
-    const unsigned long long o = t.oid[s];
-    if (o == kVoxEmpty) return;                      // fewer than min_points
-    unsigned long long* acc = sums + 9ull * o;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        // step 3: 16.16 fixed point, round half to even; the product by a power of two is exact
-        const float q = rintf((k < 3 ? frac[k] : v[k]) * 65536.0f);
-        atomicAdd(&acc[k], static_cast<unsigned long long>(static_cast<long long>(q)));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_voxel_finalise(unsigned long long nv, const unsigned long long* __restrict__ vslot,
-                                                        const VoxTable t, const unsigned long long* __restrict__ sums,
-                                                        const VoxGrid g, float* __restrict__ out,
-                                                        int32_t* __restrict__ out_cnt) {
-    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
-    if (v >= nv) return;
-    const unsigned long long s = vslot[v];
-    if (s >= t.slots) return;                        // an id the compaction did not fill (the host reports it)
-    const unsigned long long key = t.keys[s];
-    const uint32_t n = t.cnt[s];
-    const double div = static_cast<double>(n) * 65536.0;
-    const double o[3] = {static_cast<double>(g.ox), static_cast<double>(g.oy), static_cast<double>(g.oz)};
-    const unsigned long long* acc = sums + 9ull * v;
-    float* dst = out + 9ull * v;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const double mean = static_cast<double>(static_cast<long long>(acc[k])) / div;
-        if (k < 3) {
-            const double cell = static_cast<double>((key >> (21 * k)) & 0x1fffffull);
-            dst[k] = static_cast<float>(o[k] + (cell + mean) * static_cast<double>(g.size));
-        } else {
-            dst[k] = static_cast<float>(mean);
-        }
-    }
-    out_cnt[v] = static_cast<int32_t>(n);
-}
-
-hipError_t launch_voxel_min(const float* pts, unsigned long long i0, int n, uint32_t* mn, hipStream_t s) {
-    k_voxel_min<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, mn);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_insert(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
-                               unsigned long long* st, hipStream_t s) {
-    k_voxel_insert<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st, hipStream_t s) {
-    const unsigned long long blocks = std::min<unsigned long long>((t.slots + 255ull) / 256ull, 4096ull);
-    k_voxel_stats<<<static_cast<unsigned>(blocks), 256, 0, s>>>(t, min_points, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
-                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
-                                unsigned long long* st, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_voxel_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, min_points, flags, counts, st);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_voxel_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, flags, offsets, seg_base, cap, vslot, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
-                                   unsigned long long* sums, unsigned long long* st, hipStream_t s) {
-    k_voxel_accumulate<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(pts, i0, n, g, t, sums, st);
-    return hipGetLastError();
-}
-
-hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long* vslot, VoxTable t,
-                                 const unsigned long long* sums, VoxGrid g, float* out, int32_t* out_cnt, hipStream_t s) {
-    if (nv == 0) return hipSuccess;
-    k_voxel_finalise<<<static_cast<unsigned>((nv + 255ull) / 256ull), 256, 0, s>>>(nv, vslot, t, sums, g, out, out_cnt);
-    return hipGetLastError();
-}
-
-// A plain copy of n 16-byte words on the compute queue (the state export / restart of a geom pass: at HBM
-// rate, where a device-to-device hipMemcpyAsync of the same 38 MB measured ~9 ms inside the pipeline's
-// overlapped passes)
-__global__ void k_copy16(const uint4* __restrict__ src, long long n, uint4* __restrict__ dst) {
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * blockDim.x)
-        dst[i] = src[i];
-}
-__global__ void k_copy4(const uint32_t* __restrict__ src, long long n, uint32_t* __restrict__ dst) {
-    for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * blockDim.x)
-        dst[i] = src[i];
-}
-
-hipError_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s) {
-    if (bytes == 0) return hipSuccess;
-    const bool wide = bytes % 16 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
-    const long long n = static_cast<long long>(wide ? bytes / 16 : bytes / 4);
-    const unsigned grd = static_cast<unsigned>(std::min<long long>((n + 255) / 256, 8192));
-    if (wide) k_copy16<<<grd, 256, 0, s>>>(static_cast<const uint4*>(src), n, static_cast<uint4*>(dst));
-    else k_copy4<<<grd, 256, 0, s>>>(static_cast<const uint32_t*>(src), n, static_cast<uint32_t*>(dst));
-    return hipGetLastError();
-}
-
-hipError_t launch_export_depth(const float4* planes, long long P, float* dst, hipStream_t s) {
-    k_export_depth<<<static_cast<unsigned>((P + 255) / 256), 256, 0, s>>>(planes, P, dst);
-    return hipGetLastError();
-}
-
 hipError_t launch_jbu(const float* ref, int W, int H, const float* coarse, int sw, int sh, int imagescale,
                       float* out, hipStream_t s) {
     dim3 blk(16, 16), grd(cdiv(W, 16), cdiv(H, 16));
     k_jbu<<<grd, blk, 0, s>>>(ref, W, H, coarse, sw, sh, imagescale, out);
     return hipGetLastError();
 }
-
-// ------------------------------------------------------------------ diagnostic: the shader clock under load
-//
-// Not on the PatchMatch path (acmmp_clock_probe, bench.py's `clock`).  The chip lowers its clock under load,
-// by different amounts on different devices (MI355X_MICROARCH.md "DVFS give-back" (5): 1.51-1.69 GHz across
-// devices for issue-dense bodies), and k_eval_nb is issue-dense: its time tracks that clock.  Eight independent
-// chains per lane of the logistic map x <- r x (1 - x) at r = 3.99 (a multiply and an fma per step): a
-// VALU-dense body whose operands stay chaotic, so their bits keep toggling as k_eval_nb's data does (an fma
-// chain converging to a fixed point draws less power and holds a higher clock, ibid. item 1); the first lane
-// of each workgroup reads the shader-cycle counter and the constant 100 MHz counter around the loop (ibid.
-// item 6), and the host takes the median of the per-workgroup ratios.
-__global__ __launch_bounds__(256) void k_clock_probe(const float* __restrict__ rnd, int iters, ClockStamp* stamps,
-                                                     float* __restrict__ sink) {
-    const unsigned gid = blockIdx.x * 256u + threadIdx.x;
-    float x[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = 0.25f + 0.5f * fabsf(rnd[(gid * 8u + k) & 65535u]);
-    constexpr float r = 3.99f;
-    unsigned long long t0 = 0, r0 = 0;
-    if (stamps) {
-        t0 = __builtin_amdgcn_s_memtime();
-        r0 = __builtin_amdgcn_s_memrealtime();
-    }
-    for (int i = 0; i < iters; ++i) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float t = r * x[k];
-            x[k] = fmaf(-t, x[k], t);
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += x[k];
-    if (stamps) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0) {
-            ClockStamp c;
-            c.cycles = t1 - t0;
-            c.ticks = r1 - r0;
-            stamps[blockIdx.x] = c;
-        }
-    }
-    sink[gid] = s;
-}
-
-hipError_t launch_clock_probe(const float* rnd, int iters, int blocks, ClockStamp* stamps, float* sink, hipStream_t s) {
-    k_clock_probe<<<blocks, 256, 0, s>>>(rnd, iters, stamps, sink);
-    return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ exchange check: checksum of a device buffer
-//
-// sum over the buffer's 32-bit words w_i of mix64((i << 32) | w_i) mod 2^64 (acmmp_device_checksum): a word's
-// value and position both enter, and the sum does not depend on the order it is formed in.  The pipeline
-// compares every rank's checksum of each map a pass exchanged (acmmp/pipeline.py RcclExchange), so a wrong
-// root, buffer or ordering in the grouped broadcast fails the run instead of feeding a wrong map on.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-__global__ __launch_bounds__(256) void k_checksum(const uint32_t* __restrict__ w, long long n, unsigned long long* out) {
-    unsigned long long acc = 0;
-    for (long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; i < n;
-         i += static_cast<long long>(gridDim.x) * 256)
-        acc += mix64((static_cast<unsigned long long>(i) << 32) | w[i]);
-    __shared__ unsigned long long part[256];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(out, part[0]);
-}
-
-hipError_t launch_checksum(const void* ptr, size_t bytes, unsigned long long* out, hipStream_t s) {
-    const long long n = static_cast<long long>(bytes / 4);
-    const unsigned grd = static_cast<unsigned>(std::max<long long>(1, std::min<long long>((n + 255) / 256, 2048)));
-    k_checksum<<<grd, 256, 0, s>>>(static_cast<const uint32_t*>(ptr), n, out);
-    return hipGetLastError();
-}
-
 #endif  // ACMMP_IN_TU(0)
 
 }  // namespace acmmp

@@ -1,6 +1,6 @@
 // planar.h -- internal split of the planar-prior block of ProcessProblem (main.cpp:113-181) between
 // the host (planar_prior.cpp: support points, Delaunay, per-triangle planes and sampling steps) and
-// the device (kernels.hip: triangle rasterisation, prior-depth range mask, per-pixel expansion).
+// the device (aux_kernels.hip: triangle rasterisation, prior-depth range mask, per-pixel expansion).
 // Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,7 +32,7 @@ acmmp_status planar_triangles(const acmmp_camera& cam, const float* depths, cons
 acmmp_status planar_triangles_pts(const acmmp_camera& cam, const std::vector<int>& xy,
                                   const std::vector<float>& depth_at, int W, int H, PlanarTriangles* out);
 
-// Device half (kernels.hip).  mask: P uint32 zeroed by the caller; prior: P float4.
+// Device half (aux_kernels.hip).  mask: P uint32 zeroed by the caller; prior: P float4.
 struct PlanarDev {
     const int* tri;
     const float* step;

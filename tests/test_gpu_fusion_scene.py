@@ -184,3 +184,82 @@ def test_scene_errors_leave_the_object_unchanged():
     gf.set_view(1, depths[1], normals[1], colours[1])
     assert not gf.used(1).any() and np.array_equal(gf.used(0), marks[0]) and np.array_equal(gf.used(2), marks[2])
     gf.close()
+
+
+def _same(got, want, what):
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert_bitwise_equal(a, b, what)
+
+
+def _scene(fu, refs, lists, unique=False):
+    """(counts, points, reference positions, pixels, source masks) of one run_scene."""
+    total, counts = fu.run_scene(refs, lists, unique=unique)
+    assert total == int(counts.sum())
+    return (counts, *fu.scene_points(0, total, provenance=True))
+
+
+def _voxels(fu):
+    """(points, counts per voxel, [voxels, occupied, rejected], origin) of voxelize(0.25)."""
+    nv, info = fu.voxelize(0.25)
+    return (*fu.voxel_points(0, nv, counts=True), np.array([nv, info["n_occupied"], info["n_rejected"]], np.int64),
+            info["origin"])
+
+
+def _oracle_scene(cams, depths, normals, colours, refs, lists):
+    of = fill(OracleFusion(cams), cams, depths, normals, colours)
+    want = [of.run(r, s) for r, s in zip(refs, lists)]
+    return np.array([w.shape[0] for w in want], np.int32), np.concatenate(want, 0)
+
+
+def test_one_object_across_regrowth_and_replacement():
+    """One capi.Fusion reused while its buffers are reallocated and replaced: scratch sized for the half-size
+    view then grown, a scene result replaced by a larger one (and the voxel result dropped with it), a view's
+    buffers replaced by set_view, the used masks filled and reset.  After each step the object gives what a fresh
+    object given the same inputs gives, and what the oracle / the restatement give."""
+    cams, depths, normals, colours, refs, lists = PLAIN_SCENES["rig_50x30_edges"]()
+    gf = fill(capi.Fusion(0, cams), cams, depths, normals, colours)
+    first_total, _ = gf.run_scene([3], [[0, 4]])                          # scratch sized for 25x15
+    first_vox = _voxels(gf)
+    assert first_total > 0 and first_vox[0].shape[0] > 0
+
+    # the whole list: the scratch grows, the scene result is replaced, the voxel result is gone
+    got4 = _scene(gf, refs, lists)
+    with pytest.raises(capi.AcmmpError):
+        gf.voxel_points(0, 1)
+    fresh = fill(capi.Fusion(0, cams), cams, depths, normals, colours)
+    _same(got4, _scene(fresh, refs, lists), "first full run vs a fresh object")
+    fresh.close()
+    want_counts, want_pts = _oracle_scene(cams, depths, normals, colours, refs, lists)
+    print("counts with view 2 empty", got4[0].tolist(), "after", first_total, "points of view 3 alone")
+    assert got4[0].tolist() == want_counts.tolist() and got4[0][1] == 0 and int(got4[0].sum()) > first_total
+    assert_bitwise_equal(got4[1], want_pts, "first full run vs oracle")
+
+    # view 2 gets its real depth map
+    depths = list(depths)
+    depths[2] = rig_inputs(50, 30, 5)[1][2]
+    gf.set_view(2, depths[2], normals[2], colours[2])
+    fresh = fill(capi.Fusion(0, cams), cams, depths, normals, colours)
+    rf = fill(RestatedFusion(cams), cams, depths, normals, colours)
+
+    got_u = _scene(gf, refs, lists, unique=True)
+    _same(got_u, _scene(fresh, refs, lists, unique=True), "unique run vs a fresh object")
+    rf_total, rf_counts = rf.run_scene(refs, lists, unique=True)
+    _same(got_u, (rf_counts, *rf.scene_points(0, rf_total, provenance=True)), "unique run vs the restatement")
+    for v in range(len(cams)):
+        assert np.array_equal(gf.used(v), rf.marks[v]) and np.array_equal(fresh.used(v), rf.marks[v])
+
+    gf.reset_used()
+    fresh.reset_used()
+    got6 = _scene(gf, refs, lists)
+    _same(got6, _scene(fresh, refs, lists), "second full run vs a fresh object")
+    want_counts, want_pts = _oracle_scene(cams, depths, normals, colours, refs, lists)
+    print("counts with view 2 set", got6[0].tolist(), "unique", got_u[0].tolist())
+    assert got6[0].tolist() == want_counts.tolist() and got6[0][1] > 0 and got6[0].tolist() != got4[0].tolist()
+    assert_bitwise_equal(got6[1], want_pts, "second full run vs oracle")
+
+    got_vox = _voxels(gf)
+    _same(got_vox, _voxels(fresh), "voxels vs a fresh object")
+    assert got_vox[0].shape[0] > 0
+    fresh.close()
+    gf.close()
