@@ -113,6 +113,8 @@ EXPORTS = [
     "acmmp_fusion_create", "acmmp_fusion_set_view", "acmmp_fusion_run", "acmmp_fusion_last_error",
     "acmmp_fusion_destroy", "acmmp_fusion_run_scene", "acmmp_fusion_scene_points", "acmmp_fusion_reset_used",
     "acmmp_fusion_download_used", "acmmp_fusion_voxelize", "acmmp_fusion_voxel_points", "acmmp_fusion_voxel_table",
+    "acmmp_fusion_set_scene", "acmmp_fusion_voxel_clean", "acmmp_fusion_clean_points", "acmmp_fusion_voxel_labels",
+    "acmmp_fusion_component_table",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -208,6 +210,11 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_voxelize.argtypes = [vp, C.c_float, vp, i32, vp, vp, vp, vp]
     L.acmmp_fusion_voxel_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_voxel_table.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.acmmp_fusion_set_scene.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.acmmp_fusion_voxel_clean.argtypes = [vp, i32, i32, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]
+    L.acmmp_fusion_clean_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_voxel_labels.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    L.acmmp_fusion_component_table.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -947,6 +954,60 @@ class Fusion:
         self._check(self.L.acmmp_fusion_voxel_table(self.h, int(force_slots), _p(st[0:1]), _p(st[1:2]), _p(st[2:3]),
                                                     _p(st[3:4])), "fusion_voxel_table")
         return {"slots": int(st[0]), "occupied": int(st[1]), "max_probe": int(st[2]), "wrapped": int(st[3])}
+
+    def set_scene(self, points, ref_index=None, pixel=None, src_mask=None):
+        """Replace the scene result with a host cloud, (n, 9) float32 taken bit for bit; the provenance arrays
+        default to -1 / -1 / 0 (acmmp_fusion_set_scene).  Discards the voxel and the clean result.  Returns n."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 9)
+        n = pts.shape[0]
+        opt = [None if a is None else np.ascontiguousarray(a, dt).reshape(-1)
+               for a, dt in ((ref_index, np.int32), (pixel, np.int32), (src_mask, np.uint32))]
+        if any(a is not None and a.size != n for a in opt):
+            raise ValueError("one provenance entry per point")
+        self._check(self.L.acmmp_fusion_set_scene(self.h, n, _p(pts) if n else None,
+                                                  *[None if a is None or n == 0 else _p(a) for a in opt]), "fusion_set_scene")
+        self.scene_total = n
+        return n
+
+    def voxel_clean(self, connectivity: int = 26, min_neighbours: int = 0, min_component_voxels: int = 1,
+                    min_component_points: int = 1):
+        """Drop the voxels of the last voxelize with fewer than min_neighbours occupied neighbours (6-, 18- or
+        26-connectivity), label the connected components of the rest and keep those of at least
+        min_component_voxels voxels and min_component_points points (acmmp_fusion_voxel_clean, include/acmmp.h).
+        The result stays on the GPU (clean_points, voxel_labels, component_table) until the next voxel_clean,
+        voxelize, run_scene or set_scene.
+        Returns (kept voxels, {"components", "components_kept", "unsupported", "rounds"})."""
+        out = np.zeros(5, np.int64)
+        self._check(self.L.acmmp_fusion_voxel_clean(self.h, int(connectivity), int(min_neighbours), int(min_component_voxels),
+                                                    int(min_component_points), *[_p(out[k:k + 1]) for k in range(5)]),
+                    "fusion_voxel_clean")
+        return int(out[0]), {"components": int(out[1]), "components_kept": int(out[2]), "unsupported": int(out[3]),
+                             "rounds": int(out[4])}
+
+    def clean_points(self, first: int, n: int, counts: bool = False, component: bool = False):
+        """Kept voxels [first, first + n) of the last voxel_clean, in voxel order: (n, 9) float32; with counts also
+        the points per voxel (int32), with component also the component id (int64)."""
+        pts = host_empty((max(n, 0), 9), np.float32)          # (a negative n is refused below)
+        cnt = np.empty(max(n, 0), np.int32) if counts else None
+        comp = np.empty(max(n, 0), np.int64) if component else None
+        self._check(self.L.acmmp_fusion_clean_points(self.h, first, n, _p(pts), None if cnt is None else _p(cnt),
+                                                     None if comp is None else _p(comp)), "fusion_clean_points")
+        extra = tuple(a for a in (cnt, comp) if a is not None)
+        return (pts, *extra) if extra else pts
+
+    def voxel_labels(self, first: int, n: int):
+        """(label int64, support int32) of voxels [first, first + n) of the voxel result, from the last voxel_clean:
+        the smallest voxel index of the voxel's component (-1: dropped for lack of support) and its neighbours."""
+        lab, sup = np.empty(max(n, 0), np.int64), np.empty(max(n, 0), np.int32)
+        self._check(self.L.acmmp_fusion_voxel_labels(self.h, first, n, _p(lab), _p(sup)), "fusion_voxel_labels")
+        return lab, sup
+
+    def component_table(self, first: int, n: int):
+        """(root, voxels, points), int64 each, of components [first, first + n) of the last voxel_clean, in
+        ascending order of root."""
+        out = [np.empty(max(n, 0), np.int64) for _ in range(3)]
+        self._check(self.L.acmmp_fusion_component_table(self.h, first, n, *[_p(a) for a in out]), "fusion_component_table")
+        return tuple(out)
 
     def close(self):
         if self.h:

@@ -789,7 +789,9 @@ class Pipeline:
     # -- RunFusionCuda (ACMMP.cu:1817-2105), after the last pass
     def run_fusion(self, fusion_factory=None, ply_path: str | None = None, unique: bool = False,
                    chunk_points: int = 1 << 22, max_host_points: int | None = None,
-                   voxel_size: float | None = None, voxel_min_points: int = 1):
+                   voxel_size: float | None = None, voxel_min_points: int = 1, voxel_connectivity: int = 26,
+                   voxel_min_neighbours: int = 0, voxel_min_component_voxels: int = 1,
+                   voxel_min_component_points: int = 1):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -807,8 +809,17 @@ class Pipeline:
         voxel_min_points points are dropped (acmmp_fusion_voxelize, include/acmmp.h) -- and that cloud, bounded
         by the scene's surface and not by the number of views, is what is streamed to the PLY, kept in self.fused
         and held to max_host_points.  self.fusion_info then tells the scene's points, the voxels and the
-        rejected points.  It needs a fusion object with voxelize (capi.Fusion)."""
+        rejected points.  It needs a fusion object with voxelize (capi.Fusion).
+
+        voxel_connectivity (6, 18, 26), voxel_min_neighbours, voxel_min_component_voxels, voxel_min_component_points:
+        when one of them is not its default (voxel_size is then required), the voxel cloud is cleaned on the device
+        -- voxels with fewer occupied neighbours are dropped, then connected components below either size
+        (acmmp_fusion_voxel_clean, include/acmmp.h) -- and the clean cloud takes the voxel cloud's place;
+        self.fusion_info gains clean_voxels, components, components_kept, unsupported, rounds and the four values."""
         self.fusion_info = None
+        clean = (voxel_connectivity, voxel_min_neighbours, voxel_min_component_voxels, voxel_min_component_points) != (26, 0, 1, 1)
+        if clean and voxel_size is None:
+            raise ValueError("cleaning the voxel cloud needs voxel_size")
         if self.world > 1:
             views = [p.ref_image_id for p in self.problems]
             owners = {self.problems[i].ref_image_id: self.owner(i) for i in range(len(self.problems))}
@@ -843,6 +854,18 @@ class Pipeline:
                                     "rejected": int(info["n_rejected"]), "occupied": int(info["n_occupied"]),
                                     "origin": [float(x) for x in info["origin"]], "voxel_size": float(voxel_size),
                                     "min_points": int(voxel_min_points)}
+                if clean:
+                    if not hasattr(fu, "voxel_clean"):
+                        raise ValueError("cleaning the voxel cloud needs a fusion object with voxel_clean (capi.Fusion)")
+                    total, cinfo = fu.voxel_clean(voxel_connectivity, voxel_min_neighbours, voxel_min_component_voxels,
+                                                  voxel_min_component_points)
+                    read = fu.clean_points
+                    self.fusion_info.update(
+                        clean_voxels=int(total), components=int(cinfo["components"]),
+                        components_kept=int(cinfo["components_kept"]), unsupported=int(cinfo["unsupported"]),
+                        rounds=int(cinfo["rounds"]), connectivity=int(voxel_connectivity),
+                        min_neighbours=int(voxel_min_neighbours), min_component_voxels=int(voxel_min_component_voxels),
+                        min_component_points=int(voxel_min_component_points))
             keep = max_host_points is None or total <= max_host_points
             points = np.zeros((total, 9), np.float32) if keep else None
             writer = io.PlyWriter(path, total) if path else None
@@ -958,6 +981,14 @@ def arg_parser():
                          "(centroid, mean normal, mean colour) and write that cloud")
     ap.add_argument("--voxel-min-points", type=int, default=1,
                     help="with --voxel-size: drop cells of fewer points than this")
+    ap.add_argument("--voxel-connectivity", type=int, choices=[6, 18, 26], default=26,
+                    help="with --voxel-size: which cells count as neighbours when the voxel cloud is cleaned")
+    ap.add_argument("--voxel-min-neighbours", type=int, default=0,
+                    help="with --voxel-size: drop voxels with fewer occupied neighbouring cells than this")
+    ap.add_argument("--min-component-voxels", type=int, default=1,
+                    help="with --voxel-size: drop connected components of fewer voxels than this")
+    ap.add_argument("--min-component-points", type=int, default=1,
+                    help="with --voxel-size: drop connected components of fewer fused points than this")
     return ap
 
 
@@ -982,7 +1013,10 @@ def main(argv=None):
     n_points = None
     if not a.no_fusion:
         pts = pipe.run_fusion(ply_path=os.path.join(a.dense_folder, "ACMMP", "ACMM_model_cuda_5.ply"),
-                              unique=a.unique_fusion, voxel_size=a.voxel_size, voxel_min_points=a.voxel_min_points)
+                              unique=a.unique_fusion, voxel_size=a.voxel_size, voxel_min_points=a.voxel_min_points,
+                              voxel_connectivity=a.voxel_connectivity, voxel_min_neighbours=a.voxel_min_neighbours,
+                              voxel_min_component_voxels=a.min_component_voxels,
+                              voxel_min_component_points=a.min_component_points)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -79,16 +79,29 @@ struct acmmp_fusion {
     // voxel-grid reduction of the scene result (acmmp_fusion_voxelize): its resident result ...
     DevBuf<float> v_pts;                         // 9 floats per voxel
     DevBuf<int32_t> v_cnt;                       // points per voxel
+    DevBuf<unsigned long long> v_slot;           // table slot per voxel (for acmmp_fusion_voxel_clean)
     unsigned long long v_total = 0;              // voxels held
+    bool v_have = false;                         // a voxelize has succeeded on this scene result
+    bool v_tab_live = false;                     // v_tab is the table of the voxel result held (else scratch)
     long long v_force_slots = 0;                 // test hook: table size of the next run, 0 = automatic
     long long v_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful run
     // ... and its scratch, kept between runs and dropped with the scene result it was sized for
-    VoxTableBuf v_tab;
+    VoxTableBuf v_tab, v_tab_spare;              // v_tab_spare: filled by a voxelize while v_tab belongs to a result
     DevBuf<int> v_flags;                         // per point of a segment
     DevBuf<int> v_counts, v_offsets;             // per 256-point chunk of a segment
     size_t v_cap_seg = 0;
     DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the segment base, then 3 minima (as 2 words)
     DevBuf<int> v_seg_count;
+    // cleaning of the voxel result (acmmp_fusion_voxel_clean): its resident result
+    DevBuf<float> c_pts;                         // 9 floats per kept voxel
+    DevBuf<int32_t> c_cnt;                       // points per kept voxel
+    DevBuf<long long> c_comp;                    // component id per kept voxel
+    DevBuf<unsigned long long> c_lab;            // per voxel of the voxel result: label, ~0 = unsupported
+    DevBuf<uint32_t> c_mask;                     // per voxel: its neighbours, one bit each
+    DevBuf<long long> c_table;                   // roots, then voxels, then points, c_comps of each
+    unsigned long long c_total = 0, c_comps = 0; // kept voxels, components
+    bool c_have = false;                         // a clean has succeeded on this voxel result
+    DevBuf<unsigned long long> c_words;          // kCleanWords device words
     std::string err;
 };
 
@@ -245,8 +258,26 @@ namespace {
 
 void voxel_scratch_release(acmmp_fusion* f) {
     f->v_tab = VoxTableBuf();
+    f->v_tab_spare = VoxTableBuf();
+    f->v_tab_live = false;
     f->v_flags.reset(); f->v_counts.reset(); f->v_offsets.reset();
     f->v_cap_seg = 0;
+}
+
+void clean_release(acmmp_fusion* f) {
+    f->c_pts.reset(); f->c_cnt.reset(); f->c_comp.reset(); f->c_lab.reset(); f->c_mask.reset(); f->c_table.reset();
+    f->c_total = f->c_comps = 0;
+    f->c_have = false;
+}
+
+// A new scene result is in place: the voxel result and the clean result described the previous one and go, with
+// the scratch sized for that scene.
+void scene_replaced(acmmp_fusion* f) {
+    f->v_pts.reset(); f->v_cnt.reset(); f->v_slot.reset();
+    f->v_total = 0;
+    f->v_have = false;
+    clean_release(f);
+    voxel_scratch_release(f);
 }
 
 // b := arrays of at least `need` points (geometric growth) holding b's first `live` points.  b is unchanged
@@ -387,10 +418,7 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
     f->scene = std::move(out);
     f->s_total = total;
     f->s_have = true;
-    // the voxel result described the previous scene: it goes, with the scratch sized for that scene
-    f->v_pts.reset(); f->v_cnt.reset();
-    f->v_total = 0;
-    voxel_scratch_release(f);
+    scene_replaced(f);
     if (counts) std::copy(view_counts.begin(), view_counts.end(), counts);
     *n_points = static_cast<int64_t>(total);
     return ACMMP_OK;
@@ -408,6 +436,44 @@ acmmp_status acmmp_fusion_scene_points(acmmp_fusion* f, int64_t first, int64_t n
     if (ref_index) F_HIP(f, hipMemcpy(ref_index, f->scene.ref + a, sizeof(int) * m, hipMemcpyDeviceToHost));
     if (pixel) F_HIP(f, hipMemcpy(pixel, f->scene.pix + a, sizeof(int) * m, hipMemcpyDeviceToHost));
     if (src_mask) F_HIP(f, hipMemcpy(src_mask, f->scene.mask + a, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_set_scene(acmmp_fusion* f, int64_t n, const float* points, const int32_t* ref_index,
+                                    const int32_t* pixel, const uint32_t* src_mask) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (n < 0 || (n > 0 && !points)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t m = static_cast<size_t>(n);
+    // built beside the present scene result, installed when every copy has succeeded
+    SceneBuf out;
+    out.cap = m;
+    F_HIP(f, alloc(out.pts, 9 * m));
+    F_HIP(f, alloc(out.ref, m));
+    F_HIP(f, alloc(out.pix, m));
+    F_HIP(f, alloc(out.mask, m));
+    hipStream_t s = f->stream;
+    const hipError_t e = [&]() -> hipError_t {
+        if (m == 0) return hipSuccess;
+        hipError_t r = hipMemcpyAsync(out.pts, points, sizeof(float) * 9 * m, hipMemcpyHostToDevice, s);
+        if (r == hipSuccess)
+            r = ref_index ? hipMemcpyAsync(out.ref, ref_index, sizeof(int) * m, hipMemcpyHostToDevice, s)
+                          : hipMemsetAsync(out.ref, 0xff, sizeof(int) * m, s);
+        if (r == hipSuccess)
+            r = pixel ? hipMemcpyAsync(out.pix, pixel, sizeof(int) * m, hipMemcpyHostToDevice, s)
+                      : hipMemsetAsync(out.pix, 0xff, sizeof(int) * m, s);
+        if (r == hipSuccess)
+            r = src_mask ? hipMemcpyAsync(out.mask, src_mask, sizeof(uint32_t) * m, hipMemcpyHostToDevice, s)
+                         : hipMemsetAsync(out.mask, 0, sizeof(uint32_t) * m, s);
+        return r;
+    }();
+    const hipError_t w = hipStreamSynchronize(s);      // the host arrays are the caller's again, also after a failure
+    F_HIP(f, e);
+    F_HIP(f, w);
+    f->scene = std::move(out);
+    f->s_total = static_cast<unsigned long long>(n);
+    f->s_have = true;
+    scene_replaced(f);
     return ACMMP_OK;
 }
 
@@ -460,30 +526,39 @@ struct VoxelOut {
     DevBuf<unsigned long long> vslot;        // scratch: table slot per kept voxel
 };
 
-acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_points, unsigned long long slots,
-                       int log2_slots, VoxelOut& out, unsigned long long words[kVoxWords]) {
-    hipStream_t s = f->stream;
-    const unsigned long long N = f->s_total, seg = voxel_segment_points();
-    const size_t seg_pts = static_cast<size_t>(std::min(N, seg)), seg_chunks = (seg_pts + 255) / 256;
-    // scratch
-    if (!f->v_words) F_HIP(f, alloc(f->v_words, kVoxWords + 3));
+// The per-segment scratch of the compactions (voxelize's per point, clean's per voxel).
+acmmp_status segment_scratch(acmmp_fusion* f, size_t seg_pts) {
     if (!f->v_seg_count) F_HIP(f, alloc(f->v_seg_count, 1));
-    if (f->v_tab.slots != slots) {
-        f->v_tab.slots = 0;
-        F_HIP(f, alloc(f->v_tab.keys, slots));
-        F_HIP(f, alloc(f->v_tab.first, slots));
-        F_HIP(f, alloc(f->v_tab.oid, slots));
-        F_HIP(f, alloc(f->v_tab.cnt, slots));
-        f->v_tab.slots = slots;
-    }
     if (f->v_cap_seg < seg_pts) {
+        const size_t seg_chunks = (seg_pts + 255) / 256;
         f->v_cap_seg = 0;
         F_HIP(f, alloc(f->v_flags, seg_pts));
         F_HIP(f, alloc(f->v_counts, seg_chunks));
         F_HIP(f, alloc(f->v_offsets, seg_chunks));
         f->v_cap_seg = seg_pts;
     }
-    const VoxTable t = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, slots, log2_slots};
+    return ACMMP_OK;
+}
+
+// `tab`: the table the run fills -- the object's scratch table, or a new one while the object's belongs to the
+// voxel result held, which a failed run must leave usable.
+acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_points, unsigned long long slots,
+                       int log2_slots, VoxTableBuf& tab, VoxelOut& out, unsigned long long words[kVoxWords]) {
+    hipStream_t s = f->stream;
+    const unsigned long long N = f->s_total, seg = voxel_segment_points();
+    // scratch
+    if (!f->v_words) F_HIP(f, alloc(f->v_words, kVoxWords + 3));
+    if (tab.slots != slots) {
+        tab.slots = 0;
+        F_HIP(f, alloc(tab.keys, slots));
+        F_HIP(f, alloc(tab.first, slots));
+        F_HIP(f, alloc(tab.oid, slots));
+        F_HIP(f, alloc(tab.cnt, slots));
+        tab.slots = slots;
+    }
+    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(N, seg)));
+    if (scratch != ACMMP_OK) return scratch;
+    const VoxTable t = {tab.keys, tab.first, tab.oid, tab.cnt, slots, log2_slots};
     unsigned long long* st = f->v_words;
     unsigned long long* seg_base = f->v_words + kVoxWords;
     uint32_t* mn = reinterpret_cast<uint32_t*>(f->v_words + kVoxWords + 1);
@@ -577,20 +652,32 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     g.inv = 1.0f / voxel_size;
     VoxelOut out;
     unsigned long long words[kVoxWords] = {0};
+    // the table of the voxel result held stays as it is until the run has succeeded: the run fills the spare one,
+    // and the two change places
+    VoxTableBuf& from = f->v_tab_live ? f->v_tab_spare : f->v_tab;
+    VoxTableBuf tab = std::move(from);
+    from = VoxTableBuf();
     if (N > 0) {
-        const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, log2_slots, out, words);
+        const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, log2_slots, tab, out, words);
         if (st != ACMMP_OK) {
             const std::string why = f->err;
             (void)hipGetLastError();
             (void)hipStreamSynchronize(f->stream);
+            from = std::move(tab);
             f->err = why;
             return st;
         }
     }
-    out.sums.reset(); out.vslot.reset();
+    out.sums.reset();
+    if (f->v_tab_live) f->v_tab_spare = std::move(f->v_tab);
+    f->v_tab = std::move(tab);
+    f->v_tab_live = N > 0;
     f->v_pts = std::move(out.pts);
     f->v_cnt = std::move(out.cnt);
+    f->v_slot = std::move(out.vslot);
     f->v_total = words[kVoxKept];
+    f->v_have = true;
+    clean_release(f);                                 // it described the previous voxel result
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
     f->v_stats[2] = static_cast<long long>(words[kVoxMaxProbe]);
@@ -622,6 +709,185 @@ acmmp_status acmmp_fusion_voxel_table(acmmp_fusion* f, int64_t force_slots, int6
     if (occupied) *occupied = f->v_stats[1];
     if (max_probe) *max_probe = f->v_stats[2];
     if (wrapped) *wrapped = f->v_stats[3];
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- cleaning the voxel result (include/acmmp.h; kernels: k_clean_*) ---------------------------------------
+
+namespace {
+
+// The new result of a clean run, swapped in only when the whole run succeeded.
+struct CleanOut {
+    DevBuf<float> pts;
+    DevBuf<int32_t> cnt;
+    DevBuf<long long> comp, table;
+    DevBuf<unsigned long long> lab;
+    DevBuf<uint32_t> mask;
+    DevBuf<unsigned long long> scratch;      // per voxel: component voxels, points, dense id
+    unsigned long long kept = 0, comps = 0, comps_kept = 0, unsupported = 0, rounds = 0;
+};
+
+acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, unsigned long long min_voxels,
+                       unsigned long long min_points, CleanOut& out) {
+    hipStream_t s = f->stream;
+    const unsigned long long nv = f->v_total, seg = voxel_segment_points();
+    const size_t n = static_cast<size_t>(nv);
+    if (!f->c_words) F_HIP(f, alloc(f->c_words, kCleanWords));
+    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(nv, seg)));
+    if (scratch != ACMMP_OK) return scratch;
+    F_HIP(f, alloc(out.lab, n));
+    F_HIP(f, alloc(out.mask, n));
+    F_HIP(f, alloc(out.scratch, 3 * n));
+    int log2_slots = 0;
+    while ((1ull << log2_slots) < f->v_tab.slots) ++log2_slots;
+    const VoxTable t = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, f->v_tab.slots, log2_slots};
+    unsigned long long* w = f->c_words;
+    const CleanComp c = {out.scratch, out.scratch + n, out.scratch + 2 * n, min_voxels, min_points};
+    unsigned long long h[kCleanWords] = {0};
+    F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kCleanWords, s));
+    F_HIP(f, hipMemsetAsync(out.scratch, 0, sizeof(unsigned long long) * 2 * n, s));
+    F_HIP(f, launch_clean_support(nv, f->v_slot, t, connectivity, min_neighbours, out.mask, out.lab, w, s));
+    // Rounds until one lowers no label.  After k rounds a label is at most the smallest index within k edges, so
+    // nv rounds settle every label and one more sees no change: a run past that bound has gone wrong.
+    for (;;) {
+        if (out.rounds > nv + 1) return ffail(f, ACMMP_ERR_HIP, "voxel clean: the labelling did not settle in nv + 2 rounds");
+        ++out.rounds;
+        F_HIP(f, hipMemsetAsync(w + kCleanChanged, 0, sizeof(unsigned long long), s));
+        F_HIP(f, launch_clean_round(nv, f->v_slot, t, out.mask, out.lab, w, s));
+        F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        if (h[kCleanErr]) return ffail(f, ACMMP_ERR_HIP, "voxel clean: lookup failed (flags " + std::to_string(h[kCleanErr]) + ")");
+        if (!h[kCleanChanged]) break;
+    }
+    F_HIP(f, launch_clean_sizes(nv, out.lab, f->v_cnt, c, w, s));
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kCleanWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    out.unsupported = h[kCleanUnsupported];
+    out.comps = h[kCleanComps];
+    out.comps_kept = h[kCleanCompsKept];
+    out.kept = h[kCleanKept];
+    if (out.comps > nv || out.kept > nv) return ffail(f, ACMMP_ERR_HIP, "voxel clean: counts beyond the voxel result");
+    const size_t nc = static_cast<size_t>(out.comps), nk = static_cast<size_t>(out.kept);
+    F_HIP(f, alloc(out.table, 3 * nc));
+    F_HIP(f, alloc(out.pts, 9 * nk));
+    F_HIP(f, alloc(out.cnt, nk));
+    F_HIP(f, alloc(out.comp, nk));
+    // the roots, then the kept voxels, each compacted in voxel order, segment after segment
+    unsigned long long* running = w + kCleanRunning;
+    unsigned long long* seg_base = w + kCleanSegBase;
+    unsigned long long done[2] = {0, 0};
+    for (unsigned long long i0 = 0; i0 < nv; i0 += seg)
+        F_HIP(f, launch_clean_compact_roots(nv, i0, static_cast<int>(std::min(seg, nv - i0)), out.lab, c, f->v_flags,
+                                            f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.comps,
+                                            out.table, out.table + nc, out.table + 2 * nc, s));
+    F_HIP(f, hipMemcpyAsync(&done[0], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
+    for (unsigned long long i0 = 0; i0 < nv; i0 += seg)
+        F_HIP(f, launch_clean_compact_kept(nv, i0, static_cast<int>(std::min(seg, nv - i0)), out.lab, c, f->v_flags,
+                                           f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
+                                           f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, s));
+    F_HIP(f, hipMemcpyAsync(&done[1], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (done[0] != out.comps || done[1] != out.kept)
+        return ffail(f, ACMMP_ERR_HIP, "voxel clean: compacted " + std::to_string(done[0]) + " of " + std::to_string(out.comps) +
+                                           " components, " + std::to_string(done[1]) + " of " + std::to_string(out.kept) + " voxels");
+    return ACMMP_OK;
+}
+
+// Copies [first, first + n) of `count`-element device arrays to the host ones that are not NULL.
+template <typename T>
+hipError_t read_range(T* dst, const T* src, size_t first, size_t n, size_t per = 1) {
+    return dst ? hipMemcpy(dst, src + per * first, sizeof(T) * per * n, hipMemcpyDeviceToHost) : hipSuccess;
+}
+
+bool bad_range(int64_t first, int64_t n, unsigned long long total) {
+    return static_cast<unsigned long long>(first) > total || static_cast<unsigned long long>(n) > total - first;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min_neighbours, int64_t min_component_voxels,
+                                      int64_t min_component_points, int64_t* n_kept, int64_t* n_components,
+                                      int64_t* n_components_kept, int64_t* n_unsupported, int64_t* rounds) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "connectivity must be 6, 18 or 26");
+    if (min_neighbours < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_neighbours must not be negative");
+    if (min_component_voxels < 1 || min_component_points < 1)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "component thresholds must be at least 1");
+    if (!f->v_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no voxel result: acmmp_fusion_voxelize first");
+    F_HIP(f, hipSetDevice(f->device));
+    CleanOut out;
+    if (f->v_total > 0) {
+        const acmmp_status st = clean_run(f, connectivity, min_neighbours, static_cast<unsigned long long>(min_component_voxels),
+                                          static_cast<unsigned long long>(min_component_points), out);
+        if (st != ACMMP_OK) {
+            const std::string why = f->err;
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(f->stream);
+            f->err = why;
+            return st;
+        }
+    }
+    f->c_pts = std::move(out.pts);
+    f->c_cnt = std::move(out.cnt);
+    f->c_comp = std::move(out.comp);
+    f->c_lab = std::move(out.lab);
+    f->c_mask = std::move(out.mask);
+    f->c_table = std::move(out.table);
+    f->c_total = out.kept;
+    f->c_comps = out.comps;
+    f->c_have = true;
+    if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
+    if (n_components) *n_components = static_cast<int64_t>(out.comps);
+    if (n_components_kept) *n_components_kept = static_cast<int64_t>(out.comps_kept);
+    if (n_unsupported) *n_unsupported = static_cast<int64_t>(out.unsupported);
+    if (rounds) *rounds = static_cast<int64_t>(out.rounds);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_clean_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts,
+                                       int64_t* component) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->c_total)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the clean result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    F_HIP(f, read_range<float>(points, f->c_pts, a, m, 9));
+    F_HIP(f, read_range<int32_t>(counts, f->c_cnt, a, m));
+    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(component), f->c_comp, a, m));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_voxel_labels(acmmp_fusion* f, int64_t first, int64_t n, int64_t* label, int32_t* support) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->c_have ? f->v_total : 0ull))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the labelled voxel result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    // the device holds ~0 for an unsupported voxel, which reads as -1, and the neighbours as one bit each
+    F_HIP(f, read_range<unsigned long long>(reinterpret_cast<unsigned long long*>(label), f->c_lab, a, m));
+    F_HIP(f, read_range<uint32_t>(reinterpret_cast<uint32_t*>(support), f->c_mask, a, m));
+    if (support)
+        for (size_t i = 0; i < m; ++i) support[i] = __builtin_popcount(static_cast<uint32_t>(support[i]));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_component_table(acmmp_fusion* f, int64_t first, int64_t n, int64_t* root, int64_t* voxels,
+                                          int64_t* points) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->c_comps)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the component table");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n), nc = static_cast<size_t>(f->c_comps);
+    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(root), f->c_table, a, m));
+    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(voxels), f->c_table + nc, a, m));
+    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(points), f->c_table + 2 * nc, a, m));
     return ACMMP_OK;
 }
 

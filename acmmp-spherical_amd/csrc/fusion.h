@@ -90,4 +90,43 @@ hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int 
 hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long* vslot, VoxTable t,
                                  const unsigned long long* sums, VoxGrid g, float* out, int32_t* out_cnt, hipStream_t s);
 
+// Cleaning the voxel cloud (acmmp_fusion_voxel_clean, include/acmmp.h): over the voxels [0, nv) of a
+// voxel result, vslot[v] their slots in the table `t` that voxelize filled, one lane per voxel.
+// Device words of a clean run (all zero before it; kCleanChanged is zeroed before every round).
+enum { kCleanErr = 0, kCleanChanged = 1, kCleanUnsupported = 2, kCleanComps = 3, kCleanCompsKept = 4, kCleanKept = 5,
+       kCleanRunning = 6, kCleanSegBase = 7, kCleanWords = 8 };
+// Per-voxel scratch of the component table, meaningful at a component's root (its smallest voxel): voxels, points
+// (both zero before the run), dense id; and the two thresholds of step 5.
+struct CleanComp {
+    unsigned long long* voxels;
+    unsigned long long* points;
+    unsigned long long* id;
+    unsigned long long min_voxels, min_points;
+};
+// nbmask[v] = bit (dz+1)*9 + (dy+1)*3 + (dx+1) per neighbouring voxel under `connectivity` (6, 18, 26); lab[v] = v when
+// their number is >= min_neighbours, else ~0; words[kCleanUnsupported] += the others.  words[kCleanErr] |= 1 for a
+// slot outside the table, 2 for a probe sequence that covered every slot.
+hipError_t launch_clean_support(unsigned long long nv, const unsigned long long* vslot, VoxTable t, int connectivity,
+                                int min_neighbours, uint32_t* nbmask, unsigned long long* lab, unsigned long long* words,
+                                hipStream_t s);
+// One labelling round (k_clean_round): words[kCleanChanged] |= 1 when a label was lowered; words[kCleanErr] |= 4 for
+// a neighbour of nbmask that the table no longer gives, 8 for a label chain longer than nv.
+hipError_t launch_clean_round(unsigned long long nv, const unsigned long long* vslot, VoxTable t, const uint32_t* nbmask,
+                              unsigned long long* lab, unsigned long long* words, hipStream_t s);
+// After the last round: c.voxels / c.points at every root, then words[kCleanComps], [kCleanCompsKept], [kCleanKept].
+hipError_t launch_clean_sizes(unsigned long long nv, const unsigned long long* lab, const int32_t* cnt, CleanComp c,
+                              unsigned long long* words, hipStream_t s);
+// Compaction of voxels [i0, i0 + n) (one segment, as launch_voxel_compact): the roots to the component table and
+// c.id[root]; then, once every segment's roots are through, the kept voxels to the clean cloud.  Nothing is written
+// at or past `cap` entries.
+hipError_t launch_clean_compact_roots(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
+                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
+                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                      long long* out_root, long long* out_voxels, long long* out_points, hipStream_t s);
+hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
+                                     CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
+                                     unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                     const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
+                                     long long* out_comp, hipStream_t s);
+
 }  // namespace acmmp

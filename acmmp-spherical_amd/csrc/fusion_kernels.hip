@@ -593,4 +593,294 @@ hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ cleaning the voxel cloud
+//
+// acmmp_fusion_voxel_clean (include/acmmp.h): support count, connected components and the kept
+// voxels of the resident voxel result, through the table that voxelize left (cell -> slot -> oid).  Everything
+// is an integer, and every atomic is a minimum, an or or an integer add: no result depends on the order they land in.
+
+// The lookup of a cell that may be absent: 0 = found, 1 = absent, 2 = the probe sequence covered every slot.
+__device__ __forceinline__ int clean_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        const unsigned long long k = t.keys[s];
+        if (k == key) { slot = s; return 0; }
+        if (k == kVoxEmpty) return 1;
+        s = (s + 1ull) & mask;
+    }
+    return 2;
+}
+
+// Neighbour `b` (0 .. 27, b = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)) of the cell `key`, offsets applied per axis
+// on the unpacked 21-bit indices; false = that cell does not exist.
+__device__ __forceinline__ bool clean_neighbour(unsigned long long key, int b, unsigned long long& nkey) {
+    const int d[3] = {b % 3 - 1, (b / 3) % 3 - 1, b / 9 - 1};
+    nkey = 0;
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int g = static_cast<int>((key >> (21 * a)) & 0x1fffffull) + d[a];
+        ok = ok && g >= 0 && g < (1 << 21);
+        nkey |= static_cast<unsigned long long>(ok ? g : 0) << (21 * a);
+    }
+    return ok;
+}
+
+// *word |= the or of `bits` over the workgroup, one atomic per workgroup.  Every lane calls it.
+__device__ __forceinline__ void block_or(unsigned bits, unsigned long long* word) {
+    __shared__ unsigned acc;
+    if (threadIdx.x == 0) acc = 0u;
+    __syncthreads();
+    if (bits) atomicOr(&acc, bits);
+    __syncthreads();
+    if (threadIdx.x == 0 && acc) atomicOr(word, static_cast<unsigned long long>(acc));
+}
+
+// *word += the sum of x over the wave, one atomic per wave.  Every lane of the wave calls it.
+__device__ __forceinline__ void wave_add(unsigned long long x, unsigned long long* word) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+    if ((threadIdx.x & 63) == 0 && x) atomicAdd(word, x);
+}
+
+// Step 1 and 2: nbmask[v] = bit b set when neighbour b of voxel v is a voxel (its popcount is support(v)),
+// lab[v] = v for a supported voxel and ~0 for the others.
+__global__ __launch_bounds__(256) void k_clean_support(unsigned long long nv, const unsigned long long* __restrict__ vslot,
+                                                       const VoxTable t, int max_l1, int min_neighbours,
+                                                       uint32_t* __restrict__ nbmask, unsigned long long* __restrict__ lab,
+                                                       unsigned long long* __restrict__ words) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    unsigned long long unsupported = 0;
+    if (v < nv) {
+        const unsigned long long s = vslot[v];
+        uint32_t m = 0u;
+        if (s >= t.slots) {
+            err |= 1u;
+        } else {
+            const unsigned long long key = t.keys[s];
+            for (int b = 0; b < 27; ++b) {
+                const int l1 = abs(b % 3 - 1) + abs((b / 3) % 3 - 1) + abs(b / 9 - 1);
+                unsigned long long nkey, ns;
+                if (l1 == 0 || l1 > max_l1 || !clean_neighbour(key, b, nkey)) continue;
+                const int r = clean_find(t, nkey, ns);
+                if (r == 2) err |= 2u;
+                if (r == 0 && t.oid[ns] < nv) m |= 1u << b;          // a cell below min_points has no oid
+            }
+        }
+        const bool in = __popc(m) >= min_neighbours;
+        nbmask[v] = m;
+        lab[v] = in ? v : kVoxEmpty;
+        unsupported = in ? 0ull : 1ull;
+    }
+    wave_add(unsupported, &words[kCleanUnsupported]);
+    block_or(err, &words[kCleanErr]);
+}
+
+// One labelling round.  lab[x] only ever holds the index of a supported voxel of x's component that is <= x, and
+// only ever decreases, so whatever a load returns here -- the value at the start of the launch or one that another
+// workgroup has written since -- is such an index: a stale load can cost a round, never correctness.  A voxel takes
+// the smallest label among its own and its supported neighbours', follows the labels from there to a voxel that
+// labels itself (at most nv steps: each is strictly smaller), and lowers its label and its previous label's to it.
+// A launch in which no lane lowers anything has read only the values of its start, which then satisfy
+// lab[v] <= lab[u] over every edge and lab[lab[v]] = lab[v]: the smallest index of each component.
+__global__ __launch_bounds__(256) void k_clean_round(unsigned long long nv, const unsigned long long* __restrict__ vslot,
+                                                     const VoxTable t, const uint32_t* __restrict__ nbmask,
+                                                     unsigned long long* lab, unsigned long long* __restrict__ words) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u, changed = 0u;
+    const unsigned long long cur = v < nv ? lab[v] : kVoxEmpty;
+    const unsigned long long slot = v < nv ? vslot[v] : kVoxEmpty;
+    if (cur != kVoxEmpty && slot >= t.slots) {
+        err |= 1u;
+    } else if (cur != kVoxEmpty) {
+        unsigned long long m = cur;
+        const unsigned long long key = t.keys[slot];
+        for (uint32_t left = nbmask[v]; left; left &= left - 1u) {
+            unsigned long long nkey, ns;
+            if (!clean_neighbour(key, __ffs(static_cast<int>(left)) - 1, nkey) || clean_find(t, nkey, ns) != 0) { err |= 4u; continue; }
+            const unsigned long long o = t.oid[ns];
+            if (o >= nv) { err |= 4u; continue; }
+            m = min(m, lab[o]);                                      // ~0 (unsupported) never wins
+        }
+        unsigned long long steps = 0;
+        for (; steps <= nv && m < nv; ++steps) {
+            const unsigned long long p = lab[m];
+            if (p >= m) break;
+            m = p;
+        }
+        if (steps > nv || m >= nv) {
+            err |= 8u;
+        } else if (m < cur) {
+            atomicMin(&lab[v], m);
+            atomicMin(&lab[cur], m);
+            changed = 1u;
+        }
+    }
+    block_or(changed, &words[kCleanChanged]);
+    block_or(err, &words[kCleanErr]);
+}
+
+// Step 4's sizes: cvox[label] += 1, cpts[label] += count, 64-bit integer adds.  A wave whose supported lanes share
+// one label -- the usual case, a surface is few components -- adds once.
+__global__ __launch_bounds__(256) void k_clean_sizes(unsigned long long nv, const unsigned long long* __restrict__ lab,
+                                                     const int32_t* __restrict__ cnt, unsigned long long* __restrict__ cvox,
+                                                     unsigned long long* __restrict__ cpts) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    const unsigned long long L = v < nv ? lab[v] : kVoxEmpty;
+    const bool in = L < nv;
+    unsigned long long c = in ? static_cast<unsigned long long>(cnt[v]) : 0ull;
+    const unsigned long long active = __ballot(in);
+    if (!active) return;
+    const int leader = __ffsll(active) - 1;
+    const unsigned long long Lf = __shfl(L, leader);
+    if (__all(!in || L == Lf)) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+        if ((threadIdx.x & 63) == leader) {
+            atomicAdd(&cvox[Lf], static_cast<unsigned long long>(__popcll(active)));
+            atomicAdd(&cpts[Lf], c);
+        }
+    } else if (in) {
+        atomicAdd(&cvox[L], 1ull);
+        atomicAdd(&cpts[L], c);
+    }
+}
+
+__device__ __forceinline__ bool clean_component_kept(unsigned long long L, const unsigned long long* __restrict__ cvox,
+                                                     const unsigned long long* __restrict__ cpts, unsigned long long min_voxels,
+                                                     unsigned long long min_points) {
+    return cvox[L] >= min_voxels && cpts[L] >= min_points;
+}
+
+// components, kept components and kept voxels
+__global__ __launch_bounds__(256) void k_clean_count(unsigned long long nv, const unsigned long long* __restrict__ lab,
+                                                     const unsigned long long* __restrict__ cvox,
+                                                     const unsigned long long* __restrict__ cpts, unsigned long long min_voxels,
+                                                     unsigned long long min_points, unsigned long long* __restrict__ words) {
+    const unsigned long long v = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    const unsigned long long L = v < nv ? lab[v] : kVoxEmpty;
+    const bool in = L < nv;
+    const bool kept = in && clean_component_kept(L, cvox, cpts, min_voxels, min_points);
+    wave_add(in && L == v ? 1ull : 0ull, &words[kCleanComps]);
+    wave_add(kept && L == v ? 1ull : 0ull, &words[kCleanCompsKept]);
+    wave_add(kept ? 1ull : 0ull, &words[kCleanKept]);
+}
+
+// flags[i] of voxel i0 + i: KEPT = false, it labels itself (the root of a component); KEPT = true, it is kept.
+template <bool KEPT>
+__global__ __launch_bounds__(256) void k_clean_mark(unsigned long long nv, unsigned long long i0, int n,
+                                                    const unsigned long long* __restrict__ lab,
+                                                    const unsigned long long* __restrict__ cvox,
+                                                    const unsigned long long* __restrict__ cpts, unsigned long long min_voxels,
+                                                    unsigned long long min_points, int* __restrict__ flags,
+                                                    int* __restrict__ counts) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const unsigned long long v = i0 + static_cast<unsigned long long>(i);
+    int f = 0;
+    if (i < n) {
+        const unsigned long long L = lab[v];
+        if (L < nv) f = KEPT ? (clean_component_kept(L, cvox, cpts, min_voxels, min_points) ? 1 : 0) : (L == v ? 1 : 0);
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// the roots in ascending order: component id = *seg_base + offsets[chunk] + rank, its table entry, cid[root] = id
+__global__ __launch_bounds__(256) void k_clean_scatter_roots(unsigned long long i0, int n, const int* __restrict__ flags,
+                                                             const int* __restrict__ offsets,
+                                                             const unsigned long long* __restrict__ seg_base,
+                                                             unsigned long long cap, const unsigned long long* __restrict__ cvox,
+                                                             const unsigned long long* __restrict__ cpts,
+                                                             unsigned long long* __restrict__ cid, long long* __restrict__ out_root,
+                                                             long long* __restrict__ out_voxels, long long* __restrict__ out_points) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    if (f && pos < cap) {
+        const unsigned long long v = i0 + static_cast<unsigned long long>(i);
+        cid[v] = pos;
+        out_root[pos] = static_cast<long long>(v);
+        out_voxels[pos] = static_cast<long long>(cvox[v]);
+        out_points[pos] = static_cast<long long>(cpts[v]);
+    }
+}
+
+// the kept voxels in ascending order: the voxel's 9 floats and count as they are, and its component's id
+__global__ __launch_bounds__(256) void k_clean_scatter_kept(unsigned long long i0, int n, const int* __restrict__ flags,
+                                                            const int* __restrict__ offsets,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            unsigned long long cap, const unsigned long long* __restrict__ lab,
+                                                            const unsigned long long* __restrict__ cid,
+                                                            const float* __restrict__ v_pts, const int32_t* __restrict__ v_cnt,
+                                                            float* __restrict__ out, int32_t* __restrict__ out_cnt,
+                                                            long long* __restrict__ out_comp) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    if (f && pos < cap) {
+        const unsigned long long v = i0 + static_cast<unsigned long long>(i);
+        const float* src = v_pts + 9ull * v;
+        float* dst = out + 9ull * pos;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dst[k] = src[k];
+        out_cnt[pos] = v_cnt[v];
+        out_comp[pos] = static_cast<long long>(cid[lab[v]]);
+    }
+}
+
+static unsigned clean_blocks(unsigned long long nv) { return static_cast<unsigned>((nv + 255ull) / 256ull); }
+
+hipError_t launch_clean_support(unsigned long long nv, const unsigned long long* vslot, VoxTable t, int connectivity,
+                                int min_neighbours, uint32_t* nbmask, unsigned long long* lab, unsigned long long* words,
+                                hipStream_t s) {
+    const int max_l1 = connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3;
+    k_clean_support<<<clean_blocks(nv), 256, 0, s>>>(nv, vslot, t, max_l1, min_neighbours, nbmask, lab, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_clean_round(unsigned long long nv, const unsigned long long* vslot, VoxTable t, const uint32_t* nbmask,
+                              unsigned long long* lab, unsigned long long* words, hipStream_t s) {
+    k_clean_round<<<clean_blocks(nv), 256, 0, s>>>(nv, vslot, t, nbmask, lab, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_clean_sizes(unsigned long long nv, const unsigned long long* lab, const int32_t* cnt, CleanComp c,
+                              unsigned long long* words, hipStream_t s) {
+    k_clean_sizes<<<clean_blocks(nv), 256, 0, s>>>(nv, lab, cnt, c.voxels, c.points);
+    k_clean_count<<<clean_blocks(nv), 256, 0, s>>>(nv, lab, c.voxels, c.points, c.min_voxels, c.min_points, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_clean_compact_roots(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
+                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
+                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                      long long* out_root, long long* out_voxels, long long* out_points, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_clean_mark<false><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(nv, i0, n, lab, c.voxels, c.points, c.min_voxels,
+                                                                        c.min_points, flags, counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_clean_scatter_roots<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, c.voxels,
+                                                                          c.points, c.id, out_root, out_voxels, out_points);
+    return hipGetLastError();
+}
+
+hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
+                                     CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
+                                     unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                     const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
+                                     long long* out_comp, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_clean_mark<true><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(nv, i0, n, lab, c.voxels, c.points, c.min_voxels,
+                                                                       c.min_points, flags, counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_clean_scatter_kept<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, lab, c.id,
+                                                                         v_pts, v_cnt, out, out_cnt, out_comp);
+    return hipGetLastError();
+}
+
 }  // namespace acmmp

@@ -378,7 +378,7 @@ acmmp_status acmmp_fusion_download_used(acmmp_fusion *f, int view, uint8_t *mask
  * acmmp_fusion_voxelize reduces the resident scene result, points 0 .. N in their order, to one point per
  * occupied cell of a grid of `voxel_size` (finite, > 0): centroid, mean normal, mean colour and the number of
  * points.  The scene result is left untouched; the voxel result stays in HBM beside it until the next
- * successful voxelize replaces it or the next successful acmmp_fusion_run_scene discards it.
+ * successful voxelize replaces it or the next successful acmmp_fusion_run_scene / acmmp_fusion_set_scene discards it.
  *
  * The result is defined in integers, so that it is bit-reproducible and the same whatever order the device's
  * atomics land in.  With inv = 1.0f / voxel_size and plain IEEE float32 arithmetic (no contraction):
@@ -415,6 +415,59 @@ acmmp_status acmmp_fusion_voxel_points(acmmp_fusion *f, int64_t first, int64_t n
  * number of cells stored at a slot index below their home slot (independent of it). */
 acmmp_status acmmp_fusion_voxel_table(acmmp_fusion *f, int64_t force_slots, int64_t *slots, int64_t *occupied,
                                       int64_t *max_probe, int64_t *wrapped);
+
+/* ---- a scene result from the host --------------------------------------------------------------------
+ * acmmp_fusion_set_scene replaces the scene result with n >= 0 host points, 9 floats each, taken bit for bit (a
+ * cloud of an earlier run, of another rank, or one built for a test).  ref_index / pixel / src_mask (n each) may
+ * be NULL and are then stored as -1 / -1 / 0.  For lifetimes it is a successful acmmp_fusion_run_scene: the voxel
+ * result, the clean result and the scratch sized for the previous scene are discarded; the used masks are not
+ * touched.  n = 0 is an empty scene.  Any error leaves the object as it was. */
+acmmp_status acmmp_fusion_set_scene(acmmp_fusion *f, int64_t n, const float *points, const int32_t *ref_index,
+                                    const int32_t *pixel, const uint32_t *src_mask);
+
+/* ---- cleaning the voxel result: support and connected components (no reference counterpart) -------------
+ * acmmp_fusion_voxel_clean is defined over the resident voxel result V: voxels 0 .. nv in their order, each with
+ * its cell (gx, gy, gz) of step 2 above and its point count c.
+ *  1. Neighbours.  Voxel u is a neighbour of v when u is in V and the offset d = cell(u) - cell(v) has d != 0,
+ *     |d_a| <= 1 on every axis and |dx| + |dy| + |dz| <= 1, 2 or 3 for connectivity 6, 18 or 26.  Offsets are
+ *     applied per axis to the 21-bit indices, never to the packed key: a cell with an index outside [0, 2^21) does
+ *     not exist.  Cells that min_points dropped at voxelize time are not in V.
+ *  2. Support.  support(v) = the number of neighbours of v; S = { v : support(v) >= min_neighbours }, one pass,
+ *     not iterated.  min_neighbours = 0 keeps every voxel.  *n_unsupported = nv - |S|.
+ *  3. Labels.  The components are those of the neighbour graph induced on S; label(v) = the smallest voxel index
+ *     of v's component, -1 for v outside S.
+ *  4. Component table.  The components in ascending order of label, ids 0 .. *n_components; each entry holds
+ *     root (the label), voxels, and points (the int64 sum of c).
+ *  5. Kept voxels.  v is kept when it is in S and its component has voxels >= min_component_voxels and
+ *     points >= min_component_points (both >= 1).  *n_components_kept = the components that pass.
+ *  6. Clean result.  The kept voxels in ascending voxel index: their 9 floats and counts copied bit for bit from
+ *     the voxel result, each with the id of its component in the table of step 4.  *n_kept = their number.
+ * Every quantity is an integer and every device atomic a minimum or an integer add, so the result is the same
+ * whatever order they land in.  *rounds = the labelling passes the host waited for (the last one changes
+ * nothing); it depends on timing and is informational.  Any of the five outputs may be NULL.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a connectivity not in {6, 18, 26}, min_neighbours < 0, a threshold < 1, no voxel
+ * result (an empty one gives 0 / 0 / 0).  The voxel result and the scene result are untouched.  The clean result
+ * stays in HBM until the next successful clean replaces it or the next successful acmmp_fusion_voxelize,
+ * acmmp_fusion_run_scene or acmmp_fusion_set_scene discards it.  Any error -- an out-of-memory part-way included,
+ * or a labelling that exceeds its bound of nv + 2 rounds (ACMMP_ERR_HIP) -- leaves the object as it was.
+ * Device memory: the voxel result keeps its hash table (28 bytes per slot) and 8 bytes per voxel for this call,
+ * so a voxelize that replaces a voxel result fills a spare table and keeps both; the clean result holds 12 bytes per
+ * voxel (label, neighbours), 48 per kept voxel and 24 per component; 24 bytes per voxel of scratch while it runs. */
+acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion *f, int connectivity, int min_neighbours,
+                                      int64_t min_component_voxels, int64_t min_component_points, int64_t *n_kept,
+                                      int64_t *n_components, int64_t *n_components_kept, int64_t *n_unsupported,
+                                      int64_t *rounds);
+/* Kept voxels [first, first + n) of the clean result to host arrays, any of which may be NULL: points n x 9
+ * floats, counts n int32, component n int64.  Ranges as acmmp_fusion_voxel_points. */
+acmmp_status acmmp_fusion_clean_points(acmmp_fusion *f, int64_t first, int64_t n, float *points, int32_t *counts,
+                                       int64_t *component);
+/* label and support of voxels [first, first + n) of the voxel result, as the last successful clean computed them
+ * (no clean result: every range but an empty one at 0 is refused); either array may be NULL. */
+acmmp_status acmmp_fusion_voxel_labels(acmmp_fusion *f, int64_t first, int64_t n, int64_t *label, int32_t *support);
+/* Entries [first, first + n) of the component table; any array may be NULL. */
+acmmp_status acmmp_fusion_component_table(acmmp_fusion *f, int64_t first, int64_t n, int64_t *root, int64_t *voxels,
+                                          int64_t *points);
 
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
