@@ -110,6 +110,7 @@ EXPORTS = [
     "acmmp_comm_allreduce_max", "acmmp_comm_band_exchange", "acmmp_run_patchmatch_band",
     "acmmp_band_begin", "acmmp_band_sweep", "acmmp_band_sweeps_left", "acmmp_band_halo_ranges",
     "acmmp_band_copy_rows", "acmmp_band_get_rows", "acmmp_band_set_rows", "acmmp_band_end",
+    "acmmp_strip_plan",
     "acmmp_fusion_create", "acmmp_fusion_set_view", "acmmp_fusion_run", "acmmp_fusion_last_error",
     "acmmp_fusion_destroy", "acmmp_fusion_run_scene", "acmmp_fusion_scene_points", "acmmp_fusion_reset_used",
     "acmmp_fusion_download_used", "acmmp_fusion_voxelize", "acmmp_fusion_voxel_points", "acmmp_fusion_voxel_table",
@@ -122,6 +123,19 @@ EXPORTS = [
 
 class AcmmpError(RuntimeError):
     pass
+
+
+def strip_plan(rows: int, want_strips: int):
+    """The strip schedule of a run over `rows` checkerboard rows (acmmp_strip_plan; no GPU needed):
+    (bounds, waits) with strip i = rows [bounds[i], bounds[i + 1]) and waits[i] the strips whose previous
+    half-sweep strip i's next one waits for."""
+    L = load_library()
+    bounds = np.zeros(65, np.int32)
+    waits = np.full(192, -1, np.int32)
+    ns = int(L.acmmp_strip_plan(int(rows), int(want_strips), _p(bounds), _p(waits)))
+    if ns < 1:
+        raise AcmmpError(f"strip_plan: invalid arguments (rows={rows})")
+    return [int(b) for b in bounds[:ns + 1]], [[int(w) for w in waits[3 * i:3 * i + 3] if w >= 0] for i in range(ns)]
 
 
 _lib = None
@@ -194,6 +208,7 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_band_sweep.argtypes = [vp, C.POINTER(i32)]
     L.acmmp_band_sweeps_left.argtypes = [vp]
     L.acmmp_band_halo_ranges.argtypes = [vp, vp]
+    L.acmmp_strip_plan.argtypes = [i32, i32, vp, vp]
     L.acmmp_band_copy_rows.argtypes = [vp, vp, i32, i32, i32]
     L.acmmp_band_get_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.acmmp_band_set_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]

@@ -2,7 +2,8 @@
 //
 // Owns every device buffer of one reference-view problem, like the reference's ACMMP
 // object (ACMMP.h:82-111), and sequences the kernels of ACMMP::RunPatchMatch
-// (ACMMP.cu:1506-1556) on one HIP stream.  No OpenCV, no textures: images live in
+// (ACMMP.cu:1506-1556) on the context's HIP stream (the half-sweeps' row strips on up to three more,
+// DESIGN.md §4).  No OpenCV, no textures: images live in
 // plain padded fp32 buffers (engine.h).
 #include "../../include/acmmp.h"
 
@@ -123,7 +124,13 @@ struct acmmp_ctx {
 
     float timing[3] = {0.f, 0.f, 0.f};
     float planar_ms[4] = {0.f, 0.f, 0.f, 0.f}; // acmmp_last_planar_timing
-    std::vector<hipEvent_t> kev;              // 5 per half-sweep (per-kernel timing)
+    std::vector<hipEvent_t> kev;              // 5 per (half-sweep, strip) (per-kernel timing)
+    // strip schedule: the strips' extra streams (created on first use), one completion event
+    // per (half-sweep, strip), the event the strip streams start behind, and the strips' queue slices
+    hipStream_t xstream[kMaxStripStreams - 1] = {nullptr, nullptr, nullptr};
+    std::vector<hipEvent_t> sev;
+    hipEvent_t fork_ev = nullptr;
+    std::vector<StripSlice> strips;
     float ktiming[4] = {0.f, 0.f, 0.f, 0.f};
     unsigned long long* d_work = nullptr;       // [256] k_eval_nb work counters + [256] the run's status word
     unsigned long long* h_work = nullptr;       // its pinned host copy, enqueued behind the run's last kernel
@@ -305,6 +312,14 @@ void acmmp_destroy(acmmp_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (auto& xs : c->xstream) {
+        if (!xs) continue;
+        (void)hipStreamSynchronize(xs);
+        (void)hipStreamDestroy(xs);
+        xs = nullptr;
+    }
+    for (auto& e : c->sev) (void)hipEventDestroy(e);
+    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     unpin_views(c);
     dfree(c->d_cams); dfree(c->d_img); dfree(c->d_img16); dfree(c->d_dep); dfree(c->d_dirs);
     dfree(c->d_stage); dfree(c->d_flag);
@@ -963,7 +978,24 @@ static int ref_split_point(int V, size_t Pc, bool interp_ref) {
     return V <= 4 ? V / 2 : 4;
 }
 
-static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed) {
+// Strips of a run when ACMMP_STRIPS does not say (profiles/strips_ab.txt).
+// Two strips for SPHERE views of 2 Mpixel and up (metric -4.5%, 2000x1000 -2.7% per step; four and more lose
+// again); smaller views, where a strip's launches no longer fill the chip, pinhole and more than 4 source views
+// (not measured; the fast mode's interpolating runs with V > 4 ignore the knob too, build_kparams) stay at one.
+static int default_strips(int model, int W, int H, int V) {
+    return (model == kSphere && V <= 4 && static_cast<long long>(W) * H >= 2000000LL) ? 2 : 1;
+}
+
+int acmmp_strip_plan(int rows, int want_strips, int* bounds, int* waits) {
+    if (rows < 1 || !bounds) return 0;
+    const int ns = strip_plan(rows, want_strips, bounds);
+    for (int i = 0; waits && i < ns; ++i) strip_waits(ns, i, waits + 3 * i);
+    return ns;
+}
+
+// want_strips: the strip schedule's strip count before clamping (strip_plan); the queues a half-sweep indexes by
+// block number get one slice per strip (c->strips), and kp's own queue pointers are strip 0's.
+static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int want_strips = 1) {
     const acmmp_params& p = c->params;
     if (!c->has_params) return fail(c, ACMMP_ERR_STATE, "set_params first");
     if (c->N == 0) return fail(c, ACMMP_ERR_STATE, "upload_views first");
@@ -1049,17 +1081,34 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed) {
     if (const char* e = std::getenv("ACMMP_NBFIX_MAX_PC")) fix_max_pc = std::min<size_t>(fix_max_pc, std::strtoull(e, nullptr, 10));
     const bool fixq = c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc < fix_max_pc;
     if (!fixq && c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc >= fix_max_pc) kp.interp = 0;
-    const size_t nb_blocks = static_cast<size_t>(nb_block_count(kp.rows, kp.Wh, kp.nb_tile));
+    // One strip where the fast mode's refinement has two arithmetic forms for the same cost: pinhole (k_eval_ref's
+    // homogeneous sample points against the per-sample projection of k_eval_ref_tail and k_select's cache misses)
+    // and SPHERE with interpolated coordinates and V > 4 (k_eval_ref's interpolated instance against the same two).
+    // Which of a candidate's views the tail evaluates, and so which form a cached cost has, depends on the views
+    // the other lanes of its wave selected; a strip start regroups the waves, and the low bits of some costs follow
+    // (two strips run one after the other on one stream already differ from one).  A knob changes no
+    // result, so these runs ignore ACMMP_STRIPS.  Everywhere else every form of a cost has the same bits.
+    if (c->math == ACMMP_MATH_FAST && (c->model != kSphere || (kp.interp && kp.V > 4))) want_strips = 1;
+    int sb[kMaxStrips + 1];
+    const int ns = strip_plan(kp.rows, want_strips, sb);
     // the refinement's interpolated instance (fast SPHERE, V > 4) queues its survivors' fallback views of
     // [0, ref_split) into the same regions after k_eval_nb's queue is drained: a region's k_eval_ref blocks x
     // kRefSlots survivors x ref_split views.  The room is the larger of the two producers' worst cases (the
     // split can exceed the view chunk: ACMMP_REF_SPLIT_AT / ACMMP_NB_VIEW_CHUNK)
     const int ref_split = ref_split_point(kp.V, Pc, kp.model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 &&
                                                         kp.interp && kp.V > 4);
-    const size_t ref_blocks = (static_cast<size_t>(kp.rows) * kp.Wh + kRefPix - 1) / kRefPix;
-    const size_t fix_cap = !fixq ? 0 : std::max(
-        (nb_blocks + kNbFixRegions - 1) / kNbFixRegions * kNbPix * 8 * static_cast<size_t>(kp.nb_chunk),
-        (ref_blocks + kNbFixRegions - 1) / kNbFixRegions * kRefSlots * static_cast<size_t>(std::max(ref_split, 0)));
+    // per strip, by its own share of blocks: its launches number their blocks from 0
+    size_t ref_blocks[kMaxStrips], fix_cap[kMaxStrips], fix_total = 0, ref_total = 0;
+    for (int i = 0; i < ns; ++i) {
+        const size_t srows = static_cast<size_t>(sb[i + 1] - sb[i]);
+        const size_t nb_blocks = static_cast<size_t>(nb_block_count(static_cast<long long>(srows), kp.Wh, kp.nb_tile));
+        ref_blocks[i] = (srows * kp.Wh + kRefPix - 1) / kRefPix;
+        fix_cap[i] = !fixq ? 0 : std::max(
+            (nb_blocks + kNbFixRegions - 1) / kNbFixRegions * kNbPix * 8 * static_cast<size_t>(kp.nb_chunk),
+            (ref_blocks[i] + kNbFixRegions - 1) / kNbFixRegions * kRefSlots * static_cast<size_t>(std::max(ref_split, 0)));
+        fix_total += fix_cap[i];
+        ref_total += ref_blocks[i];
+    }
     // half-sweep scratch slab: carve the pieces of engine.h's KParams out of one allocation
     size_t off[18];
     {
@@ -1067,11 +1116,12 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed) {
         const size_t sizes[17] = {sizeof(float) * 8 * VP, sizeof(int) * 8 * Pc,
                                   sizeof(float4) * 5 * Pc, sizeof(float) * 5 * Pc, sizeof(float) * 5 * Pc,
                                   sizeof(PixState) * Pc, sizeof(float) * VP, sizeof(float) * VP,
-                                  sizeof(float) * 5 * VP, sizeof(uint32_t) * (5 * Pc + 256),
-                                  sizeof(unsigned) * (Pc / 51 + 2),
-                                  sizeof(float4) * Pc, sizeof(uint32_t) * kNbFixRegions * fix_cap,
-                                  sizeof(unsigned) * kNbFixRegions,
-                                  sizeof(unsigned) * (Pc / 51 + 3), sizeof(uint32_t) * (5 * Pc + 256),
+                                  sizeof(float) * 5 * VP, sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
+                                  sizeof(unsigned) * std::max(Pc / 51 + 2, ref_total),
+                                  sizeof(float4) * Pc, sizeof(uint32_t) * kNbFixRegions * fix_total,
+                                  sizeof(unsigned) * kNbFixRegions * ns,
+                                  sizeof(unsigned) * std::max(Pc / 51 + 3, ref_total + ns),
+                                  sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
                                   sizeof(uint32_t) * 5 * Pc};
         off[0] = 0;
         for (int k = 0; k < 17; ++k) off[k + 1] = (off[k] + sizes[k] + 255) & ~static_cast<size_t>(255);
@@ -1113,7 +1163,24 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed) {
     kp.surv_pre = reinterpret_cast<unsigned*>(c->d_scratch + off[14]);
     kp.surv_dense = reinterpret_cast<uint32_t*>(c->d_scratch + off[15]);
     kp.cand_rough = reinterpret_cast<uint32_t*>(c->d_scratch + off[16]);
-    kp.nbfix_cap = static_cast<unsigned>(fix_cap);
+    kp.nbfix_cap = static_cast<unsigned>(fix_cap[0]);
+    c->strips.assign(ns, StripSlice{});
+    {
+        size_t ref_at = 0, fix_at = 0;
+        for (int i = 0; i < ns; ++i) {
+            StripSlice& t = c->strips[i];
+            t.row_lo = sb[i]; t.row_hi = sb[i + 1];
+            t.surv = kp.surv + ref_at * kRefSlots;
+            t.surv_count = kp.surv_count + ref_at;
+            t.surv_pre = kp.surv_pre + ref_at + i;          // ref_blocks + 1 entries each
+            t.surv_dense = kp.surv_dense + ref_at * kRefSlots;
+            t.nbfix = kp.nbfix ? kp.nbfix + kNbFixRegions * fix_at : nullptr;
+            t.nbfix_count = kp.nbfix_count + kNbFixRegions * i;
+            t.nbfix_cap = static_cast<unsigned>(fix_cap[i]);
+            ref_at += ref_blocks[i];
+            fix_at += fix_cap[i];
+        }
+    }
     kp.ref_split = ref_split;
     if (!c->d_work) HIP_TRY(c, dalloc(c->d_work, 257));
     kp.work = c->d_work;
@@ -1127,11 +1194,32 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
     if (!c) return ACMMP_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipSetDevice(c->device));
     KParams kp;
-    acmmp_status st = build_kparams(c, kp, seed);
+    // strip schedule: ACMMP_STRIPS strips over ACMMP_STRIP_STREAMS streams, read per run; they
+    // change no result (tests/test_gpu_strips.py)
+    int want_strips = default_strips(c->model, c->W, c->H, c->N - 1);
+    if (const char* e = std::getenv("ACMMP_STRIPS")) { if (std::atoi(e) > 0) want_strips = std::atoi(e); }
+    int want_streams = kMaxStripStreams;
+    if (const char* e = std::getenv("ACMMP_STRIP_STREAMS")) { if (std::atoi(e) > 0) want_streams = std::atoi(e); }
+    acmmp_status st = build_kparams(c, kp, seed, want_strips);
     if (st != ACMMP_OK) return st;
     if (n_half_sweeps < 0) n_half_sweeps = 2 * c->params.max_iterations;
     const size_t Pc = static_cast<size_t>(kp.Pc);
     hipStream_t s = c->stream;
+    const int NS = static_cast<int>(c->strips.size());
+    const int NQ = std::max(1, std::min(std::min(want_streams, NS), kMaxStripStreams));
+    hipStream_t qs[kMaxStripStreams] = {s, nullptr, nullptr, nullptr};
+    for (int q = 1; q < NQ; ++q) {
+        if (!c->xstream[q - 1]) HIP_TRY(c, hipStreamCreateWithFlags(&c->xstream[q - 1], hipStreamNonBlocking));
+        qs[q] = c->xstream[q - 1];
+    }
+    if (NS > 1) {
+        while (c->sev.size() < static_cast<size_t>(NS) * n_half_sweeps) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            c->sev.push_back(e);
+        }
+        if (!c->fork_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+    }
     HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 257, s));
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     HIP_TRY(c, launch_init(kp, s));
@@ -1143,7 +1231,7 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         HIP_TRY(c, hipMemcpyAsync(c->d_cost_cs[k][1], c->d_cost_cs[k][0], sizeof(float) * Pc,
                                   hipMemcpyDeviceToDevice, s));
     }
-    while (c->kev.size() < static_cast<size_t>(5 * n_half_sweeps)) {
+    while (c->kev.size() < static_cast<size_t>(5 * n_half_sweeps) * NS) {
         hipEvent_t e = nullptr;
         HIP_TRY(c, hipEventCreate(&e));
         c->kev.push_back(e);
@@ -1154,13 +1242,49 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
     const char* e_kt = std::getenv("ACMMP_KERNEL_TIMING");
     const bool time_all = e_kt && std::strcmp(e_kt, "all") == 0;
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    for (int sw = 0; sw < n_half_sweeps; ++sw) {
-        const int colour = sw & 1, iter = sw / 2;
-        SweepOut out{c->d_plane_cs[colour][cur[colour] ^ 1], c->d_cost_cs[colour][cur[colour] ^ 1]};
-        HIP_TRY(c, launch_propagate(kp, colour, iter, out, s, &c->kev[5 * sw], time_all));
-        cur[colour] ^= 1;
-        kp.plane_cs[colour] = c->d_plane_cs[colour][cur[colour]];
-        kp.cost_cs[colour] = c->d_cost_cs[colour][cur[colour]];
+    // Fork, the strips' chains and the join.  A failure partway leaves work queued on the extra streams that
+    // nothing has joined to the context's stream yet: they are waited for before the error goes back, so that
+    // whatever the caller queues next on the context's stream still follows all of this run's kernels.
+    const acmmp_status st_strips = [&]() -> acmmp_status {
+        // the strip streams start behind k_init and the buffer copies
+        if (NQ > 1) {
+            HIP_TRY(c, hipEventRecord(c->fork_ev, s));
+            for (int q = 1; q < NQ; ++q) HIP_TRY(c, hipStreamWaitEvent(qs[q], c->fork_ev, 0));
+        }
+        for (int sw = 0; sw < n_half_sweeps; ++sw) {
+            const int colour = sw & 1, iter = sw / 2;
+            SweepOut out{c->d_plane_cs[colour][cur[colour] ^ 1], c->d_cost_cs[colour][cur[colour] ^ 1]};
+            for (int i = 0; i < NS; ++i) {
+                // strip i's chain k_pick .. k_finish on stream i % NQ, behind the previous half-sweep of strips
+                // i - 1, i and i + 1 (its own stream orders the ones it ran itself).  No barrier between half-sweeps:
+                // a strip goes on as soon as its neighbours allow, so the strips drift into different stages.
+                hipStream_t q = qs[i % NQ];
+                int waits[3];
+                strip_waits(NS, i, waits);
+                for (int w = 0; sw > 0 && w < 3; ++w)
+                    if (waits[w] >= 0 && waits[w] % NQ != i % NQ)
+                        HIP_TRY(c, hipStreamWaitEvent(q, c->sev[static_cast<size_t>(sw - 1) * NS + waits[w]], 0));
+                KParams ks = kp;
+                const StripSlice& t = c->strips[i];
+                ks.row_lo = t.row_lo; ks.row_hi = t.row_hi;
+                ks.surv = t.surv; ks.surv_count = t.surv_count; ks.surv_pre = t.surv_pre; ks.surv_dense = t.surv_dense;
+                ks.nbfix = t.nbfix; ks.nbfix_count = t.nbfix_count; ks.nbfix_cap = t.nbfix_cap;
+                HIP_TRY(c, launch_propagate(ks, colour, iter, out, q, &c->kev[5 * (static_cast<size_t>(sw) * NS + i)], time_all));
+                if (NS > 1) HIP_TRY(c, hipEventRecord(c->sev[static_cast<size_t>(sw) * NS + i], q));
+            }
+            cur[colour] ^= 1;
+            kp.plane_cs[colour] = c->d_plane_cs[colour][cur[colour]];
+            kp.cost_cs[colour] = c->d_cost_cs[colour][cur[colour]];
+        }
+        // join: the post stage follows the last half-sweep of every strip (the context's stream ran some itself)
+        for (int i = 0; n_half_sweeps > 0 && i < NS; ++i)
+            if (i % NQ != 0) HIP_TRY(c, hipStreamWaitEvent(s, c->sev[static_cast<size_t>(n_half_sweeps - 1) * NS + i], 0));
+        return ACMMP_OK;
+    }();
+    if (st_strips != ACMMP_OK) {
+        for (int q = 1; q < NQ; ++q) (void)hipStreamSynchronize(qs[q]);
+        (void)hipStreamSynchronize(s);
+        return st_strips;
     }
     HIP_TRY(c, hipEventRecord(c->ev[2], s));
     HIP_TRY(c, launch_post(kp, do_post, s));
@@ -1189,7 +1313,9 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         for (int sw = 0; sw < n_half_sweeps; ++sw) c->work_total += colour_pixels(c, kp, sw & 1);
     }
     for (int k = 0; k < 4; ++k) { c->ktiming[k] = 0.f; c->klaunch[k] = k == 0 || time_all ? n_half_sweeps : 0; }
-    for (int sw = 0; sw < n_half_sweeps; ++sw)
+    // with several strips a bucket is the sum of the strips' event intervals, which under overlap also hold
+    // other streams' kernels; the launch count stays the number of half-sweeps
+    for (int sw = 0; sw < n_half_sweeps * NS; ++sw)
         for (int k = 0; k < (time_all ? 4 : 1); ++k) {
             float ms = 0.f;
             HIP_TRY(c, hipEventElapsedTime(&ms, c->kev[5 * sw + k], c->kev[5 * sw + k + 1]));

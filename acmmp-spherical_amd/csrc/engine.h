@@ -165,6 +165,52 @@ struct SweepOut {
     float* cost;
 };
 
+// Strip schedule of a run's half-sweeps: the checkerboard rows [0, rows) cut into contiguous
+// strips, each running its own k_pick .. k_finish chain on one of a few streams.
+constexpr int kMaxStrips = 64;
+constexpr int kMaxStripStreams = 4;  // the context's stream included: the runtime's default hardware queues
+
+// The queues of one strip's launches: everything a half-sweep indexes by block number or resets per launch
+// (engine.h's KParams fields of the same names), carved per strip out of the scratch slab.
+struct StripSlice {
+    int row_lo, row_hi;
+    uint32_t* surv;
+    unsigned* surv_count;
+    unsigned* surv_pre;
+    uint32_t* surv_dense;
+    uint32_t* nbfix;
+    unsigned* nbfix_count;
+    unsigned nbfix_cap;
+};
+
+// Strip boundaries: `want` strips clamped so that every boundary but the last is a multiple of 4 rows
+// (k_eval_nb's 8 x 4 tiles keep their shape) and every strip is at least ACMMP_BAND_HALO rows tall (24, the
+// next multiple of 4), so a half-sweep reads no strip beyond its two neighbours.  The 4-row units are dealt
+// evenly, the first strips one more; the last strip takes the rows past the last whole unit.  Returns the
+// strip count NS >= 1 and writes bounds[0 .. NS].
+inline int strip_plan(int rows, int want, int* bounds) {
+    const int units = rows / 4, per = (ACMMP_BAND_HALO + 3) / 4;
+    int ns = want < 1 ? 1 : (want > kMaxStrips ? kMaxStrips : want);
+    if (ns > units / per) ns = units / per;
+    if (ns < 1) ns = 1;
+    int at = 0;
+    for (int i = 0; i < ns; ++i) {
+        bounds[i] = 4 * at;
+        at += units / ns + (i < units % ns ? 1 : 0);
+    }
+    bounds[0] = 0;
+    bounds[ns] = rows;
+    return ns;
+}
+
+// Strips whose half-sweep n must be complete before strip i's half-sweep n + 1 starts: i - 1, i and i + 1
+// where they exist (-1 otherwise); none with a single strip, whose one stream orders its launches.
+inline void strip_waits(int ns, int i, int waits[3]) {
+    waits[0] = (ns > 1 && i > 0) ? i - 1 : -1;
+    waits[1] = ns > 1 ? i : -1;
+    waits[2] = (ns > 1 && i + 1 < ns) ? i + 1 : -1;
+}
+
 // Grid size of a launch: ceil(a / b).
 inline int cdiv(long long a, int b) { return static_cast<int>((a + b - 1) / b); }
 

@@ -237,6 +237,16 @@ int acmmp_texel_bytes(const acmmp_ctx *ctx);
  * a whole-view acmmp_run_patchmatch with the same seed.  Bands must span >= ACMMP_BAND_HALO rows. */
 #define ACMMP_BAND_HALO 23
 
+/* The strip schedule of acmmp_run_patchmatch (no GPU needed): the checkerboard rows
+ * [0, rows) cut into `want_strips` strips, clamped so that boundaries fall on multiples of 4 rows and every
+ * strip spans >= ACMMP_BAND_HALO rows.  Returns the strip count NS (0: invalid arguments) and writes
+ * bounds[0 .. NS] (room for 65) and, when `waits` is not null, for each strip i the three strips whose
+ * previous half-sweep its next one waits for, waits[3 i .. 3 i + 2] = i - 1, i, i + 1, -1 where there is
+ * none (room for 192).  The environment variables ACMMP_STRIPS and ACMMP_STRIP_STREAMS (read per run) set
+ * the strip and stream counts of a run; neither changes a result.  Fast-math pinhole runs and fast-math
+ * SPHERE runs with interpolated sample coordinates and more than 4 source views always run one strip. */
+int acmmp_strip_plan(int rows, int want_strips, int *bounds, int *waits);
+
 /* RandomInitialization of the band +- halo (the same per-pixel values every band computes). */
 acmmp_status acmmp_band_begin(acmmp_ctx *ctx, uint64_t seed, int row0, int row1);
 /* The next half-sweep (black, red, black, ...) on the band's rows; *colour = the colour updated. */
