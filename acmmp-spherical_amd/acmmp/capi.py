@@ -116,6 +116,7 @@ EXPORTS = [
     "acmmp_fusion_download_used", "acmmp_fusion_voxelize", "acmmp_fusion_voxel_points", "acmmp_fusion_voxel_table",
     "acmmp_fusion_set_scene", "acmmp_fusion_voxel_clean", "acmmp_fusion_clean_points", "acmmp_fusion_voxel_labels",
     "acmmp_fusion_component_table",
+    "acmmp_fusion_voxel_visibility", "acmmp_fusion_visible_points", "acmmp_fusion_visibility_tallies",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -230,6 +231,9 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_clean_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_fusion_voxel_labels.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_component_table.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_voxel_visibility.argtypes = [vp, i32, i32, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp]
+    L.acmmp_fusion_visible_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_visibility_tallies.argtypes = [vp, C.c_int64, C.c_int64, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -860,6 +864,7 @@ class Comm:
 # ---- GPU fusion (RunFusionCuda / SimpleFusionKernel, ACMMP.cu:1662-2105) ---------------------------
 
 FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
+VIS_SOURCES = {"voxel": 0, "clean": 1}     # ACMMP_VIS_FROM_VOXELS, ACMMP_VIS_FROM_CLEAN
 
 
 class Fusion:
@@ -1023,6 +1028,46 @@ class Fusion:
         out = [np.empty(max(n, 0), np.int64) for _ in range(3)]
         self._check(self.L.acmmp_fusion_component_table(self.h, first, n, *[_p(a) for a in out]), "fusion_component_table")
         return tuple(out)
+
+    def voxel_visibility(self, views, rel_tol: float, radius: int = 0, min_support: int = 1, max_conflicts: int = 0,
+                         source: str = "voxel"):
+        """Check the voxel result (source "voxel") or the clean result ("clean") against the depth maps of `views`
+        (indices into the set; a view listed twice counts twice): every entry is projected into every view and is
+        supported where a depth of the window of `radius` pixels agrees within rel_tol, occluded where the view's
+        surface is nearer, in conflict where the view sees through it, unobserved otherwise; entries with at least
+        min_support supports and at most max_conflicts conflicts are kept (acmmp_fusion_voxel_visibility,
+        include/acmmp.h).  The result stays on the GPU (visible_points, visibility_tallies) until the next
+        voxel_visibility or until its source goes.
+        Returns (kept entries, {"unsupported", "conflicting", "class_totals"}), class_totals = [support, conflict,
+        occluded, unobserved] summed over entries and views."""
+        if source not in VIS_SOURCES:
+            raise ValueError('source must be "voxel" or "clean"')
+        v = np.ascontiguousarray(views, np.int32).reshape(-1)
+        out = np.zeros(7, np.int64)
+        self._check(self.L.acmmp_fusion_voxel_visibility(self.h, VIS_SOURCES[source], v.size, _p(v) if v.size else None,
+                                                         float(rel_tol), int(radius), int(min_support), int(max_conflicts),
+                                                         _p(out[0:1]), _p(out[1:2]), _p(out[2:3]), _p(out[3:7])),
+                    "fusion_voxel_visibility")
+        return int(out[0]), {"unsupported": int(out[1]), "conflicting": int(out[2]),
+                             "class_totals": [int(x) for x in out[3:7]]}
+
+    def visible_points(self, first: int, n: int, counts: bool = False, tallies: bool = False):
+        """Kept entries [first, first + n) of the last voxel_visibility, in the source's order: (n, 9) float32; with
+        counts also the points per entry (int32), with tallies also (support, conflict, occluded), (n, 3) int32."""
+        pts = host_empty((max(n, 0), 9), np.float32)          # (a negative n is refused below)
+        cnt = np.empty(max(n, 0), np.int32) if counts else None
+        tal = np.empty((max(n, 0), 3), np.int32) if tallies else None
+        self._check(self.L.acmmp_fusion_visible_points(self.h, first, n, _p(pts), None if cnt is None else _p(cnt),
+                                                       None if tal is None else _p(tal)), "fusion_visible_points")
+        extra = tuple(a for a in (cnt, tal) if a is not None)
+        return (pts, *extra) if extra else pts
+
+    def visibility_tallies(self, first: int, n: int):
+        """(support, conflict, occluded) of entries [first, first + n) of the source of the last voxel_visibility,
+        kept or not: (n, 3) int32."""
+        tal = np.empty((max(n, 0), 3), np.int32)
+        self._check(self.L.acmmp_fusion_visibility_tallies(self.h, first, n, _p(tal)), "fusion_visibility_tallies")
+        return tal
 
     def close(self):
         if self.h:

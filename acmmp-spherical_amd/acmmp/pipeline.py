@@ -791,7 +791,8 @@ class Pipeline:
                    chunk_points: int = 1 << 22, max_host_points: int | None = None,
                    voxel_size: float | None = None, voxel_min_points: int = 1, voxel_connectivity: int = 26,
                    voxel_min_neighbours: int = 0, voxel_min_component_voxels: int = 1,
-                   voxel_min_component_points: int = 1):
+                   voxel_min_component_points: int = 1, visibility_tol: float | None = None,
+                   visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -815,8 +816,17 @@ class Pipeline:
         when one of them is not its default (voxel_size is then required), the voxel cloud is cleaned on the device
         -- voxels with fewer occupied neighbours are dropped, then connected components below either size
         (acmmp_fusion_voxel_clean, include/acmmp.h) -- and the clean cloud takes the voxel cloud's place;
-        self.fusion_info gains clean_voxels, components, components_kept, unsupported, rounds and the four values."""
+        self.fusion_info gains clean_voxels, components, components_kept, unsupported, rounds and the four values.
+
+        visibility_tol (voxel_size is then required): last of all, the voxel cloud -- the clean cloud when it was
+        cleaned -- is checked on the device against every view's depth map: an entry needs a depth that agrees within
+        visibility_tol (relative, in a window of visibility_radius pixels, 0 or 1) in at least visibility_min_support
+        views and may lie in the free space of at most visibility_max_conflicts views (acmmp_fusion_voxel_visibility,
+        include/acmmp.h).  The visible cloud takes the place of the cloud it checked; self.fusion_info gains
+        visible_voxels, vis_unsupported, vis_conflicting, vis_class_totals and the four values."""
         self.fusion_info = None
+        if visibility_tol is not None and voxel_size is None:
+            raise ValueError("the visibility check needs voxel_size")
         clean = (voxel_connectivity, voxel_min_neighbours, voxel_min_component_voxels, voxel_min_component_points) != (26, 0, 1, 1)
         if clean and voxel_size is None:
             raise ValueError("cleaning the voxel cloud needs voxel_size")
@@ -866,6 +876,20 @@ class Pipeline:
                         rounds=int(cinfo["rounds"]), connectivity=int(voxel_connectivity),
                         min_neighbours=int(voxel_min_neighbours), min_component_voxels=int(voxel_min_component_voxels),
                         min_component_points=int(voxel_min_component_points))
+                if visibility_tol is not None:
+                    if not hasattr(fu, "voxel_visibility"):
+                        raise ValueError("the visibility check needs a fusion object with voxel_visibility (capi.Fusion)")
+                    total, vinfo = fu.voxel_visibility(list(range(len(cams))), visibility_tol, visibility_radius,
+                                                       visibility_min_support, visibility_max_conflicts,
+                                                       source="clean" if clean else "voxel")
+                    read = fu.visible_points
+                    self.fusion_info.update(
+                        visible_voxels=int(total), vis_unsupported=int(vinfo["unsupported"]),
+                        vis_conflicting=int(vinfo["conflicting"]),
+                        vis_class_totals=[int(x) for x in vinfo["class_totals"]],
+                        visibility_tol=float(visibility_tol), visibility_radius=int(visibility_radius),
+                        visibility_min_support=int(visibility_min_support),
+                        visibility_max_conflicts=int(visibility_max_conflicts))
             keep = max_host_points is None or total <= max_host_points
             points = np.zeros((total, 9), np.float32) if keep else None
             writer = io.PlyWriter(path, total) if path else None
@@ -989,6 +1013,15 @@ def arg_parser():
                     help="with --voxel-size: drop connected components of fewer voxels than this")
     ap.add_argument("--min-component-points", type=int, default=1,
                     help="with --voxel-size: drop connected components of fewer fused points than this")
+    ap.add_argument("--visibility-tol", type=float, default=None,
+                    help="with --voxel-size: check the voxel (or clean) cloud against every view's depth map; a depth "
+                         "agrees with a voxel within this relative tolerance")
+    ap.add_argument("--visibility-radius", type=int, choices=[0, 1], default=0,
+                    help="with --visibility-tol: pixels around the projection whose depths are compared")
+    ap.add_argument("--visibility-min-support", type=int, default=1,
+                    help="with --visibility-tol: drop voxels that fewer views than this agree with")
+    ap.add_argument("--visibility-max-conflicts", type=int, default=0,
+                    help="with --visibility-tol: drop voxels that more views than this see through")
     return ap
 
 
@@ -1016,7 +1049,9 @@ def main(argv=None):
                               unique=a.unique_fusion, voxel_size=a.voxel_size, voxel_min_points=a.voxel_min_points,
                               voxel_connectivity=a.voxel_connectivity, voxel_min_neighbours=a.voxel_min_neighbours,
                               voxel_min_component_voxels=a.min_component_voxels,
-                              voxel_min_component_points=a.min_component_points)
+                              voxel_min_component_points=a.min_component_points, visibility_tol=a.visibility_tol,
+                              visibility_radius=a.visibility_radius, visibility_min_support=a.visibility_min_support,
+                              visibility_max_conflicts=a.visibility_max_conflicts)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

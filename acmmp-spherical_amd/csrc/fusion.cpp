@@ -102,6 +102,16 @@ struct acmmp_fusion {
     unsigned long long c_total = 0, c_comps = 0; // kept voxels, components
     bool c_have = false;                         // a clean has succeeded on this voxel result
     DevBuf<unsigned long long> c_words;          // kCleanWords device words
+    // visibility check of the voxel or clean result (acmmp_fusion_voxel_visibility): its resident result
+    DevBuf<float> vis_pts;                       // 9 floats per kept entry
+    DevBuf<int32_t> vis_cnt;                     // points per kept entry
+    DevBuf<int32_t> vis_kept_tal;                // 3 per kept entry
+    DevBuf<int32_t> vis_tal;                     // 3 per entry of the source
+    unsigned long long vis_total = 0, vis_entries = 0;   // kept entries, entries of the source
+    int vis_source = 0;                          // ACMMP_VIS_FROM_*
+    bool vis_have = false;                       // a visibility call has succeeded on this source
+    DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
+    DevBuf<unsigned long long> vis_words;        // kVisWords device words
     std::string err;
 };
 
@@ -270,13 +280,20 @@ void clean_release(acmmp_fusion* f) {
     f->c_have = false;
 }
 
-// A new scene result is in place: the voxel result and the clean result described the previous one and go, with
-// the scratch sized for that scene.
+void visibility_release(acmmp_fusion* f) {
+    f->vis_pts.reset(); f->vis_cnt.reset(); f->vis_kept_tal.reset(); f->vis_tal.reset();
+    f->vis_total = f->vis_entries = 0;
+    f->vis_have = false;
+}
+
+// A new scene result is in place: the voxel result, the clean result and the visible result described the previous
+// one and go, with the scratch sized for that scene.
 void scene_replaced(acmmp_fusion* f) {
     f->v_pts.reset(); f->v_cnt.reset(); f->v_slot.reset();
     f->v_total = 0;
     f->v_have = false;
     clean_release(f);
+    visibility_release(f);
     voxel_scratch_release(f);
 }
 
@@ -678,6 +695,7 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     f->v_total = words[kVoxKept];
     f->v_have = true;
     clean_release(f);                                 // it described the previous voxel result
+    visibility_release(f);                            // and so did this one, from either source
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
     f->v_stats[2] = static_cast<long long>(words[kVoxMaxProbe]);
@@ -842,6 +860,7 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
     f->c_total = out.kept;
     f->c_comps = out.comps;
     f->c_have = true;
+    if (f->vis_have && f->vis_source == ACMMP_VIS_FROM_CLEAN) visibility_release(f);   // its source is replaced
     if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
     if (n_components) *n_components = static_cast<int64_t>(out.comps);
     if (n_components_kept) *n_components_kept = static_cast<int64_t>(out.comps_kept);
@@ -888,6 +907,142 @@ acmmp_status acmmp_fusion_component_table(acmmp_fusion* f, int64_t first, int64_
     F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(root), f->c_table, a, m));
     F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(voxels), f->c_table + nc, a, m));
     F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(points), f->c_table + 2 * nc, a, m));
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- visibility check of the voxel or clean result (include/acmmp.h; kernels: k_vis_*) ----------------------
+
+namespace {
+
+constexpr int kVisMaxList = 4096;
+
+// The new result of a visibility run, swapped in only when the whole run succeeded.
+struct VisOut {
+    DevBuf<float> pts;
+    DevBuf<int32_t> cnt, kept_tal, tal;
+    unsigned long long kept = 0, no_support = 0, conflicting = 0, classes[4] = {0, 0, 0, 0};
+};
+
+acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t* src_cnt, unsigned long long N,
+                            int n_list, const int* views, float rel_tol, int radius, int min_support, int max_conflicts,
+                            VisOut& out) {
+    hipStream_t s = f->stream;
+    const unsigned long long seg = voxel_segment_points();
+    if (!f->vis_words) F_HIP(f, alloc(f->vis_words, kVisWords));
+    if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
+    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(N, seg)));
+    if (scratch != ACMMP_OK) return scratch;
+    F_HIP(f, alloc(out.tal, 3 * static_cast<size_t>(N)));
+    unsigned long long* w = f->vis_words;
+    unsigned long long h[kVisWords] = {0};
+    F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kVisWords, s));
+    F_HIP(f, hipMemcpyAsync(f->vis_list, views, sizeof(int) * n_list, hipMemcpyHostToDevice, s));
+    F_HIP(f, launch_vis_tally(f->model, f->d_cams, f->d_views, f->vis_list, n_list, src_pts, N, rel_tol, radius, out.tal, s));
+    F_HIP(f, launch_vis_count(N, out.tal, n_list, min_support, max_conflicts, w, s));
+    // the first host wait: the kept count, to size the result before anything is written there
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kVisWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    out.kept = h[kVisKept];
+    out.no_support = h[kVisNoSupport];
+    out.conflicting = h[kVisConflicting];
+    for (int k = 0; k < 4; ++k) out.classes[k] = h[kVisSupport + k];
+    if (out.kept > N) return ffail(f, ACMMP_ERR_HIP, "voxel visibility: kept count beyond the source");
+    const size_t nk = static_cast<size_t>(out.kept);
+    F_HIP(f, alloc(out.pts, 9 * nk));
+    F_HIP(f, alloc(out.cnt, nk));
+    F_HIP(f, alloc(out.kept_tal, 3 * nk));
+    // the kept entries, compacted in entry order, segment after segment
+    unsigned long long* running = w + kVisRunning;
+    unsigned long long* seg_base = w + kVisSegBase;
+    unsigned long long done = 0;
+    for (unsigned long long i0 = 0; i0 < N; i0 += seg)
+        F_HIP(f, launch_vis_compact(i0, static_cast<int>(std::min(seg, N - i0)), out.tal, min_support, max_conflicts,
+                                    f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
+                                    src_pts, src_cnt, out.pts, out.cnt, out.kept_tal, s));
+    F_HIP(f, hipMemcpyAsync(&done, running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (done != out.kept)
+        return ffail(f, ACMMP_ERR_HIP, "voxel visibility: compacted " + std::to_string(done) + " of " +
+                                           std::to_string(out.kept) + " entries");
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_list, const int* views, float rel_tol,
+                                           int radius, int min_support, int max_conflicts, int64_t* n_kept,
+                                           int64_t* n_unsupported, int64_t* n_conflicting, int64_t class_totals[4]) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (source != ACMMP_VIS_FROM_VOXELS && source != ACMMP_VIS_FROM_CLEAN)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be ACMMP_VIS_FROM_VOXELS or ACMMP_VIS_FROM_CLEAN");
+    if (source == ACMMP_VIS_FROM_VOXELS ? !f->v_have : !f->c_have)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, source == ACMMP_VIS_FROM_VOXELS
+                                                        ? "no voxel result: acmmp_fusion_voxelize first"
+                                                        : "no clean result: acmmp_fusion_voxel_clean first");
+    if (n_list < 1 || n_list > kVisMaxList || !views)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the view list must hold 1 to 4096 views");
+    for (int j = 0; j < n_list; ++j) {
+        if (views[j] < 0 || views[j] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
+        if (!f->views[views[j]].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for every view listed");
+    }
+    if (!finite32(rel_tol) || !(rel_tol >= 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "rel_tol must be finite and >= 0");
+    if (radius != 0 && radius != 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "radius must be 0 or 1");
+    if (min_support < 0 || max_conflicts < 0)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_support and max_conflicts must not be negative");
+    F_HIP(f, hipSetDevice(f->device));
+    const bool clean = source == ACMMP_VIS_FROM_CLEAN;
+    const unsigned long long N = clean ? f->c_total : f->v_total;
+    VisOut out;
+    if (N > 0) {
+        const acmmp_status st = visibility_run(f, clean ? f->c_pts : f->v_pts, clean ? f->c_cnt : f->v_cnt, N, n_list, views,
+                                               rel_tol, radius, min_support, max_conflicts, out);
+        if (st != ACMMP_OK) {
+            const std::string why = f->err;
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(f->stream);
+            f->err = why;
+            return st;
+        }
+    }
+    f->vis_pts = std::move(out.pts);
+    f->vis_cnt = std::move(out.cnt);
+    f->vis_kept_tal = std::move(out.kept_tal);
+    f->vis_tal = std::move(out.tal);
+    f->vis_total = out.kept;
+    f->vis_entries = N;
+    f->vis_source = source;
+    f->vis_have = true;
+    if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
+    if (n_unsupported) *n_unsupported = static_cast<int64_t>(out.no_support);
+    if (n_conflicting) *n_conflicting = static_cast<int64_t>(out.conflicting);
+    if (class_totals)
+        for (int k = 0; k < 4; ++k) class_totals[k] = static_cast<int64_t>(out.classes[k]);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_visible_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts,
+                                         int32_t* tallies) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->vis_total)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the visible result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    F_HIP(f, read_range<float>(points, f->vis_pts, a, m, 9));
+    F_HIP(f, read_range<int32_t>(counts, f->vis_cnt, a, m));
+    F_HIP(f, read_range<int32_t>(tallies, f->vis_kept_tal, a, m, 3));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion* f, int64_t first, int64_t n, int32_t* tallies) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->vis_entries)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the tallied source");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, read_range<int32_t>(tallies, f->vis_tal, static_cast<size_t>(first), static_cast<size_t>(n), 3));
     return ACMMP_OK;
 }
 

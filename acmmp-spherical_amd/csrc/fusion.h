@@ -129,4 +129,29 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
                                      const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
                                      long long* out_comp, hipStream_t s);
 
+// Visibility check of the voxel or clean cloud (acmmp_fusion_voxel_visibility, include/acmmp.h): over
+// the entries [0, n) of `pts` (9 floats each), one lane per entry.
+// List positions per workgroup row of the tally kernel: a list of more takes several rows and integer atomics.
+constexpr int kVisChunk = 32;
+// Device words of a visibility run (all zero before it).
+enum { kVisSupport = 0, kVisConflict = 1, kVisOccluded = 2, kVisUnobserved = 3, kVisKept = 4, kVisNoSupport = 5,
+       kVisConflicting = 6, kVisRunning = 7, kVisSegBase = 8, kVisWords = 9 };
+// tallies[3 e ..] = (support, conflict, occluded) of entry e over the views list[0 .. n_list) (indices into cams /
+// views, every one set), the entry classed per view by its projection against the view's raw depth in the window
+// of `radius` pixels.  More than kVisChunk positions: the tallies are zeroed and added to, else stored.
+hipError_t launch_vis_tally(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
+                            const float* pts, unsigned long long n, float rel_tol, int radius, int32_t* tallies,
+                            hipStream_t s);
+// words[kVisSupport .. kVisUnobserved] += the class sums (unobserved = n_list - the three tallies), words[kVisKept],
+// [kVisNoSupport], [kVisConflicting] += the entries with support >= min_support and conflict <= max_conflicts, those
+// failing the first, those failing the second.
+hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_list, int min_support, int max_conflicts,
+                            unsigned long long* words, hipStream_t s);
+// Compaction of entries [i0, i0 + n) (one segment, as launch_voxel_compact): the kept entries' floats, counts and
+// tallies in ascending order.  Nothing is written at or past `cap` entries.
+hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
+                              int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                              unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
+                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal, hipStream_t s);
+
 }  // namespace acmmp

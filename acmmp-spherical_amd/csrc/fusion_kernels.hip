@@ -1,6 +1,7 @@
 // fusion_kernels.hip -- gfx950 kernels of the depth-map fusion (SimpleFusionKernel, ACMMP.cu:1662-1814, its
-// whole-scene pass and their in-order compaction) and of the voxel-grid reduction of the fused scene cloud
-// (DESIGN.md §8), with their host launchers (fusion.h).  One translation unit, compiled once.
+// whole-scene pass and their in-order compaction), of the voxel-grid reduction of the fused scene cloud and of the
+// cleaning and the visibility check of that voxel cloud, with their host launchers (fusion.h).  One
+// translation unit, compiled once.
 #include <algorithm>
 
 #include "camera_dev.h"
@@ -880,6 +881,162 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
     k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
     k_clean_scatter_kept<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, lab, c.id,
                                                                          v_pts, v_cnt, out, out_cnt, out_comp);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ visibility check of the voxel cloud
+//
+// acmmp_fusion_voxel_visibility (include/acmmp.h): every entry of the voxel or clean result is
+// projected into every listed view and classed against that view's raw depth map.  The classes are decided by
+// float32 comparisons of one entry against one pixel; what is summed is the integer count of each class, so no
+// result depends on the order the adds land in.
+
+// The class of entry X in one view: 0 support, 1 conflict, 2 occluded, 3 unobserved.
+template <int MODEL>
+__device__ __forceinline__ int vis_class(const DevCam& cam, const FuseView& view, float3 X, float rel_tol, int radius) {
+    float px, py, pd;
+    project<MODEL, const DevCam, true>(cam, X, px, py, pd);
+    if (vox_nonfinite(px) || vox_nonfinite(py) || vox_nonfinite(pd) || !(pd > 0.0f)) return 3;
+    const int c = f2i_sat(px + 0.5f), r = f2i_sat(py + 0.5f);
+    if (c < 0 || c >= view.W || r < 0 || r >= view.H) return 3;
+    bool any = false, agree = false, behind = false;
+    for (int dy = -radius; dy <= radius; ++dy) {
+        const int rr = r + dy;
+        if (rr < 0 || rr >= view.H) continue;
+        for (int dx = -radius; dx <= radius; ++dx) {
+            const int cc = c + dx;
+            if (cc < 0 || cc >= view.W) continue;
+            const float sd = view.depth[static_cast<long long>(rr) * view.W + cc];
+            if (vox_nonfinite(sd) || !(sd > 0.0f)) continue;
+            const float t = rel_tol * sd, d = pd - sd;
+            any = true;
+            agree = agree || fabsf(d) <= t;
+            behind = behind || d > t;
+        }
+    }
+    return !any ? 3 : agree ? 0 : behind ? 2 : 1;
+}
+
+// One lane per entry, blockIdx.y = a chunk of kVisChunk list positions.  The view index of a position is the same
+// for every lane, so the camera and the view's addresses load as scalars; neighbouring entries are neighbours in
+// space (first-appearance order), so a wave's depth gathers fall close together.  ATOMIC: more than one chunk, the
+// lane adds its chunk's counts to tallies that were zeroed; otherwise it stores them.
+template <int MODEL, bool ATOMIC>
+__global__ __launch_bounds__(256) void k_vis_tally(const DevCam* __restrict__ cams, const FuseView* __restrict__ views,
+                                                   const int* __restrict__ list, int n_list, const float* __restrict__ pts,
+                                                   unsigned long long n, float rel_tol, int radius, int32_t* tallies) {
+    const unsigned long long e = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (e >= n) return;
+    const float* p = pts + 9ull * e;
+    const float3 X = make_float3(p[0], p[1], p[2]);
+    const int j0 = static_cast<int>(blockIdx.y) * kVisChunk;
+    const int j1 = min(j0 + kVisChunk, n_list);
+    int cls[3] = {0, 0, 0};
+    for (int j = j0; j < j1; ++j) {
+        const int vi = list[j];
+        const FuseView view = views[vi];
+        const int k = vis_class<MODEL>(cams[vi], view, X, rel_tol, radius);
+        cls[0] += k == 0 ? 1 : 0;
+        cls[1] += k == 1 ? 1 : 0;
+        cls[2] += k == 2 ? 1 : 0;
+    }
+    int32_t* t = tallies + 3ull * e;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if constexpr (ATOMIC) { if (cls[k]) atomicAdd(&t[k], cls[k]); }
+        else t[k] = cls[k];
+    }
+}
+
+__device__ __forceinline__ bool vis_kept(const int32_t* __restrict__ t, int min_support, int max_conflicts) {
+    return t[0] >= min_support && t[1] <= max_conflicts;
+}
+
+// the sums of the four classes, and the entries that are kept, that lack support, that conflict
+__global__ __launch_bounds__(256) void k_vis_count(unsigned long long n, const int32_t* __restrict__ tallies, int n_list,
+                                                   int min_support, int max_conflicts, unsigned long long* __restrict__ words) {
+    const unsigned long long e = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    const bool in = e < n;
+    const int32_t* t = tallies + 3ull * (in ? e : 0ull);
+    const unsigned long long s = in ? t[0] : 0, c = in ? t[1] : 0, o = in ? t[2] : 0;
+    wave_add(s, &words[kVisSupport]);
+    wave_add(c, &words[kVisConflict]);
+    wave_add(o, &words[kVisOccluded]);
+    wave_add(in ? static_cast<unsigned long long>(n_list) - s - c - o : 0ull, &words[kVisUnobserved]);
+    wave_add(in && vis_kept(t, min_support, max_conflicts) ? 1ull : 0ull, &words[kVisKept]);
+    wave_add(in && t[0] < min_support ? 1ull : 0ull, &words[kVisNoSupport]);
+    wave_add(in && t[1] > max_conflicts ? 1ull : 0ull, &words[kVisConflicting]);
+}
+
+// flags[i] = entry i0 + i is kept; counts[chunk] as k_fuse_count
+__global__ __launch_bounds__(256) void k_vis_mark(unsigned long long i0, int n, const int32_t* __restrict__ tallies,
+                                                  int min_support, int max_conflicts, int* __restrict__ flags,
+                                                  int* __restrict__ counts) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    int f = 0;
+    if (i < n) {
+        f = vis_kept(tallies + 3ull * (i0 + static_cast<unsigned long long>(i)), min_support, max_conflicts) ? 1 : 0;
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// the kept entries in ascending order: the entry's 9 floats and count as they are, and its tallies
+__global__ __launch_bounds__(256) void k_vis_scatter(unsigned long long i0, int n, const int* __restrict__ flags,
+                                                     const int* __restrict__ offsets,
+                                                     const unsigned long long* __restrict__ seg_base, unsigned long long cap,
+                                                     const float* __restrict__ src_pts, const int32_t* __restrict__ src_cnt,
+                                                     const int32_t* __restrict__ tallies, float* __restrict__ out,
+                                                     int32_t* __restrict__ out_cnt, int32_t* __restrict__ out_tal) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    if (f && pos < cap) {
+        const unsigned long long e = i0 + static_cast<unsigned long long>(i);
+        const float* src = src_pts + 9ull * e;
+        float* dst = out + 9ull * pos;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dst[k] = src[k];
+        out_cnt[pos] = src_cnt[e];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out_tal[3ull * pos + k] = tallies[3ull * e + k];
+    }
+}
+
+hipError_t launch_vis_tally(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
+                            const float* pts, unsigned long long n, float rel_tol, int radius, int32_t* tallies,
+                            hipStream_t s) {
+    const int chunks = cdiv(n_list, kVisChunk);
+    const dim3 grd(clean_blocks(n), static_cast<unsigned>(chunks));
+    if (chunks > 1) {
+        const hipError_t e = hipMemsetAsync(tallies, 0, sizeof(int32_t) * 3ull * n, s);
+        if (e != hipSuccess) return e;
+        if (model == kSphere) k_vis_tally<kSphere, true><<<grd, 256, 0, s>>>(cams, views, list, n_list, pts, n, rel_tol, radius, tallies);
+        else k_vis_tally<kPinhole, true><<<grd, 256, 0, s>>>(cams, views, list, n_list, pts, n, rel_tol, radius, tallies);
+    } else {
+        if (model == kSphere) k_vis_tally<kSphere, false><<<grd, 256, 0, s>>>(cams, views, list, n_list, pts, n, rel_tol, radius, tallies);
+        else k_vis_tally<kPinhole, false><<<grd, 256, 0, s>>>(cams, views, list, n_list, pts, n, rel_tol, radius, tallies);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_list, int min_support, int max_conflicts,
+                            unsigned long long* words, hipStream_t s) {
+    k_vis_count<<<clean_blocks(n), 256, 0, s>>>(n, tallies, n_list, min_support, max_conflicts, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
+                              int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                              unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
+                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_vis_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, tallies, min_support, max_conflicts, flags, counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_vis_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, src_pts, src_cnt,
+                                                                   tallies, out, out_cnt, out_tal);
     return hipGetLastError();
 }
 

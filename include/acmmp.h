@@ -479,6 +479,56 @@ acmmp_status acmmp_fusion_voxel_labels(acmmp_fusion *f, int64_t first, int64_t n
 acmmp_status acmmp_fusion_component_table(acmmp_fusion *f, int64_t first, int64_t n, int64_t *root, int64_t *voxels,
                                           int64_t *points);
 
+/* ---- visibility check of the voxel or clean result against the views' depth maps (no reference counterpart) ----
+ * acmmp_fusion_voxel_visibility is defined over the entries e = 0 .. N of its source, in their order: the voxel result
+ * (ACMMP_VIS_FROM_VOXELS) or the clean result's kept voxels (ACMMP_VIS_FROM_CLEAN), 9 floats and a count each.  X =
+ * an entry's first three floats.  For list position j = 0 .. n_list, view i = views[j] (a view listed twice counts
+ * twice), in plain IEEE float32 arithmetic with no contraction:
+ *  1. Projection.  (px, py, pd) = the projection of X into camera i with its depth, exactly as the fusion projects a
+ *     reference point into a source view (ProjectonCamera_cu, ACMMP.cu:602-644; SPHERE: pd = sqrtf of the squared
+ *     camera-frame distance, pinhole: pd = the camera-frame z).
+ *  2. Pixel.  The pair (e, j) is unobserved unless px, py and pd are finite and pd > 0.  Then c = (int)(px + 0.5f),
+ *     r = (int)(py + 0.5f), saturated, and the pair is unobserved unless 0 <= c < W_i and 0 <= r < H_i.
+ *  3. Samples.  The window is the pixels (c + dx, r + dy), |dx|, |dy| <= radius, that lie inside the image (no wrap
+ *     across the SPHERE seam, as in the fusion).  A pixel whose raw depth sd -- as acmmp_fusion_set_view uploaded it;
+ *     the used masks are never read -- is finite and > 0 is a sample.  With t = rel_tol * sd and d = pd - sd the sample
+ *     agrees when fabsf(d) <= t, lies behind when d > t (the view's surface is nearer than the entry) and in front
+ *     otherwise.
+ *  4. Class of the pair.  No sample: unobserved.  Any sample that agrees: support.  Otherwise any sample behind:
+ *     occluded.  Otherwise conflict: the entry lies in front of everything the view sees there, in the view's free
+ *     space.  The class does not depend on the order of the samples.
+ *  5. Tallies.  tallies[e] = (support, conflict, occluded): the int32 numbers of list positions of each class.  Entry e
+ *     is kept when support >= min_support and conflict <= max_conflicts.
+ *  6. Visible result.  The kept entries in ascending e: their 9 floats and counts copied bit for bit from the source,
+ *     each with its tallies.  *n_kept = their number, *n_unsupported = the entries with support < min_support,
+ *     *n_conflicting = those with conflict > max_conflicts (an entry may be in both), class_totals[4] = the int64 sums
+ *     over the entries of support, conflict, occluded and unobserved.  Any of the four may be NULL.
+ * Every quantity that is summed is an integer, so the result is the same whatever order the device's atomics land in.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a source that is neither constant, no such source result (an empty one gives zeros),
+ * n_list outside [1, 4096], a view index outside the set or a view never given to acmmp_fusion_set_view, rel_tol not
+ * finite or < 0, a radius not in {0, 1}, min_support < 0, max_conflicts < 0.  The source results, the scene result and
+ * the used masks are never modified.  The visible result stays in HBM until the next successful visibility call
+ * replaces it or its source is replaced or discarded: by a successful acmmp_fusion_voxelize, acmmp_fusion_run_scene or
+ * acmmp_fusion_set_scene, and by a successful acmmp_fusion_voxel_clean when the source was the clean result (a clean
+ * leaves a visible result of the voxel result alone).  acmmp_fusion_set_view does not touch it.  Any error -- an
+ * out-of-memory part-way included -- leaves the object as it was (the new result is built beside the previous one).
+ * Device memory: 12 bytes of tallies per entry of the source and 52 bytes per kept entry (point, count, tallies),
+ * both held with the result; 4 bytes of flag per entry of a compaction segment (at most 2^30 entries) and 8 bytes per
+ * 256 entries of one while it runs.  The host waits twice: for the counts, to size the result, and at the end. */
+#define ACMMP_VIS_FROM_VOXELS 0   /* entries = the voxel result */
+#define ACMMP_VIS_FROM_CLEAN 1    /* entries = the clean result's kept voxels */
+acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion *f, int source, int n_list, const int *views, float rel_tol,
+                                           int radius, int min_support, int max_conflicts, int64_t *n_kept,
+                                           int64_t *n_unsupported, int64_t *n_conflicting, int64_t class_totals[4]);
+/* Kept entries [first, first + n) of the visible result to host arrays, any of which may be NULL: points n x 9
+ * floats, counts n int32, tallies n x 3 int32.  Ranges as acmmp_fusion_voxel_points. */
+acmmp_status acmmp_fusion_visible_points(acmmp_fusion *f, int64_t first, int64_t n, float *points, int32_t *counts,
+                                         int32_t *tallies);
+/* tallies (n x 3 int32) of entries [first, first + n) of the source, as the last successful visibility call computed
+ * them (no visible result: every range but an empty one at 0 is refused). */
+acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion *f, int64_t first, int64_t n, int32_t *tallies);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
