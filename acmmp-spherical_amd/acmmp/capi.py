@@ -117,6 +117,8 @@ EXPORTS = [
     "acmmp_fusion_set_scene", "acmmp_fusion_voxel_clean", "acmmp_fusion_clean_points", "acmmp_fusion_voxel_labels",
     "acmmp_fusion_component_table",
     "acmmp_fusion_voxel_visibility", "acmmp_fusion_visible_points", "acmmp_fusion_visibility_tallies",
+    "acmmp_fusion_voxel_mesh", "acmmp_fusion_mesh_vertices", "acmmp_fusion_mesh_faces", "acmmp_fusion_mesh_samples",
+    "acmmp_fusion_mesh_table",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -234,6 +236,11 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_voxel_visibility.argtypes = [vp, i32, i32, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp]
     L.acmmp_fusion_visible_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_fusion_visibility_tallies.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.acmmp_fusion_voxel_mesh.argtypes = [vp, i32, i32, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp]
+    L.acmmp_fusion_mesh_vertices.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.acmmp_fusion_mesh_faces.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.acmmp_fusion_mesh_samples.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_mesh_table.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -865,6 +872,7 @@ class Comm:
 
 FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
 VIS_SOURCES = {"voxel": 0, "clean": 1}     # ACMMP_VIS_FROM_VOXELS, ACMMP_VIS_FROM_CLEAN
+MESH_SOURCES = {"voxel": 0, "clean": 1, "visible": 2}     # ACMMP_MESH_FROM_VOXELS, _CLEAN, _VISIBLE
 
 
 class Fusion:
@@ -1068,6 +1076,52 @@ class Fusion:
         tal = np.empty((max(n, 0), 3), np.int32)
         self._check(self.L.acmmp_fusion_visibility_tallies(self.h, first, n, _p(tal)), "fusion_visibility_tallies")
         return tal
+
+    def voxel_mesh(self, views, trunc: float, min_weight: int = 1, source: str = "voxel"):
+        """Surface mesh of the voxel result (source "voxel"), the clean result ("clean") or the visible result
+        ("visible"): a signed distance, truncated at `trunc`, of the cells within one cell of an entry to the depth maps
+        of `views`, summed in integers; surface-nets vertices in the cubes of samples seen by at least min_weight views
+        whose signs differ, and two triangles per sign change along an axis (acmmp_fusion_voxel_mesh, include/acmmp.h).
+        The result stays on the GPU (mesh_vertices, mesh_faces) until the next voxel_mesh or until its source goes.
+        Returns (vertices, faces, {"samples", "valid", "cubes", "uncoloured"})."""
+        if source not in MESH_SOURCES:
+            raise ValueError('source must be "voxel", "clean" or "visible"')
+        v = np.ascontiguousarray(views, np.int32).reshape(-1)
+        out = np.zeros(6, np.int64)
+        self._check(self.L.acmmp_fusion_voxel_mesh(self.h, MESH_SOURCES[source], v.size, _p(v) if v.size else None,
+                                                   float(trunc), int(min_weight), *[_p(out[k:k + 1]) for k in range(6)]),
+                    "fusion_voxel_mesh")
+        return int(out[0]), int(out[1]), {"samples": int(out[2]), "valid": int(out[3]), "cubes": int(out[4]),
+                                          "uncoloured": int(out[5])}
+
+    def mesh_vertices(self, first: int, n: int):
+        """Vertices [first, first + n) of the last voxel_mesh: (n, 9) float32 (position, normal, colour)."""
+        v = host_empty((max(n, 0), 9), np.float32)            # (a negative n is refused below)
+        self._check(self.L.acmmp_fusion_mesh_vertices(self.h, first, n, _p(v)), "fusion_mesh_vertices")
+        return v
+
+    def mesh_faces(self, first: int, n: int):
+        """Triangles [first, first + n) of the last voxel_mesh: (n, 3) int32 vertex indices, counter-clockwise seen
+        from free space."""
+        t = np.empty((max(n, 0), 3), np.int32)
+        self._check(self.L.acmmp_fusion_mesh_faces(self.h, first, n, _p(t)), "fusion_mesh_faces")
+        return t
+
+    def mesh_samples(self, first: int, n: int):
+        """Test hook: (cells (n, 3) int32, tsdf (n, 2) int32 = (S, n), entry (n,) int64) of samples [first, first + n)
+        of the last voxel_mesh."""
+        cells, tsdf = np.empty((max(n, 0), 3), np.int32), np.empty((max(n, 0), 2), np.int32)
+        ent = np.empty(max(n, 0), np.int64)
+        self._check(self.L.acmmp_fusion_mesh_samples(self.h, first, n, _p(cells), _p(tsdf), _p(ent)), "fusion_mesh_samples")
+        return cells, tsdf, ent
+
+    def mesh_table(self, force_slots: int = 0):
+        """Test hook: sets the sample-table size of the next voxel_mesh (0 = automatic) and returns the last
+        successful call's {"slots", "occupied", "max_probe", "wrapped"}."""
+        st = np.zeros(4, np.int64)
+        self._check(self.L.acmmp_fusion_mesh_table(self.h, int(force_slots), _p(st[0:1]), _p(st[1:2]), _p(st[2:3]),
+                                                   _p(st[3:4])), "fusion_mesh_table")
+        return {"slots": int(st[0]), "occupied": int(st[1]), "max_probe": int(st[2]), "wrapped": int(st[3])}
 
     def close(self):
         if self.h:

@@ -259,3 +259,91 @@ def read_ply(path: str) -> np.ndarray:
     dt = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                    ("r", "u1"), ("g", "u1"), ("b", "u1")])
     return np.frombuffer(data[end:end + n * dt.itemsize], dtype=dt).copy()
+
+
+_PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+class MeshPlyWriter:
+    """A triangle mesh as a binary PLY in pieces: write_ply's vertex records, then `element face` with
+    `property list uchar int vertex_indices`.  The counts are known up front; the vertices come in any number of
+    write_vertices() calls, then the faces in any number of write_faces() calls.  close() (or leaving the `with`
+    block without an exception) checks that exactly the announced numbers were written."""
+
+    def __init__(self, path: str, n_vertices: int, n_faces: int):
+        self.nv, self.nf, self.wv, self.wf = int(n_vertices), int(n_faces), 0, 0
+        header = ("ply\nformat binary_little_endian 1.0\n"
+                  f"element vertex {self.nv}\n"
+                  "property float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                  f"element face {self.nf}\n"
+                  "property list uchar int vertex_indices\nend_header\n")
+        self.f = open(path, "wb")
+        self.f.write(header.encode("ascii"))
+
+    def write_vertices(self, vertices: np.ndarray) -> None:
+        rec = _ply_records(vertices)
+        if self.wf:
+            raise ValueError("vertices after the first face")
+        if self.wv + rec.shape[0] > self.nv:
+            raise ValueError(f"more than the {self.nv} vertices the header announced")
+        self.f.write(rec.tobytes())
+        self.wv += rec.shape[0]
+
+    def write_faces(self, faces: np.ndarray) -> None:
+        t = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        if self.wv != self.nv:
+            raise ValueError(f"faces after {self.wv} of {self.nv} vertices")
+        if self.wf + t.shape[0] > self.nf:
+            raise ValueError(f"more than the {self.nf} faces the header announced")
+        if t.size and (t.min() < 0 or t.max() >= self.nv):
+            raise ValueError("a face index outside the vertices")
+        rec = np.zeros(t.shape[0], _PLY_FACE)
+        rec["n"], rec["v"] = 3, t
+        self.f.write(rec.tobytes())
+        self.wf += t.shape[0]
+
+    def close(self) -> None:
+        if self.f is None:
+            return
+        self.f.close()
+        self.f = None
+        if self.wv != self.nv or self.wf != self.nf:
+            raise ValueError(f"{self.wv} vertices and {self.wf} faces written, the header announced {self.nv} and {self.nf}")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self.f is not None:
+            self.f.close()
+            self.f = None
+        return False
+
+
+def write_mesh_ply(path: str, vertices: np.ndarray, faces: np.ndarray) -> None:
+    """vertices: (n, 9) float32 rows as write_ply's points; faces: (m, 3) int32 vertex indices."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 9)
+    t = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    with MeshPlyWriter(path, v.shape[0], t.shape[0]) as w:
+        w.write_vertices(v)
+        w.write_faces(t)
+
+
+def read_mesh_ply(path: str):
+    """Reader for write_mesh_ply's layout (tests): (read_ply's structured vertex array, faces (m, 3) int32)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode().splitlines()
+    nv = int([l for l in lines if l.startswith("element vertex")][0].split()[2])
+    nf = int([l for l in lines if l.startswith("element face")][0].split()[2])
+    verts = np.frombuffer(data[end:end + nv * _PLY_RECORD.itemsize], dtype=_PLY_RECORD).copy()
+    at = end + nv * _PLY_RECORD.itemsize
+    rec = np.frombuffer(data[at:at + nf * _PLY_FACE.itemsize], dtype=_PLY_FACE)
+    if len(data) != at + nf * _PLY_FACE.itemsize or (rec["n"] != 3).any():
+        raise ValueError("not a triangle mesh of write_mesh_ply's layout")
+    return verts, rec["v"].astype(np.int32)

@@ -792,7 +792,8 @@ class Pipeline:
                    voxel_size: float | None = None, voxel_min_points: int = 1, voxel_connectivity: int = 26,
                    voxel_min_neighbours: int = 0, voxel_min_component_voxels: int = 1,
                    voxel_min_component_points: int = 1, visibility_tol: float | None = None,
-                   visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0):
+                   visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0,
+                   mesh_trunc: float | None = None, mesh_min_weight: int = 1, mesh_path: str | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -823,8 +824,21 @@ class Pipeline:
         visibility_tol (relative, in a window of visibility_radius pixels, 0 or 1) in at least visibility_min_support
         views and may lie in the free space of at most visibility_max_conflicts views (acmmp_fusion_voxel_visibility,
         include/acmmp.h).  The visible cloud takes the place of the cloud it checked; self.fusion_info gains
-        visible_voxels, vis_unsupported, vis_conflicting, vis_class_totals and the four values."""
+        visible_voxels, vis_unsupported, vis_conflicting, vis_class_totals and the four values.
+
+        mesh_trunc (voxel_size is then required): after all of that, a surface mesh of the cloud that is written --
+        the visible cloud, else the clean cloud, else the voxel cloud -- is extracted on the device: a signed distance
+        to every view's depth map, truncated at mesh_trunc, over the cells within one cell of the cloud, surface-nets
+        vertices where at least mesh_min_weight views see all eight corners of a cube, two triangles per sign change
+        (acmmp_fusion_voxel_mesh, include/acmmp.h).  It is streamed to mesh_path (default: ACMMP/ACMM_mesh.ply of the
+        output folder) chunk_points vertices and faces at a time; the cloud and its PLY are what they are without the
+        mesh.  self.fusion_info gains mesh_vertices, mesh_faces, mesh_samples, mesh_valid, mesh_cubes,
+        mesh_uncoloured and the two values."""
         self.fusion_info = None
+        if (mesh_trunc is not None or mesh_path is not None) and voxel_size is None:
+            raise ValueError("the mesh needs voxel_size")
+        if mesh_path is not None and mesh_trunc is None:
+            raise ValueError("the mesh needs mesh_trunc")
         if visibility_tol is not None and voxel_size is None:
             raise ValueError("the visibility check needs voxel_size")
         clean = (voxel_connectivity, voxel_min_neighbours, voxel_min_component_voxels, voxel_min_component_points) != (26, 0, 1, 1)
@@ -902,6 +916,24 @@ class Pipeline:
                     points[first:first + part.shape[0]] = part
             if writer:
                 writer.close()
+            if mesh_trunc is not None:
+                if not hasattr(fu, "voxel_mesh"):
+                    raise ValueError("the mesh needs a fusion object with voxel_mesh (capi.Fusion)")
+                source = "visible" if visibility_tol is not None else "clean" if clean else "voxel"
+                nv, nf, minfo = fu.voxel_mesh(list(range(len(cams))), mesh_trunc, mesh_min_weight, source=source)
+                self.fusion_info.update(
+                    mesh_vertices=int(nv), mesh_faces=int(nf), mesh_samples=int(minfo["samples"]),
+                    mesh_valid=int(minfo["valid"]), mesh_cubes=int(minfo["cubes"]),
+                    mesh_uncoloured=int(minfo["uncoloured"]), mesh_trunc=float(mesh_trunc),
+                    mesh_min_weight=int(mesh_min_weight))
+                mpath = mesh_path or (os.path.join(self.out_folder, "ACMMP", "ACMM_mesh.ply") if self.out_folder else None)
+                if mpath:
+                    os.makedirs(os.path.dirname(os.path.abspath(mpath)), exist_ok=True)
+                    with io.MeshPlyWriter(mpath, nv, nf) as mw:
+                        for first in range(0, nv, step):
+                            mw.write_vertices(fu.mesh_vertices(first, min(step, nv - first)))
+                        for first in range(0, nf, step):
+                            mw.write_faces(fu.mesh_faces(first, min(step, nf - first)))
         else:
             if unique:
                 raise ValueError("unique fusion needs a fusion object with run_scene (capi.Fusion)")
@@ -1022,6 +1054,13 @@ def arg_parser():
                     help="with --visibility-tol: drop voxels that fewer views than this agree with")
     ap.add_argument("--visibility-max-conflicts", type=int, default=0,
                     help="with --visibility-tol: drop voxels that more views than this see through")
+    ap.add_argument("--mesh", metavar="PATH", default=None,
+                    help="with --voxel-size: also extract a triangle mesh of the cloud that is written (truncated signed "
+                         "distance to the depth maps, surface nets) and write it to this PLY")
+    ap.add_argument("--mesh-trunc", type=float, default=None,
+                    help="with --mesh: the truncation distance, in scene units (default: three voxel sizes)")
+    ap.add_argument("--mesh-min-weight", type=int, default=1,
+                    help="with --mesh: a cell needs a distance from at least this many views")
     return ap
 
 
@@ -1051,7 +1090,10 @@ def main(argv=None):
                               voxel_min_component_voxels=a.min_component_voxels,
                               voxel_min_component_points=a.min_component_points, visibility_tol=a.visibility_tol,
                               visibility_radius=a.visibility_radius, visibility_min_support=a.visibility_min_support,
-                              visibility_max_conflicts=a.visibility_max_conflicts)
+                              visibility_max_conflicts=a.visibility_max_conflicts,
+                              mesh_trunc=(a.mesh_trunc if a.mesh_trunc is not None or a.mesh is None or a.voxel_size is None
+                                          else 3.0 * a.voxel_size),
+                              mesh_min_weight=a.mesh_min_weight, mesh_path=a.mesh)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -85,6 +85,7 @@ struct acmmp_fusion {
     bool v_tab_live = false;                     // v_tab is the table of the voxel result held (else scratch)
     long long v_force_slots = 0;                 // test hook: table size of the next run, 0 = automatic
     long long v_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful run
+    VoxGrid v_grid = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // origin and size of the voxel result held
     // ... and its scratch, kept between runs and dropped with the scene result it was sized for
     VoxTableBuf v_tab, v_tab_spare;              // v_tab_spare: filled by a voxelize while v_tab belongs to a result
     DevBuf<int> v_flags;                         // per point of a segment
@@ -96,6 +97,7 @@ struct acmmp_fusion {
     DevBuf<float> c_pts;                         // 9 floats per kept voxel
     DevBuf<int32_t> c_cnt;                       // points per kept voxel
     DevBuf<long long> c_comp;                    // component id per kept voxel
+    DevBuf<unsigned long long> c_vox;            // voxel index per kept voxel
     DevBuf<unsigned long long> c_lab;            // per voxel of the voxel result: label, ~0 = unsupported
     DevBuf<uint32_t> c_mask;                     // per voxel: its neighbours, one bit each
     DevBuf<long long> c_table;                   // roots, then voxels, then points, c_comps of each
@@ -107,11 +109,24 @@ struct acmmp_fusion {
     DevBuf<int32_t> vis_cnt;                     // points per kept entry
     DevBuf<int32_t> vis_kept_tal;                // 3 per kept entry
     DevBuf<int32_t> vis_tal;                     // 3 per entry of the source
+    DevBuf<unsigned long long> vis_vox;          // voxel index per kept entry
     unsigned long long vis_total = 0, vis_entries = 0;   // kept entries, entries of the source
     int vis_source = 0;                          // ACMMP_VIS_FROM_*
     bool vis_have = false;                       // a visibility call has succeeded on this source
     DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
     DevBuf<unsigned long long> vis_words;        // kVisWords device words
+    // surface mesh of the voxel, clean or visible result (acmmp_fusion_voxel_mesh): its resident result
+    DevBuf<float> m_verts;                       // 9 floats per vertex
+    DevBuf<int32_t> m_faces;                     // 3 per triangle
+    DevBuf<unsigned long long> m_skey;           // packed cell per sample
+    DevBuf<int32_t> m_tsdf;                      // (S, n) per sample
+    DevBuf<long long> m_sent;                    // remembered entry per sample, -1 = none
+    unsigned long long m_nv = 0, m_nf = 0, m_ns = 0;   // vertices, triangles, samples
+    int m_source = 0;                            // ACMMP_MESH_FROM_*
+    bool m_have = false;                         // a mesh call has succeeded on this source
+    long long m_force_slots = 0;                 // test hook: sample table size of the next call, 0 = automatic
+    long long m_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful call
+    DevBuf<unsigned long long> m_words;          // kMeshWords device words
     std::string err;
 };
 
@@ -274,16 +289,26 @@ void voxel_scratch_release(acmmp_fusion* f) {
     f->v_cap_seg = 0;
 }
 
+void mesh_release(acmmp_fusion* f) {
+    f->m_verts.reset(); f->m_faces.reset(); f->m_skey.reset(); f->m_tsdf.reset(); f->m_sent.reset();
+    f->m_nv = f->m_nf = f->m_ns = 0;
+    f->m_have = false;
+}
+
+// The clean result and the visible result go with a mesh result built from them.
 void clean_release(acmmp_fusion* f) {
-    f->c_pts.reset(); f->c_cnt.reset(); f->c_comp.reset(); f->c_lab.reset(); f->c_mask.reset(); f->c_table.reset();
+    f->c_pts.reset(); f->c_cnt.reset(); f->c_comp.reset(); f->c_vox.reset(); f->c_lab.reset(); f->c_mask.reset();
+    f->c_table.reset();
     f->c_total = f->c_comps = 0;
     f->c_have = false;
+    if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
 }
 
 void visibility_release(acmmp_fusion* f) {
-    f->vis_pts.reset(); f->vis_cnt.reset(); f->vis_kept_tal.reset(); f->vis_tal.reset();
+    f->vis_pts.reset(); f->vis_cnt.reset(); f->vis_kept_tal.reset(); f->vis_tal.reset(); f->vis_vox.reset();
     f->vis_total = f->vis_entries = 0;
     f->vis_have = false;
+    if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);
 }
 
 // A new scene result is in place: the voxel result, the clean result and the visible result described the previous
@@ -294,6 +319,7 @@ void scene_replaced(acmmp_fusion* f) {
     f->v_have = false;
     clean_release(f);
     visibility_release(f);
+    mesh_release(f);
     voxel_scratch_release(f);
 }
 
@@ -696,6 +722,8 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     f->v_have = true;
     clean_release(f);                                 // it described the previous voxel result
     visibility_release(f);                            // and so did this one, from either source
+    mesh_release(f);                                  // and this one, from any source
+    f->v_grid = g;
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
     f->v_stats[2] = static_cast<long long>(words[kVoxMaxProbe]);
@@ -741,7 +769,7 @@ struct CleanOut {
     DevBuf<float> pts;
     DevBuf<int32_t> cnt;
     DevBuf<long long> comp, table;
-    DevBuf<unsigned long long> lab;
+    DevBuf<unsigned long long> lab, vox;
     DevBuf<uint32_t> mask;
     DevBuf<unsigned long long> scratch;      // per voxel: component voxels, points, dense id
     unsigned long long kept = 0, comps = 0, comps_kept = 0, unsupported = 0, rounds = 0;
@@ -792,6 +820,7 @@ acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, un
     F_HIP(f, alloc(out.pts, 9 * nk));
     F_HIP(f, alloc(out.cnt, nk));
     F_HIP(f, alloc(out.comp, nk));
+    F_HIP(f, alloc(out.vox, nk));
     // the roots, then the kept voxels, each compacted in voxel order, segment after segment
     unsigned long long* running = w + kCleanRunning;
     unsigned long long* seg_base = w + kCleanSegBase;
@@ -805,7 +834,7 @@ acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, un
     for (unsigned long long i0 = 0; i0 < nv; i0 += seg)
         F_HIP(f, launch_clean_compact_kept(nv, i0, static_cast<int>(std::min(seg, nv - i0)), out.lab, c, f->v_flags,
                                            f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
-                                           f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, s));
+                                           f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, out.vox, s));
     F_HIP(f, hipMemcpyAsync(&done[1], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
     if (done[0] != out.comps || done[1] != out.kept)
@@ -854,6 +883,7 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
     f->c_pts = std::move(out.pts);
     f->c_cnt = std::move(out.cnt);
     f->c_comp = std::move(out.comp);
+    f->c_vox = std::move(out.vox);
     f->c_lab = std::move(out.lab);
     f->c_mask = std::move(out.mask);
     f->c_table = std::move(out.table);
@@ -861,6 +891,7 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
     f->c_comps = out.comps;
     f->c_have = true;
     if (f->vis_have && f->vis_source == ACMMP_VIS_FROM_CLEAN) visibility_release(f);   // its source is replaced
+    if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
     if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
     if (n_components) *n_components = static_cast<int64_t>(out.comps);
     if (n_components_kept) *n_components_kept = static_cast<int64_t>(out.comps_kept);
@@ -922,10 +953,12 @@ constexpr int kVisMaxList = 4096;
 struct VisOut {
     DevBuf<float> pts;
     DevBuf<int32_t> cnt, kept_tal, tal;
+    DevBuf<unsigned long long> vox;
     unsigned long long kept = 0, no_support = 0, conflicting = 0, classes[4] = {0, 0, 0, 0};
 };
 
-acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t* src_cnt, unsigned long long N,
+acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t* src_cnt,
+                            const unsigned long long* src_vox, unsigned long long N,
                             int n_list, const int* views, float rel_tol, int radius, int min_support, int max_conflicts,
                             VisOut& out) {
     hipStream_t s = f->stream;
@@ -953,6 +986,7 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
     F_HIP(f, alloc(out.pts, 9 * nk));
     F_HIP(f, alloc(out.cnt, nk));
     F_HIP(f, alloc(out.kept_tal, 3 * nk));
+    F_HIP(f, alloc(out.vox, nk));
     // the kept entries, compacted in entry order, segment after segment
     unsigned long long* running = w + kVisRunning;
     unsigned long long* seg_base = w + kVisSegBase;
@@ -960,7 +994,7 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
     for (unsigned long long i0 = 0; i0 < N; i0 += seg)
         F_HIP(f, launch_vis_compact(i0, static_cast<int>(std::min(seg, N - i0)), out.tal, min_support, max_conflicts,
                                     f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
-                                    src_pts, src_cnt, out.pts, out.cnt, out.kept_tal, s));
+                                    src_pts, src_cnt, out.pts, out.cnt, out.kept_tal, src_vox, out.vox, s));
     F_HIP(f, hipMemcpyAsync(&done, running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
     if (done != out.kept)
@@ -998,8 +1032,9 @@ acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_li
     const unsigned long long N = clean ? f->c_total : f->v_total;
     VisOut out;
     if (N > 0) {
-        const acmmp_status st = visibility_run(f, clean ? f->c_pts : f->v_pts, clean ? f->c_cnt : f->v_cnt, N, n_list, views,
-                                               rel_tol, radius, min_support, max_conflicts, out);
+        const acmmp_status st = visibility_run(f, clean ? f->c_pts : f->v_pts, clean ? f->c_cnt : f->v_cnt,
+                                               clean ? f->c_vox.get() : nullptr, N, n_list, views, rel_tol, radius,
+                                               min_support, max_conflicts, out);
         if (st != ACMMP_OK) {
             const std::string why = f->err;
             (void)hipGetLastError();
@@ -1012,6 +1047,8 @@ acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_li
     f->vis_cnt = std::move(out.cnt);
     f->vis_kept_tal = std::move(out.kept_tal);
     f->vis_tal = std::move(out.tal);
+    f->vis_vox = std::move(out.vox);
+    if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);          // its source is replaced
     f->vis_total = out.kept;
     f->vis_entries = N;
     f->vis_source = source;
@@ -1043,6 +1080,242 @@ acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion* f, int64_t first, int
     if (n == 0) return ACMMP_OK;
     F_HIP(f, hipSetDevice(f->device));
     F_HIP(f, read_range<int32_t>(tallies, f->vis_tal, static_cast<size_t>(first), static_cast<size_t>(n), 3));
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- surface mesh of the voxel, clean or visible result (include/acmmp.h; kernels: k_mesh_*) -----------------
+
+namespace {
+
+// The sample table of one mesh call (scratch) and the new result, swapped in only when the whole call succeeded.
+struct MeshOut {
+    DevBuf<unsigned long long> keys, rank, ent, sid;       // the table
+    DevBuf<unsigned long long> ekey;                       // per entry
+    DevBuf<uint8_t> cflag, fbits;                          // per sample
+    DevBuf<int32_t> vid;                                   // per sample
+    DevBuf<float> verts;
+    DevBuf<int32_t> faces, tsdf;
+    DevBuf<unsigned long long> skey;
+    DevBuf<long long> sent;
+    unsigned long long nv = 0, nf = 0, ns = 0, valid = 0, cubes = 0, uncoloured = 0;
+    long long stats[4] = {0, 0, 0, 0};
+};
+
+acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long long* src_vox, unsigned long long ne,
+                      int n_list, const int* views, float trunc, int min_weight, unsigned long long slots, MeshOut& out) {
+    hipStream_t s = f->stream;
+    const unsigned long long seg = voxel_segment_points(), pairs = 27ull * ne;
+    if (!f->m_words) F_HIP(f, alloc(f->m_words, kMeshWords));
+    if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
+    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(pairs, seg)));
+    if (scratch != ACMMP_OK) return scratch;
+    int log2_slots = 0, v_log2 = 0;
+    while ((1ull << log2_slots) < slots) ++log2_slots;
+    while ((1ull << v_log2) < f->v_tab.slots) ++v_log2;
+    F_HIP(f, alloc(out.keys, slots));
+    F_HIP(f, alloc(out.rank, slots));
+    F_HIP(f, alloc(out.ent, slots));
+    F_HIP(f, alloc(out.sid, slots));
+    F_HIP(f, alloc(out.ekey, static_cast<size_t>(ne)));
+    const VoxTable vt = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, f->v_tab.slots, v_log2};
+    const MeshTable m = {out.keys, out.rank, out.ent, out.sid, slots, log2_slots};
+    unsigned long long* w = f->m_words;
+    unsigned long long* running = w + kMeshRunning;
+    unsigned long long* seg_base = w + kMeshSegBase;
+    unsigned long long h[kMeshWords] = {0};
+    F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kMeshWords, s));
+    F_HIP(f, hipMemsetAsync(m.keys, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(m.rank, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(m.ent, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemsetAsync(m.sid, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, hipMemcpyAsync(f->vis_list, views, sizeof(int) * n_list, hipMemcpyHostToDevice, s));
+    // the samples: insert, then the table's counts
+    F_HIP(f, launch_mesh_keys(ne, src_vox, f->v_total, f->v_slot, vt, out.ekey, w, s));
+    for (unsigned long long p0 = 0; p0 < pairs; p0 += seg)
+        F_HIP(f, launch_mesh_insert(p0, static_cast<int>(std::min(seg, pairs - p0)), out.ekey, m, w, s));
+    F_HIP(f, launch_mesh_stats(m, w, s));
+    // the first host wait: the sample count, to size the per-sample arrays
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (h[kMeshErr] & 1ull) return ffail(f, ACMMP_ERR_HIP, "voxel mesh: an entry's voxel is not in the voxel table");
+    if (h[kMeshErr]) return ffail(f, ACMMP_ERR_HIP, "voxel mesh: the sample table is full (" + std::to_string(slots) + " slots)");
+    out.ns = h[kMeshOccupied];
+    out.stats[0] = static_cast<long long>(slots);
+    out.stats[1] = static_cast<long long>(h[kMeshOccupied]);
+    out.stats[2] = static_cast<long long>(h[kMeshMaxProbe]);
+    out.stats[3] = static_cast<long long>(h[kMeshWrapped]);
+    if (out.ns > pairs) return ffail(f, ACMMP_ERR_HIP, "voxel mesh: more samples than (entry, offset) pairs");
+    const size_t ns = static_cast<size_t>(out.ns);
+    // the compactions run over the 27 ne pairs, the ns samples and the 3 ns (sample, axis) pairs
+    const acmmp_status scratch2 = segment_scratch(f, static_cast<size_t>(std::min(std::max(pairs, 3ull * out.ns), seg)));
+    if (scratch2 != ACMMP_OK) return scratch2;
+    F_HIP(f, alloc(out.skey, ns));
+    F_HIP(f, alloc(out.tsdf, 2 * ns));
+    F_HIP(f, alloc(out.sent, ns));
+    F_HIP(f, alloc(out.cflag, ns));
+    F_HIP(f, alloc(out.fbits, ns));
+    F_HIP(f, alloc(out.vid, ns));
+    const MeshSamples smp = {out.skey, out.tsdf, out.sent, out.ns};
+    for (unsigned long long p0 = 0; p0 < pairs; p0 += seg)
+        F_HIP(f, launch_mesh_number(p0, static_cast<int>(std::min(seg, pairs - p0)), out.ekey, m, f->v_flags, f->v_counts,
+                                    f->v_offsets, f->v_seg_count, running, seg_base, smp, w, s));
+    unsigned long long done[3] = {0, 0, 0};
+    F_HIP(f, hipMemcpyAsync(&done[0], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
+    // the distances, the cubes, the pairs that emit faces
+    F_HIP(f, launch_mesh_tsdf(f->model, f->d_cams, f->d_views, f->vis_list, n_list, smp, f->v_grid, trunc, s));
+    F_HIP(f, launch_mesh_cubes(smp, m, min_weight, out.cflag, out.fbits, w, s));
+    // the second host wait: the vertex and face counts, to size the result
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (h[kMeshErr] || done[0] != out.ns)
+        return ffail(f, ACMMP_ERR_HIP, "voxel mesh: sample lookup failed (flags " + std::to_string(h[kMeshErr]) + ", numbered " +
+                                           std::to_string(done[0]) + " of " + std::to_string(out.ns) + ")");
+    out.valid = h[kMeshValid];
+    out.cubes = h[kMeshCubes];
+    out.nv = h[kMeshActive];
+    const unsigned long long n_pairs = h[kMeshPairs];
+    out.nf = 2ull * n_pairs;
+    if (out.nv > out.ns || n_pairs > 3ull * out.ns) return ffail(f, ACMMP_ERR_HIP, "voxel mesh: counts beyond the samples");
+    if (out.nv > 0x7fffffffull) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "voxel mesh: more than 2^31 - 1 vertices");
+    F_HIP(f, alloc(out.verts, 9 * static_cast<size_t>(out.nv)));
+    F_HIP(f, alloc(out.faces, 6 * static_cast<size_t>(n_pairs)));
+    F_HIP(f, hipMemsetAsync(out.vid, 0xff, sizeof(int32_t) * ns, s));
+    for (unsigned long long i0 = 0; i0 < out.ns; i0 += seg)
+        F_HIP(f, launch_mesh_vertices(i0, static_cast<int>(std::min(seg, out.ns - i0)), smp, m, f->v_grid, out.cflag, src_pts,
+                                      f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.nv,
+                                      out.verts, out.vid, w, s));
+    F_HIP(f, hipMemcpyAsync(&done[1], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
+    const unsigned long long fp = 3ull * out.ns;
+    for (unsigned long long p0 = 0; p0 < fp; p0 += seg)
+        F_HIP(f, launch_mesh_faces(p0, static_cast<int>(std::min(seg, fp - p0)), smp, m, out.cflag, out.fbits, out.vid,
+                                   f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, n_pairs,
+                                   out.faces, w, s));
+    F_HIP(f, hipMemcpyAsync(&done[2], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    // the third host wait: the end
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (h[kMeshErr] || done[1] != out.nv || done[2] != n_pairs)
+        return ffail(f, ACMMP_ERR_HIP, "voxel mesh: extraction failed (flags " + std::to_string(h[kMeshErr]) + ", " +
+                                           std::to_string(done[1]) + " of " + std::to_string(out.nv) + " vertices, " +
+                                           std::to_string(done[2]) + " of " + std::to_string(n_pairs) + " quads)");
+    out.uncoloured = h[kMeshUncoloured];
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, const int* views, float trunc, int min_weight,
+                                     int64_t* n_vertices, int64_t* n_faces, int64_t* n_samples, int64_t* n_valid,
+                                     int64_t* n_cubes, int64_t* n_uncoloured) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (source != ACMMP_MESH_FROM_VOXELS && source != ACMMP_MESH_FROM_CLEAN && source != ACMMP_MESH_FROM_VISIBLE)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_MESH_FROM_*");
+    const bool have = source == ACMMP_MESH_FROM_VOXELS ? f->v_have : source == ACMMP_MESH_FROM_CLEAN ? f->c_have : f->vis_have;
+    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such source result");
+    if (n_list < 1 || n_list > kVisMaxList || !views)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the view list must hold 1 to 4096 views");
+    for (int j = 0; j < n_list; ++j) {
+        if (views[j] < 0 || views[j] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
+        if (!f->views[views[j]].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for every view listed");
+    }
+    if (!finite32(trunc) || !(trunc > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "trunc must be finite and > 0");
+    if (min_weight < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_weight must be at least 1");
+    const float* src_pts = source == ACMMP_MESH_FROM_VOXELS ? f->v_pts : source == ACMMP_MESH_FROM_CLEAN ? f->c_pts : f->vis_pts;
+    const unsigned long long* src_vox =
+        source == ACMMP_MESH_FROM_VOXELS ? nullptr : source == ACMMP_MESH_FROM_CLEAN ? f->c_vox.get() : f->vis_vox.get();
+    const unsigned long long ne = source == ACMMP_MESH_FROM_VOXELS ? f->v_total : source == ACMMP_MESH_FROM_CLEAN ? f->c_total : f->vis_total;
+    unsigned long long slots = 1024;
+    if (f->m_force_slots != 0) {
+        const long long v = f->m_force_slots;
+        if (v < 64 || (v & (v - 1)) != 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "forced table size must be a power of two >= 64");
+        slots = static_cast<unsigned long long>(v);
+    } else {
+        if (ne > (1ull << 54)) return ffail(f, ACMMP_ERR_UNSUPPORTED, "source too large for the sample table");
+        while (slots < 54ull * ne) slots <<= 1;
+    }
+    F_HIP(f, hipSetDevice(f->device));
+    MeshOut out;
+    if (ne > 0) {
+        const acmmp_status st = mesh_run(f, src_pts, src_vox, ne, n_list, views, trunc, min_weight, slots, out);
+        if (st != ACMMP_OK) {
+            const std::string why = f->err;
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(f->stream);
+            f->err = why;
+            return st;
+        }
+    } else {
+        out.stats[0] = static_cast<long long>(slots);
+    }
+    f->m_verts = std::move(out.verts);
+    f->m_faces = std::move(out.faces);
+    f->m_skey = std::move(out.skey);
+    f->m_tsdf = std::move(out.tsdf);
+    f->m_sent = std::move(out.sent);
+    f->m_nv = out.nv;
+    f->m_nf = out.nf;
+    f->m_ns = out.ns;
+    f->m_source = source;
+    f->m_have = true;
+    std::copy(out.stats, out.stats + 4, f->m_stats);
+    if (n_vertices) *n_vertices = static_cast<int64_t>(out.nv);
+    if (n_faces) *n_faces = static_cast<int64_t>(out.nf);
+    if (n_samples) *n_samples = static_cast<int64_t>(out.ns);
+    if (n_valid) *n_valid = static_cast<int64_t>(out.valid);
+    if (n_cubes) *n_cubes = static_cast<int64_t>(out.cubes);
+    if (n_uncoloured) *n_uncoloured = static_cast<int64_t>(out.uncoloured);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_mesh_vertices(acmmp_fusion* f, int64_t first, int64_t n, float* vertices) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->m_nv)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's vertices");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, read_range<float>(vertices, f->m_verts, static_cast<size_t>(first), static_cast<size_t>(n), 9));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_mesh_faces(acmmp_fusion* f, int64_t first, int64_t n, int32_t* faces) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->m_nf)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's faces");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, read_range<int32_t>(faces, f->m_faces, static_cast<size_t>(first), static_cast<size_t>(n), 3));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_mesh_samples(acmmp_fusion* f, int64_t first, int64_t n, int32_t* cells, int32_t* tsdf, int64_t* entry) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->m_ns)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's samples");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    if (cells) {
+        std::vector<unsigned long long> keys(m);
+        F_HIP(f, read_range<unsigned long long>(keys.data(), f->m_skey, a, m));
+        for (size_t i = 0; i < m; ++i)
+            for (int k = 0; k < 3; ++k) cells[3 * i + k] = static_cast<int32_t>((keys[i] >> (21 * k)) & 0x1fffffull);
+    }
+    F_HIP(f, read_range<int32_t>(tsdf, f->m_tsdf, a, m, 2));
+    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(entry), f->m_sent, a, m));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_mesh_table(acmmp_fusion* f, int64_t force_slots, int64_t* slots, int64_t* occupied,
+                                     int64_t* max_probe, int64_t* wrapped) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->m_force_slots = force_slots;                   // checked by the next mesh call
+    if (slots) *slots = f->m_stats[0];
+    if (occupied) *occupied = f->m_stats[1];
+    if (max_probe) *max_probe = f->m_stats[2];
+    if (wrapped) *wrapped = f->m_stats[3];
     return ACMMP_OK;
 }
 

@@ -117,8 +117,8 @@ hipError_t launch_clean_round(unsigned long long nv, const unsigned long long* v
 hipError_t launch_clean_sizes(unsigned long long nv, const unsigned long long* lab, const int32_t* cnt, CleanComp c,
                               unsigned long long* words, hipStream_t s);
 // Compaction of voxels [i0, i0 + n) (one segment, as launch_voxel_compact): the roots to the component table and
-// c.id[root]; then, once every segment's roots are through, the kept voxels to the clean cloud.  Nothing is written
-// at or past `cap` entries.
+// c.id[root]; then, once every segment's roots are through, the kept voxels to the clean cloud (out_vox: their
+// voxel index).  Nothing is written at or past `cap` entries.
 hipError_t launch_clean_compact_roots(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
                                       CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
                                       unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
@@ -127,7 +127,7 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
                                      const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
-                                     long long* out_comp, hipStream_t s);
+                                     long long* out_comp, unsigned long long* out_vox, hipStream_t s);
 
 // Visibility check of the voxel or clean cloud (acmmp_fusion_voxel_visibility, include/acmmp.h): over
 // the entries [0, n) of `pts` (9 floats each), one lane per entry.
@@ -148,10 +148,70 @@ hipError_t launch_vis_tally(int model, const DevCam* cams, const FuseView* views
 hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_list, int min_support, int max_conflicts,
                             unsigned long long* words, hipStream_t s);
 // Compaction of entries [i0, i0 + n) (one segment, as launch_voxel_compact): the kept entries' floats, counts and
-// tallies in ascending order.  Nothing is written at or past `cap` entries.
+// tallies in ascending order, and out_vox = their voxel index (src_vox[e], or e itself when src_vox is NULL).  Nothing
+// is written at or past `cap` entries.
 hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
                               int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
                               unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
-                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal, hipStream_t s);
+                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal,
+                              const unsigned long long* src_vox, unsigned long long* out_vox, hipStream_t s);
+
+// Surface mesh of the voxel, clean or visible result (acmmp_fusion_voxel_mesh, include/acmmp.h).
+// The sample table: open addressing as VoxTable.  keys (~0 = empty), rank (smallest e * 27 + offset index), ent (the
+// entry whose own cell this is, ~0 = none) and sid (the sample's number) start as all-ones bytes.
+struct MeshTable {
+    unsigned long long* keys;
+    unsigned long long* rank;
+    unsigned long long* ent;
+    unsigned long long* sid;
+    unsigned long long slots;
+    int log2_slots;
+};
+// Device words of a mesh run (all zero before it).
+enum { kMeshErr = 0, kMeshOccupied = 1, kMeshWrapped = 2, kMeshMaxProbe = 3, kMeshValid = 4, kMeshCubes = 5, kMeshActive = 6,
+       kMeshPairs = 7, kMeshUncoloured = 8, kMeshRunning = 9, kMeshSegBase = 10, kMeshWords = 11 };
+// Bits of a sample's flag byte (launch_mesh_cubes).
+enum { kMeshCubeExists = 1, kMeshCubeActive = 2, kMeshSampleValid = 4, kMeshSampleInside = 8 };
+// The per-sample arrays of a mesh result: packed cell, (S, n), remembered entry (-1 = none).
+struct MeshSamples {
+    unsigned long long* key;
+    int32_t* tsdf;
+    long long* ent;
+    unsigned long long n;
+};
+// ekey[e] = the packed cell of entry e: t.keys[vslot[vox ? vox[e] : e]]; words[kMeshErr] |= 1 for an index outside.
+hipError_t launch_mesh_keys(unsigned long long ne, const unsigned long long* vox, unsigned long long nv,
+                            const unsigned long long* vslot, VoxTable t, unsigned long long* ekey,
+                            unsigned long long* words, hipStream_t s);
+// Pairs [p0, p0 + n) of the 27 ne (entry, offset) pairs, one lane each: the cell's slot (CAS on keys), rank =
+// min(rank, p), ent = e for the entry's own cell; words[kMeshErr] |= 2 when a probe sequence walked the whole table.
+hipError_t launch_mesh_insert(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m,
+                              unsigned long long* words, hipStream_t s);
+// Over the slots: words[kMeshOccupied], [kMeshWrapped], [kMeshMaxProbe] as launch_voxel_stats.
+hipError_t launch_mesh_stats(MeshTable m, unsigned long long* words, hipStream_t s);
+// Compaction of pairs [p0, p0 + n) (one segment, as launch_voxel_compact): the pairs that own their cell's rank, in
+// ascending order, number the samples: sid[slot], out.key, out.ent.  Nothing is written at or past out.n samples.
+hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, int* flags,
+                              int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                              unsigned long long* seg_base, MeshSamples out, unsigned long long* words, hipStream_t s);
+// out.tsdf[2 s ..] = (S, n) of every sample over the views list[0 .. n_list), as launch_vis_tally.
+hipError_t launch_mesh_tsdf(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
+                            MeshSamples smp, VoxGrid g, float trunc, hipStream_t s);
+// cflag[s] = the sample's kMesh* bits, then fbits[s] = bit a set when the pair (s, axis a) emits faces; words[kMeshValid],
+// [kMeshCubes], [kMeshActive], [kMeshPairs] += their numbers, words[kMeshErr] |= 4 for a failed lookup.
+hipError_t launch_mesh_cubes(MeshSamples smp, MeshTable m, int min_weight, uint8_t* cflag, uint8_t* fbits,
+                             unsigned long long* words, hipStream_t s);
+// Compaction of samples [i0, i0 + n): the active cubes' vertices (9 floats each) in ascending s, vid[s] = their number
+// (all-ones before); src_pts: the entries' 9 floats.  Nothing is written at or past `cap` vertices.
+hipError_t launch_mesh_vertices(unsigned long long i0, int n, MeshSamples smp, MeshTable m, VoxGrid g, const uint8_t* cflag,
+                                const float* src_pts, int* flags, int* counts, int* offsets, int* seg_count,
+                                unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                float* verts, int32_t* vid, unsigned long long* words, hipStream_t s);
+// Compaction of the (sample, axis) pairs [p0, p0 + n) of 3 ns: two triangles (6 indices) per flagged pair, in ascending
+// order.  Nothing is written at or past `cap` pairs.
+hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, MeshTable m, const uint8_t* cflag,
+                             const uint8_t* fbits, const int32_t* vid, int* flags, int* counts, int* offsets,
+                             int* seg_count, unsigned long long* running, unsigned long long* seg_base,
+                             unsigned long long cap, int32_t* faces, unsigned long long* words, hipStream_t s);
 
 }  // namespace acmmp

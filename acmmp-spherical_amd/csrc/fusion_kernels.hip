@@ -1,7 +1,7 @@
 // fusion_kernels.hip -- gfx950 kernels of the depth-map fusion (SimpleFusionKernel, ACMMP.cu:1662-1814, its
 // whole-scene pass and their in-order compaction), of the voxel-grid reduction of the fused scene cloud and of the
-// cleaning and the visibility check of that voxel cloud, with their host launchers (fusion.h).  One
-// translation unit, compiled once.
+// cleaning, the visibility check and the surface mesh of that voxel cloud, with their host launchers
+// (fusion.h).  One translation unit, compiled once.
 #include <algorithm>
 
 #include "camera_dev.h"
@@ -818,7 +818,8 @@ __global__ __launch_bounds__(256) void k_clean_scatter_kept(unsigned long long i
                                                             const unsigned long long* __restrict__ cid,
                                                             const float* __restrict__ v_pts, const int32_t* __restrict__ v_cnt,
                                                             float* __restrict__ out, int32_t* __restrict__ out_cnt,
-                                                            long long* __restrict__ out_comp) {
+                                                            long long* __restrict__ out_comp,
+                                                            unsigned long long* __restrict__ out_vox) {
     const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
     const int f = i < n ? flags[i] : 0;
     const int rank = chunk_rank(f, offsets);
@@ -831,6 +832,7 @@ __global__ __launch_bounds__(256) void k_clean_scatter_kept(unsigned long long i
         for (int k = 0; k < 9; ++k) dst[k] = src[k];
         out_cnt[pos] = v_cnt[v];
         out_comp[pos] = static_cast<long long>(cid[lab[v]]);
+        out_vox[pos] = v;
     }
 }
 
@@ -874,13 +876,13 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
                                      const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
-                                     long long* out_comp, hipStream_t s) {
+                                     long long* out_comp, unsigned long long* out_vox, hipStream_t s) {
     const int n_chunks = cdiv(n, 256);
     k_clean_mark<true><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(nv, i0, n, lab, c.voxels, c.points, c.min_voxels,
                                                                        c.min_points, flags, counts);
     k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
     k_clean_scatter_kept<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, lab, c.id,
-                                                                         v_pts, v_cnt, out, out_cnt, out_comp);
+                                                                         v_pts, v_cnt, out, out_cnt, out_comp, out_vox);
     return hipGetLastError();
 }
 
@@ -891,14 +893,23 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
 // float32 comparisons of one entry against one pixel; what is summed is the integer count of each class, so no
 // result depends on the order the adds land in.
 
+// Steps 1 and 2: the projection of X into one view, its depth pd and its pixel (c, r); false = unobserved.
+template <int MODEL>
+__device__ __forceinline__ bool vis_pixel(const DevCam& cam, const FuseView& view, float3 X, int& c, int& r, float& pd) {
+    float px, py;
+    project<MODEL, const DevCam, true>(cam, X, px, py, pd);
+    if (vox_nonfinite(px) || vox_nonfinite(py) || vox_nonfinite(pd) || !(pd > 0.0f)) return false;
+    c = f2i_sat(px + 0.5f);
+    r = f2i_sat(py + 0.5f);
+    return c >= 0 && c < view.W && r >= 0 && r < view.H;
+}
+
 // The class of entry X in one view: 0 support, 1 conflict, 2 occluded, 3 unobserved.
 template <int MODEL>
 __device__ __forceinline__ int vis_class(const DevCam& cam, const FuseView& view, float3 X, float rel_tol, int radius) {
-    float px, py, pd;
-    project<MODEL, const DevCam, true>(cam, X, px, py, pd);
-    if (vox_nonfinite(px) || vox_nonfinite(py) || vox_nonfinite(pd) || !(pd > 0.0f)) return 3;
-    const int c = f2i_sat(px + 0.5f), r = f2i_sat(py + 0.5f);
-    if (c < 0 || c >= view.W || r < 0 || r >= view.H) return 3;
+    int c, r;
+    float pd;
+    if (!vis_pixel<MODEL>(cam, view, X, c, r, pd)) return 3;
     bool any = false, agree = false, behind = false;
     for (int dy = -radius; dy <= radius; ++dy) {
         const int rr = r + dy;
@@ -988,7 +999,9 @@ __global__ __launch_bounds__(256) void k_vis_scatter(unsigned long long i0, int 
                                                      const unsigned long long* __restrict__ seg_base, unsigned long long cap,
                                                      const float* __restrict__ src_pts, const int32_t* __restrict__ src_cnt,
                                                      const int32_t* __restrict__ tallies, float* __restrict__ out,
-                                                     int32_t* __restrict__ out_cnt, int32_t* __restrict__ out_tal) {
+                                                     int32_t* __restrict__ out_cnt, int32_t* __restrict__ out_tal,
+                                                     const unsigned long long* __restrict__ src_vox,
+                                                     unsigned long long* __restrict__ out_vox) {
     const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
     const int f = i < n ? flags[i] : 0;
     const int rank = chunk_rank(f, offsets);
@@ -1002,6 +1015,7 @@ __global__ __launch_bounds__(256) void k_vis_scatter(unsigned long long i0, int 
         out_cnt[pos] = src_cnt[e];
 #pragma unroll
         for (int k = 0; k < 3; ++k) out_tal[3ull * pos + k] = tallies[3ull * e + k];
+        out_vox[pos] = src_vox ? src_vox[e] : e;
     }
 }
 
@@ -1031,12 +1045,473 @@ hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_
 hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
                               int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
                               unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
-                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal, hipStream_t s) {
+                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal,
+                              const unsigned long long* src_vox, unsigned long long* out_vox, hipStream_t s) {
     const int n_chunks = cdiv(n, 256);
     k_vis_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, tallies, min_support, max_conflicts, flags, counts);
     k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
     k_vis_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, src_pts, src_cnt,
-                                                                   tallies, out, out_cnt, out_tal);
+                                                                   tallies, out, out_cnt, out_tal, src_vox, out_vox);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ surface mesh of the voxel cloud
+//
+// acmmp_fusion_voxel_mesh (include/acmmp.h): the cells within one cell of an entry are the samples of
+// a truncated signed distance to the views' raw depth maps, summed as integers; the cubes of eight valid samples
+// whose signs differ give one vertex each (surface nets) and the sign changes along the axes give the quads between
+// them.  The sample table is VoxTable's scheme; which slot a cell gets is the only racy thing, and nothing that is
+// read back depends on it: samples are numbered by rank, vertices by sample, faces by (sample, axis).
+
+// The number of the sample at offset `b` (clean_neighbour's index) of the cell `key`: 0 = found, 1 = no such sample,
+// 2 = the probe sequence covered every slot or the slot holds no number.
+__device__ __forceinline__ int mesh_sample(const MeshTable& m, unsigned long long ns, unsigned long long key, int b,
+                                           unsigned long long& sid) {
+    unsigned long long nkey;
+    if (!clean_neighbour(key, b, nkey)) return 1;
+    const unsigned long long mask = m.slots - 1ull;
+    unsigned long long s = vox_home(nkey, m.log2_slots);
+    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
+        const unsigned long long k = m.keys[s];
+        if (k == nkey) {
+            sid = m.sid[s];
+            return sid < ns ? 0 : 2;
+        }
+        if (k == kVoxEmpty) return 1;
+        s = (s + 1ull) & mask;
+    }
+    return 2;
+}
+
+// clean_neighbour's index of the offset (dx, dy, dz)
+__device__ __forceinline__ int mesh_offset(int dx, int dy, int dz) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
+
+__global__ __launch_bounds__(256) void k_mesh_keys(unsigned long long ne, const unsigned long long* __restrict__ vox,
+                                                   unsigned long long nv, const unsigned long long* __restrict__ vslot,
+                                                   const VoxTable t, unsigned long long* __restrict__ ekey,
+                                                   unsigned long long* __restrict__ words) {
+    const unsigned long long e = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    if (e < ne) {
+        const unsigned long long v = vox ? vox[e] : e;
+        const unsigned long long s = v < nv ? vslot[v] : kVoxEmpty;
+        if (s < t.slots) ekey[e] = t.keys[s];
+        else { ekey[e] = kVoxEmpty; err = 1u; }
+    }
+    block_or(err, &words[kMeshErr]);
+}
+
+__global__ __launch_bounds__(256) void k_mesh_insert(unsigned long long p0, int n, const unsigned long long* __restrict__ ekey,
+                                                     const MeshTable m, unsigned long long* __restrict__ words) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    if (i >= n) return;
+    const unsigned long long p = p0 + static_cast<unsigned long long>(i);
+    const unsigned long long e = p / 27ull;
+    const int b = static_cast<int>(p % 27ull);
+    const unsigned long long key = ekey[e];
+    unsigned long long nkey;
+    if (key == kVoxEmpty || !clean_neighbour(key, b, nkey)) return;
+    const unsigned long long mask = m.slots - 1ull;
+    unsigned long long s = vox_home(nkey, m.log2_slots);
+    bool found = false;
+    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
+        unsigned long long k = m.keys[s];                 // (a key changes once, from empty: see k_voxel_insert)
+        if (k == kVoxEmpty) k = atomicCAS(&m.keys[s], kVoxEmpty, nkey);
+        if (k == kVoxEmpty || k == nkey) { found = true; break; }
+        s = (s + 1ull) & mask;
+    }
+    if (!found) { atomicOr(&words[kMeshErr], 2ull); return; }
+    atomicMin(&m.rank[s], p);
+    if (b == 13) m.ent[s] = e;                            // one entry at most has this cell
+}
+
+__global__ __launch_bounds__(256) void k_mesh_stats(const MeshTable m, unsigned long long* __restrict__ words) {
+    unsigned long long occ = 0, wrapped = 0, far = 0;
+    const unsigned long long mask = m.slots - 1ull;
+    for (unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x; s < m.slots;
+         s += static_cast<unsigned long long>(gridDim.x) * 256) {
+        const unsigned long long k = m.keys[s];
+        if (k == kVoxEmpty) continue;
+        const unsigned long long h = vox_home(k, m.log2_slots);
+        ++occ;
+        wrapped += s < h ? 1ull : 0ull;
+        far = max(far, ((s - h) & mask) + 1ull);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        occ += __shfl_xor(occ, d);
+        wrapped += __shfl_xor(wrapped, d);
+        far = max(far, static_cast<unsigned long long>(__shfl_xor(far, d)));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (occ) atomicAdd(&words[kMeshOccupied], occ);
+        if (wrapped) atomicAdd(&words[kMeshWrapped], wrapped);
+        if (far) atomicMax(&words[kMeshMaxProbe], far);
+    }
+}
+
+// The slot of pair p's cell when the pair owns the cell's rank: the pair that numbers the sample.
+__device__ __forceinline__ bool mesh_owner(const MeshTable& m, const unsigned long long* __restrict__ ekey,
+                                           unsigned long long p, unsigned long long& nkey, unsigned long long& slot,
+                                           unsigned& err) {
+    const unsigned long long key = ekey[p / 27ull];
+    if (key == kVoxEmpty || !clean_neighbour(key, static_cast<int>(p % 27ull), nkey)) return false;
+    const unsigned long long mask = m.slots - 1ull;
+    unsigned long long s = vox_home(nkey, m.log2_slots);
+    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
+        const unsigned long long k = m.keys[s];
+        if (k == nkey) { slot = s; return m.rank[s] == p; }
+        if (k == kVoxEmpty) break;
+        s = (s + 1ull) & mask;
+    }
+    err |= 4u;                                            // the insert pass put every pair's cell there
+    return false;
+}
+
+__global__ __launch_bounds__(256) void k_mesh_mark_samples(unsigned long long p0, int n,
+                                                           const unsigned long long* __restrict__ ekey, const MeshTable m,
+                                                           int* __restrict__ flags, int* __restrict__ counts,
+                                                           unsigned long long* __restrict__ words) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    int f = 0;
+    unsigned err = 0u;
+    if (i < n) {
+        unsigned long long nkey, slot;
+        f = mesh_owner(m, ekey, p0 + static_cast<unsigned long long>(i), nkey, slot, err) ? 1 : 0;
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+    block_or(err, &words[kMeshErr]);
+}
+
+__global__ __launch_bounds__(256) void k_mesh_scatter_samples(unsigned long long p0, int n,
+                                                              const unsigned long long* __restrict__ ekey, const MeshTable m,
+                                                              const int* __restrict__ flags, const int* __restrict__ offsets,
+                                                              const unsigned long long* __restrict__ seg_base,
+                                                              const MeshSamples out) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    if (f && pos < out.n) {
+        unsigned long long nkey, slot;
+        unsigned err = 0u;
+        if (mesh_owner(m, ekey, p0 + static_cast<unsigned long long>(i), nkey, slot, err)) {
+            m.sid[slot] = pos;
+            out.key[pos] = nkey;
+            out.ent[pos] = static_cast<long long>(m.ent[slot]);          // ~0 reads as -1
+        }
+    }
+}
+
+// One lane per sample, blockIdx.y = a chunk of kVisChunk list positions, as k_vis_tally.
+template <int MODEL, bool ATOMIC>
+__global__ __launch_bounds__(256) void k_mesh_tsdf(const DevCam* __restrict__ cams, const FuseView* __restrict__ views,
+                                                   const int* __restrict__ list, int n_list, const MeshSamples smp,
+                                                   const VoxGrid g, float trunc, float k) {
+    const unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (s >= smp.n) return;
+    const unsigned long long key = smp.key[s];
+    const double o[3] = {static_cast<double>(g.ox), static_cast<double>(g.oy), static_cast<double>(g.oz)};
+    float x[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        x[a] = static_cast<float>(o[a] + (static_cast<double>((key >> (21 * a)) & 0x1fffffull) + 0.5) * static_cast<double>(g.size));
+    const float3 X = make_float3(x[0], x[1], x[2]);
+    const int j0 = static_cast<int>(blockIdx.y) * kVisChunk;
+    const int j1 = min(j0 + kVisChunk, n_list);
+    int S = 0, cnt = 0;
+    for (int j = j0; j < j1; ++j) {
+        const int vi = list[j];
+        const FuseView view = views[vi];
+        int c, r;
+        float pd;
+        if (!vis_pixel<MODEL>(cams[vi], view, X, c, r, pd)) continue;
+        const float sd = view.depth[static_cast<long long>(r) * view.W + c];
+        if (vox_nonfinite(sd) || !(sd > 0.0f)) continue;
+        const float u = sd - pd;
+        if (u < -trunc) continue;
+        S += static_cast<int>(rintf(fminf(u, trunc) * k));
+        ++cnt;
+    }
+    int32_t* t = smp.tsdf + 2ull * s;
+    if constexpr (ATOMIC) {
+        if (S) atomicAdd(&t[0], S);
+        if (cnt) atomicAdd(&t[1], cnt);
+    } else {
+        t[0] = S;
+        t[1] = cnt;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mesh_cubes(const MeshSamples smp, const MeshTable m, int min_weight,
+                                                    uint8_t* __restrict__ cflag, unsigned long long* __restrict__ words) {
+    const unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    unsigned bits = 0u;
+    if (s < smp.n) {
+        const unsigned long long key = smp.key[s];
+        const bool valid = smp.tsdf[2ull * s + 1] >= min_weight, inside = smp.tsdf[2ull * s] < 0;
+        bool exists = valid, differ = false;
+        for (int c = 1; c < 8 && exists; ++c) {
+            unsigned long long q;
+            const int r = mesh_sample(m, smp.n, key, mesh_offset(c & 1, (c >> 1) & 1, c >> 2), q);
+            if (r == 2) err |= 4u;
+            exists = r == 0 && smp.tsdf[2ull * q + 1] >= min_weight;
+            if (exists) differ = differ || (smp.tsdf[2ull * q] < 0) != inside;
+        }
+        bits = (exists ? kMeshCubeExists : 0u) | (exists && differ ? kMeshCubeActive : 0u) | (valid ? kMeshSampleValid : 0u) |
+               (inside ? kMeshSampleInside : 0u);
+        cflag[s] = static_cast<uint8_t>(bits);
+    }
+    wave_add((bits & kMeshSampleValid) ? 1ull : 0ull, &words[kMeshValid]);
+    wave_add((bits & kMeshCubeExists) ? 1ull : 0ull, &words[kMeshCubes]);
+    wave_add((bits & kMeshCubeActive) ? 1ull : 0ull, &words[kMeshActive]);
+    block_or(err, &words[kMeshErr]);
+}
+
+// The four cubes around the edge from sample s along axis a, in the order Q0 .. Q3; false = one of them is no sample.
+__device__ __forceinline__ int mesh_quad(const MeshTable& m, unsigned long long ns, unsigned long long key, int a,
+                                         unsigned long long s, unsigned long long q[4]) {
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    const int qu[4] = {0, 1, 1, 0}, qv[4] = {0, 0, 1, 1};
+    q[0] = s;
+    for (int k = 1; k < 4; ++k) {
+        int d[3] = {0, 0, 0};
+        d[b] = -qu[k];
+        d[c] = -qv[k];
+        const int r = mesh_sample(m, ns, key, mesh_offset(d[0], d[1], d[2]), q[k]);
+        if (r != 0) return r;
+    }
+    return 0;
+}
+
+// fbits[s]: bit a = the pair (s, axis a) emits its two triangles (step 4)
+__global__ __launch_bounds__(256) void k_mesh_pairs(const MeshSamples smp, const MeshTable m, const uint8_t* __restrict__ cflag,
+                                                    uint8_t* __restrict__ fbits, unsigned long long* __restrict__ words) {
+    const unsigned long long s = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u, bits = 0u;
+    if (s < smp.n) {
+        const unsigned long long key = smp.key[s];
+        const unsigned me = cflag[s];
+        if (me & kMeshSampleValid) {
+            for (int a = 0; a < 3; ++a) {
+                unsigned long long o, q[4];
+                int r = mesh_sample(m, smp.n, key, mesh_offset(a == 0, a == 1, a == 2), o);
+                if (r == 2) err |= 4u;
+                if (r != 0) continue;
+                const unsigned other = cflag[o];
+                if (!(other & kMeshSampleValid) || ((other ^ me) & kMeshSampleInside) == 0u) continue;
+                r = mesh_quad(m, smp.n, key, a, s, q);
+                if (r == 2) err |= 4u;
+                if (r != 0) continue;
+                bool all = true;
+                for (int k = 0; k < 4; ++k) all = all && (cflag[q[k]] & kMeshCubeExists);
+                if (all) bits |= 1u << a;
+            }
+        }
+        fbits[s] = static_cast<uint8_t>(bits);
+    }
+    wave_add(static_cast<unsigned long long>(__popc(bits)), &words[kMeshPairs]);
+    block_or(err, &words[kMeshErr]);
+}
+
+// flags[i] = bit `bit` of bytes[(i0 + i) / per] shifted by (i0 + i) % per: the active cubes (per 1) or the face pairs (per 3)
+__global__ __launch_bounds__(256) void k_mesh_mark(unsigned long long i0, int n, const uint8_t* __restrict__ bytes, int per,
+                                                   int bit, int* __restrict__ flags, int* __restrict__ counts) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    int f = 0;
+    if (i < n) {
+        const unsigned long long p = i0 + static_cast<unsigned long long>(i);
+        f = (bytes[p / static_cast<unsigned>(per)] >> (bit + static_cast<int>(p % static_cast<unsigned>(per)))) & 1;
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+}
+
+// Step 3 for the active cubes of samples [i0, i0 + n), in ascending order: position, normal, colour.
+__global__ __launch_bounds__(256) void k_mesh_scatter_vertices(unsigned long long i0, int n, const MeshSamples smp,
+                                                               const MeshTable m, const VoxGrid g,
+                                                               const float* __restrict__ src_pts, const int* __restrict__ flags,
+                                                               const int* __restrict__ offsets,
+                                                               const unsigned long long* __restrict__ seg_base,
+                                                               unsigned long long cap, float* __restrict__ verts,
+                                                               int32_t* __restrict__ vid, unsigned long long* __restrict__ words) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    unsigned err = 0u;
+    unsigned long long uncoloured = 0;
+    if (f && pos < cap) {
+        const unsigned long long s = i0 + static_cast<unsigned long long>(i);
+        const unsigned long long key = smp.key[s];
+        long long S[8], N[8], ent[8];
+        bool ok = true;
+        for (int c = 0; c < 8; ++c) {
+            unsigned long long q = s;
+            if (c > 0 && mesh_sample(m, smp.n, key, mesh_offset(c & 1, (c >> 1) & 1, c >> 2), q) != 0) { ok = false; q = s; }
+            S[c] = smp.tsdf[2ull * q];
+            N[c] = smp.tsdf[2ull * q + 1];
+            ent[c] = smp.ent[q];
+        }
+        if (!ok) {
+            err |= 8u;
+        } else {
+            double L[3] = {0.0, 0.0, 0.0}, G[3] = {0.0, 0.0, 0.0};
+            int crossings = 0;
+            for (int e = 0; e < 12; ++e) {
+                const int ax = e >> 2, k = e & 3;
+                // the four edges of an axis: the corners whose bit `ax` is clear, in ascending order
+                const int lowm = (1 << ax) - 1;
+                const int p = ((k & ~lowm) << 1) | (k & lowm), q = p | (1 << ax);
+                const double fp = static_cast<double>(S[p]) / (1024.0 * static_cast<double>(N[p]));
+                const double fq = static_cast<double>(S[q]) / (1024.0 * static_cast<double>(N[q]));
+                G[ax] += fq - fp;
+                if ((S[p] < 0) == (S[q] < 0)) continue;
+                const double A = static_cast<double>(S[p] * N[q]), B = static_cast<double>(S[q] * N[p]);
+                const double t = A / (A - B);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) L[a] += static_cast<double>((p >> a) & 1) + (a == ax ? t : 0.0);
+                ++crossings;
+            }
+            const double o[3] = {static_cast<double>(g.ox), static_cast<double>(g.oy), static_cast<double>(g.oz)};
+            float* dst = verts + 9ull * pos;
+            const double len = sqrt(G[0] * G[0] + G[1] * G[1] + G[2] * G[2]);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double cell = static_cast<double>((key >> (21 * a)) & 0x1fffffull);
+                dst[a] = static_cast<float>(o[a] + ((cell + 0.5) + L[a] / static_cast<double>(crossings)) * static_cast<double>(g.size));
+                dst[3 + a] = len > 0.0 ? static_cast<float>(G[a] / len) : 0.0f;
+            }
+            double col[3] = {0.0, 0.0, 0.0};
+            int coloured = 0;
+            for (int c = 0; c < 8; ++c) {
+                if (ent[c] < 0) continue;
+                const float* src = src_pts + 9ull * static_cast<unsigned long long>(ent[c]);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) col[a] += static_cast<double>(src[6 + a]);
+                ++coloured;
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) dst[6 + a] = coloured ? static_cast<float>(col[a] / static_cast<double>(coloured)) : 128.0f;
+            uncoloured = coloured ? 0ull : 1ull;
+            vid[s] = static_cast<int32_t>(pos);
+        }
+    }
+    wave_add(uncoloured, &words[kMeshUncoloured]);
+    block_or(err, &words[kMeshErr]);
+}
+
+// Step 4 for the flagged pairs of [p0, p0 + n), in ascending order: two triangles each.
+__global__ __launch_bounds__(256) void k_mesh_scatter_faces(unsigned long long p0, int n, const MeshSamples smp, const MeshTable m,
+                                                            const uint8_t* __restrict__ cflag, const int32_t* __restrict__ vid,
+                                                            const int* __restrict__ flags, const int* __restrict__ offsets,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            unsigned long long cap, int32_t* __restrict__ faces,
+                                                            unsigned long long* __restrict__ words) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    unsigned err = 0u;
+    if (f && pos < cap) {
+        const unsigned long long p = p0 + static_cast<unsigned long long>(i);
+        const unsigned long long s = p / 3ull;
+        unsigned long long q[4];
+        int32_t v[4] = {-1, -1, -1, -1};
+        if (mesh_quad(m, smp.n, smp.key[s], static_cast<int>(p % 3ull), s, q) == 0)
+            for (int k = 0; k < 4; ++k) v[k] = vid[q[k]];
+        int32_t* dst = faces + 6ull * pos;
+        if (v[0] < 0 || v[1] < 0 || v[2] < 0 || v[3] < 0) {
+            err |= 16u;
+        } else if (cflag[s] & kMeshSampleInside) {
+            dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2];
+            dst[3] = v[0]; dst[4] = v[2]; dst[5] = v[3];
+        } else {
+            dst[0] = v[0]; dst[1] = v[3]; dst[2] = v[2];
+            dst[3] = v[0]; dst[4] = v[2]; dst[5] = v[1];
+        }
+    }
+    block_or(err, &words[kMeshErr]);
+}
+
+hipError_t launch_mesh_keys(unsigned long long ne, const unsigned long long* vox, unsigned long long nv,
+                            const unsigned long long* vslot, VoxTable t, unsigned long long* ekey,
+                            unsigned long long* words, hipStream_t s) {
+    k_mesh_keys<<<clean_blocks(ne), 256, 0, s>>>(ne, vox, nv, vslot, t, ekey, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_insert(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m,
+                              unsigned long long* words, hipStream_t s) {
+    k_mesh_insert<<<static_cast<unsigned>(cdiv(n, 256)), 256, 0, s>>>(p0, n, ekey, m, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_stats(MeshTable m, unsigned long long* words, hipStream_t s) {
+    const unsigned long long blocks = std::min<unsigned long long>((m.slots + 255ull) / 256ull, 4096ull);
+    k_mesh_stats<<<static_cast<unsigned>(blocks), 256, 0, s>>>(m, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, int* flags,
+                              int* counts, int* offsets, int* seg_count, unsigned long long* running,
+                              unsigned long long* seg_base, MeshSamples out, unsigned long long* words, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_mesh_mark_samples<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, ekey, m, flags, counts, words);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_mesh_scatter_samples<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, ekey, m, flags, offsets, seg_base, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_tsdf(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
+                            MeshSamples smp, VoxGrid g, float trunc, hipStream_t s) {
+    const int chunks = cdiv(n_list, kVisChunk);
+    const dim3 grd(clean_blocks(smp.n), static_cast<unsigned>(chunks));
+    const float k = 1024.0f / trunc;
+    if (chunks > 1) {
+        const hipError_t e = hipMemsetAsync(smp.tsdf, 0, sizeof(int32_t) * 2ull * smp.n, s);
+        if (e != hipSuccess) return e;
+        if (model == kSphere) k_mesh_tsdf<kSphere, true><<<grd, 256, 0, s>>>(cams, views, list, n_list, smp, g, trunc, k);
+        else k_mesh_tsdf<kPinhole, true><<<grd, 256, 0, s>>>(cams, views, list, n_list, smp, g, trunc, k);
+    } else {
+        if (model == kSphere) k_mesh_tsdf<kSphere, false><<<grd, 256, 0, s>>>(cams, views, list, n_list, smp, g, trunc, k);
+        else k_mesh_tsdf<kPinhole, false><<<grd, 256, 0, s>>>(cams, views, list, n_list, smp, g, trunc, k);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_cubes(MeshSamples smp, MeshTable m, int min_weight, uint8_t* cflag, uint8_t* fbits,
+                             unsigned long long* words, hipStream_t s) {
+    k_mesh_cubes<<<clean_blocks(smp.n), 256, 0, s>>>(smp, m, min_weight, cflag, words);
+    k_mesh_pairs<<<clean_blocks(smp.n), 256, 0, s>>>(smp, m, cflag, fbits, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_vertices(unsigned long long i0, int n, MeshSamples smp, MeshTable m, VoxGrid g, const uint8_t* cflag,
+                                const float* src_pts, int* flags, int* counts, int* offsets, int* seg_count,
+                                unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
+                                float* verts, int32_t* vid, unsigned long long* words, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_mesh_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, cflag, 1, 1, flags, counts);     // kMeshCubeActive
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_mesh_scatter_vertices<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, smp, m, g, src_pts, flags, offsets, seg_base,
+                                                                             cap, verts, vid, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, MeshTable m, const uint8_t* cflag,
+                             const uint8_t* fbits, const int32_t* vid, int* flags, int* counts, int* offsets,
+                             int* seg_count, unsigned long long* running, unsigned long long* seg_base,
+                             unsigned long long cap, int32_t* faces, unsigned long long* words, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_mesh_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, fbits, 3, 0, flags, counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
+    k_mesh_scatter_faces<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, smp, m, cflag, vid, flags, offsets, seg_base, cap,
+                                                                          faces, words);
     return hipGetLastError();
 }
 

@@ -529,6 +529,82 @@ acmmp_status acmmp_fusion_visible_points(acmmp_fusion *f, int64_t first, int64_t
  * them (no visible result: every range but an empty one at 0 is refused). */
 acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion *f, int64_t first, int64_t n, int32_t *tallies);
 
+/* ---- surface mesh of the voxel, clean or visible result: TSDF and surface nets (no reference counterpart) ----
+ * acmmp_fusion_voxel_mesh is defined over the entries e = 0 .. ne of its source, in their order: the voxel result
+ * (ACMMP_MESH_FROM_VOXELS), the clean result's kept voxels (ACMMP_MESH_FROM_CLEAN) or the visible result's kept
+ * entries (ACMMP_MESH_FROM_VISIBLE).  An entry's cell (gx, gy, gz) is the cell step 2 of acmmp_fusion_voxelize gave
+ * its voxel; it is carried with the entry (the clean and the visible result hold their entries' voxel indices), never
+ * recomputed from the centroid.  o and voxel_size are the voxel result's.  Arithmetic is plain IEEE with no
+ * contraction, float32 or float64 as said.
+ *  1. Samples.  The sample cells are all g + d, d in {-1, 0, 1}^3, of all entries; offsets are applied per axis to the
+ *     21-bit indices, and a cell with an index outside [0, 2^21) does not exist (as for acmmp_fusion_voxel_clean).  A
+ *     sample's rank is the smallest e * 27 + (dz+1)*9 + (dy+1)*3 + (dx+1) over the pairs (e, d) that produce it;
+ *     samples are numbered s = 0 .. ns in ascending rank.  A sample whose cell is an entry's own cell (d = 0)
+ *     remembers that entry (at most one entry has that cell).  The dilation is one cell.
+ *  2. TSDF.  X(s) = the cell centre, per axis (float)((double)o + ((double)g + 0.5) * (double)voxel_size).  For list
+ *     position j, view i = views[j] (a view listed twice counts twice): (px, py, pd) and the pixel (c, r) exactly as
+ *     steps 1-2 of acmmp_fusion_voxel_visibility, the pair being unobserved under the same conditions.  The only
+ *     pixel read is (c, r) itself (radius 0, raw depth sd); a depth that is not finite and > 0 makes the pair
+ *     unobserved.  With u = sd - pd in float32 the pair contributes nothing when u < -trunc (the sample is hidden
+ *     behind that view's surface); otherwise it contributes q = (int32) rintf(fminf(u, trunc) * k), k = 1024.0f / trunc
+ *     formed once in float32.  Per sample S = the int32 sum of q, n = the int32 number of contributions.  A sample is
+ *     valid when n >= min_weight and inside when S < 0 (S == 0 is outside).  Only integers are summed.
+ *  3. Cubes and vertices.  The cube of sample s with cell g has the corners g + (a, b, c), a, b, c in {0, 1}, corner
+ *     index a + 2b + 4c.  It exists when all eight corners are valid samples and is active when it exists and its
+ *     corners' inside flags differ.  Each active cube gives one vertex; vertices are numbered in ascending s.
+ *     Position: over the 12 edges (p, q) in the order (0,1) (2,3) (4,5) (6,7), (0,2) (1,3) (4,6) (5,7), (0,4) (1,5)
+ *     (2,6) (3,7), an edge whose flags differ has, in float64, t = (double)(Sp*nq) / ((double)(Sp*nq) - (double)(Sq*np))
+ *     (products exact in int64) and the crossing = corner p's offset + t along the edge's axis; L = the float64 sum of
+ *     the crossings in edge order, per axis, divided by their number; the position is per axis
+ *     (float)((double)o + (((double)g + 0.5) + L) * (double)voxel_size).
+ *     Normal: f = (double)S / (1024.0 * (double)n); G_axis = the float64 sum, in edge order over the axis's four
+ *     edges, of f(q) - f(p); the normal is (float)(G / sqrt(Gx*Gx + Gy*Gy + Gz*Gz)), the sum taken left to right, and
+ *     zero when G is zero.  It points into free space.
+ *     Colour: over the corners that remember an entry, in corner order, the float64 sum of the entries' three colour
+ *     floats divided by their number, rounded to float32; with no such corner (128, 128, 128), and the vertex counts in
+ *     *n_uncoloured.
+ *  4. Faces.  For each sample s in order and each axis a = 0, 1, 2, with s' the sample at g + e_a: s and s' must both be
+ *     valid with differing inside flags, and with b = (a+1)%3, c = (a+2)%3 the four cubes at g - u e_b - v e_c, (u, v) =
+ *     Q0 (0,0), Q1 (1,0), Q2 (1,1), Q3 (0,1), must all exist (they are then active).  The pair emits the triangles
+ *     (Q0,Q1,Q2), (Q0,Q2,Q3) when s is inside and (Q0,Q3,Q2), (Q0,Q2,Q1) when s' is: counter-clockwise seen from free
+ *     space.  Faces are int32 vertex indices, listed in ascending (s, a).
+ * *n_vertices, *n_faces (triangles), *n_samples, *n_valid (valid samples), *n_cubes (cubes that exist) and
+ * *n_uncoloured may each be NULL.  Every atomic of the device is an integer add or a minimum, and nothing a reader can
+ * see depends on which slot of the sample table a cell got.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a source that is none of the three constants, no such source result (an empty one gives
+ * an empty mesh), n_list outside [1, 4096], a view index outside the set or a view never given to
+ * acmmp_fusion_set_view, trunc not finite or <= 0, min_weight < 1, more than 2^31 - 1 vertices.  The mesh result stays
+ * in HBM until the next successful mesh call replaces it or its source is replaced or discarded (as the visible
+ * result's; a successful acmmp_fusion_voxel_visibility discards a mesh of the visible result);
+ * acmmp_fusion_set_view does not touch it.  Any error -- an out-of-memory part-way and a full sample table
+ * (ACMMP_ERR_HIP) included -- leaves the object as it was (the new result is built beside the previous one).
+ * Device memory: 8 bytes per entry held with the clean and the visible result (the voxel index) and 8 per entry
+ * while the call runs; the sample table, 32 bytes per slot with the smallest power of two >= max(54 ne, 1024) slots
+ * (27 cells per entry, at most half full), while the call runs; 24 bytes per sample (cell, S, n, entry), 36 per vertex
+ * and 12 per face held with the result; 6 bytes per sample, and 4 bytes of flag per lane of a compaction segment (at
+ * most 2^30 lanes), while it runs.  The host waits three times: for the sample count, for the vertex and face counts,
+ * and at the end. */
+#define ACMMP_MESH_FROM_VOXELS 0    /* entries = the voxel result */
+#define ACMMP_MESH_FROM_CLEAN 1     /* entries = the clean result's kept voxels */
+#define ACMMP_MESH_FROM_VISIBLE 2   /* entries = the visible result's kept entries */
+acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion *f, int source, int n_list, const int *views, float trunc,
+                                     int min_weight, int64_t *n_vertices, int64_t *n_faces, int64_t *n_samples,
+                                     int64_t *n_valid, int64_t *n_cubes, int64_t *n_uncoloured);
+/* Vertices [first, first + n) of the mesh result: n x 9 floats (position, normal, colour: a cloud point's layout). */
+acmmp_status acmmp_fusion_mesh_vertices(acmmp_fusion *f, int64_t first, int64_t n, float *vertices);
+/* Triangles [first, first + n) of the mesh result: n x 3 int32 vertex indices. */
+acmmp_status acmmp_fusion_mesh_faces(acmmp_fusion *f, int64_t first, int64_t n, int32_t *faces);
+/* Test hook: samples [first, first + n) of the mesh result to host arrays, any of which may be NULL: cells n x 3 int32
+ * (gx, gy, gz), tsdf n x 2 int32 (S, n), entry n int64 (the remembered entry, -1 = none). */
+acmmp_status acmmp_fusion_mesh_samples(acmmp_fusion *f, int64_t first, int64_t n, int32_t *cells, int32_t *tsdf,
+                                       int64_t *entry);
+/* Test hook, as acmmp_fusion_voxel_table for the sample table.  force_slots = 0: automatic size; otherwise the size of
+ * the next mesh call's table, a power of two >= 64 (else that call returns ACMMP_ERR_INVALID_ARGUMENT); one too small
+ * for the samples makes that call fail with ACMMP_ERR_HIP.  The outputs describe the last successful mesh call. */
+acmmp_status acmmp_fusion_mesh_table(acmmp_fusion *f, int64_t force_slots, int64_t *slots, int64_t *occupied,
+                                     int64_t *max_probe, int64_t *wrapped);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
