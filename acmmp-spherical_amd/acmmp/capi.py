@@ -118,7 +118,8 @@ EXPORTS = [
     "acmmp_fusion_component_table",
     "acmmp_fusion_voxel_visibility", "acmmp_fusion_visible_points", "acmmp_fusion_visibility_tallies",
     "acmmp_fusion_voxel_mesh", "acmmp_fusion_mesh_vertices", "acmmp_fusion_mesh_faces", "acmmp_fusion_mesh_samples",
-    "acmmp_fusion_mesh_table",
+    "acmmp_fusion_mesh_table", "acmmp_fusion_set_mesh", "acmmp_fusion_mesh_render", "acmmp_fusion_render_maps",
+    "acmmp_fusion_render_plan",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -241,6 +242,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_mesh_faces.argtypes = [vp, C.c_int64, C.c_int64, vp]
     L.acmmp_fusion_mesh_samples.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_fusion_mesh_table.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+    L.acmmp_fusion_set_mesh.argtypes = [vp, C.c_int64, vp, C.c_int64, vp]
+    L.acmmp_fusion_mesh_render.argtypes = [vp, i32, vp, C.c_float, vp, vp]
+    L.acmmp_fusion_render_maps.argtypes = [vp, vp, vp, vp, vp]
+    L.acmmp_fusion_render_plan.argtypes = [vp, i32, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -873,6 +878,7 @@ class Comm:
 FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
 VIS_SOURCES = {"voxel": 0, "clean": 1}     # ACMMP_VIS_FROM_VOXELS, ACMMP_VIS_FROM_CLEAN
 MESH_SOURCES = {"voxel": 0, "clean": 1, "visible": 2}     # ACMMP_MESH_FROM_VOXELS, _CLEAN, _VISIBLE
+RENDER_COUNTS = ("agree", "mesh_in_front", "mesh_behind", "mesh_only", "raw_only", "neither", "back_facing")
 
 
 class Fusion:
@@ -1122,6 +1128,54 @@ class Fusion:
         self._check(self.L.acmmp_fusion_mesh_table(self.h, int(force_slots), _p(st[0:1]), _p(st[1:2]), _p(st[2:3]),
                                                    _p(st[3:4])), "fusion_mesh_table")
         return {"slots": int(st[0]), "occupied": int(st[1]), "max_probe": int(st[2]), "wrapped": int(st[3])}
+
+    def set_mesh(self, vertices, faces):
+        """Makes a host mesh the mesh result, as set_scene does for clouds: vertices (nv, 9) float32 (position, normal,
+        colour), faces (nf, 3) int32.  It has no source: it stays until the next voxel_mesh or set_mesh."""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 9)
+        t = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        self._check(self.L.acmmp_fusion_set_mesh(self.h, v.shape[0], _p(v) if v.size else None, t.shape[0],
+                                                 _p(t) if t.size else None), "fusion_set_mesh")
+        return v.shape[0], t.shape[0]
+
+    def render_mesh(self, view=None, camera=None, rel_tol: float = 0.01):
+        """Renders the mesh result into view `view`'s camera, or with view None into `camera` (one CAMERA_DTYPE record of
+        the set's model): a z-buffer over all faces, exact at shared edges, the seam and the poles
+        (acmmp_fusion_mesh_render, include/acmmp.h).  The maps stay on the GPU (render_maps) until the next render or
+        until the mesh goes.  Returns {"width", "height", "skipped", "counts": {"agree", "mesh_in_front", "mesh_behind",
+        "mesh_only", "raw_only", "neither", "back_facing"}}: the pixels by how the rendered depth agrees with the view's
+        raw depth within rel_tol (all zero with view None) and the faces skipped."""
+        counts, skipped = np.zeros(7, np.int64), np.zeros(1, np.int64)
+        if view is None:
+            cam = None if camera is None else np.frombuffer(np.ascontiguousarray(camera, dtype=CAMERA_DTYPE).tobytes(),
+                                                            CAMERA_DTYPE).copy().reshape(-1)[:1]
+            rc = self.L.acmmp_fusion_mesh_render(self.h, -1, None if cam is None else _p(cam), float(rel_tol), _p(counts), _p(skipped))
+        else:
+            if camera is not None:
+                raise ValueError("a view or a camera, not both")
+            cam = self.cams[view:view + 1] if 0 <= int(view) < len(self.cams) else None
+            rc = self.L.acmmp_fusion_mesh_render(self.h, int(view), None, float(rel_tol), _p(counts), _p(skipped))
+        self._check(rc, "fusion_mesh_render")
+        self._render_shape = (int(cam[0]["height"]), int(cam[0]["width"]))
+        return {"width": self._render_shape[1], "height": self._render_shape[0], "skipped": int(skipped[0]),
+                "counts": dict(zip(RENDER_COUNTS, (int(x) for x in counts)))}
+
+    def render_maps(self):
+        """The last render_mesh: (depth (H, W) float32, 0 = nothing; face (H, W) int32, -1 = nothing; normal (H, W, 3)
+        float32, world space; colour (H, W, 3) float32)."""
+        H, W = getattr(self, "_render_shape", None) or (0, 0)
+        depth, face = host_empty((H, W), np.float32), np.empty((H, W), np.int32)
+        normal, colour = host_empty((H, W, 3), np.float32), host_empty((H, W, 3), np.float32)
+        self._check(self.L.acmmp_fusion_render_maps(self.h, _p(depth), _p(face), _p(normal), _p(colour)), "fusion_render_maps")
+        return depth, face, normal, colour
+
+    def render_plan(self, small_max: int = 0):
+        """Test hook: sets the candidate count up to which a face is rendered by its own lane (0 = the default) and
+        returns the last render's {"small", "large", "candidates"}."""
+        st = np.zeros(3, np.int64)
+        self._check(self.L.acmmp_fusion_render_plan(self.h, int(small_max), _p(st[0:1]), _p(st[1:2]), _p(st[2:3])),
+                    "fusion_render_plan")
+        return {"small": int(st[0]), "large": int(st[1]), "candidates": int(st[2])}
 
     def close(self):
         if self.h:

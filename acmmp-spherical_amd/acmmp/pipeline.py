@@ -793,7 +793,8 @@ class Pipeline:
                    voxel_min_neighbours: int = 0, voxel_min_component_voxels: int = 1,
                    voxel_min_component_points: int = 1, visibility_tol: float | None = None,
                    visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0,
-                   mesh_trunc: float | None = None, mesh_min_weight: int = 1, mesh_path: str | None = None):
+                   mesh_trunc: float | None = None, mesh_min_weight: int = 1, mesh_path: str | None = None,
+                   render_mesh: bool = False, render_tol: float = 0.01):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -833,8 +834,17 @@ class Pipeline:
         (acmmp_fusion_voxel_mesh, include/acmmp.h).  It is streamed to mesh_path (default: ACMMP/ACMM_mesh.ply of the
         output folder) chunk_points vertices and faces at a time; the cloud and its PLY are what they are without the
         mesh.  self.fusion_info gains mesh_vertices, mesh_faces, mesh_samples, mesh_valid, mesh_cubes,
-        mesh_uncoloured and the two values."""
+        mesh_uncoloured and the two values.
+
+        render_mesh (mesh_trunc is then required): after the mesh, it is rendered on the device into every view
+        (acmmp_fusion_mesh_render, include/acmmp.h), and with an output folder the rendered depth and normal maps are
+        written as depths_mesh.dmb and normals_mesh.dmb beside the view's depths.dmb: depth maps that are complete and
+        consistent with the surface.  self.fusion_info gains render_tol and render_views, per view the image id, the
+        faces skipped and the pixels by how the rendered depth agrees with the view's own depth map within render_tol
+        (relative).  Everything else is what it is without the option."""
         self.fusion_info = None
+        if render_mesh and mesh_trunc is None:
+            raise ValueError("rendering the mesh needs the mesh (mesh_trunc)")
         if (mesh_trunc is not None or mesh_path is not None) and voxel_size is None:
             raise ValueError("the mesh needs voxel_size")
         if mesh_path is not None and mesh_trunc is None:
@@ -934,6 +944,20 @@ class Pipeline:
                             mw.write_vertices(fu.mesh_vertices(first, min(step, nv - first)))
                         for first in range(0, nf, step):
                             mw.write_faces(fu.mesh_faces(first, min(step, nf - first)))
+                if render_mesh:
+                    if not hasattr(fu, "render_mesh"):
+                        raise ValueError("rendering the mesh needs a fusion object with render_mesh (capi.Fusion)")
+                    per_view = []
+                    for k, prob in enumerate(self.problems):
+                        rinfo = fu.render_mesh(k, rel_tol=render_tol)
+                        per_view.append(dict(rinfo["counts"], view=int(prob.ref_image_id), skipped=int(rinfo["skipped"])))
+                        if self.out_folder:
+                            rdepth, _, rnormal, _ = fu.render_maps()
+                            d = os.path.join(self.out_folder, "ACMMP", f"2333_{prob.ref_image_id:08d}")
+                            os.makedirs(d, exist_ok=True)
+                            io.write_dmb(os.path.join(d, "depths_mesh.dmb"), rdepth)
+                            io.write_dmb(os.path.join(d, "normals_mesh.dmb"), rnormal)
+                    self.fusion_info.update(render_tol=float(render_tol), render_views=per_view)
         else:
             if unique:
                 raise ValueError("unique fusion needs a fusion object with run_scene (capi.Fusion)")
@@ -1061,6 +1085,11 @@ def arg_parser():
                     help="with --mesh: the truncation distance, in scene units (default: three voxel sizes)")
     ap.add_argument("--mesh-min-weight", type=int, default=1,
                     help="with --mesh: a cell needs a distance from at least this many views")
+    ap.add_argument("--render-mesh", action="store_true",
+                    help="with --mesh: render the mesh into every view and write depths_mesh.dmb and normals_mesh.dmb "
+                         "beside the view's depths.dmb")
+    ap.add_argument("--render-tol", type=float, default=0.01,
+                    help="with --render-mesh: a rendered depth agrees with the view's own within this relative tolerance")
     return ap
 
 
@@ -1093,7 +1122,8 @@ def main(argv=None):
                               visibility_max_conflicts=a.visibility_max_conflicts,
                               mesh_trunc=(a.mesh_trunc if a.mesh_trunc is not None or a.mesh is None or a.voxel_size is None
                                           else 3.0 * a.voxel_size),
-                              mesh_min_weight=a.mesh_min_weight, mesh_path=a.mesh)
+                              mesh_min_weight=a.mesh_min_weight, mesh_path=a.mesh, render_mesh=a.render_mesh,
+                              render_tol=a.render_tol)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -127,6 +127,14 @@ struct acmmp_fusion {
     long long m_force_slots = 0;                 // test hook: sample table size of the next call, 0 = automatic
     long long m_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful call
     DevBuf<unsigned long long> m_words;          // kMeshWords device words
+    // the mesh result rendered into one camera (acmmp_fusion_mesh_render): its resident result
+    DevBuf<float> r_depth, r_normal, r_colour;   // 1, 3 and 3 floats per pixel
+    DevBuf<int32_t> r_face;                      // the winner per pixel, -1 = none
+    int r_W = 0, r_H = 0;
+    bool r_have = false;                         // a render has succeeded on this mesh result
+    long long r_small_max = 0;                   // test hook: the small / large threshold, 0 = kRenderSmallMax
+    long long r_plan[3] = {0, 0, 0};             // small faces, large faces, candidates of the last successful render
+    DevBuf<unsigned long long> r_words;          // kRenderWords device words
     std::string err;
 };
 
@@ -289,7 +297,18 @@ void voxel_scratch_release(acmmp_fusion* f) {
     f->v_cap_seg = 0;
 }
 
+// m_source of a mesh that acmmp_fusion_set_mesh installed: no result is its source.
+constexpr int kMeshNoSource = -1;
+
+void render_release(acmmp_fusion* f) {
+    f->r_depth.reset(); f->r_normal.reset(); f->r_colour.reset(); f->r_face.reset();
+    f->r_W = f->r_H = 0;
+    f->r_have = false;
+}
+
+// The render result goes with the mesh result it shows.
 void mesh_release(acmmp_fusion* f) {
+    render_release(f);
     f->m_verts.reset(); f->m_faces.reset(); f->m_skey.reset(); f->m_tsdf.reset(); f->m_sent.reset();
     f->m_nv = f->m_nf = f->m_ns = 0;
     f->m_have = false;
@@ -319,7 +338,7 @@ void scene_replaced(acmmp_fusion* f) {
     f->v_have = false;
     clean_release(f);
     visibility_release(f);
-    mesh_release(f);
+    if (f->m_source != kMeshNoSource) mesh_release(f);
     voxel_scratch_release(f);
 }
 
@@ -722,7 +741,7 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     f->v_have = true;
     clean_release(f);                                 // it described the previous voxel result
     visibility_release(f);                            // and so did this one, from either source
-    mesh_release(f);                                  // and this one, from any source
+    if (f->m_source != kMeshNoSource) mesh_release(f);   // and this one, from any source
     f->v_grid = g;
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
@@ -1253,6 +1272,7 @@ acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, co
     } else {
         out.stats[0] = static_cast<long long>(slots);
     }
+    render_release(f);                                // it showed the previous mesh result
     f->m_verts = std::move(out.verts);
     f->m_faces = std::move(out.faces);
     f->m_skey = std::move(out.skey);
@@ -1316,6 +1336,139 @@ acmmp_status acmmp_fusion_mesh_table(acmmp_fusion* f, int64_t force_slots, int64
     if (occupied) *occupied = f->m_stats[1];
     if (max_probe) *max_probe = f->m_stats[2];
     if (wrapped) *wrapped = f->m_stats[3];
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_set_mesh(acmmp_fusion* f, int64_t nv, const float* vertices, int64_t nf, const int32_t* faces) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (nv < 0 || nf < 0 || nv > 0x7fffffffll || nf > 0x7fffffffll || (nv > 0 && !vertices) || (nf > 0 && !faces))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    for (int64_t i = 0; i < 3 * nf; ++i)
+        if (faces[i] < 0 || faces[i] >= nv) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "vertex index out of range");
+    F_HIP(f, hipSetDevice(f->device));
+    // built beside the present mesh result, installed when both copies have succeeded
+    DevBuf<float> v;
+    DevBuf<int32_t> t;
+    const size_t n = static_cast<size_t>(nv), m = static_cast<size_t>(nf);
+    F_HIP(f, alloc(v, 9 * n));
+    F_HIP(f, alloc(t, 3 * m));
+    if (n > 0) F_HIP(f, hipMemcpy(v, vertices, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
+    if (m > 0) F_HIP(f, hipMemcpy(t, faces, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice));
+    mesh_release(f);
+    f->m_verts = std::move(v);
+    f->m_faces = std::move(t);
+    f->m_nv = static_cast<unsigned long long>(nv);
+    f->m_nf = static_cast<unsigned long long>(nf);
+    f->m_source = kMeshNoSource;
+    f->m_have = true;
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- the mesh result rendered into one camera (include/acmmp.h; kernels: k_render_*) ------------------------
+
+namespace {
+
+// The new result of a render, swapped in only when the whole call succeeded.
+struct RenderOut {
+    DevBuf<float> depth, normal, colour;
+    DevBuf<int32_t> face;
+    DevBuf<unsigned long long> keys;                       // scratch: the z-buffer
+    DevBuf<uint8_t> queue;                                 // scratch: the large faces
+    unsigned long long words[kRenderWords] = {0};
+};
+
+acmmp_status render_run(acmmp_fusion* f, const DevCam& cam, const float* raw, float rel_tol, RenderOut& out) {
+    hipStream_t s = f->stream;
+    const size_t P = static_cast<size_t>(cam.W) * cam.H;
+    const unsigned nf = static_cast<unsigned>(f->m_nf);
+    if (!f->r_words) F_HIP(f, alloc(f->r_words, kRenderWords));
+    F_HIP(f, alloc(out.depth, P));
+    F_HIP(f, alloc(out.face, P));
+    F_HIP(f, alloc(out.normal, 3 * P));
+    F_HIP(f, alloc(out.colour, 3 * P));
+    F_HIP(f, alloc(out.keys, P));
+    F_HIP(f, alloc(out.queue, kRenderItemBytes * static_cast<size_t>(nf)));
+    F_HIP(f, hipMemsetAsync(f->r_words, 0, sizeof(unsigned long long) * kRenderWords, s));
+    F_HIP(f, hipMemsetAsync(out.keys, 0xff, sizeof(unsigned long long) * P, s));
+    const long long small_max = f->r_small_max != 0 ? f->r_small_max : kRenderSmallMax;
+    F_HIP(f, launch_render(f->model, cam, f->m_verts, f->m_nv, f->m_faces, nf, small_max, out.keys, out.queue.get(), raw, rel_tol,
+                           out.depth, out.face, out.normal, out.colour, f->r_words, s));
+    // the one host wait: the counts
+    F_HIP(f, hipMemcpyAsync(out.words, f->r_words, sizeof(out.words), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_mesh_render(acmmp_fusion* f, int view, const acmmp_camera* cam, float rel_tol, int64_t counts[7],
+                                      int64_t* n_skipped) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (!f->m_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
+    if (!finite32(rel_tol) || !(rel_tol >= 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "rel_tol must be finite and >= 0");
+    if (view < -1 || view >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
+    DevCam dc;
+    const float* raw = nullptr;
+    if (view >= 0) {
+        if (!f->views[view].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for the view rendered");
+        dc = f->cams[view];
+        raw = f->views[view].depth;
+    } else {
+        if (!cam) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view -1 needs a camera");
+        if (cam->model != f->model) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the camera's model is not the set's");
+        if (cam->width <= 0 || cam->height <= 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the camera's size must be positive");
+        dc = make_devcam(*cam);
+    }
+    if (static_cast<long long>(dc.W) * dc.H > 0x7fffffffll) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels");
+    if (f->m_nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
+    F_HIP(f, hipSetDevice(f->device));
+    RenderOut out;
+    const acmmp_status st = render_run(f, dc, raw, rel_tol, out);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(f->stream);
+        f->err = why;
+        return st;
+    }
+    f->r_depth = std::move(out.depth);
+    f->r_face = std::move(out.face);
+    f->r_normal = std::move(out.normal);
+    f->r_colour = std::move(out.colour);
+    f->r_W = dc.W;
+    f->r_H = dc.H;
+    f->r_have = true;
+    f->r_plan[0] = static_cast<long long>(out.words[kRenderSmall]);
+    f->r_plan[1] = static_cast<long long>(out.words[kRenderLarge]);
+    f->r_plan[2] = static_cast<long long>(out.words[kRenderCandidates]);
+    if (counts)
+        for (int k = 0; k < 7; ++k) counts[k] = static_cast<int64_t>(out.words[kRenderCounts + k]);
+    if (n_skipped) *n_skipped = static_cast<int64_t>(out.words[kRenderSkipped]);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_render_maps(acmmp_fusion* f, float* depth, int32_t* face, float* normal, float* colour) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (!f->r_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no render result: acmmp_fusion_mesh_render first");
+    F_HIP(f, hipSetDevice(f->device));
+    const size_t P = static_cast<size_t>(f->r_W) * f->r_H;
+    F_HIP(f, read_range<float>(depth, f->r_depth, 0, P));
+    F_HIP(f, read_range<int32_t>(face, f->r_face, 0, P));
+    F_HIP(f, read_range<float>(normal, f->r_normal, 0, P, 3));
+    F_HIP(f, read_range<float>(colour, f->r_colour, 0, P, 3));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_render_plan(acmmp_fusion* f, int small_max, int64_t* n_small, int64_t* n_large, int64_t* n_candidates) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->r_small_max = small_max;
+    if (n_small) *n_small = f->r_plan[0];
+    if (n_large) *n_large = f->r_plan[1];
+    if (n_candidates) *n_candidates = f->r_plan[2];
     return ACMMP_OK;
 }
 

@@ -214,4 +214,18 @@ hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, Mesh
                              int* seg_count, unsigned long long* running, unsigned long long* seg_base,
                              unsigned long long cap, int32_t* faces, unsigned long long* words, hipStream_t s);
 
+// The mesh result rendered into one camera (acmmp_fusion_mesh_render, include/acmmp.h).
+// Device words of a render (all zero before it): kRenderLarge is also the queue's counter, kRenderCounts the first of
+// the seven counts of step 8.
+enum { kRenderSkipped = 0, kRenderSmall = 1, kRenderLarge = 2, kRenderCandidates = 3, kRenderCounts = 4, kRenderWords = 11 };
+constexpr size_t kRenderItemBytes = 20;      // a queue entry: the face and its bound
+constexpr int kRenderSmallMax = 256;         // candidates up to which a face is rendered by its own lane
+// In stream order: k_render_setup over the nf faces (the skip test, the bound, the small faces' pixels, the others to
+// `queue`, nf entries), k_render_large over the queue, k_render_resolve over the W x H pixels of `cam`.  keys: one word
+// per pixel, all-ones bytes before the call.  raw: the view's raw depth map, or NULL for no agreement counts.
+hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsigned long long nv, const int32_t* faces,
+                         unsigned nf, long long small_max, unsigned long long* keys, void* queue, const float* raw,
+                         float rel_tol, float* depth, int32_t* face, float* normal, float* colour, unsigned long long* words,
+                         hipStream_t s);
+
 }  // namespace acmmp

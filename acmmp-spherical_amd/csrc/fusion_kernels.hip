@@ -1,7 +1,7 @@
 // fusion_kernels.hip -- gfx950 kernels of the depth-map fusion (SimpleFusionKernel, ACMMP.cu:1662-1814, its
 // whole-scene pass and their in-order compaction), of the voxel-grid reduction of the fused scene cloud and of the
-// cleaning, the visibility check and the surface mesh of that voxel cloud, with their host launchers
-// (fusion.h).  One translation unit, compiled once.
+// cleaning, the visibility check and the surface mesh of that voxel cloud, and of the rendering of that mesh into a
+// view, with their host launchers (fusion.h).  One translation unit, compiled once.
 #include <algorithm>
 
 #include "camera_dev.h"
@@ -1512,6 +1512,314 @@ hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, Mesh
     k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
     k_mesh_scatter_faces<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, smp, m, cflag, vid, flags, offsets, seg_base, cap,
                                                                           faces, words);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the mesh rendered into a view
+//
+// acmmp_fusion_mesh_render (include/acmmp.h): every face is tested against the pixels of a conservative
+// bound of its image, in float64 on float32 inputs, and a pixel's winner is the minimum of a 64-bit key (depth bits,
+// face index) taken with atomicMin -- the same whatever order the faces arrive in.  The queue of large faces is the only
+// racy thing, and nothing that is read back depends on its order.
+
+__device__ __forceinline__ double render_dot(double ax, double ay, double az, double bx, double by, double bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+// Step 2: the face's vertex indices and its camera-frame vertices T (A, B, C).  false = the face is skipped (a
+// non-finite coordinate, pinhole: a vertex with T_z <= 0; an index outside the vertices, which no mesh result holds).
+template <int MODEL>
+__device__ __forceinline__ bool render_face(const DevCam& cam, const float* __restrict__ verts, unsigned long long nv,
+                                            const int32_t* __restrict__ faces, unsigned f, int32_t idx[3], double T[9]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        idx[j] = faces[3ull * f + j];
+        if (idx[j] < 0 || static_cast<unsigned long long>(idx[j]) >= nv) { ok = false; idx[j] = 0; }
+    }
+    if (!ok) return false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float* X = verts + 9ull * static_cast<unsigned long long>(idx[j]);
+        const double x = static_cast<double>(X[0]), y = static_cast<double>(X[1]), z = static_cast<double>(X[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double t = ((static_cast<double>(cam.R[3 * k]) * x + static_cast<double>(cam.R[3 * k + 1]) * y) +
+                              static_cast<double>(cam.R[3 * k + 2]) * z) + static_cast<double>(cam.t[k]);
+            T[3 * j + k] = t;
+            ok = ok && fabs(t) < __builtin_inf();                     // false for an infinity and for a NaN
+        }
+        if (MODEL == kPinhole) ok = ok && T[3 * j + 2] > 0.0;
+    }
+    return ok;
+}
+
+// Step 3: the ray of pixel (c, r).
+template <int MODEL>
+__device__ __forceinline__ void render_ray(const DevCam& cam, int c, int r, double d[3]) {
+    if (MODEL == kSphere) {
+        const float3 p = pixel_to_dir(cam, c, r);
+        d[0] = static_cast<double>(p.x); d[1] = static_cast<double>(p.y); d[2] = static_cast<double>(p.z);
+    } else {
+        d[0] = (static_cast<double>(c) - static_cast<double>(cam.K[2])) / static_cast<double>(cam.K[0]);
+        d[1] = (static_cast<double>(r) - static_cast<double>(cam.K[5])) / static_cast<double>(cam.K[4]);
+        d[2] = 1.0;
+    }
+}
+
+// Steps 4 and 5: whether the ray d hits the face T, with the weights (u, v, w), their sum s and the depth md.
+template <int MODEL>
+__device__ __forceinline__ bool render_hit(const double T[9], const double d[3], double& u, double& v, double& w, double& s,
+                                           float& md) {
+    const double* A = T;
+    const double* B = T + 3;
+    const double* C = T + 6;
+    u = render_dot(d[0], d[1], d[2], B[1] * C[2] - B[2] * C[1], B[2] * C[0] - B[0] * C[2], B[0] * C[1] - B[1] * C[0]);
+    v = render_dot(d[0], d[1], d[2], C[1] * A[2] - C[2] * A[1], C[2] * A[0] - C[0] * A[2], C[0] * A[1] - C[1] * A[0]);
+    w = render_dot(d[0], d[1], d[2], A[1] * B[2] - A[2] * B[1], A[2] * B[0] - A[0] * B[2], A[0] * B[1] - A[1] * B[0]);
+    s = (u + v) + w;
+    const bool inside = (s > 0.0 && u >= 0.0 && v >= 0.0 && w >= 0.0) || (s < 0.0 && u <= 0.0 && v <= 0.0 && w <= 0.0);
+    if (!inside) return false;
+    const double px = ((u * A[0] + v * B[0]) + w * C[0]) / s;
+    const double py = ((u * A[1] + v * B[1]) + w * C[1]) / s;
+    const double pz = ((u * A[2] + v * B[2]) + w * C[2]) / s;
+    if (!(render_dot(px, py, pz, d[0], d[1], d[2]) > 0.0)) return false;
+    md = static_cast<float>(MODEL == kSphere ? sqrt((px * px + py * py) + pz * pz) : pz);
+    return md > 0.0f && md < __builtin_inff();
+}
+
+// Rows [r0, r0 + nr) and columns (c0 + j) mod W, j in [0, nc), of a face's candidate pixels.
+struct RenderBound {
+    int r0, nr, c0, nc;
+};
+struct RenderItem {
+    unsigned face;
+    RenderBound b;
+};
+
+// A conservative bound of the pixels whose ray can hit the face (DESIGN.md §8 argues each case).  The whole image for
+// a face whose |det(A, B, C)| is not above 2^-30 |A||B||C| -- edge-on to the camera centre, or of no angular size: its
+// weights may be rounding noise, and any pixel may hit.
+template <int MODEL>
+__device__ __forceinline__ RenderBound render_bound(const DevCam& cam, const double T[9]) {
+    constexpr double kPi = 3.14159265358979323846, kPad = 0x1p-16, kGrow = 1.0 + 0x1p-20;
+    const int W = cam.W, H = cam.H;
+    const RenderBound all = {0, H, 0, W}, none = {0, 0, 0, 0};
+    const double* A = T;
+    const double* B = T + 3;
+    const double* C = T + 6;
+    double len[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) len[j] = sqrt(render_dot(T[3 * j], T[3 * j + 1], T[3 * j + 2], T[3 * j], T[3 * j + 1], T[3 * j + 2]));
+    const double det = render_dot(A[0], A[1], A[2], B[1] * C[2] - B[2] * C[1], B[2] * C[0] - B[0] * C[2], B[0] * C[1] - B[1] * C[0]);
+    if (!(fabs(det) > 0x1p-30 * ((len[0] * len[1]) * len[2]))) return all;
+    if (MODEL == kPinhole) {
+        // the box of the three projections, a pixel wider on every side; a vertex more than 2^10 focal lengths off
+        // the axis, or a focal length that is not positive: the whole image
+        const double fx = static_cast<double>(cam.K[0]), fy = static_cast<double>(cam.K[4]);
+        if (!(fx > 0.0 && fy > 0.0)) return all;
+        double x0 = __builtin_inf(), x1 = -__builtin_inf(), y0 = __builtin_inf(), y1 = -__builtin_inf();
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double* V = T + 3 * j;
+            if (!(V[2] * 1024.0 > len[j])) return all;
+            const double x = fx * (V[0] / V[2]) + static_cast<double>(cam.K[2]);
+            const double y = fy * (V[1] / V[2]) + static_cast<double>(cam.K[5]);
+            x0 = fmin(x0, x); x1 = fmax(x1, x); y0 = fmin(y0, y); y1 = fmax(y1, y);
+        }
+        const double cl = fmax(floor(x0) - 1.0, 0.0), ch = fmin(ceil(x1) + 1.0, static_cast<double>(W - 1));
+        const double rl = fmax(floor(y0) - 1.0, 0.0), rh = fmin(ceil(y1) + 1.0, static_cast<double>(H - 1));
+        if (!(cl <= ch && rl <= rh)) return none;
+        return {static_cast<int>(rl), static_cast<int>(rh - rl) + 1, static_cast<int>(cl), static_cast<int>(ch - cl) + 1};
+    } else {
+        // rows must map to [-pi/2, pi/2] for the latitude band below to mean rows
+        const double cx = static_cast<double>(cam.cx), cy = static_cast<double>(cam.cy);
+        if (!(cy >= 0.5 * H - 1.0 && cy <= 0.5 * H)) return all;
+        // the cap around the normalised mean of the vertex directions that contains the three of them
+        double m[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = (A[k] / len[0] + B[k] / len[1]) + C[k] / len[2];
+        const double lm = sqrt(render_dot(m[0], m[1], m[2], m[0], m[1], m[2]));
+        if (!(lm > 0x1p-10)) return all;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] /= lm;
+        double cosr = 1.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cosr = fmin(cosr, render_dot(m[0], m[1], m[2], T[3 * j], T[3 * j + 1], T[3 * j + 2]) / len[j]);
+        const double rho = acos(fmax(cosr, -1.0)) * kGrow + kPad;
+        if (!(rho < 0.5 * kPi - kPad)) return all;                    // not convex: no bound
+        const double phi = asin(fmin(fmax(m[1], -1.0), 1.0));         // the angle below the equator: row = cy + phi H / pi
+        const double rpr = static_cast<double>(H) / kPi, cpr = static_cast<double>(W) / (2.0 * kPi);
+        const double rl = fmax(floor(cy + (phi - rho) * rpr) - 1.0, 0.0);
+        const double rh = fmin(ceil(cy + (phi + rho) * rpr) + 1.0, static_cast<double>(H - 1));
+        if (!(rl <= rh)) return none;
+        const int r0 = static_cast<int>(rl), nr = static_cast<int>(rh - rl) + 1;
+        if (!(fabs(phi) + rho < 0.5 * kPi - kPad)) return {r0, nr, 0, W};          // the cap touches a pole
+        const double dl = asin(fmin(sin(rho) / cos(phi), 1.0)) * kGrow + kPad;
+        const double lam = atan2(m[0], m[2]);
+        const double lo = floor(cx + (lam - dl) * cpr) - 1.0, hi = ceil(cx + (lam + dl) * cpr) + 1.0;
+        const double n = (hi - lo) + 1.0;
+        if (!(n < static_cast<double>(W))) return {r0, nr, 0, W};
+        const long long c0 = ((static_cast<long long>(lo) % W) + W) % W;          // |lo| < W + |cx| + 2
+        return {r0, nr, static_cast<int>(c0), static_cast<int>(n)};
+    }
+}
+
+// Step 6 for one candidate pixel.
+template <int MODEL>
+__device__ __forceinline__ void render_candidate(const DevCam& cam, const double T[9], unsigned f, const RenderBound& b,
+                                                 long long k, unsigned long long* __restrict__ keys) {
+    const int r = b.r0 + static_cast<int>(k / b.nc);
+    int c = b.c0 + static_cast<int>(k % b.nc);
+    if (c >= cam.W) c -= cam.W;
+    double d[3], u, v, w, s;
+    float md;
+    render_ray<MODEL>(cam, c, r, d);
+    if (!render_hit<MODEL>(T, d, u, v, w, s, md)) return;
+    const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(md)) << 32) | f;
+    unsigned long long* dst = keys + static_cast<size_t>(r) * cam.W + c;
+    // the key only decreases: a stale value costs an atomic and never skips one that would have won
+    if (*reinterpret_cast<volatile unsigned long long*>(dst) > key) atomicMin(dst, key);
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_render_setup(const DevCam cam, const float* __restrict__ verts, unsigned long long nv,
+                                                      const int32_t* __restrict__ faces, unsigned nf, long long small_max,
+                                                      unsigned long long* __restrict__ keys, RenderItem* __restrict__ queue,
+                                                      unsigned long long* __restrict__ words) {
+    const unsigned f = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long skipped = 0, small = 0, cand = 0;
+    if (f < nf) {
+        int32_t idx[3];
+        double T[9];
+        if (!render_face<MODEL>(cam, verts, nv, faces, f, idx, T)) {
+            skipped = 1;
+        } else {
+            const RenderBound b = render_bound<MODEL>(cam, T);
+            const long long n = static_cast<long long>(b.nr) * b.nc;
+            cand = static_cast<unsigned long long>(n);
+            if (n <= small_max) {
+                small = 1;
+                for (long long k = 0; k < n; ++k) render_candidate<MODEL>(cam, T, f, b, k, keys);
+            } else {
+                const unsigned long long q = atomicAdd(&words[kRenderLarge], 1ull);   // q < nf: one per face at most
+                queue[q] = RenderItem{f, b};
+            }
+        }
+    }
+    wave_add(skipped, &words[kRenderSkipped]);
+    wave_add(small, &words[kRenderSmall]);
+    wave_add(cand, &words[kRenderCandidates]);
+}
+
+// One workgroup per queued face, its lanes striding over the face's candidates.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_render_large(const DevCam cam, const float* __restrict__ verts, unsigned long long nv,
+                                                      const int32_t* __restrict__ faces, unsigned nf,
+                                                      unsigned long long* __restrict__ keys, const RenderItem* __restrict__ queue,
+                                                      const unsigned long long* __restrict__ words) {
+    const unsigned long long n_large = words[kRenderLarge] < nf ? words[kRenderLarge] : nf;
+    for (unsigned long long q = blockIdx.x; q < n_large; q += gridDim.x) {
+        const RenderItem it = queue[q];
+        int32_t idx[3];
+        double T[9];
+        if (it.face >= nf || !render_face<MODEL>(cam, verts, nv, faces, it.face, idx, T)) continue;
+        const long long n = static_cast<long long>(it.b.nr) * it.b.nc;
+        for (long long k = threadIdx.x; k < n; k += 256) render_candidate<MODEL>(cam, T, it.face, it.b, k, keys);
+    }
+}
+
+// *word += the number of lanes of the wave with `on`, one atomic per wave.  Every lane of the wave calls it.
+__device__ __forceinline__ void wave_count(bool on, unsigned long long* word) {
+    const unsigned long long m = __ballot(on);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(word, static_cast<unsigned long long>(__popcll(m)));
+}
+
+// Steps 7 and 8, one lane per pixel: the winner's hit again, the four maps, the counts.
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_render_resolve(const DevCam cam, const float* __restrict__ verts, unsigned long long nv,
+                                                        const int32_t* __restrict__ faces, unsigned nf,
+                                                        const unsigned long long* __restrict__ keys, const float* __restrict__ raw,
+                                                        float rel_tol, float* __restrict__ depth, int32_t* __restrict__ face,
+                                                        float* __restrict__ normal, float* __restrict__ colour,
+                                                        unsigned long long* __restrict__ words) {
+    const long long P = static_cast<long long>(cam.W) * cam.H;
+    const long long p = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    int cls = -1;
+    bool back = false;
+    if (p < P) {
+        const unsigned long long key = keys[p];
+        float md = 0.0f, out[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        int32_t win = -1;
+        if (key != ~0ull) {
+            const unsigned f = static_cast<unsigned>(key & 0xffffffffull);
+            int32_t idx[3];
+            double T[9], d[3], u, v, w, s;
+            float again;
+            render_ray<MODEL>(cam, static_cast<int>(p % cam.W), static_cast<int>(p / cam.W), d);
+            if (f < nf && render_face<MODEL>(cam, verts, nv, faces, f, idx, T) && render_hit<MODEL>(T, d, u, v, w, s, again)) {
+                win = static_cast<int32_t>(f);
+                md = __uint_as_float(static_cast<unsigned>(key >> 32));
+                back = s > 0.0;
+                const float* a = verts + 9ull * static_cast<unsigned long long>(idx[0]);
+                const float* b = verts + 9ull * static_cast<unsigned long long>(idx[1]);
+                const float* c = verts + 9ull * static_cast<unsigned long long>(idx[2]);
+                double n[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    n[k] = ((u * static_cast<double>(a[3 + k]) + v * static_cast<double>(b[3 + k])) + w * static_cast<double>(c[3 + k])) / s;
+                    out[3 + k] = static_cast<float>(((u * static_cast<double>(a[6 + k]) + v * static_cast<double>(b[6 + k])) +
+                                                     w * static_cast<double>(c[6 + k])) / s);
+                }
+                const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) out[k] = len > 0.0 ? static_cast<float>(n[k] / len) : 0.0f;
+            }
+        }
+        depth[p] = md;
+        face[p] = win;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { normal[3 * p + k] = out[k]; colour[3 * p + k] = out[3 + k]; }
+        if (raw) {
+            const float sd = raw[p];
+            const bool have_raw = sd > 0.0f && sd < __builtin_inff(), have_mesh = win >= 0;
+            if (have_raw && have_mesh) {
+                const float t = rel_tol * sd;
+                cls = fabsf(md - sd) <= t ? 0 : md < sd ? 1 : 2;
+            } else {
+                cls = have_mesh ? 3 : have_raw ? 4 : 5;
+            }
+        } else {
+            back = false;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) wave_count(cls == k, &words[kRenderCounts + k]);
+    wave_count(back, &words[kRenderCounts + 6]);
+}
+
+hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsigned long long nv, const int32_t* faces,
+                         unsigned nf, long long small_max, unsigned long long* keys, void* queue, const float* raw,
+                         float rel_tol, float* depth, int32_t* face, float* normal, float* colour, unsigned long long* words,
+                         hipStream_t s) {
+    const long long P = static_cast<long long>(cam.W) * cam.H;
+    const unsigned fb = static_cast<unsigned>((static_cast<unsigned long long>(nf) + 255ull) / 256ull);
+    const unsigned lb = std::min(nf, 4096u), pb = static_cast<unsigned>((P + 255) / 256);
+    RenderItem* q = static_cast<RenderItem*>(queue);
+    static_assert(sizeof(RenderItem) == kRenderItemBytes, "fusion.cpp sizes the queue");
+    if (nf > 0) {
+        if (model == kSphere) {
+            k_render_setup<kSphere><<<fb, 256, 0, s>>>(cam, verts, nv, faces, nf, small_max, keys, q, words);
+            k_render_large<kSphere><<<lb, 256, 0, s>>>(cam, verts, nv, faces, nf, keys, q, words);
+        } else {
+            k_render_setup<kPinhole><<<fb, 256, 0, s>>>(cam, verts, nv, faces, nf, small_max, keys, q, words);
+            k_render_large<kPinhole><<<lb, 256, 0, s>>>(cam, verts, nv, faces, nf, keys, q, words);
+        }
+    }
+    if (model == kSphere)
+        k_render_resolve<kSphere><<<pb, 256, 0, s>>>(cam, verts, nv, faces, nf, keys, raw, rel_tol, depth, face, normal, colour, words);
+    else
+        k_render_resolve<kPinhole><<<pb, 256, 0, s>>>(cam, verts, nv, faces, nf, keys, raw, rel_tol, depth, face, normal, colour, words);
     return hipGetLastError();
 }
 

@@ -605,6 +605,64 @@ acmmp_status acmmp_fusion_mesh_samples(acmmp_fusion *f, int64_t first, int64_t n
 acmmp_status acmmp_fusion_mesh_table(acmmp_fusion *f, int64_t force_slots, int64_t *slots, int64_t *occupied,
                                      int64_t *max_probe, int64_t *wrapped);
 
+/* A host mesh becomes the mesh result, as acmmp_fusion_set_scene does for clouds: vertices nv x 9 floats (position,
+ * normal, colour), faces nf x 3 int32 vertex indices.  ACMMP_ERR_INVALID_ARGUMENT: a count below 0 or beyond 2^31 - 1,
+ * an index outside [0, nv), a NULL array of a count above 0; any error leaves the object as it was.  Such a mesh has no
+ * source and no samples (acmmp_fusion_mesh_samples sees none): it lives until the next successful
+ * acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh, whatever happens to the scene, voxel, clean and visible results. */
+acmmp_status acmmp_fusion_set_mesh(acmmp_fusion *f, int64_t nv, const float *vertices, int64_t nf, const int32_t *faces);
+
+/* ---- the mesh result rendered into a view: z-buffer depth, face, normal and colour maps (no reference counterpart) ----
+ * acmmp_fusion_mesh_render renders the mesh result into one camera, pinhole or SPHERE.  All arithmetic is IEEE float64
+ * with no contraction, on inputs widened from float32, unless float32 is said.
+ *  1. Camera.  View i's own camera, or with view == -1 the camera `cam`, of the set's model.  W x H, the map's size,
+ *     are the camera's.
+ *  2. Vertices in the camera frame.  For a vertex X and k = 0, 1, 2: T_k = ((R[3k]*X.x + R[3k+1]*X.y) + R[3k+2]*X.z) +
+ *     t[k].  A face with a non-finite camera-frame coordinate is skipped, and so is, for the pinhole model, a face with
+ *     any T_z <= 0 (there is no near-plane clipping); *n_skipped counts them.
+ *  3. Ray of pixel (c, r).  Pinhole: d = (((double)c - K[2]) / K[0], ((double)r - K[5]) / K[4], 1).  SPHERE: the float32
+ *     PixelToDir of the engine (lon = ((c - cx) / W * 2) * pi_f, lat = (-(r - cy) / H) * pi_f in float32, pi_f =
+ *     3.141592654f, the deterministic sine and cosine, d = (cos lat * sin lon, -sin lat, cos lat * cos lon)), widened.
+ *  4. Hit test.  For a face (A, B, C) in the camera frame u = d.(B x C), v = d.(C x A), w = d.(A x B), the cross product
+ *     (b_y c_z - b_z c_y, b_z c_x - b_x c_z, b_x c_y - b_y c_x), the dot product (d_x n_x + d_y n_y) + d_z n_z, and
+ *     s = (u + v) + w.  The ray hits when (s > 0 and u, v, w >= 0) or (s < 0 and u, v, w <= 0), and P.d > 0 for
+ *     P = ((u*A + v*B) + w*C) / s per component.  A shared edge gives exactly negated products to its two faces: a ray
+ *     on the edge hits both, a ray beside it one of them, and the rendering has no cracks.
+ *  5. Depth.  Pinhole P_z, SPHERE sqrt((P_x^2 + P_y^2) + P_z^2); md is that value rounded to float32, and the hit counts
+ *     only when md is finite and > 0.
+ *  6. Winner.  Per pixel the smallest key (bits(md) << 32) | face index over all faces of the mesh that hit: equal
+ *     depths go to the lower face index.  The definition is exhaustive over faces and pixels; the device tests a face
+ *     against a conservative bound of its pixels only.
+ *  7. Outputs per pixel.  depth: md, 0 where nothing hits.  face: int32, -1 where nothing hits.  normal: N =
+ *     ((u*nA + v*nB) + w*nC) / s per component, then N / sqrt((N_x^2 + N_y^2) + N_z^2) rounded to float32, zero unless
+ *     that length is > 0; it is in world space, as the .dmb normals are.  colour: ((u*cA + v*cB) + w*cC) / s per
+ *     component, rounded to float32.  Both are zero where nothing hits.  A winner is back-facing when s > 0: faces are
+ *     counter-clockwise seen from free space, and a camera in free space has s < 0.
+ *  8. Agreement, for view >= 0 (with view == -1 all seven counts are 0).  sd = the view's raw depth at the pixel as
+ *     uploaded; one that is not finite and > 0 is absent.  In float32 t = rel_tol * sd.  counts[0] agree: both present
+ *     and fabsf(md - sd) <= t; [1] mesh in front: both, md < sd, not agree; [2] mesh behind: both, neither of those;
+ *     [3] mesh only; [4] raw only; [5] neither; they sum to W * H.  counts[6]: the winners that are back-facing.
+ * counts and n_skipped may be NULL.  One render result is resident at a time (acmmp_fusion_render_maps reads it); it
+ * is built beside the previous one and any error leaves the object as it was; it is discarded when the mesh result is
+ * replaced or discarded; acmmp_fusion_set_view does not touch it.  ACMMP_ERR_INVALID_ARGUMENT: no mesh result, a view
+ * outside the set (below -1 included) or never given to acmmp_fusion_set_view, view == -1 with a NULL camera, a camera
+ * of another model or with a non-positive size, rel_tol not finite or < 0.  ACMMP_ERR_UNSUPPORTED: more than 2^31 - 1
+ * pixels or faces.  Every atomic of the device is an integer minimum or add, and nothing a reader can see depends on
+ * the order in which faces are taken.  Device memory: 32 bytes per pixel held with the result (depth, face, normal,
+ * colour); 8 bytes per pixel (the keys) and 20 per face (the queue of large faces) while the call runs.  The host
+ * waits once, at the end, for the counts. */
+acmmp_status acmmp_fusion_mesh_render(acmmp_fusion *f, int view, const acmmp_camera *cam, float rel_tol,
+                                      int64_t counts[7], int64_t *n_skipped);
+/* The render result to host arrays, any of which may be NULL: depth W x H floats, face W x H int32, normal and colour
+ * W x H x 3 floats, row-major.  ACMMP_ERR_INVALID_ARGUMENT without a render result. */
+acmmp_status acmmp_fusion_render_maps(acmmp_fusion *f, float *depth, int32_t *face, float *normal, float *colour);
+/* Test hook.  A face whose bound holds at most small_max candidate pixels is rendered by its own lane, the others by a
+ * workgroup each.  small_max = 0 restores the default threshold (256); any other value is the threshold of the renders
+ * that follow (below 0: every face is large).  The outputs, each of which may be NULL, describe the last successful
+ * render: faces rendered by their own lane, faces queued, candidate pixels over all faces that were not skipped. */
+acmmp_status acmmp_fusion_render_plan(acmmp_fusion *f, int small_max, int64_t *n_small, int64_t *n_large,
+                                      int64_t *n_candidates);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
