@@ -1110,10 +1110,10 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         ref_total += ref_blocks[i];
     }
     // half-sweep scratch slab: carve the pieces of engine.h's KParams out of one allocation
-    size_t off[18];
+    size_t off[19];
     {
         const size_t VP = static_cast<size_t>(kp.V) * Pc;
-        const size_t sizes[17] = {sizeof(float) * 8 * VP, sizeof(int) * 8 * Pc,
+        const size_t sizes[18] = {sizeof(float) * 8 * VP, sizeof(int) * 8 * Pc,
                                   sizeof(float4) * 5 * Pc, sizeof(float) * 5 * Pc, sizeof(float) * 5 * Pc,
                                   sizeof(PixState) * Pc, sizeof(float) * VP, sizeof(float) * VP,
                                   sizeof(float) * 5 * VP, sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
@@ -1122,13 +1122,13 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
                                   sizeof(unsigned) * kNbFixRegions * ns,
                                   sizeof(unsigned) * std::max(Pc / 51 + 3, ref_total + ns),
                                   sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
-                                  sizeof(uint32_t) * 5 * Pc};
+                                  sizeof(uint32_t) * 5 * Pc, sizeof(uint8_t) * 2 * Pc};
         off[0] = 0;
-        for (int k = 0; k < 17; ++k) off[k + 1] = (off[k] + sizes[k] + 255) & ~static_cast<size_t>(255);
+        for (int k = 0; k < 18; ++k) off[k + 1] = (off[k] + sizes[k] + 255) & ~static_cast<size_t>(255);
     }
-    if (c->scratch_bytes < off[17]) {
-        HIP_TRY(c, dalloc(c->d_scratch, off[17]));
-        c->scratch_bytes = off[17];
+    if (c->scratch_bytes < off[18]) {
+        HIP_TRY(c, dalloc(c->d_scratch, off[18]));
+        c->scratch_bytes = off[18];
     }
     kp.cams = c->d_cams;
     kp.tex16 = c->tex16;
@@ -1163,6 +1163,14 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     kp.surv_pre = reinterpret_cast<unsigned*>(c->d_scratch + off[14]);
     kp.surv_dense = reinterpret_cast<uint32_t*>(c->d_scratch + off[15]);
     kp.cand_rough = reinterpret_cast<uint32_t*>(c->d_scratch + off[16]);
+    // SPHERE dead mask (engine.h), one byte per pixel and colour, written by k_init for the rows it initialises
+    // (they cover the half-sweeps' rows, band runs included).  ACMMP_DEAD_SKIP=0 (read per run) keeps none: every
+    // pixel then takes the long paths, with the same result (A/B, tests/test_gpu_dead_skip.py)
+    {
+        const char* e = std::getenv("ACMMP_DEAD_SKIP");
+        const bool skip = c->model == kSphere && !(e && std::atoi(e) == 0);
+        for (int k = 0; k < 2; ++k) kp.dead[k] = skip ? reinterpret_cast<uint8_t*>(c->d_scratch + off[17]) + k * Pc : nullptr;
+    }
     kp.nbfix_cap = static_cast<unsigned>(fix_cap[0]);
     c->strips.assign(ns, StripSlice{});
     {
@@ -1182,9 +1190,10 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         }
     }
     kp.ref_split = ref_split;
-    if (!c->d_work) HIP_TRY(c, dalloc(c->d_work, 257));
+    if (!c->d_work) HIP_TRY(c, dalloc(c->d_work, 258));
     kp.work = c->d_work;
     kp.status = reinterpret_cast<unsigned*>(c->d_work + 256);
+    kp.dead_any = reinterpret_cast<unsigned*>(c->d_work + 257);  // zeroed with the counters before k_init
     kp.nb_views = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
     kp.nb_count_work = 1;
     return ACMMP_OK;
@@ -1220,7 +1229,7 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         }
         if (!c->fork_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 257, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     HIP_TRY(c, launch_init(kp, s));
     // rows outside the reference's checkerboard grid are never rewritten: keep both buffers equal
@@ -1393,7 +1402,7 @@ acmmp_status acmmp_band_begin(acmmp_ctx* c, uint64_t seed, int row0, int row1) {
     kp.filt_lo[1] = kp.row_lo; kp.filt_hi[1] = kp.row_hi;
     const size_t Pc = static_cast<size_t>(kp.Pc);
     hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 257, s));
+    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     HIP_TRY(c, launch_init(kp, s));
     for (int k = 0; k < 2; ++k) {

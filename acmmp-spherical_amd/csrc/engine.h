@@ -156,6 +156,13 @@ struct KParams {
     // k_eval_ref's interpolated instance (SPHERE V > 4): per queued candidate, its selected views of
     // [0, ref_split) whose interpolation fell back -- k_eval_ref_tail recomputes them and restarts the chain
     uint32_t* cand_rough;           // [5][Pc]
+    // SPHERE dead mask: per colour [Pc], 1 = the pixel's bilateral weight sum is below 1e-6, so
+    // every NCC of it is 2.0 and its half-sweeps change nothing but its cost (0/0) and draw counter (+15).
+    // k_init writes it where it forms the sum; the half-sweep kernels skip such pixels.  null = no skipping
+    // (pinhole, ACMMP_DEAD_SKIP=0)
+    uint8_t* dead[2];
+    unsigned* dead_any;             // set by k_init when the view has a dead pixel at all (zeroed per run): a view
+                                    // without one reads this word (a scalar load) and no mask byte
     unsigned* status;               // run status bits (kStatus*), zeroed per run, checked after it
 };
 

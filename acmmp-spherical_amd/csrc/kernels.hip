@@ -1521,6 +1521,12 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
     const int colour = (x + y) & 1;
     const long long ci = cs_index(kp, x, y);
     const Patch pt = make_patch<MODEL>(kp, x, y);
+    // the dead mask: ncc_chunk's own test on the sum the staged layouts form too (patch_sums)
+    if (MODEL == kSphere && kp.dead[0]) {
+        const bool dead = pt.sbw < 1e-6f;
+        (colour ? kp.dead[1] : kp.dead[0])[ci] = dead ? 1 : 0;
+        if (dead) *kp.dead_any = 1u;
+    }
     float* cvec = kp.cvec[colour] + ci;
     Rng rs;
     rs.init(kp.seed_lo, kp.seed_hi, static_cast<uint32_t>(center), 0u);
@@ -1730,6 +1736,20 @@ __device__ __forceinline__ bool colour_pixel(const KParams& kp, int colour, long
     return py < kp.row_hi && px < kp.W;
 }
 
+// The dead mask's entry of pixel ci of the colour grid (KParams::dead, written by k_init): the pixel's patch sum
+// is below 1e-6, every NCC of it is 2.0, and its half-sweep is known in advance.  False where the
+// run keeps no mask.  A view without a dead pixel reads no mask byte: k_init's word says so, read as a scalar
+// through the constant address space (it is written before the half-sweeps' launches, never during them) -- with
+// the byte load in front of every kernel's first loads such views ran 0.4-0.5% slower.
+__device__ __forceinline__ bool dead_view(const KParams& kp) {
+    typedef const __attribute__((address_space(4))) unsigned ConstWord;
+    return kp.dead[0] && *((ConstWord*)(kp.dead_any)) != 0u;
+}
+__device__ __forceinline__ bool dead_pixel(const KParams& kp, int colour, long long ci) {
+    const uint8_t* m = colour ? kp.dead[1] : kp.dead[0];
+    return dead_view(kp) && m[ci];
+}
+
 // k_eval_nb staging, 16 B per sample + 4 B per patch row: SPHERE stores (ray.x, ray.z, w, texel)
 // per sample and ray.y = -sin(lat) once per patch row (it depends on the row only); PINHOLE stores
 // (ray, w) per sample and the texels after them.  32 pixels x 36 samples = 19.2 KB per block for
@@ -1867,6 +1887,7 @@ __global__ __launch_bounds__(256) void k_pick(const KParams kp, const int colour
     int px = 0, py = 0;
     if (!colour_pixel(kp, colour, q, px, py)) return;
     const long long ci = static_cast<long long>(py) * kp.Wh + (px >> 1);
+    if (dead_pixel(kp, colour, ci)) return;                  // picks nothing: nobody reads its nbpos
     kp.nbpos[d * kp.Pc + ci] = pick_neighbour(kp, d, px, py);
 }
 
@@ -1914,14 +1935,21 @@ __global__ __launch_bounds__(256, MODEL == kSphere ? (FM ? ACMMP_NB_SPH_WAVES : 
     }
     const long long q = kp.nb_tile ? wrow * kp.Wh + wcol + (lp & 7) : static_cast<long long>(blockIdx.x) * kNbPix + lp;
     int px = 0, py = 0;
-    const bool valid = (!kp.nb_tile || wcol + (lp & 7) < kp.Wh) && colour_pixel(kp, colour, q, px, py);
+    const long long Pc = kp.Pc;
+    // the pixel's dead-mask byte, asked for before colour_pixel's division so that it arrives behind it: an existing
+    // pixel q sits at row_lo * Wh + q of the colour grid (the index clamped for the ones that do not exist)
+    bool dead = false;
+    if (MODEL == kSphere) dead = dead_pixel(kp, colour, min(static_cast<long long>(kp.row_lo) * kp.Wh + q, Pc - 1));
+    bool valid = (!kp.nb_tile || wcol + (lp & 7) < kp.Wh) && colour_pixel(kp, colour, q, px, py);
+    const long long ci = static_cast<long long>(py) * kp.Wh + (px >> 1);
+    // a dead pixel stages nothing and writes no cost: its lanes only meet the block's barriers (an all-dead
+    // block does nothing else), and with a zero patch sum it stays out of the work count as before
+    if (dead) valid = false;
     const Patch pt = coop_patch_nb<MODEL>(kp, valid, px, py, lp, h, lds4);
     // work accounting for the roofline: pixels whose NCCs are evaluated (not short-circuited)
     const int busy = __syncthreads_count(valid && h == 0 && !(MODEL == kSphere && pt.sbw < 1e-6f));
     if (t == 0 && busy && kp.nb_count_work) atomicAdd(kp.work + (blockIdx.x & 255u), static_cast<unsigned long long>(busy));
     if (!valid) return;
-    const long long Pc = kp.Pc;
-    const long long ci = static_cast<long long>(py) * kp.Wh + (px >> 1);
     const int pos = kp.nbpos[h * Pc + ci];                  // k_pick
     if (pos < 0) return;
     const float4 ph = plane_at(kp, pos);
@@ -2036,6 +2064,31 @@ __global__ __launch_bounds__(256, ACMMP_SELECT_WAVES) void k_select(const KParam
     const long long ci = static_cast<long long>(py) * kp.Wh + (px >> 1);
     const long long center = static_cast<long long>(py) * kp.W + px;
     const float4 dc = ray_at<MODEL>(kp, px, py);
+    if (MODEL == kSphere && dead_pixel(kp, colour, ci)) {
+        // Every cost of a flagged direction is 2.0 and at least four of the eight are flagged, so count_false >= 3
+        // for every view: all probabilities 0, the CDF NaN, no view drawn in the 15 draws, weight_norm 0, every
+        // aggregate 0/0, no comparison against them holds, and the refinement does not run.  What
+        // the long path below would store, without a cost load or a Philox round:
+        float zn = 0.0f, zd = 0.0f;
+        asm volatile("" : "+v"(zn), "+v"(zd));               // the long path's division (fc / weight_norm), so its NaN
+        const float nan_cost = zn / zd;
+        const float4 own = kp.plane_cs[colour][ci];
+        PixState st;
+        st.plane_now = own;
+        st.cur_plane = own;
+        st.vw = make_uint4(0u, 0u, 0u, 0u);
+        st.cost_now = nan_cost;
+        st.depth_now = depth_from_plane(own, dc);
+        st.cur_cost = nan_cost;
+        st.restricted_cost = 0.0f;
+        st.cur_sel = kp.sel_cs[colour][ci];
+        st.flags = (kp.planar && kp.mask[center] > 0) ? 1u : 0u;
+        st.weight_norm = 0.0f;
+        st.src = 8u | (8u << 8);
+        kp.pst[ci] = st;
+        kp.rng_cs[colour][ci] += 15u;
+        return;
+    }
     Rng rs;
     rs.init(kp.seed_lo, kp.seed_hi, static_cast<uint32_t>(center), kp.rng_cs[colour][ci]);
 
