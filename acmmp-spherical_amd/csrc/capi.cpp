@@ -17,9 +17,11 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
+#include "devbuf.h"
 #include "engine.h"
 #include "planar.h"
 
@@ -36,9 +38,9 @@ static_assert(offsetof(acmmp_params, geom_consistency) == 60, "PatchMatchParams 
 struct acmmp_image_cache {
     struct Entry {
         int W = 0, H = 0;
-        float* img = nullptr;            // padded (W + 2) x (H + 2) fp32
-        uint32_t* img16 = nullptr;       // row-pair binary16 copy, null when some texel is not exact
-        bool f16_checked = false;        // the binary16 conversion was attempted (img16 null: inexact)
+        DevBuf<float> img;               // padded (W + 2) x (H + 2) fp32
+        DevBuf<uint32_t> img16;          // row-pair binary16 copy, empty when some texel is not exact
+        bool f16_checked = false;        // the binary16 conversion was attempted (img16 empty: inexact)
         size_t bytes = 0;
         int pins = 0;
         uint64_t used = 0;               // LRU clock
@@ -53,6 +55,9 @@ struct acmmp_image_cache {
     unsigned long long hits = 0, misses = 0, evictions = 0;
 };
 
+// Every buffer is a DevBuf / PinnedBuf (devbuf.h): it knows its element count and frees itself, so a new
+// one needs no line anywhere else.  The grow-only ones (reserve) are refilled per call and keep their
+// allocation across problems.
 struct acmmp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -60,67 +65,58 @@ struct acmmp_ctx {
     acmmp_params params{};
     bool has_params = false;
 
+    // N > 0: views are uploaded and every per-size map below holds W x H (upload_views_impl sets it last)
     int N = 0, W = 0, H = 0, model = -1;
     std::vector<acmmp_camera> cams;
     std::vector<DevCam> dcams;
-    DevCam* d_cams = nullptr;
-    float* d_img = nullptr;          // padded fp32 images of the views not in an image cache
-    uint32_t* d_img16 = nullptr;     // their row-pair binary16 copies
-    size_t img_cap = 0, img16_cap = 0;  // texels the two image allocations hold (grow-only)
-    char* d_stage = nullptr;         // upload staging for all of a problem's images (grow-only)
-    size_t stage_cap = 0;
-    int* d_flag = nullptr;           // k_to_f16_pairs' inexact flags, one per view
-    size_t flag_cap = 0;
+    DevBuf<DevCam> d_cams;
+    DevBuf<float> d_img;             // padded fp32 images of the views not in an image cache (grow-only)
+    DevBuf<uint32_t> d_img16;        // their row-pair binary16 copies (grow-only)
+    DevBuf<char> d_stage;            // upload staging for all of a problem's images (grow-only)
+    DevBuf<int> d_flag;              // k_to_f16_pairs' inexact flags, one per view
     bool tex16 = false;              // every view of the problem has an exact binary16 copy
     acmmp_image_cache* pin_cache = nullptr;   // entries the current problem pins
     std::vector<uint64_t> pinned;
-    std::vector<float*> orphans;     // keyed images another context cached first (freed at the next upload)
-    std::vector<uint32_t*> orphans16;
-    size_t cams_cap = 0;
+    // keyed images of this call's cache misses, one slot per view; those the cache did not take (another
+    // context cached the key first, or the upload failed) stay here until the next upload
+    std::vector<DevBuf<float>> orphans;
+    std::vector<DevBuf<uint32_t>> orphans16;
 
-    float* d_dep = nullptr;
+    DevBuf<float> d_dep;
     bool has_depths = false;
 
-    float4* d_dirs = nullptr;
+    DevBuf<float4> d_dirs;
     int dirs_R = -1;
 
-    float2* d_sph_row = nullptr;
-    float2* d_sph_col = nullptr;
-    float* d_spatial = nullptr;
+    DevBuf<float2> d_sph_row;
+    DevBuf<float2> d_sph_col;
+    DevBuf<float> d_spatial;
 
-    float4* d_planes_rm = nullptr;
-    float* d_w_rm = nullptr;                    // the post stage's depth channel (k_merge -> k_filter)
-    float* d_costs_rm = nullptr;
-    float* d_pre = nullptr;
-    uint32_t* d_sel_rm = nullptr;
+    DevBuf<float4> d_planes_rm;
+    DevBuf<float> d_w_rm;                       // the post stage's depth channel (k_merge -> k_filter)
+    DevBuf<float> d_costs_rm;
+    DevBuf<float> d_pre;
+    DevBuf<uint32_t> d_sel_rm;
 
-    float4* d_scaled = nullptr;
+    DevBuf<float4> d_scaled;
     int sw = 0, sh = 0;
     bool has_scaled = false;          // set_scaled_state since the last upload_views
 
-    float4* d_prior = nullptr;
-    uint32_t* d_mask = nullptr;
-    size_t prior_cap = 0, mask_cap = 0;
-    // grow-only capacities of buffers refilled per call (a hipFree waits for the whole device, i.e. for
-    // every other context's kernels: reallocating per problem serialised the pipeline's contexts)
-    size_t dep_cap = 0, scaled_cap = 0, spatial_cap = 0;
+    DevBuf<float4> d_prior;
+    DevBuf<uint32_t> d_mask;
     bool has_prior = false;           // set_planar_prior since the last upload_views
     bool has_result = false;          // planes_rm / costs_rm hold this problem's maps (a run, set_state[_device])
-    char* d_pp = nullptr;             // planar-prior triangle tables (acmmp_set_planar_prior_from_maps)
-    size_t pp_cap = 0;
-    char* h_pp = nullptr;             // their pinned host staging (upload_planar), reused once pp_ev has passed
-    size_t h_pp_cap = 0;
+    DevBuf<char> d_pp;                // planar-prior triangle tables (acmmp_set_planar_prior_from_maps)
+    PinnedBuf<char> h_pp;             // their pinned host staging (upload_planar), reused once pp_ev has passed
     hipEvent_t pp_ev = nullptr;
     bool pp_pending = false;
-    int4* d_support = nullptr;        // support-point blocks (acmmp_set_planar_prior_from_state)
-    size_t support_cap = 0;
+    DevBuf<int4> d_support;           // support-point blocks (acmmp_set_planar_prior_from_state)
 
-    float4* d_plane_cs[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    float* d_cost_cs[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    uint32_t* d_sel_cs[2] = {nullptr, nullptr};
-    uint32_t* d_rng_cs[2] = {nullptr, nullptr};
-    char* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DevBuf<float4> d_plane_cs[2][2];
+    DevBuf<float> d_cost_cs[2][2];
+    DevBuf<uint32_t> d_sel_cs[2];
+    DevBuf<uint32_t> d_rng_cs[2];
+    DevBuf<char> d_scratch;           // the half-sweeps' slab (build_kparams carves it)
 
     float timing[3] = {0.f, 0.f, 0.f};
     float planar_ms[4] = {0.f, 0.f, 0.f, 0.f}; // acmmp_last_planar_timing
@@ -132,8 +128,8 @@ struct acmmp_ctx {
     hipEvent_t fork_ev = nullptr;
     std::vector<StripSlice> strips;
     float ktiming[4] = {0.f, 0.f, 0.f, 0.f};
-    unsigned long long* d_work = nullptr;       // [256] k_eval_nb work counters + [256] the run's status word
-    unsigned long long* h_work = nullptr;       // its pinned host copy, enqueued behind the run's last kernel
+    DevBuf<unsigned long long> d_work;          // [256] k_eval_nb work counters + [256] the run's status word
+    PinnedBuf<unsigned long long> h_work;       // its pinned host copy, enqueued behind the run's last kernel
     unsigned long long work_busy = 0, work_total = 0;
     int klaunch[4] = {0, 0, 0, 0};
     int math = ACMMP_MATH_EXACT;                // acmmp_set_math
@@ -143,6 +139,20 @@ struct acmmp_ctx {
     int band_lo = 0, band_hi = 0, band_sw = 0, band_nsw = 0;
     int band_cur[2] = {0, 0};
     std::string err;
+
+    acmmp_ctx() = default;
+    acmmp_ctx(const acmmp_ctx&) = delete;
+    acmmp_ctx& operator=(const acmmp_ctx&) = delete;
+    // Events and streams; the buffers free themselves after this body.  The caller has made `device` current
+    // and, where work may be queued, synchronised the streams (acmmp_destroy).
+    ~acmmp_ctx() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {pp_ev, fork_ev}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : sev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : kev) (void)hipEventDestroy(e);
+        for (hipStream_t xs : xstream) if (xs) (void)hipStreamDestroy(xs);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 namespace {
@@ -161,42 +171,22 @@ acmmp_status fail(acmmp_ctx* c, acmmp_status s, const std::string& msg) {
         }                                                                                          \
     } while (0)
 
-template <typename T>
-void dfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-template <typename T>
-hipError_t dalloc(T*& p, size_t count) {
-    dfree(p);
-    return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(count, 1));
-}
-
-// Grow-only allocation: reallocates only when `count` exceeds the capacity (contents not kept).
-template <typename T>
-hipError_t dreserve(T*& p, size_t& cap, size_t count) {
-    if (p && count <= cap) return hipSuccess;
-    cap = 0;
-    const hipError_t e = dalloc(p, count);
-    if (e == hipSuccess) cap = count;
-    return e;
-}
-
-// Grow-only with headroom, for buffers whose size follows the problem's scale (the planar-prior tables and
-// support blocks): the next power of two of `count`, at least `min_count`, so a pipeline's scales reuse one
-// allocation -- a reallocation frees the old buffer, and hipFree waits for the whole device, other contexts'
-// kernels included.
-template <typename T>
-hipError_t dreserve_pow2(T*& p, size_t& cap, size_t count, size_t min_count) {
-    if (p && count <= cap) return hipSuccess;
-    size_t n = std::max<size_t>(min_count, 1);
-    while (n < count) n *= 2;
-    return dreserve(p, cap, n);
-}
-
 size_t P_of(const acmmp_ctx* c) { return static_cast<size_t>(c->W) * c->H; }
 int Wh_of(const acmmp_ctx* c) { return (c->W + 1) / 2; }
+
+// The maps sized by the view, named once: f(buffer, elements) on each until one fails.  P = W x H pixels,
+// Pc = H x ceil(W / 2) pixels of one colour.
+template <typename F>
+hipError_t each_view_map(acmmp_ctx* c, size_t P, size_t Pc, F f) {
+    hipError_t e = hipSuccess;
+    auto go = [&](auto& b, size_t n) { if (e == hipSuccess) e = f(b, n); };
+    go(c->d_planes_rm, P); go(c->d_w_rm, P); go(c->d_costs_rm, P); go(c->d_pre, P); go(c->d_sel_rm, P);
+    for (int k = 0; k < 2; ++k) {
+        for (int b = 0; b < 2; ++b) { go(c->d_plane_cs[k][b], Pc); go(c->d_cost_cs[k][b], Pc); }
+        go(c->d_sel_cs[k], Pc); go(c->d_rng_cs[k], Pc);
+    }
+    return e;
+}
 
 // Camera centre exactly as Get3DPointonWorld_cu rounds it (ACMMP.cu:592-594), fused like the kernels.
 float neg_dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
@@ -298,7 +288,7 @@ acmmp_status acmmp_create(int device, acmmp_ctx** out) {
     }
     for (auto& e : c->ev) {
         if (hipEventCreate(&e) != hipSuccess) {
-            acmmp_destroy(c);
+            delete c;
             return ACMMP_ERR_HIP;
         }
     }
@@ -312,30 +302,8 @@ void acmmp_destroy(acmmp_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& xs : c->xstream) {
-        if (!xs) continue;
-        (void)hipStreamSynchronize(xs);
-        (void)hipStreamDestroy(xs);
-        xs = nullptr;
-    }
-    for (auto& e : c->sev) (void)hipEventDestroy(e);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
+    for (hipStream_t xs : c->xstream) if (xs) (void)hipStreamSynchronize(xs);
     unpin_views(c);
-    dfree(c->d_cams); dfree(c->d_img); dfree(c->d_img16); dfree(c->d_dep); dfree(c->d_dirs);
-    dfree(c->d_stage); dfree(c->d_flag);
-    dfree(c->d_sph_row); dfree(c->d_sph_col); dfree(c->d_spatial);
-    dfree(c->d_planes_rm); dfree(c->d_w_rm); dfree(c->d_costs_rm); dfree(c->d_pre); dfree(c->d_sel_rm);
-    dfree(c->d_scaled); dfree(c->d_prior); dfree(c->d_mask); dfree(c->d_pp); dfree(c->d_support); dfree(c->d_scratch); dfree(c->d_work);
-    for (int k = 0; k < 2; ++k) {
-        for (int b = 0; b < 2; ++b) { dfree(c->d_plane_cs[k][b]); dfree(c->d_cost_cs[k][b]); }
-        dfree(c->d_sel_cs[k]); dfree(c->d_rng_cs[k]);
-    }
-    for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->pp_ev) (void)hipEventDestroy(c->pp_ev);
-    if (c->h_pp) (void)hipHostFree(c->h_pp);
-    if (c->h_work) (void)hipHostFree(c->h_work);
-    for (auto& e : c->kev) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -406,11 +374,7 @@ static void cache_release(acmmp_image_cache* k) {
         last = --k->refs == 0;
     }
     if (!last) return;
-    (void)hipSetDevice(k->device);
-    for (auto& kv : k->map) {
-        dfree(kv.second.img);
-        dfree(kv.second.img16);
-    }
+    (void)hipSetDevice(k->device);                          // the entries free their images on that device
     delete k;
 }
 
@@ -430,8 +394,6 @@ acmmp_status acmmp_image_cache_stats(acmmp_image_cache* k, unsigned long long ou
 }  // extern "C"
 
 static void unpin_views(acmmp_ctx* c) {
-    for (auto& p : c->orphans) dfree(p);
-    for (auto& p : c->orphans16) dfree(p);
     c->orphans.clear();
     c->orphans16.clear();
     if (!c->pin_cache) return;
@@ -449,18 +411,18 @@ static void unpin_views(acmmp_ctx* c) {
 }
 
 // Least-recently used unpinned entries go first; the budget is soft (pinned entries stay).  Called with
-// the cache mutex held: the evicted allocations are handed back in `dead` and freed by the caller after
-// it releases the lock (hipFree waits for the device, which would stall every other context's upload).
-static void evict_over_budget(acmmp_image_cache* k, std::vector<void*>& dead) {
+// the cache mutex held: the evicted entries are handed back in `dead`, which the caller lets die after
+// it releases the lock (freeing device memory waits for the device, which would stall every other context's
+// upload).
+static void evict_over_budget(acmmp_image_cache* k, std::vector<acmmp_image_cache::Entry>& dead) {
     if (k->budget == 0) return;
     while (k->bytes > k->budget) {
         auto victim = k->map.end();
         for (auto it = k->map.begin(); it != k->map.end(); ++it)
             if (it->second.pins == 0 && (victim == k->map.end() || it->second.used < victim->second.used)) victim = it;
         if (victim == k->map.end()) return;
-        dead.push_back(victim->second.img);
-        dead.push_back(victim->second.img16);
-        k->bytes -= victim->second.bytes;
+        dead.push_back(std::move(victim->second));
+        k->bytes -= dead.back().bytes;
         k->map.erase(victim);
         ++k->evictions;
     }
@@ -491,12 +453,17 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
     // with camera entries pointing at images that are now unpinned, reallocated or freed
     c->N = 0;
     c->tex16 = false;
-    const bool resized = (c->W != cams[0].width || c->H != cams[0].height);
     // a new problem: the previous problem's prior / scaled state no longer applies (the reference
     // builds a fresh ACMMP object per ProcessProblem, main.cpp:80)
     c->has_prior = false;
     c->has_scaled = false;
     c->has_result = false;
+    if (c->W != cams[0].width || c->H != cams[0].height) {
+        // another size: nothing sized by the view survives, so no buffer below keeps a count of the old size
+        // (the grow-only prior, mask and scratch slab would otherwise hold the largest view's for good)
+        (void)each_view_map(c, 0, 0, [](auto& b, size_t) { b.reset(); return hipSuccess; });
+        c->d_prior.reset(); c->d_mask.reset(); c->d_scratch.reset();
+    }
     c->W = cams[0].width;
     c->H = cams[0].height;
     c->model = cams[0].model;
@@ -520,8 +487,8 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
             auto it = cache->map.find(keys[i]);
             if (it != cache->map.end() && it->second.W == cams[i].width && it->second.H == cams[i].height &&
                 (it->second.f16_checked || !want16)) {
-                base[i] = it->second.img;
-                base16[i] = want16 ? it->second.img16 : nullptr;
+                base[i] = it->second.img.get();
+                base16[i] = want16 ? it->second.img16.get() : nullptr;
                 ++it->second.pins;
                 it->second.used = ++cache->clock;
                 c->pinned.push_back(keys[i]);
@@ -546,27 +513,21 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
         total = (total + 63) & ~63LL;
     }
     if (total > 0) {
-        HIP_TRY(c, dreserve(c->d_img, c->img_cap, static_cast<size_t>(total)));
-        if (want16) HIP_TRY(c, dreserve(c->d_img16, c->img16_cap, static_cast<size_t>(total)));
+        HIP_TRY(c, c->d_img.reserve(static_cast<size_t>(total)));
+        if (want16) HIP_TRY(c, c->d_img16.reserve(static_cast<size_t>(total)));
     }
-    std::vector<float*> own(n, nullptr);
-    std::vector<uint32_t*> own16(n, nullptr);
-    // keyed misses that did not end up in the cache -- all of them when a step below fails -- stay with
-    // this context until its next upload (unpin_views frees them)
-    struct OwnGuard {
-        acmmp_ctx* c;
-        std::vector<float*>& own;
-        std::vector<uint32_t*>& own16;
-        ~OwnGuard() {
-            for (float* p : own) if (p) c->orphans.push_back(p);
-            for (uint32_t* p : own16) if (p) c->orphans16.push_back(p);
-        }
-    } own_guard{c, own, own16};
+    // keyed misses are allocated in the context's orphan slots and moved into the cache below: those that do
+    // not end up there -- all of them when a step below fails -- stay with this context until its next
+    // upload (unpin_views frees them)
+    std::vector<DevBuf<float>>& own = c->orphans;
+    std::vector<DevBuf<uint32_t>>& own16 = c->orphans16;
+    own.resize(n);
+    own16.resize(n);
     for (int i : miss) {
         if (keyed[i]) {
             const size_t texels = static_cast<size_t>(cams[i].width + 2) * (cams[i].height + 2);
-            HIP_TRY(c, dalloc(own[i], texels));
-            if (want16) HIP_TRY(c, dalloc(own16[i], texels));
+            HIP_TRY(c, own[i].alloc(texels));
+            if (want16) HIP_TRY(c, own16[i].alloc(texels));
             base[i] = own[i];
             base16[i] = own16[i];
         } else {
@@ -581,9 +542,9 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
             const size_t pb = pitch_bytes ? pitch_bytes[i] : rowb;
             soff[i + 1] = soff[i] + (is_miss[i] ? ((pb * (cams[i].height - 1) + rowb + 255) & ~static_cast<size_t>(255)) : 0);
         }
-        if (!device_src) HIP_TRY(c, dreserve(c->d_stage, c->stage_cap, soff[n]));
+        if (!device_src) HIP_TRY(c, c->d_stage.reserve(soff[n]));
         if (want16) {
-            HIP_TRY(c, dreserve(c->d_flag, c->flag_cap, static_cast<size_t>(n)));
+            HIP_TRY(c, c->d_flag.reserve(static_cast<size_t>(n)));
             HIP_TRY(c, hipMemsetAsync(c->d_flag, 0, sizeof(int) * n, c->stream));
         }
         for (int i : miss) {
@@ -607,12 +568,12 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
         HIP_TRY(c, hipStreamSynchronize(c->stream));      // staging, padding and flags done before returning
         for (int i : miss) {
             if (inexact[i]) {
-                if (keyed[i]) { dfree(own16[i]); own16[i] = nullptr; }
+                if (keyed[i]) own16[i].reset();
                 base16[i] = nullptr;
             }
         }
         if (cache && keys) {
-            std::vector<void*> dead;
+            std::vector<acmmp_image_cache::Entry> dead;         // dies after the lock is released
             {
                 std::lock_guard<std::mutex> lk(cache->mu);
                 for (int i : miss) {
@@ -623,26 +584,23 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
                             keyed[i] = false;
                             continue;
                         }
-                        dead.push_back(it->second.img);
-                        dead.push_back(it->second.img16);
                         cache->bytes -= it->second.bytes;
+                        dead.push_back(std::move(it->second));
                         cache->map.erase(it);
                     }
                     acmmp_image_cache::Entry e;
                     e.W = cams[i].width; e.H = cams[i].height;
-                    e.img = own[i]; e.img16 = own16[i];
+                    e.img = std::move(own[i]); e.img16 = std::move(own16[i]);   // owned by the cache now
                     e.f16_checked = want16;
-                    e.bytes = sizeof(float) * static_cast<size_t>(e.W + 2) * (e.H + 2) * (own16[i] ? 2 : 1);
+                    e.bytes = sizeof(float) * static_cast<size_t>(e.W + 2) * (e.H + 2) * (e.img16 ? 2 : 1);
                     e.pins = 1;
                     e.used = ++cache->clock;
                     cache->bytes += e.bytes;
-                    cache->map.emplace(keys[i], e);
+                    cache->map.emplace(keys[i], std::move(e));
                     c->pinned.push_back(keys[i]);
-                    own[i] = nullptr; own16[i] = nullptr;      // owned by the cache now
             }
             evict_over_budget(cache, dead);
             }
-            for (void* p : dead) dfree(p);
         }
     }
     c->tex16 = want16;
@@ -660,38 +618,28 @@ static acmmp_status upload_views_impl(acmmp_ctx* c, int n, const float* const* i
         d.dep_off = 0; d.dep_w = 1; d.dep_h = 1;
         set_relative_frame(d, cams[0], s);
     }
-    HIP_TRY(c, dreserve(c->d_cams, c->cams_cap, static_cast<size_t>(n)));
+    HIP_TRY(c, c->d_cams.reserve(static_cast<size_t>(n)));
     HIP_TRY(c, hipMemcpyAsync(c->d_cams, c->dcams.data(), sizeof(DevCam) * n, hipMemcpyHostToDevice, c->stream));
     c->has_depths = false;
 
-    if (resized || !c->d_planes_rm) {
-        const size_t P = P_of(c);
-        const size_t Pc = static_cast<size_t>(c->H) * Wh_of(c);
-        HIP_TRY(c, dalloc(c->d_planes_rm, P));
-        HIP_TRY(c, dalloc(c->d_w_rm, P));
-        HIP_TRY(c, dalloc(c->d_costs_rm, P));
-        HIP_TRY(c, dalloc(c->d_pre, P));
-        HIP_TRY(c, dalloc(c->d_sel_rm, P));
+    // every map that does not hold this size is allocated, whatever came before: all of them on first use
+    // and after a resize, the missing ones after a call that failed partway (N stays 0 until all exist)
+    const size_t P = P_of(c);
+    bool fresh = false;
+    HIP_TRY(c, each_view_map(c, P, static_cast<size_t>(c->H) * Wh_of(c), [&](auto& b, size_t count) {
+        if (b.count() == count) return hipSuccess;
+        fresh = true;
+        return b.alloc(count);
+    }));
+    if (fresh) {
         HIP_TRY(c, hipMemsetAsync(c->d_planes_rm, 0, sizeof(float4) * P, c->stream));
         HIP_TRY(c, hipMemsetAsync(c->d_costs_rm, 0, sizeof(float) * P, c->stream));
         HIP_TRY(c, hipMemsetAsync(c->d_sel_rm, 0, sizeof(uint32_t) * P, c->stream));
-        for (int k = 0; k < 2; ++k) {
-            for (int b = 0; b < 2; ++b) {
-                HIP_TRY(c, dalloc(c->d_plane_cs[k][b], Pc));
-                HIP_TRY(c, dalloc(c->d_cost_cs[k][b], Pc));
-            }
-            HIP_TRY(c, dalloc(c->d_sel_cs[k], Pc));
-            HIP_TRY(c, dalloc(c->d_rng_cs[k], Pc));
-        }
-        dfree(c->d_prior); dfree(c->d_mask);
-        c->prior_cap = c->mask_cap = 0;
-        dfree(c->d_scratch);
-        c->scratch_bytes = 0;
     }
     // pre_costs are written only by the upsample branch (ACMMP.cu:776) and otherwise read as zero
     // (DESIGN.md §2.2): zero them for every problem so a context reused across problems never leaks
     // another view's costs into k_finish's hierarchy gate
-    HIP_TRY(c, hipMemsetAsync(c->d_pre, 0, sizeof(float) * P_of(c), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_pre, 0, sizeof(float) * P, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->N = n;
     return ACMMP_OK;
@@ -710,7 +658,7 @@ static acmmp_status upload_depths(acmmp_ctx* c, int n, const float* const* depth
         off[i] = total;
         total += static_cast<size_t>(w[i]) * h[i];
     }
-    HIP_TRY(c, dreserve(c->d_dep, c->dep_cap, total));
+    HIP_TRY(c, c->d_dep.reserve(total));
     for (int i = 0; i < c->N; ++i) {
         // device sources through the copy kernel (compute queue, HBM rate), host ones through the DMA engine
         if (kind == hipMemcpyDeviceToDevice)
@@ -739,7 +687,7 @@ acmmp_status acmmp_upload_depths_device(acmmp_ctx* c, int n, const float* const*
 
 acmmp_status acmmp_export_depth(acmmp_ctx* c, float* dev_dst) {
     if (!c || !dev_dst) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "null argument");
-    if (!c->d_planes_rm) return fail(c, ACMMP_ERR_STATE, "no result yet");
+    if (c->N == 0) return fail(c, ACMMP_ERR_STATE, "no result yet");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, launch_export_depth(c->d_planes_rm, static_cast<long long>(P_of(c)), dev_dst, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -761,7 +709,7 @@ acmmp_status acmmp_set_state(acmmp_ctx* c, const float* planes, const float* cos
 
 acmmp_status acmmp_export_state(acmmp_ctx* c, float* dev_planes, float* dev_costs) {
     if (!c || (!dev_planes && !dev_costs)) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "null argument");
-    if (!c->d_planes_rm) return fail(c, ACMMP_ERR_STATE, "no result yet");
+    if (c->N == 0) return fail(c, ACMMP_ERR_STATE, "no result yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t P = P_of(c);
     if (dev_planes)
@@ -789,7 +737,7 @@ acmmp_status acmmp_set_state_device(acmmp_ctx* c, const float* dev_planes, const
 acmmp_status acmmp_set_scaled_state(acmmp_ctx* c, const float* planes, int sw, int sh) {
     if (!c || !planes || sw <= 0 || sh <= 0) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "bad scaled state");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, dreserve(c->d_scaled, c->scaled_cap, static_cast<size_t>(sw) * sh));
+    HIP_TRY(c, c->d_scaled.reserve(static_cast<size_t>(sw) * sh));
     HIP_TRY(c, hipMemcpyAsync(c->d_scaled, planes, sizeof(float4) * sw * sh, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->sw = sw;
@@ -803,8 +751,8 @@ acmmp_status acmmp_set_planar_prior(acmmp_ctx* c, const float* prior, const uint
     if (c->N == 0) return fail(c, ACMMP_ERR_STATE, "upload_views first");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t P = P_of(c);
-    HIP_TRY(c, dreserve(c->d_prior, c->prior_cap, P));
-    HIP_TRY(c, dreserve(c->d_mask, c->mask_cap, P));
+    HIP_TRY(c, c->d_prior.reserve(P));
+    HIP_TRY(c, c->d_mask.reserve(P));
     HIP_TRY(c, hipMemcpyAsync(c->d_prior, prior, sizeof(float4) * P, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_mask, masks, sizeof(uint32_t) * P, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -845,15 +793,7 @@ static acmmp_status upload_planar(acmmp_ctx* c, const PlanarTriangles& pt, float
         c->pp_pending = false;
     }
     if (!c->pp_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->pp_ev, hipEventDisableTiming));
-    if (bytes > c->h_pp_cap) {                               // (the same headroom as d_pp: hipHostFree syncs too)
-        if (c->h_pp) HIP_TRY(c, hipHostFree(c->h_pp));
-        c->h_pp = nullptr;
-        c->h_pp_cap = 0;
-        size_t n = static_cast<size_t>(16) << 20;
-        while (n < bytes) n *= 2;
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_pp), n, hipHostMallocDefault));
-        c->h_pp_cap = n;
-    }
+    HIP_TRY(c, c->h_pp.reserve_pow2(bytes, static_cast<size_t>(16) << 20));   // (the same headroom as d_pp)
     char* host = c->h_pp;
     std::memcpy(host + o_first, pt.first.data(), n_first);
     if (n_plane) std::memcpy(host + o_plane, pt.plane.data(), n_plane);
@@ -861,11 +801,9 @@ static acmmp_status upload_planar(acmmp_ctx* c, const PlanarTriangles& pt, float
     if (n_step) std::memcpy(host + o_step, pt.step.data(), n_step);
     if (n_row) std::memcpy(host + o_row, pt.row_trig.data(), n_row);
     if (n_col) std::memcpy(host + o_col, pt.col_trig.data(), n_col);
-    HIP_TRY(c, dreserve_pow2(c->d_pp, c->pp_cap, bytes, static_cast<size_t>(16) << 20));
-    HIP_TRY(c, dreserve(c->d_prior, c->prior_cap, P));
-    HIP_TRY(c, dreserve(c->d_mask, c->mask_cap, P));
-    HIP_TRY(c, hipMemcpyAsync(c->d_pp, host, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_mask, 0, sizeof(uint32_t) * P, c->stream));
+    HIP_TRY(c, c->d_pp.reserve_pow2(bytes, static_cast<size_t>(16) << 20));
+    HIP_TRY(c, c->d_prior.reserve(P));
+    HIP_TRY(c, c->d_mask.reserve(P));
     PlanarDev pd;
     pd.first = reinterpret_cast<const long long*>(c->d_pp + o_first);
     pd.plane = reinterpret_cast<const float4*>(c->d_pp + o_plane);
@@ -878,9 +816,20 @@ static acmmp_status upload_planar(acmmp_ctx* c, const PlanarTriangles& pt, float
     pd.W = W; pd.H = H; pd.model = cam.model;
     pd.K0 = cam.K[0]; pd.K2 = cam.K[2]; pd.K4 = cam.K[4]; pd.K5 = cam.K[5];
     pd.depth_min = depth_min; pd.depth_max = depth_max;
-    HIP_TRY(c, launch_planar_raster(pd, c->d_mask, c->stream));
-    HIP_TRY(c, launch_planar_mask(pd, c->d_mask, c->d_prior, c->stream));
-    HIP_TRY(c, hipEventRecord(c->pp_ev, c->stream));
+    const acmmp_status st = [&]() -> acmmp_status {
+        HIP_TRY(c, hipMemcpyAsync(c->d_pp, host, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_mask, 0, sizeof(uint32_t) * P, c->stream));
+        HIP_TRY(c, launch_planar_raster(pd, c->d_mask, c->stream));
+        HIP_TRY(c, launch_planar_mask(pd, c->d_mask, c->d_prior, c->stream));
+        HIP_TRY(c, hipEventRecord(c->pp_ev, c->stream));
+        return ACMMP_OK;
+    }();
+    if (st != ACMMP_OK) {
+        // no event stands for the copy that may be reading the staging: wait it out, so that the next call
+        // rewrites the staging only behind it
+        (void)hipStreamSynchronize(c->stream);
+        return st;
+    }
     c->pp_pending = true;
     c->planar_ms[3] = ms_since(t0);
     c->has_prior = true;
@@ -912,7 +861,7 @@ acmmp_status acmmp_set_planar_prior_from_state(acmmp_ctx* c, float depth_min, fl
     const int W = c->W, H = c->H;
     const size_t nb = static_cast<size_t>((W + 4) / 5) * ((H + 4) / 5);
     const auto t0 = planar_clock::now();
-    HIP_TRY(c, dreserve_pow2(c->d_support, c->support_cap, nb, static_cast<size_t>(1) << 17));
+    HIP_TRY(c, c->d_support.reserve_pow2(nb, static_cast<size_t>(1) << 17));
     HIP_TRY(c, launch_support_points(c->d_costs_rm, c->d_planes_rm, W, H, c->d_support, c->stream));
     std::vector<int4> blocks(nb);
     HIP_TRY(c, hipMemcpyAsync(blocks.data(), c->d_support, sizeof(int4) * nb, hipMemcpyDeviceToHost, c->stream));
@@ -1056,17 +1005,17 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     kp.cams = c->d_cams;
     if (c->dirs_R != R) {
         if (c->model == kSphere) {
-            dfree(c->d_dirs);
-            HIP_TRY(c, dalloc(c->d_sph_row, static_cast<size_t>(c->H + 2 * R)));
-            HIP_TRY(c, dalloc(c->d_sph_col, static_cast<size_t>(c->W + 2 * R)));
+            c->d_dirs.reset();
+            HIP_TRY(c, c->d_sph_row.alloc(static_cast<size_t>(c->H + 2 * R)));
+            HIP_TRY(c, c->d_sph_col.alloc(static_cast<size_t>(c->W + 2 * R)));
         } else {
-            HIP_TRY(c, dalloc(c->d_dirs, static_cast<size_t>(c->W + 2 * R) * (c->H + 2 * R)));
+            HIP_TRY(c, c->d_dirs.alloc(static_cast<size_t>(c->W + 2 * R) * (c->H + 2 * R)));
         }
         HIP_TRY(c, launch_ray_tables(kp, c->d_dirs, c->d_sph_row, c->d_sph_col, c->stream));
         c->dirs_R = R;
     }
     kp.color_den = 2.0f * p.sigma_color * p.sigma_color;
-    HIP_TRY(c, dreserve(c->d_spatial, c->spatial_cap, static_cast<size_t>(c->model == kSphere ? c->H : 1) * kp.S));
+    HIP_TRY(c, c->d_spatial.reserve(static_cast<size_t>(c->model == kSphere ? c->H : 1) * kp.S));
     HIP_TRY(c, launch_spatial_table(kp, c->d_spatial, c->stream));
     // queue of k_eval_nb's deferred interpolation fallbacks (pixel << 8 | hypothesis << 5 | view: colour
     // grids below 2^24 pixels), fast SPHERE with interpolated coordinates only: per region (blocks b with
@@ -1109,27 +1058,6 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         fix_total += fix_cap[i];
         ref_total += ref_blocks[i];
     }
-    // half-sweep scratch slab: carve the pieces of engine.h's KParams out of one allocation
-    size_t off[19];
-    {
-        const size_t VP = static_cast<size_t>(kp.V) * Pc;
-        const size_t sizes[18] = {sizeof(float) * 8 * VP, sizeof(int) * 8 * Pc,
-                                  sizeof(float4) * 5 * Pc, sizeof(float) * 5 * Pc, sizeof(float) * 5 * Pc,
-                                  sizeof(PixState) * Pc, sizeof(float) * VP, sizeof(float) * VP,
-                                  sizeof(float) * 5 * VP, sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
-                                  sizeof(unsigned) * std::max(Pc / 51 + 2, ref_total),
-                                  sizeof(float4) * Pc, sizeof(uint32_t) * kNbFixRegions * fix_total,
-                                  sizeof(unsigned) * kNbFixRegions * ns,
-                                  sizeof(unsigned) * std::max(Pc / 51 + 3, ref_total + ns),
-                                  sizeof(uint32_t) * std::max(5 * Pc + 256, ref_total * kRefSlots),
-                                  sizeof(uint32_t) * 5 * Pc, sizeof(uint8_t) * 2 * Pc};
-        off[0] = 0;
-        for (int k = 0; k < 18; ++k) off[k + 1] = (off[k] + sizes[k] + 255) & ~static_cast<size_t>(255);
-    }
-    if (c->scratch_bytes < off[18]) {
-        HIP_TRY(c, dalloc(c->d_scratch, off[18]));
-        c->scratch_bytes = off[18];
-    }
     kp.cams = c->d_cams;
     kp.tex16 = c->tex16;
     kp.fast = c->math == ACMMP_MATH_FAST;
@@ -1146,30 +1074,49 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         kp.sel_cs[k] = c->d_sel_cs[k];
         kp.rng_cs[k] = c->d_rng_cs[k];
     }
-    kp.hyp_cost = reinterpret_cast<float*>(c->d_scratch + off[0]);
-    kp.nbpos = reinterpret_cast<int*>(c->d_scratch + off[1]);
-    kp.cand = reinterpret_cast<float4*>(c->d_scratch + off[2]);
-    kp.cand_dep = reinterpret_cast<float*>(c->d_scratch + off[3]);
-    kp.cand_cost = reinterpret_cast<float*>(c->d_scratch + off[4]);
-    kp.pst = reinterpret_cast<PixState*>(c->d_scratch + off[5]);
-    kp.cvec[0] = reinterpret_cast<float*>(c->d_scratch + off[6]);
-    kp.cvec[1] = reinterpret_cast<float*>(c->d_scratch + off[7]);
-    kp.cand_vcost = reinterpret_cast<float*>(c->d_scratch + off[8]);
-    kp.surv = reinterpret_cast<uint32_t*>(c->d_scratch + off[9]);
-    kp.surv_count = reinterpret_cast<unsigned*>(c->d_scratch + off[10]);
-    kp.psum = reinterpret_cast<float4*>(c->d_scratch + off[11]);
-    kp.nbfix = fixq ? reinterpret_cast<uint32_t*>(c->d_scratch + off[12]) : nullptr;
-    kp.nbfix_count = reinterpret_cast<unsigned*>(c->d_scratch + off[13]);
-    kp.surv_pre = reinterpret_cast<unsigned*>(c->d_scratch + off[14]);
-    kp.surv_dense = reinterpret_cast<uint32_t*>(c->d_scratch + off[15]);
-    kp.cand_rough = reinterpret_cast<uint32_t*>(c->d_scratch + off[16]);
+    // half-sweep scratch slab: the pieces of engine.h's KParams carved out of one grow-only allocation, each at
+    // the next multiple of 256 bytes, in this order.  The list runs twice: without a slab it only sums the
+    // sizes, with one it hands out the pieces.
+    uint8_t* dead = nullptr;
+    auto carve = [&](char* slab) -> size_t {
+        size_t at = 0;
+        auto piece = [&](auto*& field, size_t count) {
+            using T = std::remove_reference_t<decltype(*field)>;
+            field = slab ? reinterpret_cast<T*>(slab + at) : nullptr;
+            at = (at + sizeof(T) * count + 255) & ~static_cast<size_t>(255);
+        };
+        const size_t VP = static_cast<size_t>(kp.V) * Pc;
+        const size_t surv_n = std::max(5 * Pc + 256, ref_total * kRefSlots);
+        piece(kp.hyp_cost, 8 * VP);
+        piece(kp.nbpos, 8 * Pc);
+        piece(kp.cand, 5 * Pc);
+        piece(kp.cand_dep, 5 * Pc);
+        piece(kp.cand_cost, 5 * Pc);
+        piece(kp.pst, Pc);
+        piece(kp.cvec[0], VP);
+        piece(kp.cvec[1], VP);
+        piece(kp.cand_vcost, 5 * VP);
+        piece(kp.surv, surv_n);
+        piece(kp.surv_count, std::max(Pc / 51 + 2, ref_total));
+        piece(kp.psum, Pc);
+        piece(kp.nbfix, kNbFixRegions * fix_total);              // (empty without a fallback queue)
+        piece(kp.nbfix_count, static_cast<size_t>(kNbFixRegions) * ns);
+        piece(kp.surv_pre, std::max(Pc / 51 + 3, ref_total + ns));
+        piece(kp.surv_dense, surv_n);
+        piece(kp.cand_rough, 5 * Pc);
+        piece(dead, 2 * Pc);                                     // kp.dead[0], kp.dead[1]
+        return at;
+    };
+    HIP_TRY(c, c->d_scratch.reserve(carve(nullptr)));
+    carve(c->d_scratch);
+    if (!fixq) kp.nbfix = nullptr;
     // SPHERE dead mask (engine.h), one byte per pixel and colour, written by k_init for the rows it initialises
     // (they cover the half-sweeps' rows, band runs included).  ACMMP_DEAD_SKIP=0 (read per run) keeps none: every
     // pixel then takes the long paths, with the same result (A/B, tests/test_gpu_dead_skip.py)
     {
         const char* e = std::getenv("ACMMP_DEAD_SKIP");
         const bool skip = c->model == kSphere && !(e && std::atoi(e) == 0);
-        for (int k = 0; k < 2; ++k) kp.dead[k] = skip ? reinterpret_cast<uint8_t*>(c->d_scratch + off[17]) + k * Pc : nullptr;
+        for (int k = 0; k < 2; ++k) kp.dead[k] = skip ? dead + k * Pc : nullptr;
     }
     kp.nbfix_cap = static_cast<unsigned>(fix_cap[0]);
     c->strips.assign(ns, StripSlice{});
@@ -1190,12 +1137,55 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         }
     }
     kp.ref_split = ref_split;
-    if (!c->d_work) HIP_TRY(c, dalloc(c->d_work, 258));
+    if (!c->d_work) HIP_TRY(c, c->d_work.alloc(258));
     kp.work = c->d_work;
     kp.status = reinterpret_cast<unsigned*>(c->d_work + 256);
     kp.dead_any = reinterpret_cast<unsigned*>(c->d_work + 257);  // zeroed with the counters before k_init
     kp.nb_views = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
     kp.nb_count_work = 1;
+    return ACMMP_OK;
+}
+
+// A run's prologue, whole view or band: zeroed work counters, k_init, and buffer 1 of both colours made equal to
+// buffer 0 (rows outside the reference's checkerboard grid are never rewritten).  ev[0] .. ev[1] time it.
+static acmmp_status run_begin(acmmp_ctx* c, const KParams& kp, hipStream_t s) {
+    const size_t Pc = static_cast<size_t>(kp.Pc);
+    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
+    HIP_TRY(c, hipEventRecord(c->ev[0], s));
+    HIP_TRY(c, launch_init(kp, s));
+    for (int k = 0; k < 2; ++k) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_plane_cs[k][1], c->d_plane_cs[k][0], sizeof(float4) * Pc,
+                                  hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_cost_cs[k][1], c->d_cost_cs[k][0], sizeof(float) * Pc,
+                                  hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    return ACMMP_OK;
+}
+
+// Its epilogue: the post stage (ev[2] .. ev[3]), one wait for everything, buffer 0 made the current one again
+// (cur[k]: the buffer colour k's half-sweeps left current), the three timings and the status word.  The work
+// counters are in h_work[0 .. 256) afterwards.
+static acmmp_status run_end(acmmp_ctx* c, const KParams& kp, const int cur[2], int do_post) {
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    HIP_TRY(c, launch_post(kp, do_post, s));
+    HIP_TRY(c, hipEventRecord(c->ev[3], s));
+    // the work counters and status word come back in the same wait as the kernels (a blocking copy after the
+    // synchronize cost a second host round trip, ~40 us of idle GPU per run)
+    if (!c->h_work) HIP_TRY(c, c->h_work.alloc(257));
+    HIP_TRY(c, hipMemcpyAsync(c->h_work, c->d_work, sizeof(unsigned long long) * 257, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) {
+        if (cur[k]) {
+            std::swap(c->d_plane_cs[k][0], c->d_plane_cs[k][1]);
+            std::swap(c->d_cost_cs[k][0], c->d_cost_cs[k][1]);
+        }
+    }
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&c->timing[i], c->ev[i], c->ev[i + 1]));
+    if (const unsigned long long status = c->h_work[256])
+        return fail(c, ACMMP_ERR_HIP, "run status " + std::to_string(status) + ": an interpolation fallback queue overflowed");
+    c->has_result = true;
     return ACMMP_OK;
 }
 
@@ -1212,7 +1202,6 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
     acmmp_status st = build_kparams(c, kp, seed, want_strips);
     if (st != ACMMP_OK) return st;
     if (n_half_sweeps < 0) n_half_sweeps = 2 * c->params.max_iterations;
-    const size_t Pc = static_cast<size_t>(kp.Pc);
     hipStream_t s = c->stream;
     const int NS = static_cast<int>(c->strips.size());
     const int NQ = std::max(1, std::min(std::min(want_streams, NS), kMaxStripStreams));
@@ -1229,17 +1218,6 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         }
         if (!c->fork_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, launch_init(kp, s));
-    // rows outside the reference's checkerboard grid are never rewritten: keep both buffers equal
-    int cur[2] = {0, 0};
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_plane_cs[k][1], c->d_plane_cs[k][0], sizeof(float4) * Pc,
-                                  hipMemcpyDeviceToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->d_cost_cs[k][1], c->d_cost_cs[k][0], sizeof(float) * Pc,
-                                  hipMemcpyDeviceToDevice, s));
-    }
     while (c->kev.size() < static_cast<size_t>(5 * n_half_sweeps) * NS) {
         hipEvent_t e = nullptr;
         HIP_TRY(c, hipEventCreate(&e));
@@ -1250,7 +1228,8 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
     // GPU idle ~6 us, 3 x 6 per half-sweep (0.45% of the metric's RunPatchMatch, profiles/r06_ab9_events_ab.txt)
     const char* e_kt = std::getenv("ACMMP_KERNEL_TIMING");
     const bool time_all = e_kt && std::strcmp(e_kt, "all") == 0;
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    if ((st = run_begin(c, kp, s)) != ACMMP_OK) return st;
+    int cur[2] = {0, 0};
     // Fork, the strips' chains and the join.  A failure partway leaves work queued on the extra streams that
     // nothing has joined to the context's stream yet: they are waited for before the error goes back, so that
     // whatever the caller queues next on the context's stream still follows all of this run's kernels.
@@ -1295,32 +1274,11 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         (void)hipStreamSynchronize(s);
         return st_strips;
     }
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    HIP_TRY(c, launch_post(kp, do_post, s));
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    // the work counters and status word come back in the same wait as the kernels (a blocking copy after the
-    // synchronize cost a second host round trip, ~40 us of idle GPU per run)
-    if (!c->h_work) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_work), sizeof(unsigned long long) * 257,
-                                             hipHostMallocDefault));
-    HIP_TRY(c, hipMemcpyAsync(c->h_work, c->d_work, sizeof(unsigned long long) * 257, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    // keep buffer 0 current for the next run
-    for (int k = 0; k < 2; ++k) {
-        if (cur[k]) {
-            std::swap(c->d_plane_cs[k][0], c->d_plane_cs[k][1]);
-            std::swap(c->d_cost_cs[k][0], c->d_cost_cs[k][1]);
-        }
-    }
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&c->timing[i], c->ev[i], c->ev[i + 1]));
-    {
-        const unsigned long long* w = c->h_work;
-        if (w[256]) return fail(c, ACMMP_ERR_HIP, "run status " + std::to_string(w[256]) + ": an interpolation fallback queue overflowed");
-        c->has_result = true;
-        c->work_busy = 0;
-        for (int k = 0; k < 256; ++k) c->work_busy += w[k];
-        c->work_total = 0;
-        for (int sw = 0; sw < n_half_sweeps; ++sw) c->work_total += colour_pixels(c, kp, sw & 1);
-    }
+    if ((st = run_end(c, kp, cur, do_post)) != ACMMP_OK) return st;
+    c->work_busy = 0;
+    for (int k = 0; k < 256; ++k) c->work_busy += c->h_work[k];
+    c->work_total = 0;
+    for (int sw = 0; sw < n_half_sweeps; ++sw) c->work_total += colour_pixels(c, kp, sw & 1);
     for (int k = 0; k < 4; ++k) { c->ktiming[k] = 0.f; c->klaunch[k] = k == 0 || time_all ? n_half_sweeps : 0; }
     // with several strips a bucket is the sum of the strips' event intervals, which under overlap also hold
     // other streams' kernels; the launch count stays the number of half-sweeps
@@ -1400,16 +1358,7 @@ acmmp_status acmmp_band_begin(acmmp_ctx* c, uint64_t seed, int row0, int row1) {
     kp.merge_lo = std::max(0, row0 - 10); kp.merge_hi = std::min(H, row1 + 10);
     kp.filt_lo[0] = std::min(std::max(0, row0 - 5), rows); kp.filt_hi[0] = std::min(row1 + 5, rows);
     kp.filt_lo[1] = kp.row_lo; kp.filt_hi[1] = kp.row_hi;
-    const size_t Pc = static_cast<size_t>(kp.Pc);
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
-    HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, launch_init(kp, s));
-    for (int k = 0; k < 2; ++k) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_plane_cs[k][1], c->d_plane_cs[k][0], sizeof(float4) * Pc, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->d_cost_cs[k][1], c->d_cost_cs[k][0], sizeof(float) * Pc, hipMemcpyDeviceToDevice, s));
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    if ((st = run_begin(c, kp, c->stream)) != ACMMP_OK) return st;
     c->band_lo = row0; c->band_hi = row1;
     c->band_sw = 0; c->band_nsw = 2 * c->params.max_iterations;
     c->band_cur[0] = c->band_cur[1] = 0;
@@ -1503,25 +1452,9 @@ acmmp_status acmmp_band_end(acmmp_ctx* c, int do_post) {
     if (!c) return ACMMP_ERR_INVALID_ARGUMENT;
     if (!c->band_active) return fail(c, ACMMP_ERR_STATE, "band_begin first");
     HIP_TRY(c, hipSetDevice(c->device));
-    KParams& kp = c->band_kp;
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    HIP_TRY(c, launch_post(kp, do_post, s));
-    HIP_TRY(c, hipEventRecord(c->ev[3], s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) {
-        if (c->band_cur[k]) {
-            std::swap(c->d_plane_cs[k][0], c->d_plane_cs[k][1]);
-            std::swap(c->d_cost_cs[k][0], c->d_cost_cs[k][1]);
-        }
-    }
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipEventElapsedTime(&c->timing[i], c->ev[i], c->ev[i + 1]));
+    const acmmp_status st = run_end(c, c->band_kp, c->band_cur, do_post);
     c->band_active = false;
-    unsigned long long status = 0;
-    HIP_TRY(c, hipMemcpy(&status, c->d_work + 256, sizeof status, hipMemcpyDeviceToHost));
-    if (status) return fail(c, ACMMP_ERR_HIP, "band run status " + std::to_string(status) + ": an interpolation fallback queue overflowed");
-    c->has_result = true;
-    return ACMMP_OK;
+    return st;
 }
 
 acmmp_status acmmp_download(acmmp_ctx* c, float* planes, float* costs) {
@@ -1593,17 +1526,16 @@ acmmp_status acmmp_jbu(acmmp_ctx* c, const float* ref, int W, int H, const float
     if (!c || !ref || !coarse || !out || W <= 0 || H <= 0 || sw <= 0 || sh <= 0 || imagescale < 0)
         return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "bad JBU arguments");
     HIP_TRY(c, hipSetDevice(c->device));
-    float *d_ref = nullptr, *d_coarse = nullptr, *d_out = nullptr;
+    DevBuf<float> d_ref, d_coarse, d_out;
     const size_t P = static_cast<size_t>(W) * H, p = static_cast<size_t>(sw) * sh;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_ref), sizeof(float) * P);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_coarse), sizeof(float) * p);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(float) * P);
+    hipError_t e = d_ref.alloc(P);
+    if (e == hipSuccess) e = d_coarse.alloc(p);
+    if (e == hipSuccess) e = d_out.alloc(P);
     if (e == hipSuccess) e = hipMemcpy(d_ref, ref, sizeof(float) * P, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_coarse, coarse, sizeof(float) * p, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = launch_jbu(d_ref, W, H, d_coarse, sw, sh, imagescale, d_out, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = d2h(out, d_out, sizeof(float) * P);
-    dfree(d_ref); dfree(d_coarse); dfree(d_out);
     if (e != hipSuccess) return fail(c, ACMMP_ERR_HIP, std::string("jbu: ") + hipGetErrorString(e));
     return ACMMP_OK;
 }
@@ -1621,15 +1553,15 @@ static acmmp_status debug_eval(acmmp_ctx* c, int which, int n, const int* px, co
         if (px[q] < 0 || py[q] < 0 || px[q] >= c->W || py[q] >= c->H)
             return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "query pixel outside the reference image");
     if (which == 1 && !c->has_depths) return fail(c, ACMMP_ERR_STATE, "geom cost needs upload_depths");
-    int *dx = nullptr, *dy = nullptr;
-    float4* dp = nullptr;
-    float* dout = nullptr;
+    DevBuf<int> dx, dy;
+    DevBuf<float4> dp;
+    DevBuf<float> dout;
     const int per = which == 2 ? 8 : (which == 3 ? 5 : 1);   // planes per query pixel
     const size_t nout = static_cast<size_t>(n) * per * kp.V;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dx), sizeof(int) * n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dy), sizeof(int) * n);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dp), sizeof(float4) * n * per);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), sizeof(float) * nout);
+    hipError_t e = dx.alloc(n);
+    if (e == hipSuccess) e = dy.alloc(n);
+    if (e == hipSuccess) e = dp.alloc(static_cast<size_t>(n) * per);
+    if (e == hipSuccess) e = dout.alloc(nout);
     if (e == hipSuccess) e = hipMemcpy(dx, px, sizeof(int) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dy, py, sizeof(int) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dp, planes, sizeof(float4) * n * per, hipMemcpyHostToDevice);
@@ -1639,7 +1571,6 @@ static acmmp_status debug_eval(acmmp_ctx* c, int which, int n, const int* px, co
                        : launch_debug(kp, which, n, dx, dy, dp, dout, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = d2h(out, dout, sizeof(float) * nout);
-    dfree(dx); dfree(dy); dfree(dp); dfree(dout);
     if (e != hipSuccess) return fail(c, ACMMP_ERR_HIP, std::string("debug: ") + hipGetErrorString(e));
     return ACMMP_OK;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "acmmp.h"
+#include "devbuf.h"
 #include "engine.h"
 
 static_assert(sizeof(ncclUniqueId) == ACMMP_COMM_ID_BYTES, "ncclUniqueId size");
@@ -23,8 +24,7 @@ struct acmmp_comm {
     int device = 0, nranks = 1, rank = 0;
     ncclComm_t nccl = nullptr;
     hipStream_t stream = nullptr;
-    double* d_scratch = nullptr;
-    int scratch_n = 0;
+    acmmp::DevBuf<double> d_scratch;    // allreduce staging (grow-only)
     hipEvent_t after = nullptr;         // acmmp_comm_after: engine-stream work the next collectives wait for
 };
 
@@ -71,14 +71,12 @@ acmmp_status acmmp_device_checksum(int device, const void* ptr, size_t bytes, ui
     *out = 0;
     if (!bytes) return ACMMP_OK;
     TRY_HIP(hipSetDevice(device));
-    unsigned long long* d = nullptr;
-    TRY_HIP(hipMalloc(&d, sizeof(*d)));
+    acmmp::DevBuf<unsigned long long> d;
+    TRY_HIP(d.alloc(1));
     unsigned long long h = 0;
-    hipError_t e = hipMemsetAsync(d, 0, sizeof(*d), nullptr);
-    if (e == hipSuccess) e = acmmp::launch_checksum(ptr, bytes, d, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    TRY_HIP(e);
+    TRY_HIP(hipMemsetAsync(d, 0, sizeof(h), nullptr));
+    TRY_HIP(acmmp::launch_checksum(ptr, bytes, d, nullptr));
+    TRY_HIP(hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost));
     *out = h;
     return ACMMP_OK;
 }
@@ -106,12 +104,12 @@ acmmp_status acmmp_clock_probe(int device, float warm_ms, double out[4]) {
         x ^= x << 13; x ^= x >> 17; x ^= x << 5;
         r = static_cast<float>(x >> 8) * (2.0f / 16777216.0f) - 1.0f;
     }
-    float *d_rnd = nullptr, *d_sink = nullptr;
-    acmmp::ClockStamp* d_st = nullptr;
+    acmmp::DevBuf<float> d_rnd, d_sink;
+    acmmp::DevBuf<acmmp::ClockStamp> d_st;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&d_rnd, rnd.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_sink, static_cast<size_t>(blocks) * 256 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_st, static_cast<size_t>(blocks) * sizeof(acmmp::ClockStamp));
+    hipError_t e = d_rnd.alloc(rnd.size());
+    if (e == hipSuccess) e = d_sink.alloc(static_cast<size_t>(blocks) * 256);
+    if (e == hipSuccess) e = d_st.alloc(static_cast<size_t>(blocks));
     if (e == hipSuccess) e = hipMemcpy(d_rnd, rnd.data(), rnd.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -138,9 +136,6 @@ acmmp_status acmmp_clock_probe(int device, float warm_ms, double out[4]) {
     if (e == hipSuccess) e = hipMemcpy(st.data(), d_st, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(d_rnd);
-    (void)hipFree(d_sink);
-    (void)hipFree(d_st);
     TRY_HIP(e);
     std::vector<double> ghz;
     for (const acmmp::ClockStamp& c : st)
@@ -183,7 +178,6 @@ void acmmp_comm_destroy(acmmp_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->nccl) (void)ncclCommDestroy(c->nccl);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->after) (void)hipEventDestroy(c->after);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -224,12 +218,7 @@ acmmp_status acmmp_comm_allreduce_max(acmmp_comm* c, double* vals, int n) {
     if (!c || n < 0 || (n > 0 && !vals)) return ACMMP_ERR_INVALID_ARGUMENT;
     if (n == 0) return ACMMP_OK;
     TRY_HIP(hipSetDevice(c->device));
-    if (c->scratch_n < n) {
-        if (c->d_scratch) TRY_HIP(hipFree(c->d_scratch));
-        c->d_scratch = nullptr;
-        TRY_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_scratch), sizeof(double) * n));
-        c->scratch_n = n;
-    }
+    TRY_HIP(c->d_scratch.reserve(static_cast<size_t>(n)));
     TRY_HIP(hipMemcpyAsync(c->d_scratch, vals, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     TRY_NCCL(ncclAllReduce(c->d_scratch, c->d_scratch, n, ncclFloat64, ncclMax, c->nccl, c->stream));
     TRY_HIP(hipMemcpyAsync(vals, c->d_scratch, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));

@@ -2047,6 +2047,8 @@ __global__ __launch_bounds__(256) void k_nb_fix(const KParams kp, const int colo
 // Joint view selection, aggregation, acceptance and refinement candidates (ACMMP.cu:1146-1311,
 // 797-874).  `iter` selects the view-selection threshold 0.8 exp(-iter^2 / 90) (:1163).
 // k_select: 5 waves per SIMD (96 VGPRs; r01_v24 A/B: 1 -> 5 waves -5%, 6 waves spills)
+// Its first threads also empty k_eval_ref's survivor counters: as many as that launch has blocks, the host's
+// ref_block_count(kp) -- the two expressions must stay the same.
 #ifndef ACMMP_SELECT_WAVES
 #define ACMMP_SELECT_WAVES 5
 #endif
@@ -3062,6 +3064,24 @@ hipError_t launch_spatial_table(const KParams& kp, float* spatial, hipStream_t s
 // View-chunk width: the per-view accumulators live in registers (6 per view).
 static inline int pick_vb(int V) { return V <= 1 ? 1 : (V <= 2 ? 2 : (V <= 4 ? 4 : 8)); }
 
+// Whether a launch defers interpolation fallbacks to the queue kp.nbfix: fast SPHERE with binary16 texels and
+// interpolated coordinates -- k_eval_nb at every V, the refinement's interpolated instance from V = 5 up.
+static inline bool uses_fix_queue(const KParams& kp, bool refinement) {
+    return kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.interp && (!refinement || kp.V > 4);
+}
+
+// Dynamic LDS of k_eval_ref and k_debug_ref: the separable staging up to 4 views per chunk on SPHERE.
+static inline size_t ref_lds_bytes(const KParams& kp) {
+    return (kp.model == kSphere && pick_vb(kp.V) <= 4) ? sep_lds_bytes(kp.S, kp.nside, kRefPix)
+                                                       : nb_lds_bytes(kp.model, kp.S, kp.nside, kRefPix);
+}
+
+// k_eval_ref's grid over the strip's rows: one block per kRefPix colour pixels.  k_select empties exactly this
+// many survivor counters (its first lines), and the tail's kernels take it as nref.
+static inline int ref_block_count(const KParams& kp) {
+    return cdiv(static_cast<long long>(kp.row_hi - kp.row_lo) * kp.Wh, kRefPix);
+}
+
 #define ACMMP_DISPATCH(MODEL_RT, V_RT, BODY)                                             \
     do {                                                                                \
         const int vb_ = pick_vb(V_RT);                                                  \
@@ -3172,16 +3192,16 @@ int nb_view_chunk(const KParams& kp) {
 // k_eval_nb's block shape (KParams::nb_tile): 8 x 4 tiles of the colour grid (a block's 32 pixels then span
 // 4 rows, so their patches and source footprints overlap in the CU's L1): k_eval_nb -3% at C2 (3.17 -> 3.07 ms),
 // -2.5% at C3, neutral at the metric against 32-pixel row runs (profiles/r05_ab7_ab.txt).  ACMMP_NB_TILE=0: row runs.
-int nb_tile_order(const KParams& kp) {
-    (void)kp;
+int nb_tile_order(const KParams&) {
     const char* e = std::getenv("ACMMP_NB_TILE");
     return e ? (std::atoi(e) != 0) : 1;
 }
 
+// Precondition: kp.nbfix_count[0 .. kNbFixRegions) is zero -- k_pick, the kernel launch_propagate runs right
+// before, empties it (the later view chunks' memsets are here).
 hipError_t launch_eval_nb(const KParams& kp0, int colour, hipStream_t s) {
     KParams kp = kp0;
-    // interpolation fallbacks deferred to k_nb_fix: fast SPHERE with interpolated coordinates only
-    const bool fix = kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.interp;
+    const bool fix = uses_fix_queue(kp, false);             // interpolation fallbacks deferred to k_nb_fix
     if (!fix) kp.nbfix = nullptr;
     const int chunk = kp.nb_chunk;                          // nb_view_chunk, fixed when the run's KParams were built
     for (int v0 = 0; v0 < kp.V; v0 += chunk) {
@@ -3233,7 +3253,7 @@ hipError_t launch_debug_nb(const KParams& kp0, int n, const int* px, const int* 
                            hipStream_t s) {
     // the hook takes k_eval_nb's path, deferred fallbacks included
     KParams kp = kp0;
-    const bool fix = kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.interp && n < (1 << 24);
+    const bool fix = uses_fix_queue(kp, false) && n < (1 << 24);
     if (!fix) kp.nbfix = nullptr;                           // (ncc_chunk then projects every sample)
     // the queue holds every entry: a region's blocks x 256 lanes x all V views (one launch here)
     if (fix && static_cast<long long>(cdiv(cdiv(n, kNbPix), kNbFixRegions)) * 256 * kp.V > kp.nbfix_cap)
@@ -3254,10 +3274,8 @@ hipError_t launch_debug_nb(const KParams& kp0, int n, const int* px, const int* 
 }
 
 hipError_t launch_eval_nb_views(const KParams& kp, int colour, hipStream_t s) {
-    const long long npix = static_cast<long long>(kp.row_hi - kp.row_lo) * kp.Wh;
     const size_t lds_nb = nb_lds_bytes(kp.model, kp.S, kp.nside);
     const dim3 grd = static_cast<unsigned>(nb_block_count(kp.row_hi - kp.row_lo, kp.Wh, kp.nb_tile));
-    (void)npix;
     if (kp.fast) {
         if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
         else ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 0, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
@@ -3299,20 +3317,20 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
 #endif  // ACMMP_IN_TU(3)
 
 #if ACMMP_IN_TU(4)
+// Precondition: kp.surv_count[0 .. ref_block_count(kp)) is zero -- k_select, the kernel launch_propagate runs
+// right before, empties it.
 hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
     // the interpolated refinement leaves its rough views to k_eval_ref_tail: none without a split
     KParams kp = kp0;
     if (kp.ref_split <= 0) kp.interp = 0;
-    const long long npix = static_cast<long long>(kp.row_hi - kp.row_lo) * kp.Wh;
-    const size_t lds_ref = (kp.model == kSphere && pick_vb(kp.V) <= 4) ? sep_lds_bytes(kp.S, kp.nside, kRefPix)
-                                                                       : nb_lds_bytes(kp.model, kp.S, kp.nside, kRefPix);
+    const size_t lds_ref = ref_lds_bytes(kp);
     hipError_t e = hipSuccess;
-    const dim3 grd_ref = static_cast<unsigned>(cdiv(npix, kRefPix));
-    // (surv_count[0 .. grd_ref.x) is emptied by k_select, which runs right before)
+    const int nref = ref_block_count(kp);
+    const dim3 grd_ref = static_cast<unsigned>(nref);
     // the interpolated instance (fast SPHERE, V > 4) queues its survivors' fallback views on k_eval_nb's queue
     // (drained by then): a region's k_eval_ref blocks x 255 candidates x S views fit its room (Pc S / 51 against
     // k_eval_nb's Pc x chunk / 32, S <= chunk)
-    const bool ref_fix = kp.interp && kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.V > 4;
+    const bool ref_fix = uses_fix_queue(kp, true);
     if (ref_fix && (e = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e;
     if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref<M, VBC, true, TF><<<grd_ref, 256, lds_ref, s>>>(kp, colour))));
     else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref<M, VBC, false, TF><<<grd_ref, 256, lds_ref, s>>>(kp, colour))));
@@ -3326,7 +3344,6 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
 #ifndef ACMMP_TAIL_NK
 #define ACMMP_TAIL_NK 2048
 #endif
-        const int nref = static_cast<int>(grd_ref.x);
         k_tail_scan<<<1, 1024, 0, s>>>(kp, nref);
         k_tail_compact<<<static_cast<unsigned>(nref), 256, 0, s>>>(kp);
         const unsigned grd = 8u * static_cast<unsigned>(std::min<long long>(ACMMP_TAIL_NK, std::max<long long>(1, cdiv(static_cast<long long>(nref) * kRefSlots, 8 * 256))));
@@ -3393,12 +3410,11 @@ hipError_t launch_debug_ref(const KParams& kp0, int n, const int* px, const int*
                             hipStream_t s) {
     KParams kp = kp0;
     if (kp.ref_split <= 0) kp.interp = 0;                   // launch_eval_ref's rule
-    const size_t lds_ref = (kp.model == kSphere && pick_vb(kp.V) <= 4) ? sep_lds_bytes(kp.S, kp.nside, kRefPix)
-                                                                       : nb_lds_bytes(kp.model, kp.S, kp.nside, kRefPix);
+    const size_t lds_ref = ref_lds_bytes(kp);
     const dim3 grd = static_cast<unsigned>(cdiv(n, kRefPix));
     // the interpolated instance's fallbacks on the context's queue: room for every entry (a region's blocks x
     // 255 candidates x V views), else the hook refuses
-    const bool fix = kp.interp && kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.V > 4 && n < (1 << 24);
+    const bool fix = uses_fix_queue(kp, true) && n < (1 << 24);
     if (!fix) kp.nbfix = nullptr;
     if (fix && static_cast<long long>(cdiv(grd.x, kNbFixRegions)) * kRefSlots * kp.V > kp.nbfix_cap) return hipErrorInvalidValue;
     hipError_t e0 = hipSuccess;

@@ -283,7 +283,9 @@ acmmp_status acmmp_memcpy(int device, void *dst, const void *src, size_t bytes, 
 /* 64-bit checksum of `bytes` (a multiple of 4) of device memory on `device`: the sum mod 2^64 over its
  * 32-bit words w_i of splitmix64's finaliser applied to (i << 32) | w_i (position and value both enter).
  * The pipeline's depth exchange compares every rank's checksum of each broadcast map
- * (acmmp/pipeline.py RcclExchange); acmmp.capi.checksum_host is the same function on host arrays. */
+ * (acmmp/pipeline.py RcclExchange); acmmp.capi.checksum_host is the same function on host arrays.
+ * The caller must have completed every write to the buffer (acmmp_synchronize, or its own stream's
+ * synchronize): the sum runs on the null stream, which the engine's non-blocking streams do not wait for. */
 acmmp_status acmmp_device_checksum(int device, const void *ptr, size_t bytes, uint64_t *out);
 
 /* Diagnostics for the performance record (bench.py `device`, `clock`); no reference counterpart.
