@@ -7,6 +7,7 @@ library is missing or no GPU is visible, every call fails loudly.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import mmap
 import os
 import threading
@@ -120,6 +121,8 @@ EXPORTS = [
     "acmmp_fusion_voxel_mesh", "acmmp_fusion_mesh_vertices", "acmmp_fusion_mesh_faces", "acmmp_fusion_mesh_samples",
     "acmmp_fusion_mesh_table", "acmmp_fusion_set_mesh", "acmmp_fusion_mesh_render", "acmmp_fusion_render_maps",
     "acmmp_fusion_render_plan",
+    "acmmp_fusion_set_reference_cloud", "acmmp_fusion_cloud_distance", "acmmp_fusion_distance_results",
+    "acmmp_fusion_distance_grid",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -246,6 +249,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_mesh_render.argtypes = [vp, i32, vp, C.c_float, vp, vp]
     L.acmmp_fusion_render_maps.argtypes = [vp, vp, vp, vp, vp]
     L.acmmp_fusion_render_plan.argtypes = [vp, i32, vp, vp, vp]
+    L.acmmp_fusion_set_reference_cloud.argtypes = [vp, C.c_int64, vp]
+    L.acmmp_fusion_cloud_distance.argtypes = [vp, i32, i32, C.c_float, i32, vp, vp]
+    L.acmmp_fusion_distance_results.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    L.acmmp_fusion_distance_grid.argtypes = [vp, C.c_float, vp, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -879,6 +886,35 @@ FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
 VIS_SOURCES = {"voxel": 0, "clean": 1}     # ACMMP_VIS_FROM_VOXELS, ACMMP_VIS_FROM_CLEAN
 MESH_SOURCES = {"voxel": 0, "clean": 1, "visible": 2}     # ACMMP_MESH_FROM_VOXELS, _CLEAN, _VISIBLE
 RENDER_COUNTS = ("agree", "mesh_in_front", "mesh_behind", "mesh_only", "raw_only", "neither", "back_facing")
+DIST_SOURCES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "mesh": 4}     # ACMMP_DIST_FROM_*
+DIST_DIRECTIONS = {"data_to_ref": 0, "ref_to_data": 1}     # ACMMP_DIST_DATA_TO_REF (accuracy), _REF_TO_DATA (completeness)
+DIST_SUMMARY_WORDS = 268     # ACMMP_DIST_SUMMARY_WORDS: n_query, n_valid, n_matched, sum_q, within[8], hist[256]
+
+
+@dataclasses.dataclass
+class CloudDistance:
+    """Summary of one Fusion.cloud_distance call (step 5 of acmmp_fusion_cloud_distance, include/acmmp.h)."""
+    n_query: int
+    n_valid: int
+    n_matched: int
+    sum_q: int
+    max_dist: float
+    within: list           # per threshold: the matched queries no further than it
+    hist: np.ndarray       # (256,) int64: the matched queries by distance, bins of max_dist / 256
+
+    @property
+    def mean(self) -> float:
+        """Mean distance of the matched queries (0 with none)."""
+        k = 1048576.0 / float(np.float32(self.max_dist))
+        return self.sum_q / (self.n_matched * k) if self.n_matched else 0.0
+
+    @property
+    def median_upper(self) -> float:
+        """Upper edge of the histogram bin that holds the median matched distance (0 with none)."""
+        if not self.n_matched:
+            return 0.0
+        b = int(np.searchsorted(np.cumsum(self.hist), (self.n_matched + 1) // 2))
+        return (b + 1) * float(np.float32(self.max_dist)) / 256.0
 
 
 class Fusion:
@@ -1176,6 +1212,53 @@ class Fusion:
         self._check(self.L.acmmp_fusion_render_plan(self.h, int(small_max), _p(st[0:1]), _p(st[1:2]), _p(st[2:3])),
                     "fusion_render_plan")
         return {"small": int(st[0]), "large": int(st[1]), "candidates": int(st[2])}
+
+    def set_reference_cloud(self, xyz):
+        """Makes a host cloud, (n, 3) float32 taken bit for bit, the reference cloud of cloud_distance: ground truth, or
+        another run's cloud.  It stays until the next set_reference_cloud.  Returns n."""
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self._check(self.L.acmmp_fusion_set_reference_cloud(self.h, p.shape[0], _p(p) if p.size else None),
+                    "fusion_set_reference_cloud")
+        return p.shape[0]
+
+    def cloud_distance(self, source: str = "scene", direction: str = "data_to_ref", max_dist: float = 1.0,
+                       thresholds=()) -> CloudDistance:
+        """Nearest-neighbour distances between the resident cloud `source` ("scene", "voxels", "clean", "visible",
+        "mesh") and the reference cloud, capped at max_dist: "data_to_ref" measures every point of the data cloud
+        against the reference (accuracy), "ref_to_data" the reverse (completeness).  Exhaustive by definition, bit for
+        bit (acmmp_fusion_cloud_distance, include/acmmp.h); at most 8 thresholds, each in [0, max_dist].  The per-query
+        results stay on the GPU (distance_results) until the source or the reference cloud goes."""
+        if source not in DIST_SOURCES:
+            raise ValueError('source must be one of ' + ", ".join(DIST_SOURCES))
+        if direction not in DIST_DIRECTIONS:
+            raise ValueError('direction must be "data_to_ref" or "ref_to_data"')
+        tau = np.ascontiguousarray(thresholds, np.float32).reshape(-1)
+        out = np.zeros(DIST_SUMMARY_WORDS, np.int64)
+        self._check(self.L.acmmp_fusion_cloud_distance(self.h, DIST_SOURCES[source], DIST_DIRECTIONS[direction],
+                                                       float(max_dist), tau.size, _p(tau) if tau.size else None, _p(out)),
+                    "fusion_cloud_distance")
+        self._dist_queries = int(out[0])
+        return CloudDistance(n_query=int(out[0]), n_valid=int(out[1]), n_matched=int(out[2]), sum_q=int(out[3]),
+                             max_dist=float(np.float32(max_dist)), within=[int(x) for x in out[4:4 + tau.size]],
+                             hist=out[12:268].copy())
+
+    def distance_results(self, first: int = 0, n: int | None = None, squared: bool = False):
+        """(dist (n,) float32, nearest (n,) int32) of queries [first, first + n) of the last cloud_distance (n None: to
+        the end): dist = sqrt(d2), inf for a query that is unmatched or invalid, nearest = the target's index, -1 then.
+        squared: d2 itself, the quantity the result is defined in."""
+        if n is None:
+            n = getattr(self, "_dist_queries", 0) - first
+        d2, nn = np.empty(max(n, 0), np.float32), np.empty(max(n, 0), np.int32)      # (a negative n is refused below)
+        self._check(self.L.acmmp_fusion_distance_results(self.h, first, n, _p(d2), _p(nn)), "fusion_distance_results")
+        return (d2 if squared else np.sqrt(d2)), nn
+
+    def distance_grid(self, force_cell: float = 0.0):
+        """Test hook: sets the cell of the search grid of the next cloud_distance calls (0 = automatic) and returns the
+        last successful call's {"cell", "cells", "max_list", "rings"}."""
+        cell, st = np.zeros(1, np.float32), np.zeros(3, np.int64)
+        self._check(self.L.acmmp_fusion_distance_grid(self.h, float(force_cell), _p(cell), _p(st[0:1]), _p(st[1:2]),
+                                                      _p(st[2:3])), "fusion_distance_grid")
+        return {"cell": float(cell[0]), "cells": int(st[0]), "max_list": int(st[1]), "rings": int(st[2])}
 
     def close(self):
         if self.h:

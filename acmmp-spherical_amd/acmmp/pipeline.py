@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import contextlib
 import copy
+import json
 import math
 import os
 import threading
@@ -794,7 +795,8 @@ class Pipeline:
                    voxel_min_component_points: int = 1, visibility_tol: float | None = None,
                    visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0,
                    mesh_trunc: float | None = None, mesh_min_weight: int = 1, mesh_path: str | None = None,
-                   render_mesh: bool = False, render_tol: float = 0.01):
+                   render_mesh: bool = False, render_tol: float = 0.01, eval_cloud=None,
+                   eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -841,8 +843,23 @@ class Pipeline:
         written as depths_mesh.dmb and normals_mesh.dmb beside the view's depths.dmb: depth maps that are complete and
         consistent with the surface.  self.fusion_info gains render_tol and render_views, per view the image id, the
         faces skipped and the pixels by how the rendered depth agrees with the view's own depth map within render_tol
-        (relative).  Everything else is what it is without the option."""
+        (relative).  Everything else is what it is without the option.
+
+        eval_cloud (a PLY of write_ply's layout, or an (n, 3) array; eval_max_dist is then required): after the chain,
+        the cloud eval_source ("scene", "voxels", "clean", "visible", "mesh"; default: the cloud that is written) is
+        measured on the device against that reference cloud, in both directions (acmmp_fusion_cloud_distance,
+        include/acmmp.h): accuracy, every point of the run to its nearest reference point, and completeness, the
+        reverse, each capped at eval_max_dist, with precision, recall and F-score at every one of eval_thresholds (at
+        most 8, each within eval_max_dist).  self.eval_info holds the figures (evaluate_clouds), and eval.json beside
+        the cloud PLY when one is written.  Without eval_cloud nothing is measured and nothing is written."""
         self.fusion_info = None
+        self.eval_info = None
+        if eval_cloud is None and (eval_max_dist is not None or len(tuple(eval_thresholds)) or eval_source is not None):
+            raise ValueError("the evaluation options need eval_cloud")
+        if eval_cloud is not None and eval_max_dist is None:
+            raise ValueError("the evaluation needs eval_max_dist")
+        if eval_source is not None and eval_source not in capi.DIST_SOURCES:
+            raise ValueError("eval_source must be one of " + ", ".join(capi.DIST_SOURCES))
         if render_mesh and mesh_trunc is None:
             raise ValueError("rendering the mesh needs the mesh (mesh_trunc)")
         if (mesh_trunc is not None or mesh_path is not None) and voxel_size is None:
@@ -958,7 +975,19 @@ class Pipeline:
                             io.write_dmb(os.path.join(d, "depths_mesh.dmb"), rdepth)
                             io.write_dmb(os.path.join(d, "normals_mesh.dmb"), rnormal)
                     self.fusion_info.update(render_tol=float(render_tol), render_views=per_view)
+            if eval_cloud is not None:
+                if not hasattr(fu, "cloud_distance"):
+                    raise ValueError("the evaluation needs a fusion object with cloud_distance (capi.Fusion)")
+                written = ("scene" if voxel_size is None else "visible" if visibility_tol is not None
+                           else "clean" if clean else "voxels")
+                fu.set_reference_cloud(reference_xyz(eval_cloud))
+                self.eval_info = evaluate_clouds(fu, eval_source or written, eval_max_dist, eval_thresholds)
+                if path:
+                    with open(os.path.join(os.path.dirname(os.path.abspath(path)), "eval.json"), "w") as f:
+                        json.dump(self.eval_info, f, indent=1)
         else:
+            if eval_cloud is not None:
+                raise ValueError("the evaluation needs a fusion object with run_scene and cloud_distance (capi.Fusion)")
             if unique:
                 raise ValueError("unique fusion needs a fusion object with run_scene (capi.Fusion)")
             pts = [fu.run(k, srcs) for k, srcs in enumerate(src_lists)]
@@ -989,6 +1018,40 @@ class Pipeline:
             os.makedirs(d, exist_ok=True)
             io.write_dmb(os.path.join(d, "depths.dmb"), out)
         return out
+
+
+def reference_xyz(cloud) -> np.ndarray:
+    """(n, 3) float32 positions of a reference cloud: a PLY of io.write_ply's layout, or an array whose rows start
+    with x, y, z."""
+    if isinstance(cloud, (str, os.PathLike)):
+        rec = io.read_ply(os.fspath(cloud))
+        return np.ascontiguousarray(np.stack([rec["x"], rec["y"], rec["z"]], 1), np.float32)
+    a = np.asarray(cloud, np.float32)
+    return np.ascontiguousarray(a.reshape(-1, a.shape[-1] if a.ndim > 1 else 3)[:, :3])
+
+
+def evaluate_clouds(fu, source: str, max_dist: float, thresholds=()) -> dict:
+    """The resident cloud `source` of the fusion object against its reference cloud, both directions of
+    cloud_distance: {"source", "max_dist", "accuracy": {...}, "completeness": {...}, "thresholds": [...]}.  Each
+    direction holds n_query, n_valid, n_matched, mean (of the matched distances), median_upper (the upper edge of the
+    median's histogram bin, max_dist / 256 wide) and within (the matched queries no further than each threshold); each
+    threshold holds precision = within_accuracy / n_valid_accuracy, recall = within_completeness /
+    n_valid_completeness and f_score = 2PR / (P + R), 0 when both are 0."""
+    taus = [float(np.float32(t)) for t in thresholds]
+    out = {"source": source, "max_dist": float(np.float32(max_dist))}
+    runs = {}
+    for name, direction in (("accuracy", "data_to_ref"), ("completeness", "ref_to_data")):
+        r = runs[name] = fu.cloud_distance(source, direction, max_dist, taus)
+        out[name] = {"n_query": r.n_query, "n_valid": r.n_valid, "n_matched": r.n_matched, "mean": r.mean,
+                     "median_upper": r.median_upper, "within": list(r.within)}
+    rows = []
+    for i, t in enumerate(taus):
+        a, c = runs["accuracy"], runs["completeness"]
+        p = a.within[i] / a.n_valid if a.n_valid else 0.0
+        r = c.within[i] / c.n_valid if c.n_valid else 0.0
+        rows.append({"threshold": t, "precision": p, "recall": r, "f_score": 2 * p * r / (p + r) if p + r > 0 else 0.0})
+    out["thresholds"] = rows
+    return out
 
 
 def launcher_store():
@@ -1090,6 +1153,16 @@ def arg_parser():
                          "beside the view's depths.dmb")
     ap.add_argument("--render-tol", type=float, default=0.01,
                     help="with --render-mesh: a rendered depth agrees with the view's own within this relative tolerance")
+    ap.add_argument("--eval-cloud", metavar="PLY", default=None,
+                    help="measure the run's cloud against this reference cloud on the GPU (accuracy, completeness, "
+                         "F-score) and write eval.json beside the cloud PLY")
+    ap.add_argument("--eval-max-dist", type=float, default=None,
+                    help="with --eval-cloud: distances are capped here; a point with nothing nearer is unmatched")
+    ap.add_argument("--eval-threshold", type=float, action="append", default=[],
+                    help="with --eval-cloud: a distance at which precision, recall and F-score are given (repeatable, "
+                         "at most 8, each within --eval-max-dist)")
+    ap.add_argument("--eval-source", choices=["scene", "voxels", "clean", "visible", "mesh"], default=None,
+                    help="with --eval-cloud: the cloud that is measured (default: the one that is written)")
     return ap
 
 
@@ -1123,13 +1196,16 @@ def main(argv=None):
                               mesh_trunc=(a.mesh_trunc if a.mesh_trunc is not None or a.mesh is None or a.voxel_size is None
                                           else 3.0 * a.voxel_size),
                               mesh_min_weight=a.mesh_min_weight, mesh_path=a.mesh, render_mesh=a.render_mesh,
-                              render_tol=a.render_tol)
+                              render_tol=a.render_tol, eval_cloud=a.eval_cloud, eval_max_dist=a.eval_max_dist,
+                              eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),
             "passes": [p.name for p in pipe.passes], "fused_points": n_points, "seconds": round(dt, 3)}
     if getattr(pipe, "fusion_info", None):
         line["fusion_info"] = pipe.fusion_info
+    if getattr(pipe, "eval_info", None):
+        line["eval"] = pipe.eval_info
     print(json.dumps(line), flush=True)
     exchange.close()
     return 0

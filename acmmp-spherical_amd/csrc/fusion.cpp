@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -135,6 +136,20 @@ struct acmmp_fusion {
     long long r_small_max = 0;                   // test hook: the small / large threshold, 0 = kRenderSmallMax
     long long r_plan[3] = {0, 0, 0};             // small faces, large faces, candidates of the last successful render
     DevBuf<unsigned long long> r_words;          // kRenderWords device words
+    // nearest-neighbour distances (acmmp_fusion_cloud_distance): the reference cloud ...
+    DevBuf<float> ref_pts;                       // 3 floats per point
+    unsigned long long ref_n = 0;
+    bool ref_have = false;                       // a set_reference_cloud has succeeded
+    // ... and the resident result
+    DevBuf<float> dist_d2;                       // per query
+    DevBuf<int32_t> dist_nn;                     // per query, -1 = none
+    unsigned long long dist_n = 0;               // queries
+    int dist_source = 0;                         // ACMMP_DIST_FROM_*
+    bool dist_have = false;                      // a distance call has succeeded on this source and reference cloud
+    float dist_force_cell = 0.0f;                // test hook: the cell of the next calls, 0 = automatic
+    float dist_cell = 0.0f;                      // the cell of the last successful call ...
+    long long dist_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
+    DevBuf<unsigned long long> dist_words;       // kDistWords device words
     std::string err;
 };
 
@@ -300,6 +315,17 @@ void voxel_scratch_release(acmmp_fusion* f) {
 // m_source of a mesh that acmmp_fusion_set_mesh installed: no result is its source.
 constexpr int kMeshNoSource = -1;
 
+void distance_release(acmmp_fusion* f) {
+    f->dist_d2.reset(); f->dist_nn.reset();
+    f->dist_n = 0;
+    f->dist_have = false;
+}
+
+// The data cloud `source` (ACMMP_DIST_FROM_*) has been replaced or discarded: a distance result measured on it goes.
+void distance_source_gone(acmmp_fusion* f, int source) {
+    if (f->dist_have && f->dist_source == source) distance_release(f);
+}
+
 void render_release(acmmp_fusion* f) {
     f->r_depth.reset(); f->r_normal.reset(); f->r_colour.reset(); f->r_face.reset();
     f->r_W = f->r_H = 0;
@@ -312,6 +338,7 @@ void mesh_release(acmmp_fusion* f) {
     f->m_verts.reset(); f->m_faces.reset(); f->m_skey.reset(); f->m_tsdf.reset(); f->m_sent.reset();
     f->m_nv = f->m_nf = f->m_ns = 0;
     f->m_have = false;
+    distance_source_gone(f, ACMMP_DIST_FROM_MESH);
 }
 
 // The clean result and the visible result go with a mesh result built from them.
@@ -321,6 +348,7 @@ void clean_release(acmmp_fusion* f) {
     f->c_total = f->c_comps = 0;
     f->c_have = false;
     if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
+    distance_source_gone(f, ACMMP_DIST_FROM_CLEAN);
 }
 
 void visibility_release(acmmp_fusion* f) {
@@ -328,6 +356,7 @@ void visibility_release(acmmp_fusion* f) {
     f->vis_total = f->vis_entries = 0;
     f->vis_have = false;
     if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);
+    distance_source_gone(f, ACMMP_DIST_FROM_VISIBLE);
 }
 
 // A new scene result is in place: the voxel result, the clean result and the visible result described the previous
@@ -339,6 +368,8 @@ void scene_replaced(acmmp_fusion* f) {
     clean_release(f);
     visibility_release(f);
     if (f->m_source != kMeshNoSource) mesh_release(f);
+    distance_source_gone(f, ACMMP_DIST_FROM_SCENE);
+    distance_source_gone(f, ACMMP_DIST_FROM_VOXELS);
     voxel_scratch_release(f);
 }
 
@@ -742,6 +773,7 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     clean_release(f);                                 // it described the previous voxel result
     visibility_release(f);                            // and so did this one, from either source
     if (f->m_source != kMeshNoSource) mesh_release(f);   // and this one, from any source
+    distance_source_gone(f, ACMMP_DIST_FROM_VOXELS);  // and a distance result measured on it
     f->v_grid = g;
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
@@ -911,6 +943,7 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
     f->c_have = true;
     if (f->vis_have && f->vis_source == ACMMP_VIS_FROM_CLEAN) visibility_release(f);   // its source is replaced
     if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
+    distance_source_gone(f, ACMMP_DIST_FROM_CLEAN);
     if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
     if (n_components) *n_components = static_cast<int64_t>(out.comps);
     if (n_components_kept) *n_components_kept = static_cast<int64_t>(out.comps_kept);
@@ -1068,6 +1101,7 @@ acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_li
     f->vis_tal = std::move(out.tal);
     f->vis_vox = std::move(out.vox);
     if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);          // its source is replaced
+    distance_source_gone(f, ACMMP_DIST_FROM_VISIBLE);
     f->vis_total = out.kept;
     f->vis_entries = N;
     f->vis_source = source;
@@ -1273,6 +1307,7 @@ acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, co
         out.stats[0] = static_cast<long long>(slots);
     }
     render_release(f);                                // it showed the previous mesh result
+    distance_source_gone(f, ACMMP_DIST_FROM_MESH);    // and this one was measured on it
     f->m_verts = std::move(out.verts);
     f->m_faces = std::move(out.faces);
     f->m_skey = std::move(out.skey);
@@ -1469,6 +1504,211 @@ acmmp_status acmmp_fusion_render_plan(acmmp_fusion* f, int small_max, int64_t* n
     if (n_small) *n_small = f->r_plan[0];
     if (n_large) *n_large = f->r_plan[1];
     if (n_candidates) *n_candidates = f->r_plan[2];
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- nearest-neighbour distances between two clouds (include/acmmp.h; kernels: k_dist_*) ---------------------
+
+namespace {
+
+// The new result of a distance call and its scratch, swapped in only when the whole call succeeded.
+struct DistOut {
+    DevBuf<float> d2;
+    DevBuf<int32_t> nn;
+    DevBuf<unsigned long long> keys, ckeys;                // scratch: the cell table and the coarse table
+    DevBuf<uint32_t> start, cnt;
+    DevBuf<float4> list;                                   // scratch: the cells' lists
+    double cell = 0.0;
+    unsigned long long words[kDistWords] = {0};
+};
+
+// A grid of `cell` over the box [lo, hi]: the arithmetic of dist_axis (fusion_kernels.hip), on the host.
+DistGrid dist_grid(const double lo[3], const double hi[3], double cell) {
+    DistGrid g;
+    g.cell = cell;
+    g.inv = 1.0 / cell;
+    for (int a = 0; a < 3; ++a) {
+        g.o[a] = lo[a];
+        g.cmax[a] = static_cast<int>(std::floor((hi[a] - lo[a]) * g.inv));
+    }
+    return g;
+}
+
+acmmp_status distance_run(acmmp_fusion* f, DistCloud q, DistCloud t, float max_dist, int n_tau, const float* tau,
+                          DistOut& out) {
+    hipStream_t s = f->stream;
+    if (!f->dist_words) F_HIP(f, alloc(f->dist_words, kDistWords));
+    unsigned long long* w = f->dist_words;
+    F_HIP(f, alloc(out.d2, static_cast<size_t>(q.n)));
+    F_HIP(f, alloc(out.nn, static_cast<size_t>(q.n)));
+    F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kDistWords, s));
+    F_HIP(f, hipMemsetAsync(w + kDistMin, 0xff, sizeof(unsigned long long) * 3, s));
+    DistQuery p;
+    p.m2 = max_dist * max_dist;
+    p.k = 1048576.0 / static_cast<double>(max_dist);
+    p.n_tau = n_tau;
+    for (int i = 0; i < 8; ++i) p.tau2[i] = i < n_tau ? tau[i] * tau[i] : 0.0f;
+    for (int a = 0; a < 3; ++a) p.lo[a] = p.hi[a] = 0.0;
+    p.have_targets = 0;
+    DistGrid g = {{0.0, 0.0, 0.0}, 1.0, 1.0, {0, 0, 0}}, cg = g;
+    DistTable fine = {nullptr, nullptr, nullptr, 0, 0}, coarse = fine;
+    unsigned long long valid_targets = 0;
+    if (t.n > 0) {
+        // the first host wait: the valid targets' bounding box and number, from which the cell is chosen
+        unsigned long long h[kDistSummary] = {0};
+        F_HIP(f, launch_dist_bounds(t, w, s));
+        F_HIP(f, hipMemcpyAsync(h, w, sizeof(h), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        valid_targets = h[kDistValidTargets];
+        if (valid_targets > t.n) return ffail(f, ACMMP_ERR_HIP, "cloud distance: more valid targets than targets");
+        if (valid_targets > 0) {
+            uint32_t mn[6];
+            std::memcpy(mn, h + kDistMin, sizeof(mn));
+            double ext = 0.0;
+            for (int a = 0; a < 3; ++a) {
+                p.lo[a] = static_cast<double>(vox_decode_ordered(mn[a]));
+                p.hi[a] = -static_cast<double>(vox_decode_ordered(mn[3 + a]));
+                ext = std::max(ext, p.hi[a] - p.lo[a]);
+            }
+            // a handful of targets per occupied cell for a cloud that fills its box, some tens for a surface, and no
+            // wider than max_dist, so that a few outliers that stretch the box do not put the cloud into one cell;
+            // never more than 2^20 cells on an axis, so that every target has a cell
+            double cell = f->dist_force_cell != 0.0f
+                              ? static_cast<double>(f->dist_force_cell)
+                              : std::min(ext / std::cbrt(static_cast<double>(valid_targets)), static_cast<double>(max_dist));
+            cell = std::max(cell, ext / 1048576.0);
+            if (!(cell > 0.0)) cell = 1.0;
+            g = dist_grid(p.lo, p.hi, cell);
+            out.cell = cell;
+            unsigned long long slots = 1024;
+            while (slots < 2 * t.n) slots <<= 1;
+            int log2_slots = 0;
+            while ((1ull << log2_slots) < slots) ++log2_slots;
+            F_HIP(f, alloc(out.keys, slots));
+            F_HIP(f, alloc(out.start, slots));
+            F_HIP(f, alloc(out.cnt, slots));
+            F_HIP(f, alloc(out.list, static_cast<size_t>(t.n)));
+            fine = DistTable{out.keys, out.start, out.cnt, slots, log2_slots};
+            F_HIP(f, hipMemsetAsync(out.keys, 0xff, sizeof(unsigned long long) * slots, s));
+            F_HIP(f, hipMemsetAsync(out.cnt, 0, sizeof(uint32_t) * slots, s));
+            // the coarse level, cells a little wider than max_dist; not where max_dist^2 is near the underflow range
+            const double md = static_cast<double>(max_dist);
+            if (md * md >= 0x1p-120) {
+                cg = dist_grid(p.lo, p.hi, std::max(md * (1.0 + 0x1p-10), ext / 1048576.0));
+                F_HIP(f, alloc(out.ckeys, slots));
+                F_HIP(f, hipMemsetAsync(out.ckeys, 0xff, sizeof(unsigned long long) * slots, s));
+                coarse = DistTable{out.ckeys, nullptr, nullptr, slots, log2_slots};
+            }
+            F_HIP(f, launch_dist_insert(t, g, fine, cg, coarse, w, s));
+            F_HIP(f, launch_dist_lists(t, g, fine, out.list, w, s));
+            p.have_targets = 1;
+        }
+    }
+    F_HIP(f, launch_dist_query(q, g, fine, cg, coarse, out.list, p, out.d2, out.nn, w, s));
+    // the second host wait: the end
+    F_HIP(f, hipMemcpyAsync(out.words, w, sizeof(out.words), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (out.words[kDistErr] || out.words[kDistCursor] != valid_targets)
+        return ffail(f, ACMMP_ERR_HIP, "cloud distance: the cell table failed (flags " + std::to_string(out.words[kDistErr]) +
+                                           ", listed " + std::to_string(out.words[kDistCursor]) + " of " +
+                                           std::to_string(valid_targets) + " targets)");
+    out.words[kDistSummary + ACMMP_DIST_SUMMARY_N_QUERY] = q.n;
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_set_reference_cloud(acmmp_fusion* f, int64_t n, const float* xyz) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && !xyz)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    F_HIP(f, hipSetDevice(f->device));
+    // built beside the present reference cloud, installed when the copy has succeeded
+    DevBuf<float> pts;
+    const size_t m = static_cast<size_t>(n);
+    F_HIP(f, alloc(pts, 3 * m));
+    if (m > 0) F_HIP(f, hipMemcpy(pts, xyz, sizeof(float) * 3 * m, hipMemcpyHostToDevice));
+    f->ref_pts = std::move(pts);
+    f->ref_n = static_cast<unsigned long long>(n);
+    f->ref_have = true;
+    distance_release(f);                              // it was measured against the previous reference cloud
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion* f, int source, int direction, float max_dist, int n_tau,
+                                         const float* tau, int64_t* summary) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    DistCloud data = {nullptr, 9, 0};
+    bool have = false;
+    switch (source) {
+        case ACMMP_DIST_FROM_SCENE: have = f->s_have; data.p = f->scene.pts; data.n = f->s_total; break;
+        case ACMMP_DIST_FROM_VOXELS: have = f->v_have; data.p = f->v_pts; data.n = f->v_total; break;
+        case ACMMP_DIST_FROM_CLEAN: have = f->c_have; data.p = f->c_pts; data.n = f->c_total; break;
+        case ACMMP_DIST_FROM_VISIBLE: have = f->vis_have; data.p = f->vis_pts; data.n = f->vis_total; break;
+        case ACMMP_DIST_FROM_MESH: have = f->m_have; data.p = f->m_verts; data.n = f->m_nv; break;
+        default: return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    }
+    if (direction != ACMMP_DIST_DATA_TO_REF && direction != ACMMP_DIST_REF_TO_DATA)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "direction must be ACMMP_DIST_DATA_TO_REF or ACMMP_DIST_REF_TO_DATA");
+    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
+    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
+    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
+    if (n_tau < 0 || n_tau > ACMMP_DIST_MAX_TAU || (n_tau > 0 && !tau))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "n_tau must be 0 to 8");
+    for (int i = 0; i < n_tau; ++i)
+        if (!finite32(tau[i]) || !(tau[i] >= 0.0f) || tau[i] > max_dist)
+            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every tau must be finite and in [0, max_dist]");
+    if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
+    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
+    const DistCloud q = direction == ACMMP_DIST_DATA_TO_REF ? data : ref;
+    const DistCloud t = direction == ACMMP_DIST_DATA_TO_REF ? ref : data;
+    if (t.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
+    F_HIP(f, hipSetDevice(f->device));
+    DistOut out;
+    const acmmp_status st = distance_run(f, q, t, max_dist, n_tau, tau, out);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(f->stream);
+        f->err = why;
+        return st;
+    }
+    f->dist_d2 = std::move(out.d2);
+    f->dist_nn = std::move(out.nn);
+    f->dist_n = q.n;
+    f->dist_source = source;
+    f->dist_have = true;
+    f->dist_cell = static_cast<float>(out.cell);
+    f->dist_stats[0] = static_cast<long long>(out.words[kDistOccupied]);
+    f->dist_stats[1] = static_cast<long long>(out.words[kDistMaxList]);
+    f->dist_stats[2] = static_cast<long long>(out.words[kDistRings]);
+    if (summary)
+        for (int k = 0; k < ACMMP_DIST_SUMMARY_WORDS; ++k) summary[k] = static_cast<int64_t>(out.words[kDistSummary + k]);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_distance_results(acmmp_fusion* f, int64_t first, int64_t n, float* d2, int32_t* nearest) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->dist_n)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the distance result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, read_range<float>(d2, f->dist_d2, static_cast<size_t>(first), static_cast<size_t>(n)));
+    F_HIP(f, read_range<int32_t>(nearest, f->dist_nn, static_cast<size_t>(first), static_cast<size_t>(n)));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_distance_grid(acmmp_fusion* f, float force_cell, float* cell, int64_t* cells, int64_t* max_list,
+                                        int64_t* rings) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->dist_force_cell = force_cell;                  // checked by the next distance call
+    if (cell) *cell = f->dist_cell;
+    if (cells) *cells = f->dist_stats[0];
+    if (max_list) *max_list = f->dist_stats[1];
+    if (rings) *rings = f->dist_stats[2];
     return ACMMP_OK;
 }
 

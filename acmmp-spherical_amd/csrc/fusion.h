@@ -228,4 +228,58 @@ hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsig
                          float rel_tol, float* depth, int32_t* face, float* normal, float* colour, unsigned long long* words,
                          hipStream_t s);
 
+// Nearest-neighbour distances between two clouds (acmmp_fusion_cloud_distance, include/acmmp.h).
+// A cloud for the device: point i is p[stride * i .. + 3), n points.
+struct DistCloud {
+    const float* p;
+    int stride;
+    unsigned long long n;
+};
+// A uniform grid in float64: a coordinate's cell on axis a is floor(((double)x - o[a]) * inv), clamped to [0, cmax[a]].
+// The host computes inv = 1.0 / cell and cmax from the targets' bounding box with the same two operations.
+struct DistGrid {
+    double o[3];
+    double inv, cell;
+    int cmax[3];
+};
+// The cell table: open addressing as VoxTable over keys (~0 = empty, all-ones bytes before the insert pass).  cnt is 0
+// before the insert pass and holds a cell's list length after it; launch_dist_lists turns it into the cell's cursor,
+// which ends at the list's end, and fills start.  A coarse table has keys only (start and cnt NULL).
+struct DistTable {
+    unsigned long long* keys;
+    uint32_t* start;
+    uint32_t* cnt;
+    unsigned long long slots;
+    int log2_slots;
+};
+// Device words of a distance call (all zero before it), then the summary of acmmp.h from kDistSummary on.  kDistMin holds
+// six 32-bit words, all-ones before the call: the ordered minimum of x, y, z and the ordered minimum of -x, -y, -z over the
+// valid targets (vox_decode_ordered; the second three negated give the maximum).
+enum { kDistErr = 0, kDistValidTargets = 1, kDistOccupied = 2, kDistMaxList = 3, kDistRings = 4, kDistCursor = 5,
+       kDistMin = 6, kDistSummary = 9, kDistWords = 9 + 268 };
+// words[kDistMin ..] and words[kDistValidTargets] over the targets.
+hipError_t launch_dist_bounds(DistCloud t, unsigned long long* words, hipStream_t s);
+// Insert pass over the valid targets: the fine cell's slot in `fine` with cnt += 1, the coarse cell's slot in `coarse`;
+// words[kDistErr] |= 1 when a probe sequence walked a whole table.
+hipError_t launch_dist_insert(DistCloud t, DistGrid g, DistTable fine, DistGrid cg, DistTable coarse,
+                              unsigned long long* words, hipStream_t s);
+// Every occupied slot takes its list's start from words[kDistCursor] (the order of the slots is invisible), then every
+// valid target j goes to its cell's list: list[pos] = (x, y, z, bits of j).  words[kDistOccupied], [kDistMaxList];
+// words[kDistErr] |= 2 for a failed lookup.
+hipError_t launch_dist_lists(DistCloud t, DistGrid g, DistTable fine, float4* list, unsigned long long* words,
+                             hipStream_t s);
+// The parameters of the query pass that are plain numbers.
+struct DistQuery {
+    float m2;                  // max_dist * max_dist in float32
+    double k;                  // 1048576.0 / (double)max_dist
+    int n_tau;
+    float tau2[8];             // tau[i] * tau[i] in float32
+    double lo[3], hi[3];       // the valid targets' bounding box
+    int have_targets;          // 0: every query is unmatched and no table is read
+};
+// One lane per query: d2[i], nearest[i] and the summary at words[kDistSummary ..] (n_query is the host's);
+// words[kDistRings] = the largest ring searched.
+hipError_t launch_dist_query(DistCloud q, DistGrid g, DistTable fine, DistGrid cg, DistTable coarse, const float4* list,
+                             DistQuery p, float* d2, int32_t* nearest, unsigned long long* words, hipStream_t s);
+
 }  // namespace acmmp

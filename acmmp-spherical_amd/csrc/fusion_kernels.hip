@@ -1823,4 +1823,332 @@ hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsig
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ nearest-neighbour cloud distances
+//
+// acmmp_fusion_cloud_distance (include/acmmp.h).  The result is defined over all pairs; the grid only
+// decides which pairs are looked at, and a pair is left out only where the bounds of DESIGN.md §8 prove that it loses
+// or is unmatched.  The winner is the minimum of a 64-bit (distance bits, index) key, so neither the order of a cell's
+// list nor the order of the cells matters.  Cells are computed in float64, where the rounding of the index is below
+// 2^-30 of a cell; the pair distance is the float32 expression of the definition.
+
+__device__ __forceinline__ bool dist_load(const DistCloud& c, unsigned long long i, float v[3]) {
+    const float* p = c.p + static_cast<unsigned long long>(c.stride) * i;
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    return !vox_nonfinite(v[0]) && !vox_nonfinite(v[1]) && !vox_nonfinite(v[2]);
+}
+
+// The cell of coordinate x on axis a, clamped to the grid; frac = the position inside the cell, 0 with `clamped` set
+// for a coordinate outside the grid (targets never are: the host sizes the grid from their bounding box).
+__device__ __forceinline__ int dist_axis(const DistGrid& g, int a, float x, double& frac, bool& clamped) {
+    const double u = (static_cast<double>(x) - g.o[a]) * g.inv;
+    const double c = floor(u);
+    frac = 0.0;
+    if (!(c >= 0.0)) { clamped = true; return 0; }
+    if (c > static_cast<double>(g.cmax[a])) { clamped = true; return g.cmax[a]; }
+    frac = u - c;
+    return static_cast<int>(c);
+}
+
+__device__ __forceinline__ unsigned long long dist_key(int cx, int cy, int cz) {
+    return static_cast<unsigned long long>(cx) | static_cast<unsigned long long>(cy) << 21 |
+           static_cast<unsigned long long>(cz) << 42;
+}
+
+__device__ __forceinline__ unsigned long long dist_cell_key(const DistGrid& g, const float v[3]) {
+    double fr;
+    bool cl = false;
+    const int cx = dist_axis(g, 0, v[0], fr, cl), cy = dist_axis(g, 1, v[1], fr, cl), cz = dist_axis(g, 2, v[2], fr, cl);
+    return dist_key(cx, cy, cz);
+}
+
+// The slot of `key`, claimed when the key is new (as k_voxel_insert); false = the probe sequence covered every slot.
+__device__ __forceinline__ bool dist_claim(const DistTable& t, unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        unsigned long long k = t.keys[s];
+        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
+        if (k == kVoxEmpty || k == key) { slot = s; return true; }
+        s = (s + 1ull) & mask;
+    }
+    return false;
+}
+
+// The lookup of a cell that may be absent, after the insert pass: 0 = found, 1 = absent, 2 = every slot covered.
+__device__ __forceinline__ int dist_find(const DistTable& t, unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = t.slots - 1ull;
+    unsigned long long s = vox_home(key, t.log2_slots);
+    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
+        const unsigned long long k = t.keys[s];
+        if (k == key) { slot = s; return 0; }
+        if (k == kVoxEmpty) return 1;
+        s = (s + 1ull) & mask;
+    }
+    return 2;
+}
+
+__global__ __launch_bounds__(256) void k_dist_bounds(const DistCloud t, unsigned long long* __restrict__ words) {
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    uint32_t m[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    bool ok = false;
+    if (i < t.n) {
+        float v[3];
+        ok = dist_load(t, i, v);
+        if (ok) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { m[a] = vox_ordered(v[a]); m[3 + a] = vox_ordered(-v[a]); }
+        }
+    }
+    uint32_t* mn = reinterpret_cast<uint32_t*>(words + kDistMin);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[a] = min(m[a], static_cast<uint32_t>(__shfl_xor(static_cast<int>(m[a]), d)));
+        if ((threadIdx.x & 63) == 0 && m[a] != 0xffffffffu) atomicMin(&mn[a], m[a]);
+    }
+    wave_count(ok, &words[kDistValidTargets]);
+}
+
+__global__ __launch_bounds__(256) void k_dist_insert(const DistCloud t, const DistGrid g, const DistTable fine, const DistGrid cg,
+                                                     const DistTable coarse, unsigned long long* __restrict__ words) {
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    if (i < t.n) {
+        float v[3];
+        if (dist_load(t, i, v)) {
+            unsigned long long s;
+            if (dist_claim(fine, dist_cell_key(g, v), s)) atomicAdd(&fine.cnt[s], 1u);
+            else err = 1u;
+            if (coarse.keys && !dist_claim(coarse, dist_cell_key(cg, v), s)) err = 1u;
+        }
+    }
+    block_or(err, &words[kDistErr]);
+}
+
+// Every occupied slot takes a run of the list as long as its count: an inclusive scan of the counts within the wave,
+// one atomic add of the wave's total to the cursor word.  Which run a cell gets depends on the order the waves arrive
+// in, and nothing a reader can see depends on it.  cnt becomes the cell's write cursor.
+__global__ __launch_bounds__(256) void k_dist_starts(const DistTable t, unsigned long long* __restrict__ words) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long occ = 0, longest = 0;
+    for (unsigned long long base = static_cast<unsigned long long>(blockIdx.x) * 256; base < t.slots;
+         base += static_cast<unsigned long long>(gridDim.x) * 256) {
+        const unsigned long long s = base + threadIdx.x;
+        const uint32_t c = (s < t.slots && t.keys[s] != kVoxEmpty) ? t.cnt[s] : 0u;
+        uint32_t inc = c;
+#pragma unroll
+        for (int d = 1; d <= 32; d <<= 1) {
+            const uint32_t y = static_cast<uint32_t>(__shfl_up(static_cast<int>(inc), d));
+            if (lane >= d) inc += y;
+        }
+        const uint32_t tot = static_cast<uint32_t>(__shfl(static_cast<int>(inc), 63));
+        unsigned long long b = 0;
+        if (lane == 0 && tot) b = atomicAdd(&words[kDistCursor], static_cast<unsigned long long>(tot));
+        b = __shfl(b, 0);
+        if (c) {
+            const uint32_t st = static_cast<uint32_t>(b) + inc - c;
+            t.start[s] = st;
+            t.cnt[s] = st;
+            ++occ;
+            longest = max(longest, static_cast<unsigned long long>(c));
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        occ += __shfl_xor(occ, d);
+        longest = max(longest, static_cast<unsigned long long>(__shfl_xor(longest, d)));
+    }
+    if (lane == 0) {
+        if (occ) atomicAdd(&words[kDistOccupied], occ);
+        if (longest) atomicMax(&words[kDistMaxList], longest);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dist_scatter(const DistCloud t, const DistGrid g, const DistTable fine,
+                                                      float4* __restrict__ list, unsigned long long* __restrict__ words) {
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    if (i < t.n) {
+        float v[3];
+        if (dist_load(t, i, v)) {
+            unsigned long long s;
+            if (dist_find(fine, dist_cell_key(g, v), s) == 0) {
+                const uint32_t pos = atomicAdd(&fine.cnt[s], 1u);
+                if (pos < t.n) list[pos] = make_float4(v[0], v[1], v[2], __uint_as_float(static_cast<uint32_t>(i)));
+                else err = 2u;
+            } else {
+                err = 2u;
+            }
+        }
+    }
+    block_or(err, &words[kDistErr]);
+}
+
+// A lower bound of the float32 d2 of any pair whose points lie at least L apart on one axis; 0 where
+// nothing can be said.
+__device__ __forceinline__ double dist_floor2(double L) {
+    const double s = L * L;
+    return (L > 0.0 && s >= 0x1p-120) ? s * (1.0 - 0x1p-20) : 0.0;
+}
+
+// One cell of the fine grid against the query: best = min(best, key) over its list.
+__device__ __forceinline__ void dist_visit(const DistTable& fine, const float4* __restrict__ list, const float v[3], int cx,
+                                           int cy, int cz, unsigned long long& best, unsigned& err) {
+    unsigned long long s;
+    const int r = dist_find(fine, dist_key(cx, cy, cz), s);
+    if (r == 2) err |= 4u;
+    if (r != 0) return;
+    const uint32_t a = fine.start[s], b = fine.cnt[s];
+    for (uint32_t pos = a; pos < b; ++pos) {
+        const float4 t = list[pos];
+        const float dx = v[0] - t.x, dy = v[1] - t.y, dz = v[2] - t.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const unsigned long long key =
+            static_cast<unsigned long long>(__float_as_uint(d2)) << 32 | static_cast<unsigned long long>(__float_as_uint(t.w));
+        best = min(best, key);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dist_query(const DistCloud q, const DistGrid g, const DistTable fine, const DistGrid cg,
+                                                    const DistTable coarse, const float4* __restrict__ list, const DistQuery p,
+                                                    float* __restrict__ d2out, int32_t* __restrict__ nnout,
+                                                    unsigned long long* __restrict__ words) {
+    __shared__ unsigned hist[256];
+    hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    bool valid = false, matched = false;
+    float d2 = __builtin_inff();
+    int32_t nn = -1;
+    unsigned long long rings = 0;
+    unsigned err = 0u;
+    if (i < q.n) {
+        float v[3];
+        valid = dist_load(q, i, v);
+        if (valid && p.have_targets) {
+            const double m2d = static_cast<double>(p.m2);
+            unsigned long long best = ~0ull;
+            // the bounding box of the targets: a query further from it than max_dist on one axis is unmatched
+            double gap = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                gap = fmax(gap, fmax(p.lo[a] - static_cast<double>(v[a]), static_cast<double>(v[a]) - p.hi[a]));
+            bool search = !(dist_floor2(gap) > m2d);
+            // the coarse level: cells wider than max_dist; with none of the 27 around the query occupied it is unmatched
+            if (search && coarse.keys) {
+                double fr;
+                bool cl = false;
+                int c[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) c[a] = dist_axis(cg, a, v[a], fr, cl);
+                bool any = false;
+                for (int z = max(c[2] - 1, 0); z <= min(c[2] + 1, cg.cmax[2]) && !any; ++z)
+                    for (int y = max(c[1] - 1, 0); y <= min(c[1] + 1, cg.cmax[1]) && !any; ++y)
+                        for (int x = max(c[0] - 1, 0); x <= min(c[0] + 1, cg.cmax[0]) && !any; ++x) {
+                            unsigned long long s;
+                            const int r = dist_find(coarse, dist_key(x, y, z), s);
+                            if (r == 2) err |= 4u;
+                            any = r != 1;
+                        }
+                search = any;
+            }
+            if (search) {
+                int c[3], rmax = 0;
+                double mfrac = 0.5;
+                bool clamped = false;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    double fr;
+                    c[a] = dist_axis(g, a, v[a], fr, clamped);
+                    mfrac = fmin(mfrac, fmin(fr, 1.0 - fr));
+                    rmax = max(rmax, max(c[a], g.cmax[a] - c[a]));
+                }
+                if (clamped) mfrac = 0.0;
+                for (int r = 0;; ++r) {
+                    rings = static_cast<unsigned long long>(r);
+                    // the shell of Chebyshev radius r, clipped to the grid
+                    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.cmax[0]);
+                    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.cmax[1]);
+                    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.cmax[2]);
+                    for (int z = z0; z <= z1; ++z) {
+                        const bool zface = z == c[2] - r || z == c[2] + r;
+                        for (int y = y0; y <= y1; ++y) {
+                            if (zface || y == c[1] - r || y == c[1] + r) {
+                                for (int x = x0; x <= x1; ++x) dist_visit(fine, list, v, x, y, z, best, err);
+                            } else {
+                                if (c[0] - r >= 0) dist_visit(fine, list, v, c[0] - r, y, z, best, err);
+                                if (c[0] + r <= g.cmax[0]) dist_visit(fine, list, v, c[0] + r, y, z, best, err);
+                            }
+                        }
+                    }
+                    if (r >= rmax) break;                       // every cell of the grid has been searched
+                    // a target not yet searched lies more than L from the query on one axis
+                    const double lb = dist_floor2((static_cast<double>(r) + mfrac - 0x1p-20) * g.cell);
+                    if (lb > m2d) break;                        // it is unmatched
+                    if (best != ~0ull && static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) < lb) break;   // it loses
+                }
+            }
+            if (best != ~0ull) {
+                const float w = __uint_as_float(static_cast<uint32_t>(best >> 32));
+                if (w <= p.m2) {
+                    matched = true;
+                    d2 = w;
+                    nn = static_cast<int32_t>(static_cast<uint32_t>(best & 0xffffffffull));
+                }
+            }
+        }
+        d2out[i] = d2;
+        nnout[i] = nn;
+    }
+    // the summary: integers only, reduced per wave or per workgroup first
+    unsigned long long* sm = words + kDistSummary;
+    long long qv = 0;
+    if (matched) {
+        qv = static_cast<long long>(rint(sqrt(static_cast<double>(d2)) * p.k));
+        const long long b = qv >> 12;
+        atomicAdd(&hist[b < 255 ? (b < 0 ? 0 : b) : 255], 1u);
+    }
+    wave_count(valid, &sm[1]);
+    wave_count(matched, &sm[2]);
+    wave_add(static_cast<unsigned long long>(qv), &sm[3]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wave_count(matched && k < p.n_tau && d2 <= p.tau2[k], &sm[4 + k]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) rings = max(rings, static_cast<unsigned long long>(__shfl_xor(rings, d)));
+    if ((threadIdx.x & 63) == 0 && rings) atomicMax(&words[kDistRings], rings);
+    block_or(err, &words[kDistErr]);
+    if (hist[threadIdx.x]) atomicAdd(&sm[12 + threadIdx.x], static_cast<unsigned long long>(hist[threadIdx.x]));
+}
+
+static unsigned dist_blocks(unsigned long long n) { return static_cast<unsigned>((n + 255ull) / 256ull); }
+
+hipError_t launch_dist_bounds(DistCloud t, unsigned long long* words, hipStream_t s) {
+    if (t.n == 0) return hipSuccess;
+    k_dist_bounds<<<dist_blocks(t.n), 256, 0, s>>>(t, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_insert(DistCloud t, DistGrid g, DistTable fine, DistGrid cg, DistTable coarse,
+                              unsigned long long* words, hipStream_t s) {
+    if (t.n == 0) return hipSuccess;
+    k_dist_insert<<<dist_blocks(t.n), 256, 0, s>>>(t, g, fine, cg, coarse, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_lists(DistCloud t, DistGrid g, DistTable fine, float4* list, unsigned long long* words,
+                             hipStream_t s) {
+    if (t.n == 0) return hipSuccess;
+    const unsigned long long blocks = std::min<unsigned long long>((fine.slots + 255ull) / 256ull, 4096ull);
+    k_dist_starts<<<static_cast<unsigned>(blocks), 256, 0, s>>>(fine, words);
+    k_dist_scatter<<<dist_blocks(t.n), 256, 0, s>>>(t, g, fine, list, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_dist_query(DistCloud q, DistGrid g, DistTable fine, DistGrid cg, DistTable coarse, const float4* list,
+                             DistQuery p, float* d2, int32_t* nearest, unsigned long long* words, hipStream_t s) {
+    if (q.n == 0) return hipSuccess;
+    k_dist_query<<<dist_blocks(q.n), 256, 0, s>>>(q, g, fine, cg, coarse, list, p, d2, nearest, words);
+    return hipGetLastError();
+}
+
 }  // namespace acmmp

@@ -665,6 +665,83 @@ acmmp_status acmmp_fusion_render_maps(acmmp_fusion *f, float *depth, int32_t *fa
 acmmp_status acmmp_fusion_render_plan(acmmp_fusion *f, int small_max, int64_t *n_small, int64_t *n_large,
                                       int64_t *n_candidates);
 
+/* ---- nearest-neighbour distances between a resident cloud and a reference cloud: accuracy and completeness (no
+ * reference counterpart) ----
+ * acmmp_fusion_set_reference_cloud makes n >= 0 host points, 3 floats each and taken bit for bit, the object's reference
+ * cloud: ground truth, or the cloud of another run.  It lives until the next successful call replaces it; no other call
+ * touches it.  ACMMP_ERR_INVALID_ARGUMENT: n < 0 or above 2^31 - 1, a NULL array with n > 0.  Any error leaves the object
+ * as it was; a success discards the distance result.  Device memory: 12 bytes per point.
+ *
+ * acmmp_fusion_cloud_distance measures the resident data cloud `source` against the reference cloud.  The data cloud is
+ * the first three floats of the scene points (ACMMP_DIST_FROM_SCENE), of the voxel result (_VOXELS), of the clean
+ * result's kept voxels (_CLEAN), of the visible result's kept entries (_VISIBLE) or of the mesh vertices (_MESH), in their
+ * order.  With ACMMP_DIST_DATA_TO_REF the queries are the data cloud and the targets the reference cloud (accuracy); with
+ * ACMMP_DIST_REF_TO_DATA it is the reverse (completeness).  The definition is exhaustive over the pairs, in plain IEEE
+ * arithmetic with no contraction:
+ *  1. Validity.  A point is valid when its three coordinates are finite.  Invalid queries are neither matched nor counted
+ *     as valid; invalid targets do not exist.
+ *  2. Pair distance, in float32: dx = qx - tx, dy = qy - ty, dz = qz - tz, d2 = (dx*dx + dy*dy) + dz*dz.
+ *  3. Nearest.  A valid query takes the smallest key (bits(d2) << 32) | j over all valid targets j: equal distances go to
+ *     the lower target index.  d2 may be +inf; it is never NaN for valid points.
+ *  4. Match.  The query is matched when the winner's d2 <= m2, m2 = max_dist * max_dist formed once in float32.  Per query
+ *     the result is d2, +inf when the query is unmatched, invalid or has no target, and nearest as int32, -1 in the same
+ *     cases.
+ *  5. Summary.  Only integers are summed.  summary[ACMMP_DIST_SUMMARY_WORDS] holds int64 words: [0] n_query, [1] n_valid,
+ *     [2] n_matched, [3] sum_q = the sum over the matched queries of q = (int64) rint(sqrt((double)d2) * k) with
+ *     k = 1048576.0 / (double)max_dist, [4 .. 12) within[i] = the matched queries with d2 <= tau[i] * tau[i], the product
+ *     formed in float32 (entries from n_tau on are 0), [12 .. 268) hist[b] = the matched queries with min(q >> 12, 255) == b.
+ *     summary may be NULL; tau may be NULL when n_tau is 0.
+ * The device searches a uniform grid of the targets ring by ring and skips a pair only where it can prove that the pair
+ * loses or is unmatched; every atomic is an integer add, a minimum or a maximum, and no result depends on
+ * the grid, on the order of a cell's list or on the order the atomics land in.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a source or a direction that is none of the constants, no such data result (an empty one is
+ * a valid input), no reference cloud (an empty one is valid), max_dist not finite or <= 0, n_tau outside [0, 8], a NULL tau
+ * with n_tau > 0, a tau[i] that is not finite, < 0 or > max_dist, a forced cell that is not finite and > 0
+ * (acmmp_fusion_distance_grid).  ACMMP_ERR_UNSUPPORTED: more than 2^31 - 1 targets.  No query gives zeros; no target
+ * leaves every query unmatched.  One distance result is resident at a time (acmmp_fusion_distance_results reads it); it is
+ * built beside the previous one, and any error -- an out-of-memory part-way included -- leaves the object as it was.  It is
+ * discarded when its data source is replaced or discarded -- the scene result by acmmp_fusion_run_scene and
+ * acmmp_fusion_set_scene, the others by the rules the visible and the mesh result follow, a successful call that replaces
+ * the source included -- and when the reference cloud is replaced; acmmp_fusion_set_view does not touch it.  The source
+ * results and the reference cloud are never modified.
+ * Device memory: 8 bytes per query held with the result (d2, nearest); while the call runs, with S = the smallest power
+ * of two >= max(2 T, 1024) for T targets, 16 bytes per slot of the cell table, 8 per slot of the coarse table and 16 per
+ * target (the cells' lists: position and index).  The host waits twice: for the targets' bounding box and valid count, from
+ * which it chooses the cell, and at the end.  The lists are sized from the target count, so nothing waits for the number
+ * of occupied cells. */
+#define ACMMP_DIST_FROM_SCENE 0     /* data cloud = the scene result's points */
+#define ACMMP_DIST_FROM_VOXELS 1    /* the voxel result */
+#define ACMMP_DIST_FROM_CLEAN 2     /* the clean result's kept voxels */
+#define ACMMP_DIST_FROM_VISIBLE 3   /* the visible result's kept entries */
+#define ACMMP_DIST_FROM_MESH 4      /* the mesh result's vertices */
+#define ACMMP_DIST_DATA_TO_REF 0    /* queries = data cloud, targets = reference cloud: accuracy */
+#define ACMMP_DIST_REF_TO_DATA 1    /* queries = reference cloud, targets = data cloud: completeness */
+#define ACMMP_DIST_MAX_TAU 8
+#define ACMMP_DIST_HIST_BINS 256
+#define ACMMP_DIST_SUMMARY_N_QUERY 0
+#define ACMMP_DIST_SUMMARY_N_VALID 1
+#define ACMMP_DIST_SUMMARY_N_MATCHED 2
+#define ACMMP_DIST_SUMMARY_SUM_Q 3
+#define ACMMP_DIST_SUMMARY_WITHIN 4
+#define ACMMP_DIST_SUMMARY_HIST 12
+#define ACMMP_DIST_SUMMARY_WORDS 268
+acmmp_status acmmp_fusion_set_reference_cloud(acmmp_fusion *f, int64_t n, const float *xyz);
+acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion *f, int source, int direction, float max_dist, int n_tau,
+                                         const float *tau, int64_t *summary);
+/* Results of queries [first, first + n) of the distance result to host arrays, either of which may be NULL: d2 n floats,
+ * nearest n int32.  Ranges as acmmp_fusion_voxel_points (no distance result: every range but an empty one at 0 is
+ * refused). */
+acmmp_status acmmp_fusion_distance_results(acmmp_fusion *f, int64_t first, int64_t n, float *d2, int32_t *nearest);
+/* Test hook, in the spirit of acmmp_fusion_voxel_table.  force_cell = 0: the cell of the search grid is chosen from the
+ * targets' bounding box and number; otherwise it is the cell of the distance calls that follow (enlarged where the
+ * targets' extent would need more than 2^20 cells on an axis), and one that is not finite and > 0 makes the next distance
+ * call return ACMMP_ERR_INVALID_ARGUMENT.  The outputs, each of which may be NULL, describe the last successful distance
+ * call: the cell used, the occupied cells, the longest cell list and the largest ring a query searched.  They are
+ * informational: no result depends on them. */
+acmmp_status acmmp_fusion_distance_grid(acmmp_fusion *f, float force_cell, float *cell, int64_t *cells, int64_t *max_list,
+                                        int64_t *rings);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D

@@ -1,0 +1,57 @@
+"""Two point clouds against each other on the GPU: accuracy (every point of A to its nearest point of B), completeness
+(the reverse), and precision, recall and F-score at every threshold -- acmmp_fusion_cloud_distance through set_scene
+and set_reference_cloud.  For two runs of the pipeline, for example --math exact against --math fast.
+
+    python scripts/compare_clouds.py A.ply B.ply --max-dist 0.02 --threshold 0.005 --threshold 0.01 [--out eval.json]
+
+A is the data cloud, B the reference cloud; both are PLYs of the pipeline's layout.  Prints the figures as one JSON
+line (pipeline.evaluate_clouds)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "acmmp-spherical_amd"))
+
+from acmmp import capi, pipeline  # noqa: E402
+
+
+def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None):
+    """evaluate_clouds of cloud A (n, 3) against cloud B; make: the fusion object's factory (tests)."""
+    cam = np.zeros(1, capi.CAMERA_DTYPE)
+    cam["width"], cam["height"] = 8, 8                        # the object needs a camera; no view is used
+    fu = (make or (lambda c: capi.Fusion(device, c)))(cam)
+    try:
+        pts = np.zeros((len(a_xyz), 9), np.float32)
+        pts[:, :3] = a_xyz
+        fu.set_scene(pts)
+        fu.set_reference_cloud(b_xyz)
+        return pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
+    finally:
+        if hasattr(fu, "close"):
+            fu.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("a")
+    ap.add_argument("b")
+    ap.add_argument("--max-dist", type=float, required=True)
+    ap.add_argument("--threshold", type=float, action="append", default=[])
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args(argv)
+    info = compare(pipeline.reference_xyz(a.a), pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device)
+    info.update(a=a.a, b=a.b)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(info, f, indent=1)
+    print(json.dumps(info), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
