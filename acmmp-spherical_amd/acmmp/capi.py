@@ -123,6 +123,8 @@ EXPORTS = [
     "acmmp_fusion_render_plan",
     "acmmp_fusion_set_reference_cloud", "acmmp_fusion_cloud_distance", "acmmp_fusion_distance_results",
     "acmmp_fusion_distance_grid",
+    "acmmp_fusion_set_cloud_transform", "acmmp_fusion_get_cloud_transform", "acmmp_fusion_cloud_align",
+    "acmmp_fusion_align_records",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -253,6 +255,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_cloud_distance.argtypes = [vp, i32, i32, C.c_float, i32, vp, vp]
     L.acmmp_fusion_distance_results.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_distance_grid.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.acmmp_fusion_set_cloud_transform.argtypes = [vp, vp]
+    L.acmmp_fusion_get_cloud_transform.argtypes = [vp, vp, vp]
+    L.acmmp_fusion_cloud_align.argtypes = [vp, i32, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
+    L.acmmp_fusion_align_records.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -889,6 +895,40 @@ RENDER_COUNTS = ("agree", "mesh_in_front", "mesh_behind", "mesh_only", "raw_only
 DIST_SOURCES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "mesh": 4}     # ACMMP_DIST_FROM_*
 DIST_DIRECTIONS = {"data_to_ref": 0, "ref_to_data": 1}     # ACMMP_DIST_DATA_TO_REF (accuracy), _REF_TO_DATA (completeness)
 DIST_SUMMARY_WORDS = 268     # ACMMP_DIST_SUMMARY_WORDS: n_query, n_valid, n_matched, sum_q, within[8], hist[256]
+ALIGN_MODES = {"rigid": 0, "similarity": 1}     # ACMMP_ALIGN_RIGID, ACMMP_ALIGN_SIMILARITY
+ALIGN_STOP_REASONS = ("max_iterations", "converged", "degenerate")     # ACMMP_ALIGN_MAX_ITERATIONS, _CONVERGED, _DEGENERATE
+ALIGN_RECORD_WORDS = 32     # ACMMP_ALIGN_RECORD_WORDS: n_query, n_valid, n_matched, sum_q, n_out_of_range, N, the moments
+
+
+@dataclasses.dataclass
+class AlignRecord:
+    """One iteration of Fusion.cloud_align (step 3 of acmmp_fusion_cloud_align, include/acmmp.h)."""
+    words: np.ndarray      # (32,) int64, the header's layout
+    M: np.ndarray          # (3, 4) float64: the transform the iteration ran under
+    shift: float           # the largest displacement of a corner of the targets' box under the iteration's step
+    max_dist: float
+
+    n_query = property(lambda self: int(self.words[0]))
+    n_valid = property(lambda self: int(self.words[1]))
+    n_matched = property(lambda self: int(self.words[2]))
+    sum_q = property(lambda self: int(self.words[3]))
+    n_out_of_range = property(lambda self: int(self.words[4]))
+    n_pairs = property(lambda self: int(self.words[5]))
+
+    @property
+    def mean(self) -> float:
+        """Mean distance of the matched queries (0 with none)."""
+        k = 1048576.0 / float(np.float32(self.max_dist))
+        return self.sum_q / (self.n_matched * k) if self.n_matched else 0.0
+
+
+@dataclasses.dataclass
+class CloudAlignment:
+    """What Fusion.cloud_align returns."""
+    M: np.ndarray          # (3, 4) float64: data -> reference
+    iterations: int
+    stop_reason: str       # one of ALIGN_STOP_REASONS
+    records: list          # AlignRecord per iteration
 
 
 @dataclasses.dataclass
@@ -1259,6 +1299,53 @@ class Fusion:
         self._check(self.L.acmmp_fusion_distance_grid(self.h, float(force_cell), _p(cell), _p(st[0:1]), _p(st[1:2]),
                                                       _p(st[2:3])), "fusion_distance_grid")
         return {"cell": float(cell[0]), "cells": int(st[0]), "max_list": int(st[1]), "rings": int(st[2])}
+
+    def set_cloud_transform(self, M):
+        """Sets the (3, 4) float64 transform under which cloud_distance reads the data cloud, whatever the source, in
+        both directions (a 4x4 matrix gives its first three rows); None clears it.  The reference cloud, the resident
+        results and everything that is written stay as they are.  Discards the distance result."""
+        if M is None:
+            self._check(self.L.acmmp_fusion_set_cloud_transform(self.h, None), "fusion_set_cloud_transform")
+            return
+        m = np.ascontiguousarray(np.asarray(M, np.float64).reshape(-1)[:12])
+        if m.size != 12:
+            raise ValueError("the transform is a 3x4 matrix")
+        self._check(self.L.acmmp_fusion_set_cloud_transform(self.h, _p(m)), "fusion_set_cloud_transform")
+
+    def cloud_transform(self):
+        """The (3, 4) float64 transform that is set, or None."""
+        m, is_set = np.zeros(12, np.float64), np.zeros(1, np.int32)
+        self._check(self.L.acmmp_fusion_get_cloud_transform(self.h, _p(m), _p(is_set)), "fusion_get_cloud_transform")
+        return m.reshape(3, 4) if is_set[0] else None
+
+    def cloud_align(self, source: str, mode: str, max_dist: float, max_iterations: int = 30, stride: int = 1,
+                    min_shift: float = 0.0, init=None) -> CloudAlignment:
+        """Registers the resident cloud `source` to the reference cloud by iterated closest points inside max_dist
+        (acmmp_fusion_cloud_align, include/acmmp.h): mode "rigid" or "similarity", every stride-th point, from `init`
+        (None: the identity), until the step moves no corner of the reference's box by more than min_shift or
+        max_iterations have run.  The transform that is set is neither read nor written: install the result with
+        set_cloud_transform(result.M)."""
+        if source not in DIST_SOURCES:
+            raise ValueError('source must be one of ' + ", ".join(DIST_SOURCES))
+        if mode not in ALIGN_MODES:
+            raise ValueError('mode must be "rigid" or "similarity"')
+        m0 = None if init is None else np.ascontiguousarray(np.asarray(init, np.float64).reshape(-1)[:12])
+        if m0 is not None and m0.size != 12:
+            raise ValueError("init is a 3x4 matrix")
+        M, it, stop = np.zeros(12, np.float64), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._check(self.L.acmmp_fusion_cloud_align(self.h, DIST_SOURCES[source], ALIGN_MODES[mode], float(max_dist),
+                                                    int(max_iterations), int(stride), float(min_shift),
+                                                    None if m0 is None else _p(m0), _p(M), _p(it), _p(stop)),
+                    "fusion_cloud_align")
+        return CloudAlignment(M=M.reshape(3, 4), iterations=int(it[0]), stop_reason=ALIGN_STOP_REASONS[int(stop[0])],
+                              records=self.align_records(0, int(it[0]), max_dist))
+
+    def align_records(self, first: int, n: int, max_dist: float = 1.0):
+        """AlignRecord of iterations [first, first + n) of the last cloud_align (max_dist: that call's, for mean)."""
+        w, M, sh = np.zeros((max(n, 0), ALIGN_RECORD_WORDS), np.int64), np.zeros((max(n, 0), 12)), np.zeros(max(n, 0))
+        self._check(self.L.acmmp_fusion_align_records(self.h, first, n, _p(w), _p(M), _p(sh)), "fusion_align_records")
+        return [AlignRecord(words=w[k].copy(), M=M[k].reshape(3, 4).copy(), shift=float(sh[k]),
+                            max_dist=float(np.float32(max_dist))) for k in range(n)]
 
     def close(self):
         if self.h:

@@ -796,7 +796,9 @@ class Pipeline:
                    visibility_radius: int = 0, visibility_min_support: int = 1, visibility_max_conflicts: int = 0,
                    mesh_trunc: float | None = None, mesh_min_weight: int = 1, mesh_path: str | None = None,
                    render_mesh: bool = False, render_tol: float = 0.01, eval_cloud=None,
-                   eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None):
+                   eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None,
+                   eval_align: str | None = None, eval_align_max_dist: float | None = None,
+                   eval_align_iterations: int | None = None, eval_align_stride: int | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -851,7 +853,14 @@ class Pipeline:
         include/acmmp.h): accuracy, every point of the run to its nearest reference point, and completeness, the
         reverse, each capped at eval_max_dist, with precision, recall and F-score at every one of eval_thresholds (at
         most 8, each within eval_max_dist).  self.eval_info holds the figures (evaluate_clouds), and eval.json beside
-        the cloud PLY when one is written.  Without eval_cloud nothing is measured and nothing is written."""
+        the cloud PLY when one is written.  Without eval_cloud nothing is measured and nothing is written.
+
+        eval_align ("rigid" or "similarity"; eval_cloud is then required): before the measurement, the evaluated cloud
+        is registered to the reference cloud on the device by iterated closest points (acmmp_fusion_cloud_align,
+        include/acmmp.h) inside eval_align_max_dist (default: eval_max_dist), for at most eval_align_iterations
+        iterations (default 30) over every eval_align_stride-th point (default 1); the transform is installed and
+        accuracy and completeness are measured under it.  The evaluation gains "align": mode, M, stop_reason and per
+        iteration n_matched, mean and shift.  The clouds that are written are never transformed."""
         self.fusion_info = None
         self.eval_info = None
         if eval_cloud is None and (eval_max_dist is not None or len(tuple(eval_thresholds)) or eval_source is not None):
@@ -860,6 +869,13 @@ class Pipeline:
             raise ValueError("the evaluation needs eval_max_dist")
         if eval_source is not None and eval_source not in capi.DIST_SOURCES:
             raise ValueError("eval_source must be one of " + ", ".join(capi.DIST_SOURCES))
+        if eval_align is None and (eval_align_max_dist is not None or eval_align_iterations is not None or
+                                   eval_align_stride is not None):
+            raise ValueError("the alignment options need eval_align")
+        if eval_align is not None and eval_cloud is None:
+            raise ValueError("eval_align needs eval_cloud")
+        if eval_align is not None and eval_align not in capi.ALIGN_MODES:
+            raise ValueError("eval_align must be one of " + ", ".join(capi.ALIGN_MODES))
         if render_mesh and mesh_trunc is None:
             raise ValueError("rendering the mesh needs the mesh (mesh_trunc)")
         if (mesh_trunc is not None or mesh_path is not None) and voxel_size is None:
@@ -981,7 +997,17 @@ class Pipeline:
                 written = ("scene" if voxel_size is None else "visible" if visibility_tol is not None
                            else "clean" if clean else "voxels")
                 fu.set_reference_cloud(reference_xyz(eval_cloud))
+                align = None
+                if eval_align is not None:
+                    if not hasattr(fu, "cloud_align"):
+                        raise ValueError("the alignment needs a fusion object with cloud_align (capi.Fusion)")
+                    align = align_clouds(fu, eval_source or written, eval_align,
+                                         eval_max_dist if eval_align_max_dist is None else eval_align_max_dist,
+                                         30 if eval_align_iterations is None else eval_align_iterations,
+                                         1 if eval_align_stride is None else eval_align_stride)
                 self.eval_info = evaluate_clouds(fu, eval_source or written, eval_max_dist, eval_thresholds)
+                if align is not None:
+                    self.eval_info["align"] = align
                 if path:
                     with open(os.path.join(os.path.dirname(os.path.abspath(path)), "eval.json"), "w") as f:
                         json.dump(self.eval_info, f, indent=1)
@@ -1028,6 +1054,17 @@ def reference_xyz(cloud) -> np.ndarray:
         return np.ascontiguousarray(np.stack([rec["x"], rec["y"], rec["z"]], 1), np.float32)
     a = np.asarray(cloud, np.float32)
     return np.ascontiguousarray(a.reshape(-1, a.shape[-1] if a.ndim > 1 else 3)[:, :3])
+
+
+def align_clouds(fu, source: str, mode: str, max_dist: float, iterations: int = 30, stride: int = 1) -> dict:
+    """Registers the resident cloud `source` of the fusion object to its reference cloud (cloud_align) and installs the
+    transform, so that the cloud_distance calls that follow measure under it: {"mode", "max_dist", "M" (3 rows of 4),
+    "stop_reason", "iterations": [{"n_matched", "mean", "shift"}, ...]}."""
+    r = fu.cloud_align(source, mode, max_dist, iterations, stride)
+    fu.set_cloud_transform(r.M)
+    return {"mode": mode, "max_dist": float(np.float32(max_dist)), "M": [[float(x) for x in row] for row in r.M],
+            "stop_reason": r.stop_reason,
+            "iterations": [{"n_matched": rec.n_matched, "mean": rec.mean, "shift": rec.shift} for rec in r.records]}
 
 
 def evaluate_clouds(fu, source: str, max_dist: float, thresholds=()) -> dict:
@@ -1163,6 +1200,14 @@ def arg_parser():
                          "at most 8, each within --eval-max-dist)")
     ap.add_argument("--eval-source", choices=["scene", "voxels", "clean", "visible", "mesh"], default=None,
                     help="with --eval-cloud: the cloud that is measured (default: the one that is written)")
+    ap.add_argument("--eval-align", choices=["rigid", "similarity"], default=None,
+                    help="with --eval-cloud: first register the measured cloud to the reference cloud on the GPU (ICP) "
+                         "and measure under that transform; eval.json gains the transform and the iterations")
+    ap.add_argument("--eval-align-max-dist", type=float, default=None,
+                    help="with --eval-align: the correspondence cap of the registration (default: --eval-max-dist)")
+    ap.add_argument("--eval-align-iterations", type=int, default=None, help="with --eval-align: at most this many (default 30)")
+    ap.add_argument("--eval-align-stride", type=int, default=None,
+                    help="with --eval-align: register on every n-th point of the measured cloud (default 1)")
     return ap
 
 
@@ -1197,7 +1242,9 @@ def main(argv=None):
                                           else 3.0 * a.voxel_size),
                               mesh_min_weight=a.mesh_min_weight, mesh_path=a.mesh, render_mesh=a.render_mesh,
                               render_tol=a.render_tol, eval_cloud=a.eval_cloud, eval_max_dist=a.eval_max_dist,
-                              eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source)
+                              eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source,
+                              eval_align=a.eval_align, eval_align_max_dist=a.eval_align_max_dist,
+                              eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -150,6 +150,15 @@ struct acmmp_fusion {
     float dist_cell = 0.0f;                      // the cell of the last successful call ...
     long long dist_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
     DevBuf<unsigned long long> dist_words;       // kDistWords device words
+    // the transform of the data cloud (acmmp_fusion_set_cloud_transform) ...
+    bool xf_set = false;
+    double xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    // ... and the records of the last successful acmmp_fusion_cloud_align, on the host: per iteration
+    // ACMMP_ALIGN_RECORD_WORDS words, the 12 doubles of M_k, the shift
+    std::vector<int64_t> align_words;
+    std::vector<double> align_M, align_shift;
+    int align_source = 0;                        // ACMMP_DIST_FROM_*
+    bool align_have = false;                     // an align call has succeeded on this source and reference cloud
     std::string err;
 };
 
@@ -321,9 +330,16 @@ void distance_release(acmmp_fusion* f) {
     f->dist_have = false;
 }
 
-// The data cloud `source` (ACMMP_DIST_FROM_*) has been replaced or discarded: a distance result measured on it goes.
+void align_release(acmmp_fusion* f) {
+    f->align_words.clear(); f->align_M.clear(); f->align_shift.clear();
+    f->align_have = false;
+}
+
+// The data cloud `source` (ACMMP_DIST_FROM_*) has been replaced or discarded: a distance result measured on it goes,
+// and so do the records of an align call on it.
 void distance_source_gone(acmmp_fusion* f, int source) {
     if (f->dist_have && f->dist_source == source) distance_release(f);
+    if (f->align_have && f->align_source == source) align_release(f);
 }
 
 void render_release(acmmp_fusion* f) {
@@ -1536,25 +1552,35 @@ DistGrid dist_grid(const double lo[3], const double hi[3], double cell) {
     return g;
 }
 
-acmmp_status distance_run(acmmp_fusion* f, DistCloud q, DistCloud t, float max_dist, int n_tau, const float* tau,
-                          DistOut& out) {
+// The search grid over the targets of a distance or align call, and what the query passes need of it.
+struct DistIndex {
+    DistGrid g = {{0.0, 0.0, 0.0}, 1.0, 1.0, {0, 0, 0}}, cg = g;
+    DistTable fine = {nullptr, nullptr, nullptr, 0, 0}, coarse = fine;
+    DistQuery p;
+    unsigned long long valid_targets = 0;
+};
+
+// Build: the device words cleared, the valid targets' bounding box and number (the first host wait), the cell, the
+// tables and the cells' lists into out's scratch.  n_tau thresholds go into ix.p.
+acmmp_status distance_build(acmmp_fusion* f, DistCloud t, float max_dist, int n_tau, const float* tau, DistOut& out,
+                            DistIndex& ix) {
     hipStream_t s = f->stream;
     if (!f->dist_words) F_HIP(f, alloc(f->dist_words, kDistWords));
     unsigned long long* w = f->dist_words;
-    F_HIP(f, alloc(out.d2, static_cast<size_t>(q.n)));
-    F_HIP(f, alloc(out.nn, static_cast<size_t>(q.n)));
     F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kDistWords, s));
     F_HIP(f, hipMemsetAsync(w + kDistMin, 0xff, sizeof(unsigned long long) * 3, s));
-    DistQuery p;
+    DistQuery& p = ix.p;
     p.m2 = max_dist * max_dist;
     p.k = 1048576.0 / static_cast<double>(max_dist);
     p.n_tau = n_tau;
     for (int i = 0; i < 8; ++i) p.tau2[i] = i < n_tau ? tau[i] * tau[i] : 0.0f;
     for (int a = 0; a < 3; ++a) p.lo[a] = p.hi[a] = 0.0;
     p.have_targets = 0;
-    DistGrid g = {{0.0, 0.0, 0.0}, 1.0, 1.0, {0, 0, 0}}, cg = g;
-    DistTable fine = {nullptr, nullptr, nullptr, 0, 0}, coarse = fine;
-    unsigned long long valid_targets = 0;
+    DistGrid& g = ix.g;
+    DistGrid& cg = ix.cg;
+    DistTable& fine = ix.fine;
+    DistTable& coarse = ix.coarse;
+    unsigned long long& valid_targets = ix.valid_targets;
     if (t.n > 0) {
         // the first host wait: the valid targets' bounding box and number, from which the cell is chosen
         unsigned long long h[kDistSummary] = {0};
@@ -1606,16 +1632,48 @@ acmmp_status distance_run(acmmp_fusion* f, DistCloud q, DistCloud t, float max_d
             p.have_targets = 1;
         }
     }
-    F_HIP(f, launch_dist_query(q, g, fine, cg, coarse, out.list, p, out.d2, out.nn, w, s));
+    return ACMMP_OK;
+}
+
+// The flags and the cursor of the device words after a query pass.
+acmmp_status distance_check(acmmp_fusion* f, const unsigned long long* words, unsigned long long valid_targets) {
+    if (words[kDistErr] || words[kDistCursor] != valid_targets)
+        return ffail(f, ACMMP_ERR_HIP, "cloud distance: the cell table failed (flags " + std::to_string(words[kDistErr]) +
+                                           ", listed " + std::to_string(words[kDistCursor]) + " of " +
+                                           std::to_string(valid_targets) + " targets)");
+    return ACMMP_OK;
+}
+
+acmmp_status distance_run(acmmp_fusion* f, DistCloud q, DistCloud t, float max_dist, int n_tau, const float* tau,
+                          DistOut& out) {
+    hipStream_t s = f->stream;
+    F_HIP(f, alloc(out.d2, static_cast<size_t>(q.n)));
+    F_HIP(f, alloc(out.nn, static_cast<size_t>(q.n)));
+    DistIndex ix;
+    const acmmp_status st = distance_build(f, t, max_dist, n_tau, tau, out, ix);
+    if (st != ACMMP_OK) return st;
+    unsigned long long* w = f->dist_words;
+    F_HIP(f, launch_dist_query(q, ix.g, ix.fine, ix.cg, ix.coarse, out.list, ix.p, out.d2, out.nn, w, s));
     // the second host wait: the end
     F_HIP(f, hipMemcpyAsync(out.words, w, sizeof(out.words), hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
-    if (out.words[kDistErr] || out.words[kDistCursor] != valid_targets)
-        return ffail(f, ACMMP_ERR_HIP, "cloud distance: the cell table failed (flags " + std::to_string(out.words[kDistErr]) +
-                                           ", listed " + std::to_string(out.words[kDistCursor]) + " of " +
-                                           std::to_string(valid_targets) + " targets)");
+    const acmmp_status ck = distance_check(f, out.words, ix.valid_targets);
+    if (ck != ACMMP_OK) return ck;
     out.words[kDistSummary + ACMMP_DIST_SUMMARY_N_QUERY] = q.n;
     return ACMMP_OK;
+}
+
+// The data cloud `source` without a transform; false = no such constant.
+bool distance_data(acmmp_fusion* f, int source, DistCloud& data, bool& have) {
+    switch (source) {
+        case ACMMP_DIST_FROM_SCENE: have = f->s_have; data.p = f->scene.pts; data.n = f->s_total; break;
+        case ACMMP_DIST_FROM_VOXELS: have = f->v_have; data.p = f->v_pts; data.n = f->v_total; break;
+        case ACMMP_DIST_FROM_CLEAN: have = f->c_have; data.p = f->c_pts; data.n = f->c_total; break;
+        case ACMMP_DIST_FROM_VISIBLE: have = f->vis_have; data.p = f->vis_pts; data.n = f->vis_total; break;
+        case ACMMP_DIST_FROM_MESH: have = f->m_have; data.p = f->m_verts; data.n = f->m_nv; break;
+        default: return false;
+    }
+    return true;
 }
 
 }  // namespace
@@ -1635,6 +1693,7 @@ acmmp_status acmmp_fusion_set_reference_cloud(acmmp_fusion* f, int64_t n, const 
     f->ref_n = static_cast<unsigned long long>(n);
     f->ref_have = true;
     distance_release(f);                              // it was measured against the previous reference cloud
+    align_release(f);                                 // and these were aligned to it
     return ACMMP_OK;
 }
 
@@ -1643,13 +1702,10 @@ acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion* f, int source, int direct
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
     DistCloud data = {nullptr, 9, 0};
     bool have = false;
-    switch (source) {
-        case ACMMP_DIST_FROM_SCENE: have = f->s_have; data.p = f->scene.pts; data.n = f->s_total; break;
-        case ACMMP_DIST_FROM_VOXELS: have = f->v_have; data.p = f->v_pts; data.n = f->v_total; break;
-        case ACMMP_DIST_FROM_CLEAN: have = f->c_have; data.p = f->c_pts; data.n = f->c_total; break;
-        case ACMMP_DIST_FROM_VISIBLE: have = f->vis_have; data.p = f->vis_pts; data.n = f->vis_total; break;
-        case ACMMP_DIST_FROM_MESH: have = f->m_have; data.p = f->m_verts; data.n = f->m_nv; break;
-        default: return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    if (f->xf_set) {
+        data.xf = 1;
+        std::memcpy(data.M, f->xf, sizeof(data.M));
     }
     if (direction != ACMMP_DIST_DATA_TO_REF && direction != ACMMP_DIST_REF_TO_DATA)
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "direction must be ACMMP_DIST_DATA_TO_REF or ACMMP_DIST_REF_TO_DATA");
@@ -1709,6 +1765,275 @@ acmmp_status acmmp_fusion_distance_grid(acmmp_fusion* f, float force_cell, float
     if (cells) *cells = f->dist_stats[0];
     if (max_list) *max_list = f->dist_stats[1];
     if (rings) *rings = f->dist_stats[2];
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- registration of the data cloud to the reference cloud (include/acmmp.h; kernel: k_align_iter) -----------
+
+namespace {
+
+typedef __int128 i128;
+
+// hi * 2^32 + lo of a split product sum.
+i128 align_join(const int64_t* w) { return static_cast<i128>(w[0]) * (static_cast<i128>(1) << 32) + static_cast<i128>(w[1]); }
+
+void align_cross(const double a[3], const double b[3], double c[3]) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// H = U diag(d) V^T by one-sided Jacobi rotations of H's columns, d sorted descending, columns of U and V in u[i], v[i].
+// u[2] and v[2] are the cross products of the first two, so that both bases are right-handed and the third singular
+// value carries a sign: sd2 = u2^T H v2, |sd2| = d2, and its sign is sign det(V U^T) of the unsigned decomposition.
+void align_svd(const double H[9], double d[3], double u[3][3], double v[3][3], double& sd2) {
+    double a[3][3], w[3][3];                               // a[j] = column j of H V, w[j] = column j of V
+    for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) { a[j][i] = H[3 * i + j]; w[j][i] = i == j ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double al = 0.0, be = 0.0, ga = 0.0;
+                for (int i = 0; i < 3; ++i) { al += a[p][i] * a[p][i]; be += a[q][i] * a[q][i]; ga += a[p][i] * a[q][i]; }
+                if (ga == 0.0 || std::fabs(ga) <= 0x1p-53 * std::sqrt(al * be)) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), sn = c * t;
+                for (int i = 0; i < 3; ++i) {
+                    const double x = a[p][i], y = a[q][i];
+                    a[p][i] = c * x - sn * y; a[q][i] = sn * x + c * y;
+                    const double vx = w[p][i], vy = w[q][i];
+                    w[p][i] = c * vx - sn * vy; w[q][i] = sn * vx + c * vy;
+                }
+            }
+        if (!rotated) break;
+    }
+    double n[3];
+    int o[3] = {0, 1, 2};
+    for (int j = 0; j < 3; ++j) n[j] = std::sqrt(a[j][0] * a[j][0] + a[j][1] * a[j][1] + a[j][2] * a[j][2]);
+    std::sort(o, o + 3, [&](int x, int y) { return n[x] > n[y] || (n[x] == n[y] && x < y); });
+    for (int k = 0; k < 3; ++k) {
+        d[k] = n[o[k]];
+        for (int i = 0; i < 3; ++i) {
+            u[k][i] = d[k] > 0.0 ? a[o[k]][i] / d[k] : 0.0;
+            v[k][i] = w[o[k]][i];
+        }
+    }
+    align_cross(u[0], u[1], u[2]);
+    align_cross(v[0], v[1], v[2]);
+    double hv[3];
+    for (int i = 0; i < 3; ++i) hv[i] = H[3 * i] * v[2][0] + H[3 * i + 1] * v[2][1] + H[3 * i + 2] * v[2][2];
+    sd2 = u[2][0] * hv[0] + u[2][1] * hv[1] + u[2][2] * hv[2];
+}
+
+// Step 4 of acmmp_fusion_cloud_align: D from the record; false = degenerate.
+bool align_fit(const int64_t* r, const double c[3], double kq, int mode, double D[12]) {
+    const i128 N = r[ACMMP_ALIGN_RECORD_N];
+    if (N < 3) return false;
+    const double NN = static_cast<double>(r[ACMMP_ALIGN_RECORD_N]) * static_cast<double>(r[ACMMP_ALIGN_RECORD_N]);
+    const int64_t* sp = r + ACMMP_ALIGN_RECORD_SUM_P;
+    const int64_t* sq = r + ACMMP_ALIGN_RECORD_SUM_Q3;
+    double H[9];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            const i128 A = N * align_join(r + ACMMP_ALIGN_RECORD_PQ + 2 * (3 * a + b)) - static_cast<i128>(sp[a]) * static_cast<i128>(sq[b]);
+            H[3 * a + b] = static_cast<double>(A) / NN;
+        }
+    i128 V = N * align_join(r + ACMMP_ALIGN_RECORD_PP);
+    for (int a = 0; a < 3; ++a) V -= static_cast<i128>(sp[a]) * static_cast<i128>(sp[a]);
+    if (V == 0) return false;
+    const double var = static_cast<double>(V) / NN;
+    double d[3], u[3][3], v[3][3], sd2;
+    align_svd(H, d, u, v, sd2);
+    if (!(d[1] > d[0] * 0x1p-40)) return false;
+    const double s = mode == ACMMP_ALIGN_SIMILARITY ? (d[0] + d[1] + sd2) / var : 1.0;
+    const double n = static_cast<double>(r[ACMMP_ALIGN_RECORD_N]);
+    double pm[3], qm[3];
+    for (int a = 0; a < 3; ++a) {
+        pm[a] = c[a] + (static_cast<double>(sp[a]) / n) / kq;
+        qm[a] = c[a] + (static_cast<double>(sq[a]) / n) / kq;
+    }
+    for (int a = 0; a < 3; ++a) {
+        double t = qm[a];
+        for (int b = 0; b < 3; ++b) {
+            // R = V diag(1, 1, g) U^T with the unsigned third pair = v0 u0^T + v1 u1^T + v2 u2^T with the signed one
+            const double R = (v[0][a] * u[0][b] + v[1][a] * u[1][b]) + v[2][a] * u[2][b];
+            D[4 * a + b] = s * R;
+            t -= D[4 * a + b] * pm[b];
+        }
+        D[4 * a + 3] = t;
+    }
+    return true;
+}
+
+// Step 5: M := D o M, and the largest displacement of a corner of the box [lo, hi] under D.
+double align_step(const double D[12], const double lo[3], const double hi[3], double M[12]) {
+    double out[12];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 4; ++b) {
+            out[4 * a + b] = (D[4 * a] * M[b] + D[4 * a + 1] * M[4 + b]) + D[4 * a + 2] * M[8 + b];
+            if (b == 3) out[4 * a + b] += D[4 * a + 3];
+        }
+    std::memcpy(M, out, sizeof(out));
+    double shift = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        const double x[3] = {k & 1 ? hi[0] : lo[0], k & 2 ? hi[1] : lo[1], k & 4 ? hi[2] : lo[2]};
+        double e2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double y = ((D[4 * a] * x[0] + D[4 * a + 1] * x[1]) + D[4 * a + 2] * x[2]) + D[4 * a + 3];
+            e2 += (y - x[a]) * (y - x[a]);
+        }
+        shift = std::max(shift, std::sqrt(e2));
+    }
+    return shift;
+}
+
+// What a successful align call installs.
+struct AlignOut {
+    std::vector<int64_t> words;
+    std::vector<double> M, shift;
+    double last[12];
+    int stop = ACMMP_ALIGN_MAX_ITERATIONS;
+    double cell = 0.0;
+    unsigned long long stats[3] = {0, 0, 0};
+};
+
+acmmp_status align_run(acmmp_fusion* f, DistCloud data, DistCloud ref, int mode, float max_dist, int max_iterations,
+                       unsigned long long stride, double min_shift, AlignOut& out) {
+    hipStream_t s = f->stream;
+    DistOut scratch;
+    DistIndex ix;
+    const acmmp_status st = distance_build(f, ref, max_dist, 0, nullptr, scratch, ix);   // the one build of the call
+    if (st != ACMMP_OK) return st;
+    out.cell = scratch.cell;
+    unsigned long long* w = f->dist_words;
+    unsigned long long* rec = w + kDistSummary;            // the summary's words are free in an align call
+    static_assert(kAlignWords <= ACMMP_DIST_SUMMARY_WORDS, "the record lives in the summary's words");
+    const double kq = 65536.0 / static_cast<double>(max_dist);
+    const unsigned long long nq = (data.n + stride - 1ull) / stride;
+    data.xf = 1;
+    std::memcpy(data.M, out.last, sizeof(data.M));
+    for (int k = 0; k < max_iterations; ++k) {
+        unsigned long long h[kDistSummary + kAlignWords];
+        F_HIP(f, hipMemsetAsync(rec, 0, sizeof(unsigned long long) * kAlignWords, s));
+        F_HIP(f, launch_align_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, w, rec, s));
+        // the iteration's host wait: the record, from which the host fits and decides whether to stop
+        F_HIP(f, hipMemcpyAsync(h, w, sizeof(h), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        const acmmp_status ck = distance_check(f, h, ix.valid_targets);
+        if (ck != ACMMP_OK) return ck;
+        out.stats[0] = h[kDistOccupied]; out.stats[1] = h[kDistMaxList]; out.stats[2] = h[kDistRings];
+        int64_t r[kAlignWords];
+        for (int i = 0; i < kAlignWords; ++i) r[i] = static_cast<int64_t>(h[kDistSummary + i]);
+        r[ACMMP_ALIGN_RECORD_N_QUERY] = static_cast<int64_t>(nq);
+        out.words.insert(out.words.end(), r, r + kAlignWords);
+        out.M.insert(out.M.end(), data.M, data.M + 12);
+        double D[12];
+        if (!align_fit(r, ix.p.lo, kq, mode, D)) {
+            out.shift.push_back(0.0);
+            out.stop = ACMMP_ALIGN_DEGENERATE;
+            break;
+        }
+        const double shift = align_step(D, ix.p.lo, ix.p.hi, data.M);
+        bool finite = std::isfinite(shift);
+        for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(data.M[i]);
+        if (!finite) {                                     // a fit that left float64: keep M_k
+            std::memcpy(data.M, &out.M[out.M.size() - 12], sizeof(data.M));
+            out.shift.push_back(0.0);
+            out.stop = ACMMP_ALIGN_DEGENERATE;
+            break;
+        }
+        out.shift.push_back(shift);
+        if (shift <= min_shift) { out.stop = ACMMP_ALIGN_CONVERGED; break; }
+    }
+    std::memcpy(out.last, data.M, sizeof(out.last));
+    return ACMMP_OK;
+}
+
+bool finite12(const double* M) {
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(M[i])) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_set_cloud_transform(acmmp_fusion* f, const double M[12]) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (M && !finite12(M)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every entry of the transform must be finite");
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::memcpy(f->xf, M ? M : I, sizeof(f->xf));
+    f->xf_set = M != nullptr;
+    distance_release(f);                              // it was measured under the previous transform
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_get_cloud_transform(const acmmp_fusion* f, double M[12], int* is_set) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (M) std::memcpy(M, f->xf, sizeof(f->xf));
+    if (is_set) *is_set = f->xf_set ? 1 : 0;
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, float max_dist, int max_iterations, int stride,
+                                      double min_shift, const double init[12], double M_out[12], int* n_iterations,
+                                      int* stop_reason) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    DistCloud data = {nullptr, 9, 0};
+    bool have = false;
+    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    if (mode != ACMMP_ALIGN_RIGID && mode != ACMMP_ALIGN_SIMILARITY)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "mode must be ACMMP_ALIGN_RIGID or ACMMP_ALIGN_SIMILARITY");
+    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
+    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
+    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
+    if (max_iterations < 1 || max_iterations > 1024) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_iterations must be 1 to 1024");
+    if (stride < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "stride must be at least 1");
+    if (!std::isfinite(min_shift) || min_shift < 0.0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_shift must be finite and >= 0");
+    if (init && !finite12(init)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every entry of init must be finite");
+    if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
+    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
+    if (ref.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
+    F_HIP(f, hipSetDevice(f->device));
+    AlignOut out;
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::memcpy(out.last, init ? init : I, sizeof(out.last));
+    const acmmp_status st = align_run(f, data, ref, mode, max_dist, max_iterations, static_cast<unsigned long long>(stride),
+                                      min_shift, out);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(f->stream);
+        f->err = why;
+        return st;
+    }
+    f->align_words = std::move(out.words);
+    f->align_M = std::move(out.M);
+    f->align_shift = std::move(out.shift);
+    f->align_source = source;
+    f->align_have = true;
+    f->dist_cell = static_cast<float>(out.cell);
+    for (int k = 0; k < 3; ++k) f->dist_stats[k] = static_cast<long long>(out.stats[k]);
+    if (M_out) std::memcpy(M_out, out.last, sizeof(out.last));
+    if (n_iterations) *n_iterations = static_cast<int>(f->align_shift.size());
+    if (stop_reason) *stop_reason = out.stop;
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_align_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->align_shift.size())) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the align records");
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
+    if (words && m) std::memcpy(words, f->align_words.data() + kAlignWords * a, sizeof(int64_t) * kAlignWords * m);
+    if (M && m) std::memcpy(M, f->align_M.data() + 12 * a, sizeof(double) * 12 * m);
+    if (shift && m) std::memcpy(shift, f->align_shift.data() + a, sizeof(double) * m);
     return ACMMP_OK;
 }
 

@@ -229,11 +229,14 @@ hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsig
                          hipStream_t s);
 
 // Nearest-neighbour distances between two clouds (acmmp_fusion_cloud_distance, include/acmmp.h).
-// A cloud for the device: point i is p[stride * i .. + 3), n points.
+// A cloud for the device: point i is p[stride * i .. + 3), n points.  With xf set every point is read through the
+// row-major 3x4 transform M (acmmp_fusion_set_cloud_transform, include/acmmp.h); with xf 0 M is not looked at.
 struct DistCloud {
     const float* p;
     int stride;
     unsigned long long n;
+    int xf;
+    double M[12];
 };
 // A uniform grid in float64: a coordinate's cell on axis a is floor(((double)x - o[a]) * inv), clamped to [0, cmax[a]].
 // The host computes inv = 1.0 / cell and cmax from the targets' bounding box with the same two operations.
@@ -281,5 +284,13 @@ struct DistQuery {
 // words[kDistRings] = the largest ring searched.
 hipError_t launch_dist_query(DistCloud q, DistGrid g, DistTable fine, DistGrid cg, DistTable coarse, const float4* list,
                              DistQuery p, float* d2, int32_t* nearest, unsigned long long* words, hipStream_t s);
+// One iteration of acmmp_fusion_cloud_align over the grid of a distance call's build: the queries are the points
+// 0, stride, 2 stride, ... of q (read through q's transform), t is the target cloud the grid was built from.  rec: the
+// ACMMP_ALIGN_RECORD_WORDS words of the record, zero before the launch (n_query is the host's); words: the distance
+// call's words, of which [kDistErr] (|= 8: a winner that is no valid target) and [kDistRings] are written.
+constexpr int kAlignWords = ACMMP_ALIGN_RECORD_WORDS;
+hipError_t launch_align_iter(DistCloud q, unsigned long long stride, DistCloud t, DistGrid g, DistTable fine, DistGrid cg,
+                             DistTable coarse, const float4* list, DistQuery p, double kq, unsigned long long* words,
+                             unsigned long long* rec, hipStream_t s);
 
 }  // namespace acmmp

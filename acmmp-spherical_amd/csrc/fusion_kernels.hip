@@ -1834,6 +1834,12 @@ hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsig
 __device__ __forceinline__ bool dist_load(const DistCloud& c, unsigned long long i, float v[3]) {
     const float* p = c.p + static_cast<unsigned long long>(c.stride) * i;
     v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+    if (c.xf) {                                      // the cloud transform of acmmp.h: float64, rounded once
+        const double x = static_cast<double>(v[0]), y = static_cast<double>(v[1]), z = static_cast<double>(v[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            v[k] = static_cast<float>(((c.M[4 * k] * x + c.M[4 * k + 1] * y) + c.M[4 * k + 2] * z) + c.M[4 * k + 3]);
+    }
     return !vox_nonfinite(v[0]) && !vox_nonfinite(v[1]) && !vox_nonfinite(v[2]);
 }
 
@@ -2009,6 +2015,77 @@ __device__ __forceinline__ void dist_visit(const DistTable& fine, const float4* 
     }
 }
 
+// Steps 2 and 3 for one valid query v: the smallest (bits(d2) << 32 | j) key over the valid targets that the bounds of
+// DESIGN.md §8 cannot rule out, ~0 with none.  Shared by k_dist_query and k_align_iter.  rings = the largest ring searched.
+__device__ __forceinline__ unsigned long long dist_nearest(const float v[3], const DistGrid& g, const DistTable& fine,
+                                                           const DistGrid& cg, const DistTable& coarse,
+                                                           const float4* __restrict__ list, const DistQuery& p,
+                                                           unsigned long long& rings, unsigned& err) {
+    const double m2d = static_cast<double>(p.m2);
+    unsigned long long best = ~0ull;
+    // the bounding box of the targets: a query further from it than max_dist on one axis is unmatched
+    double gap = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        gap = fmax(gap, fmax(p.lo[a] - static_cast<double>(v[a]), static_cast<double>(v[a]) - p.hi[a]));
+    bool search = !(dist_floor2(gap) > m2d);
+    // the coarse level: cells wider than max_dist; with none of the 27 around the query occupied it is unmatched
+    if (search && coarse.keys) {
+        double fr;
+        bool cl = false;
+        int c[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) c[a] = dist_axis(cg, a, v[a], fr, cl);
+        bool any = false;
+        for (int z = max(c[2] - 1, 0); z <= min(c[2] + 1, cg.cmax[2]) && !any; ++z)
+            for (int y = max(c[1] - 1, 0); y <= min(c[1] + 1, cg.cmax[1]) && !any; ++y)
+                for (int x = max(c[0] - 1, 0); x <= min(c[0] + 1, cg.cmax[0]) && !any; ++x) {
+                    unsigned long long s;
+                    const int r = dist_find(coarse, dist_key(x, y, z), s);
+                    if (r == 2) err |= 4u;
+                    any = r != 1;
+                }
+        search = any;
+    }
+    if (search) {
+        int c[3], rmax = 0;
+        double mfrac = 0.5;
+        bool clamped = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double fr;
+            c[a] = dist_axis(g, a, v[a], fr, clamped);
+            mfrac = fmin(mfrac, fmin(fr, 1.0 - fr));
+            rmax = max(rmax, max(c[a], g.cmax[a] - c[a]));
+        }
+        if (clamped) mfrac = 0.0;
+        for (int r = 0;; ++r) {
+            rings = static_cast<unsigned long long>(r);
+            // the shell of Chebyshev radius r, clipped to the grid
+            const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.cmax[0]);
+            const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.cmax[1]);
+            const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.cmax[2]);
+            for (int z = z0; z <= z1; ++z) {
+                const bool zface = z == c[2] - r || z == c[2] + r;
+                for (int y = y0; y <= y1; ++y) {
+                    if (zface || y == c[1] - r || y == c[1] + r) {
+                        for (int x = x0; x <= x1; ++x) dist_visit(fine, list, v, x, y, z, best, err);
+                    } else {
+                        if (c[0] - r >= 0) dist_visit(fine, list, v, c[0] - r, y, z, best, err);
+                        if (c[0] + r <= g.cmax[0]) dist_visit(fine, list, v, c[0] + r, y, z, best, err);
+                    }
+                }
+            }
+            if (r >= rmax) break;                       // every cell of the grid has been searched
+            // a target not yet searched lies more than L from the query on one axis
+            const double lb = dist_floor2((static_cast<double>(r) + mfrac - 0x1p-20) * g.cell);
+            if (lb > m2d) break;                        // it is unmatched
+            if (best != ~0ull && static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) < lb) break;   // it loses
+        }
+    }
+    return best;
+}
+
 __global__ __launch_bounds__(256) void k_dist_query(const DistCloud q, const DistGrid g, const DistTable fine, const DistGrid cg,
                                                     const DistTable coarse, const float4* __restrict__ list, const DistQuery p,
                                                     float* __restrict__ d2out, int32_t* __restrict__ nnout,
@@ -2026,68 +2103,7 @@ __global__ __launch_bounds__(256) void k_dist_query(const DistCloud q, const Dis
         float v[3];
         valid = dist_load(q, i, v);
         if (valid && p.have_targets) {
-            const double m2d = static_cast<double>(p.m2);
-            unsigned long long best = ~0ull;
-            // the bounding box of the targets: a query further from it than max_dist on one axis is unmatched
-            double gap = 0.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-                gap = fmax(gap, fmax(p.lo[a] - static_cast<double>(v[a]), static_cast<double>(v[a]) - p.hi[a]));
-            bool search = !(dist_floor2(gap) > m2d);
-            // the coarse level: cells wider than max_dist; with none of the 27 around the query occupied it is unmatched
-            if (search && coarse.keys) {
-                double fr;
-                bool cl = false;
-                int c[3];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) c[a] = dist_axis(cg, a, v[a], fr, cl);
-                bool any = false;
-                for (int z = max(c[2] - 1, 0); z <= min(c[2] + 1, cg.cmax[2]) && !any; ++z)
-                    for (int y = max(c[1] - 1, 0); y <= min(c[1] + 1, cg.cmax[1]) && !any; ++y)
-                        for (int x = max(c[0] - 1, 0); x <= min(c[0] + 1, cg.cmax[0]) && !any; ++x) {
-                            unsigned long long s;
-                            const int r = dist_find(coarse, dist_key(x, y, z), s);
-                            if (r == 2) err |= 4u;
-                            any = r != 1;
-                        }
-                search = any;
-            }
-            if (search) {
-                int c[3], rmax = 0;
-                double mfrac = 0.5;
-                bool clamped = false;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    double fr;
-                    c[a] = dist_axis(g, a, v[a], fr, clamped);
-                    mfrac = fmin(mfrac, fmin(fr, 1.0 - fr));
-                    rmax = max(rmax, max(c[a], g.cmax[a] - c[a]));
-                }
-                if (clamped) mfrac = 0.0;
-                for (int r = 0;; ++r) {
-                    rings = static_cast<unsigned long long>(r);
-                    // the shell of Chebyshev radius r, clipped to the grid
-                    const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.cmax[0]);
-                    const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.cmax[1]);
-                    const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.cmax[2]);
-                    for (int z = z0; z <= z1; ++z) {
-                        const bool zface = z == c[2] - r || z == c[2] + r;
-                        for (int y = y0; y <= y1; ++y) {
-                            if (zface || y == c[1] - r || y == c[1] + r) {
-                                for (int x = x0; x <= x1; ++x) dist_visit(fine, list, v, x, y, z, best, err);
-                            } else {
-                                if (c[0] - r >= 0) dist_visit(fine, list, v, c[0] - r, y, z, best, err);
-                                if (c[0] + r <= g.cmax[0]) dist_visit(fine, list, v, c[0] + r, y, z, best, err);
-                            }
-                        }
-                    }
-                    if (r >= rmax) break;                       // every cell of the grid has been searched
-                    // a target not yet searched lies more than L from the query on one axis
-                    const double lb = dist_floor2((static_cast<double>(r) + mfrac - 0x1p-20) * g.cell);
-                    if (lb > m2d) break;                        // it is unmatched
-                    if (best != ~0ull && static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) < lb) break;   // it loses
-                }
-            }
+            const unsigned long long best = dist_nearest(v, g, fine, cg, coarse, list, p, rings, err);
             if (best != ~0ull) {
                 const float w = __uint_as_float(static_cast<uint32_t>(best >> 32));
                 if (w <= p.m2) {
@@ -2120,6 +2136,90 @@ __global__ __launch_bounds__(256) void k_dist_query(const DistCloud q, const Dis
     if (hist[threadIdx.x]) atomicAdd(&sm[12 + threadIdx.x], static_cast<unsigned long long>(hist[threadIdx.x]));
 }
 
+// One iteration of acmmp_fusion_cloud_align (include/acmmp.h): lane i takes the data point i * stride under q's
+// transform, searches as k_dist_query does, quantises the matched pair and forms the kAlignWords words of the record;
+// they are summed over the wave with shuffles, over the workgroup through LDS, and 32 lanes add one word each to
+// rec[0 .. 32) (n_query is the host's).  Only integers are summed; nothing is written per query.
+__global__ __launch_bounds__(256) void k_align_iter(const DistCloud q, unsigned long long stride, unsigned long long nq,
+                                                    const DistCloud t, const DistGrid g, const DistTable fine, const DistGrid cg,
+                                                    const DistTable coarse, const float4* __restrict__ list, const DistQuery p,
+                                                    double kq, unsigned long long* __restrict__ words,
+                                                    unsigned long long* __restrict__ rec) {
+    __shared__ unsigned long long part[4][kAlignWords];
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    long long m[kAlignWords];
+#pragma unroll
+    for (int k = 0; k < kAlignWords; ++k) m[k] = 0;
+    unsigned long long rings = 0;
+    unsigned err = 0u;
+    if (i < nq) {
+        float v[3];
+        if (dist_load(q, i * stride, v)) {
+            m[ACMMP_ALIGN_RECORD_N_VALID] = 1;
+            unsigned long long best = ~0ull;
+            if (p.have_targets) best = dist_nearest(v, g, fine, cg, coarse, list, p, rings, err);
+            const float d2 = __uint_as_float(static_cast<uint32_t>(best >> 32));
+            const unsigned long long j = best & 0xffffffffull;
+            if (best != ~0ull && d2 <= p.m2) {
+                float tv[3];
+                if (j >= t.n || !dist_load(t, j, tv)) {
+                    err |= 8u;
+                } else {
+                    m[ACMMP_ALIGN_RECORD_N_MATCHED] = 1;
+                    m[ACMMP_ALIGN_RECORD_SUM_Q] = static_cast<long long>(rint(sqrt(static_cast<double>(d2)) * p.k));
+                    double P[3], Q[3];
+                    bool in = true;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        P[a] = rint((static_cast<double>(v[a]) - p.lo[a]) * kq);
+                        Q[a] = rint((static_cast<double>(tv[a]) - p.lo[a]) * kq);
+                        in = in && fabs(P[a]) < 0x1p30 && fabs(Q[a]) < 0x1p30;
+                    }
+                    if (!in) {
+                        m[ACMMP_ALIGN_RECORD_N_OUT_OF_RANGE] = 1;
+                    } else {
+                        long long Pi[3], Qi[3];
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) { Pi[a] = static_cast<long long>(P[a]); Qi[a] = static_cast<long long>(Q[a]); }
+                        m[ACMMP_ALIGN_RECORD_N] = 1;
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) {
+                            m[ACMMP_ALIGN_RECORD_SUM_P + a] = Pi[a];
+                            m[ACMMP_ALIGN_RECORD_SUM_Q3 + a] = Qi[a];
+#pragma unroll
+                            for (int b = 0; b < 3; ++b) {
+                                const long long w = Pi[a] * Qi[b];
+                                m[ACMMP_ALIGN_RECORD_PQ + 2 * (3 * a + b)] = w >> 32;
+                                m[ACMMP_ALIGN_RECORD_PQ + 2 * (3 * a + b) + 1] = w & 0xffffffffll;
+                            }
+                        }
+                        const long long w = Pi[0] * Pi[0] + Pi[1] * Pi[1] + Pi[2] * Pi[2];
+                        m[ACMMP_ALIGN_RECORD_PP] = w >> 32;
+                        m[ACMMP_ALIGN_RECORD_PP + 1] = w & 0xffffffffll;
+                    }
+                }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kAlignWords; ++k) {
+        unsigned long long x = static_cast<unsigned long long>(m[k]);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+        if (lane == 0) part[wave][k] = x;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) rings = max(rings, static_cast<unsigned long long>(__shfl_xor(rings, d)));
+    if (lane == 0 && rings) atomicMax(&words[kDistRings], rings);
+    __syncthreads();
+    if (threadIdx.x < kAlignWords) {
+        const unsigned long long x = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if (x) atomicAdd(&rec[threadIdx.x], x);
+    }
+    block_or(err, &words[kDistErr]);
+}
+
 static unsigned dist_blocks(unsigned long long n) { return static_cast<unsigned>((n + 255ull) / 256ull); }
 
 hipError_t launch_dist_bounds(DistCloud t, unsigned long long* words, hipStream_t s) {
@@ -2148,6 +2248,15 @@ hipError_t launch_dist_query(DistCloud q, DistGrid g, DistTable fine, DistGrid c
                              DistQuery p, float* d2, int32_t* nearest, unsigned long long* words, hipStream_t s) {
     if (q.n == 0) return hipSuccess;
     k_dist_query<<<dist_blocks(q.n), 256, 0, s>>>(q, g, fine, cg, coarse, list, p, d2, nearest, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_align_iter(DistCloud q, unsigned long long stride, DistCloud t, DistGrid g, DistTable fine, DistGrid cg,
+                             DistTable coarse, const float4* list, DistQuery p, double kq, unsigned long long* words,
+                             unsigned long long* rec, hipStream_t s) {
+    const unsigned long long nq = (q.n + stride - 1ull) / stride;
+    if (nq == 0) return hipSuccess;
+    k_align_iter<<<dist_blocks(nq), 256, 0, s>>>(q, stride, nq, t, g, fine, cg, coarse, list, p, kq, words, rec);
     return hipGetLastError();
 }
 

@@ -742,6 +742,88 @@ acmmp_status acmmp_fusion_distance_results(acmmp_fusion *f, int64_t first, int64
 acmmp_status acmmp_fusion_distance_grid(acmmp_fusion *f, float force_cell, float *cell, int64_t *cells, int64_t *max_list,
                                         int64_t *rings);
 
+/* ---- registration of the data cloud to the reference cloud: a transform and ICP (no reference counterpart) ----
+ * acmmp_fusion_set_cloud_transform gives the object a row-major 3x4 float64 matrix M; NULL clears it.  While it is set,
+ * acmmp_fusion_cloud_distance reads every data point (x, y, z) of every ACMMP_DIST_FROM_* source, in both directions, as
+ * x', per row k:
+ *   x'_k = (float)(((M[4k] * (double)x + M[4k+1] * (double)y) + M[4k+2] * (double)z) + M[4k+3]),
+ * IEEE float64 with no contraction, rounded once to float32; step 1 of the distance definition (validity) then applies to
+ * x'.  The reference cloud is never transformed and the source results are never modified.  The transform belongs to the
+ * object, not to a source: it lives until it is cleared or replaced, and no other call touches it.  A successful set or
+ * clear discards the distance result, as replacing the reference cloud does.  ACMMP_ERR_INVALID_ARGUMENT: an entry that
+ * is not finite; an error leaves the object as it was.  acmmp_fusion_get_cloud_transform copies M out (is_set 0: the
+ * identity); either output may be NULL.
+ *
+ * acmmp_fusion_cloud_align registers the data cloud `source` to the reference cloud by iterated closest points and returns
+ * the transform in M_out; it neither reads nor writes the transform that has been set (the caller installs M_out with
+ * acmmp_fusion_set_cloud_transform).  init = M_0, NULL for the identity.  Iteration k = 0, 1, ... under M_k:
+ *  1. Queries.  The data points i with i % stride == 0, read as x'_i under M_k as above.  The targets are the valid
+ *     reference points.  Nearest and match are steps 1 to 4 of acmmp_fusion_cloud_distance with max_dist: the float32 d2,
+ *     the (bits(d2) << 32 | j) key, the cap m2.
+ *  2. Quantisation, in float64.  c = the per-axis minimum of the valid targets (0 with none), kq = 65536.0 /
+ *     (double)max_dist.  For a matched pair P_a = (int64) rint(((double)x'_a - c_a) * kq) and Q_a the same of the target.
+ *     The pair is in range when every |P_a| and |Q_a| is < 2^30; otherwise it counts in n_out_of_range and enters no
+ *     moment.
+ *  3. Record.  ACMMP_ALIGN_RECORD_WORDS int64 words, only integers are summed: n_query (the queries of step 1), n_valid,
+ *     n_matched and sum_q exactly as the distance summary forms them; n_out_of_range; N = the matched pairs in range;
+ *     over those pairs the sums of P_a (3 words) and of Q_a (3 words); for each of the nine products w = P_a * Q_b, at
+ *     ACMMP_ALIGN_RECORD_PQ + 2 (3 a + b), the sum of w >> 32 (arithmetic shift) and then the sum of w & 0xffffffff; the
+ *     same two sums of w = P_x^2 + P_y^2 + P_z^2 at ACMMP_ALIGN_RECORD_PP.  The true sum of a product is hi * 2^32 + lo.
+ *     Nothing overflows for up to 2^31 - 1 pairs: |P_a|, |Q_b| < 2^30 give |w| < 2^60 (< 2^62 for the three squares), so
+ *     |w >> 32| < 2^30 and its sum is < 2^61; 0 <= w & 0xffffffff < 2^32 and its sum is < 2^63; |sum of P_a| < 2^61.
+ *  4. Fit.  The host solves in exact 128-bit integers, then float64.  A_ab = N * sum(P_a Q_b) - sum(P_a) * sum(Q_b),
+ *     exact because |A_ab| < 2^123; H_ab = (double)A_ab / ((double)N * (double)N); var = (double)(N * sum|P|^2 -
+ *     |sum P|^2) / ((double)N * (double)N).  H = U diag(d) V^T with d0 >= d1 >= d2 >= 0, g = sign det(V U^T),
+ *     R = V diag(1, 1, g) U^T, s = (d0 + d1 + g d2) / var for ACMMP_ALIGN_SIMILARITY and 1 for ACMMP_ALIGN_RIGID,
+ *     D = (s R | t) with t = (c + Qm / kq) - s R (c + Pm / kq), Pm = sum P / N, Qm = sum Q / N.  The iteration is
+ *     degenerate when N < 3, var is 0 or d1 <= d0 * 2^-40 (collinear pairs): the call ends with ACMMP_ALIGN_DEGENERATE
+ *     and M_out = M_k.
+ *  5. Step.  M_{k+1} = D o M_k, per entry (D_a0 * M_0b + D_a1 * M_1b) + D_a2 * M_2b, plus D_a3 in the last column.
+ *     shift = the largest float64 Euclidean |D c' - c'| over the eight corners c' of the valid targets' bounding box.  The
+ *     call stops with ACMMP_ALIGN_CONVERGED when shift <= min_shift, else with ACMMP_ALIGN_MAX_ITERATIONS after
+ *     max_iterations iterations.  M_out = the last M.
+ * n_iterations = the iterations that ran; M_out, n_iterations and stop_reason may each be NULL.
+ * acmmp_fusion_align_records reads iterations [first, first + n) of the last successful align call: per iteration the
+ * ACMMP_ALIGN_RECORD_WORDS words, the 12 doubles of the M_k it ran under, and its shift (0 for a degenerate iteration);
+ * each array may be NULL.  Ranges as acmmp_fusion_distance_results (no records: every range but an empty one at 0 is
+ * refused).  The records follow the distance result's lifetime rules with respect to the source and
+ * the reference cloud; the cloud transform and acmmp_fusion_set_view do not touch them, and an align call does not touch
+ * the distance result.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a source or a mode that is none of the constants, no such data result (an empty one is
+ * valid and degenerate), no reference cloud, max_dist not finite or <= 0, max_iterations outside [1, 1024], stride < 1,
+ * min_shift not finite or < 0, an init entry that is not finite, a forced cell that is not finite and > 0.
+ * ACMMP_ERR_UNSUPPORTED: more than 2^31 - 1 targets.  Any error -- an out-of-memory part-way included -- leaves the object
+ * as it was.  acmmp_fusion_distance_grid's forced cell applies to align calls too, and its outputs describe the last
+ * successful distance or align call.
+ * The grid over the targets is built once per call and serves every iteration; an iteration is one launch, which reduces
+ * its words over the wave and the workgroup and issues one integer atomic add per word per workgroup, so no result
+ * depends on the order of execution.  Device memory: a distance call's scratch (no per-query array) and the 32 words.
+ * The host waits once for the targets' bounding box and once per iteration for the words. */
+#define ACMMP_ALIGN_RIGID 0
+#define ACMMP_ALIGN_SIMILARITY 1
+#define ACMMP_ALIGN_MAX_ITERATIONS 0   /* stop_reason: max_iterations iterations ran */
+#define ACMMP_ALIGN_CONVERGED 1        /* shift <= min_shift */
+#define ACMMP_ALIGN_DEGENERATE 2       /* step 4 could not fit */
+#define ACMMP_ALIGN_RECORD_N_QUERY 0
+#define ACMMP_ALIGN_RECORD_N_VALID 1
+#define ACMMP_ALIGN_RECORD_N_MATCHED 2
+#define ACMMP_ALIGN_RECORD_SUM_Q 3
+#define ACMMP_ALIGN_RECORD_N_OUT_OF_RANGE 4
+#define ACMMP_ALIGN_RECORD_N 5
+#define ACMMP_ALIGN_RECORD_SUM_P 6     /* 3 words */
+#define ACMMP_ALIGN_RECORD_SUM_Q3 9    /* 3 words: the sums of Q_a */
+#define ACMMP_ALIGN_RECORD_PQ 12       /* 18 words: (hi, lo) of P_a Q_b at + 2 (3 a + b) */
+#define ACMMP_ALIGN_RECORD_PP 30       /* 2 words: (hi, lo) of |P|^2 */
+#define ACMMP_ALIGN_RECORD_WORDS 32
+acmmp_status acmmp_fusion_set_cloud_transform(acmmp_fusion *f, const double M[12]);
+acmmp_status acmmp_fusion_get_cloud_transform(const acmmp_fusion *f, double M[12], int *is_set);
+acmmp_status acmmp_fusion_cloud_align(acmmp_fusion *f, int source, int mode, float max_dist, int max_iterations,
+                                      int stride, double min_shift, const double init[12], double M_out[12],
+                                      int *n_iterations, int *stop_reason);
+acmmp_status acmmp_fusion_align_records(acmmp_fusion *f, int64_t first, int64_t n, int64_t *words, double *M,
+                                        double *shift);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D

@@ -3,9 +3,11 @@
 and set_reference_cloud.  For two runs of the pipeline, for example --math exact against --math fast.
 
     python scripts/compare_clouds.py A.ply B.ply --max-dist 0.02 --threshold 0.005 --threshold 0.01 [--out eval.json]
+                                     [--align rigid|similarity [--align-max-dist D] [--align-iterations K] [--align-stride S]]
 
-A is the data cloud, B the reference cloud; both are PLYs of the pipeline's layout.  Prints the figures as one JSON
-line (pipeline.evaluate_clouds)."""
+A is the data cloud, B the reference cloud; both are PLYs of the pipeline's layout.  With --align, A is first registered
+to B on the GPU (acmmp_fusion_cloud_align) and measured under that transform, which the output then holds under "align".
+Prints the figures as one JSON line (pipeline.evaluate_clouds)."""
 import argparse
 import json
 import os
@@ -19,8 +21,10 @@ sys.path.insert(0, os.path.join(REPO, "acmmp-spherical_amd"))
 from acmmp import capi, pipeline  # noqa: E402
 
 
-def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None):
-    """evaluate_clouds of cloud A (n, 3) against cloud B; make: the fusion object's factory (tests)."""
+def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=None, align_max_dist=None,
+            align_iterations=30, align_stride=1):
+    """evaluate_clouds of cloud A (n, 3) against cloud B, after align_clouds when align is "rigid" or "similarity";
+    make: the fusion object's factory (tests)."""
     cam = np.zeros(1, capi.CAMERA_DTYPE)
     cam["width"], cam["height"] = 8, 8                        # the object needs a camera; no view is used
     fu = (make or (lambda c: capi.Fusion(device, c)))(cam)
@@ -29,7 +33,14 @@ def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None):
         pts[:, :3] = a_xyz
         fu.set_scene(pts)
         fu.set_reference_cloud(b_xyz)
-        return pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
+        registered = None
+        if align is not None:
+            registered = pipeline.align_clouds(fu, "scene", align, max_dist if align_max_dist is None else align_max_dist,
+                                               align_iterations, align_stride)
+        info = pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
+        if registered is not None:
+            info["align"] = registered
+        return info
     finally:
         if hasattr(fu, "close"):
             fu.close()
@@ -41,10 +52,16 @@ def main(argv=None):
     ap.add_argument("b")
     ap.add_argument("--max-dist", type=float, required=True)
     ap.add_argument("--threshold", type=float, action="append", default=[])
+    ap.add_argument("--align", choices=["rigid", "similarity"], default=None)
+    ap.add_argument("--align-max-dist", type=float, default=None, help="default: --max-dist")
+    ap.add_argument("--align-iterations", type=int, default=30)
+    ap.add_argument("--align-stride", type=int, default=1)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
-    info = compare(pipeline.reference_xyz(a.a), pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device)
+    info = compare(pipeline.reference_xyz(a.a), pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device,
+                   align=a.align, align_max_dist=a.align_max_dist, align_iterations=a.align_iterations,
+                   align_stride=a.align_stride)
     info.update(a=a.a, b=a.b)
     if a.out:
         with open(a.out, "w") as f:
