@@ -984,6 +984,13 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     // force fallbacks with a small one, A/B without any with a huge one)
     kp.spread_max = 256.0f;
     if (const char* e = std::getenv("ACMMP_SPREAD_MAX")) kp.spread_max = std::strtof(e, nullptr);
+    // the interpolated loop's negligible-sample threshold (stage_neg_mask): 36 dropped terms of at
+    // most tau x the patch sum each move a source sum by 36 tau = 2^-29.8 of its scale, 1 / 57 of one binary32
+    // rounding (2^-24) of that sum.  ACMMP_NEG_TAU overrides it (tests); ACMMP_NEG_SKIP=0 (read per run) keeps
+    // every sample.  Only where k_eval_nb interpolates; the exact mode never reads it.
+    kp.neg_tau = 0x1p-35f;
+    if (const char* e = std::getenv("ACMMP_NEG_TAU")) kp.neg_tau = std::strtof(e, nullptr);
+    if (const char* e = std::getenv("ACMMP_NEG_SKIP")) if (std::atoi(e) == 0) kp.neg_tau = -1.0f;
     kp.rows = std::min(c->H, 32 * (((c->H / 2) + 15) / 16));
     kp.row_lo = 0; kp.row_hi = kp.rows;
     kp.init_lo = 0; kp.init_hi = c->H;
@@ -1030,6 +1037,9 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     if (const char* e = std::getenv("ACMMP_NBFIX_MAX_PC")) fix_max_pc = std::min<size_t>(fix_max_pc, std::strtoull(e, nullptr, 10));
     const bool fixq = c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc < fix_max_pc;
     if (!fixq && c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc >= fix_max_pc) kp.interp = 0;
+    // (the mask is per wave: only the 8 x 4 tile order keeps a wave's 8 pixels the same under every strip and band cut --
+    // with row runs, ACMMP_NB_TILE=0, a cut regroups them -- so no mask there)
+    if (!kp.interp || !kp.nb_tile) kp.neg_tau = -1.0f;
     // One strip where the fast mode's refinement has two arithmetic forms for the same cost: pinhole (k_eval_ref's
     // homogeneous sample points against the per-sample projection of k_eval_ref_tail and k_select's cache misses)
     // and SPHERE with interpolated coordinates and V > 4 (k_eval_ref's interpolated instance against the same two).

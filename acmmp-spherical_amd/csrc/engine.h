@@ -111,6 +111,8 @@ struct KParams {
     const float2* sph_col;          // SPHERE (sin, cos) longitude, cols -R .. W+R-1
     const float* spatial;           // [(SPHERE ? H : 1)][S]: -dist / (2 sigma_s^2) (ACMMP.cu:398-403)
     float color_den;                // 2 * sigma_color^2
+    float neg_tau;                  // k_eval_nb's interpolated loop skips a sample whose weight is <= neg_tau x the patch sum
+                                    // in every live pixel of its wave (ACMMP_NEG_TAU, 2^-35); < 0: none (ACMMP_NEG_SKIP=0)
     float4* planes_rm;              // persistent row-major state
     float* w_rm;                    // planes_rm's .w (depth) as its own array: k_merge -> k_filter's taps (post only)
     float* costs_rm;

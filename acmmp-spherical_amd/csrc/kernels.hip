@@ -332,6 +332,8 @@ struct Patch {
     int stride;
     float center;                   // reference texel at the pixel
     float sbw, sref, srr;
+    // k_eval_nb's fast SPHERE instance: the wave's mask of negligible samples, two words in LDS (stage_neg_mask)
+    const uint32_t* neg = nullptr;
 };
 
 typedef float float2u __attribute__((ext_vector_type(2), aligned(4)));
@@ -603,7 +605,7 @@ __device__ __forceinline__ int lane_id_here() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, bool NB = false>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, int NB = 0>
 __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                           const int (&vlist)[VB], int nv_rt, float (&cost)[VB],
                                           uint32_t fixkey = kFixNone) {
@@ -775,6 +777,18 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                     }
                 }
                 float x00 = 0.f;                            // the first node's x (set below)
+                // The wave's negligible samples (stage_neg_mask; bit s = sample s of the patch): their source terms
+                // are not formed at all -- no Lagrange term, wrap, clamp, fetch, lerp or sums.  Read from LDS into
+                // SGPRs per view, so every test below is a scalar branch for the whole wave and nothing of it is
+                // live in a VGPR across the views.  The other samples keep their order: an empty mask gives the
+                // bits of the unmasked loop.
+                unsigned long long neg = 0ull;
+                if constexpr (NB == 2) {
+                    const volatile uint32_t* nm = pt.neg;
+                    const uint32_t lo = nm[0], hi = nm[1];
+                    neg = static_cast<unsigned long long>(static_cast<uint32_t>(uniform_int(static_cast<int>(hi)))) << 32 |
+                          static_cast<uint32_t>(uniform_int(static_cast<int>(lo)));
+                }
                 // one patch column's six samples from its four row nodes (x, y): the bilinear tap and the
                 // sums of ACMMP.cu:488-498
                 // (x, y) of a sample as one packed pair: the interpolation's x and y share their Lagrange
@@ -799,6 +813,7 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
 #pragma unroll
                         for (int k = 0; k < G; ++k) {
                             const int cj = c0 + k;
+                            if (NB == 2 && ((neg >> (ci * 6 + cj)) & 1ull)) continue;
                             f32x2 xy;
                             if (cj == 0 || cj == 2 || cj == 3 || cj == 5) {
                                 xy = nd[cj == 0 ? 0 : (cj == 2 ? 1 : (cj == 3 ? 2 : 3))];
@@ -818,6 +833,7 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                         }
 #pragma unroll
                         for (int k = 0; k < G; ++k) {
+                            if (NB == 2 && ((neg >> (ci * 6 + c0 + k)) & 1ull)) continue;
                             const float w = wg[k];
                             const f32x2 wwr = (f32x2){w, w * rg[k]};
                             // unguarded: the view loop skips absent views (`has` re-read per sample kept the
@@ -1266,7 +1282,7 @@ __device__ __forceinline__ float4 perturbed_normal(float4 v, float4 n, Rng& rs, 
 // ------------------------------------------------------------------ cost-vector helpers
 
 // Evaluate all source views of plane `ph` and hand each cost to f(view0, cost) in view order.
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, bool NOFULL = false, typename F>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, int NOFULL = 0, typename F>
 __device__ __forceinline__ void for_all_views_t(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                                 uint32_t wave_mask, F&& f, uint32_t fixkey = kFixNone) {
     int v = 0;
@@ -1814,6 +1830,39 @@ __device__ __forceinline__ Patch coop_patch_nb(const KParams& kp, bool valid, in
     return pt;
 }
 
+// The fast SPHERE k_eval_nb's negligible samples: the bilateral weights of a live patch span
+// tens of binary orders (sigma in radians), and a sample whose weight is at most neg_tau times
+// its pixel's weight sum adds less to the non-negative source sums than their binary32 rounding.  Per wave (8
+// pixels x 8 lanes of coop_patch_nb's layout) one mask: bit s is set when sample s is that small in every live
+// pixel of the wave (staged, patch sum >= 1e-6; the others evaluate nothing).  Lane h tests the samples it staged
+// (h, h + 8, ...); a ballot per round folds the wave's 8 pixels.  Two words per wave after the staged patch
+// (kNbMaskBytes), read back as scalars by ncc_chunk's interpolated loop.  neg_tau < 0 (ACMMP_NEG_SKIP=0, or
+// nothing interpolated): the launch takes the instance without any of this.  Called by all lanes of the block, after coop_patch_nb.
+constexpr size_t kNbMaskBytes = 8 * (256 / 64);
+__device__ __forceinline__ void stage_neg_mask(const KParams& kp, bool valid, Patch& pt, int h, float4* lds) {
+    uint32_t* words = reinterpret_cast<uint32_t*>(reinterpret_cast<float*>(lds + kNbPix * kp.S) + kNbPix * kp.nside) +
+                      2 * uniform_int(static_cast<int>(threadIdx.x >> 6));
+    const bool live = valid && !(pt.sbw < 1e-6f);
+    const float lim = kp.neg_tau * pt.sbw;
+    unsigned long long keep = 0ull;
+    for (int s0 = 0; s0 < kp.S; s0 += kNbLanes) {
+        const int s = s0 + h;
+        const bool k = live && s < kp.S && !(pt.rw[(s < kp.S ? s : 0) * kNbPix].z <= lim);
+        unsigned long long b = __ballot(k);                 // lane 8 p + h: pixel p, sample s0 + h
+        b |= b >> 32; b |= b >> 16; b |= b >> 8;
+        keep |= (b & 0xffull) << s0;
+    }
+    // (capi.cpp sets neg_tau >= 0 only where k_eval_nb interpolates: 36 samples)
+    const unsigned long long neg = ~keep & ((1ull << 36) - 1ull);
+    // written by the wave's first lane and read back by the same wave only (ncc_chunk, through a volatile pointer the
+    // store aliases): a wave's LDS operations complete in order, so no barrier stands between the two
+    if ((threadIdx.x & 63u) == 0u) {
+        words[0] = static_cast<uint32_t>(neg);
+        words[1] = static_cast<uint32_t>(neg >> 32);
+    }
+    pt.neg = words;
+}
+
 // Separable SPHERE staging (STAGED 4): (w, texel) per sample, (sin, cos) of the latitude per patch row
 // and of the longitude per patch column -- a sample's ray is ray_at's two products of them, the same
 // bits.  8 S + 16 nside bytes per pixel (384 B at 36 samples, vs 600 B for coop_patch_nb), so
@@ -1904,7 +1953,7 @@ __global__ __launch_bounds__(256) void k_pick(const KParams kp, const int colour
 // (round 5, profiles/r05_ab3_ab.txt): not kept.  Round 6: two samples' loads issued before either's sums (the sums
 // in order, not a pipeline across iterations) at 5 waves (96 VGPRs, 2 spilled) -- C2 k_eval_nb 3.05 -> 2.93 ms
 // (profiles/r06_ab17_pinpairs_ab.txt); at 6 waves the pair spilled 44 dwords.
-template <int MODEL, int VB, int TEX, int FM>
+template <int MODEL, int VB, int TEX, int FM, int NEG = 0>
 #ifndef ACMMP_NB_PIN_WAVES
 #define ACMMP_NB_PIN_WAVES 5
 #endif
@@ -1945,7 +1994,8 @@ __global__ __launch_bounds__(256, MODEL == kSphere ? (FM ? ACMMP_NB_SPH_WAVES : 
     // a dead pixel stages nothing and writes no cost: its lanes only meet the block's barriers (an all-dead
     // block does nothing else), and with a zero patch sum it stays out of the work count as before
     if (dead) valid = false;
-    const Patch pt = coop_patch_nb<MODEL>(kp, valid, px, py, lp, h, lds4);
+    Patch pt = coop_patch_nb<MODEL>(kp, valid, px, py, lp, h, lds4);
+    if constexpr (NEG) stage_neg_mask(kp, valid, pt, h, lds4);
     // work accounting for the roofline: pixels whose NCCs are evaluated (not short-circuited)
     const int busy = __syncthreads_count(valid && h == 0 && !(MODEL == kSphere && pt.sbw < 1e-6f));
     if (t == 0 && busy && kp.nb_count_work) atomicAdd(kp.work + (blockIdx.x & 255u), static_cast<unsigned long long>(busy));
@@ -1959,7 +2009,7 @@ __global__ __launch_bounds__(256, MODEL == kSphere ? (FM ? ACMMP_NB_SPH_WAVES : 
     const uint32_t wbase = static_cast<uint32_t>(uniform_int(static_cast<int>(
         kp.nb_tile ? (kp.row_lo + wrow) * kp.Wh + wcol : kp.row_lo * kp.Wh + blockIdx.x * kNbPix + (t >> 6) * 8)));
     const uint32_t fixkey = kp.nbfix ? wbase : kFixNone;
-    for_all_views_t<MODEL, nb_vb<MODEL, VB, FM>(), 3, FM ? kNbPipeFast : kNbPipeExact, TEX, FM, true>(
+    for_all_views_t<MODEL, nb_vb<MODEL, VB, FM>(), 3, FM ? kNbPipeFast : kNbPipeExact, TEX, FM, NEG ? 2 : 1>(
         kp, px, py, pt, ph, all, [&](int v, float c) {
             const int l = lane_id_here();
             kp.hyp_cost[(static_cast<long long>(l & 7) * kp.V + v) * Pc + (wbase + (l >> 3))] = c;
@@ -3228,7 +3278,7 @@ hipError_t launch_eval_nb(const KParams& kp0, int colour, hipStream_t s) {
 // instance (view chunk, STAGED 3, PIPE, TEX, FM), so in the fast SPHERE mode of views >= 1600x800 the
 // interpolated source coordinates of DESIGN.md §2.4, which acmmp_debug_ncc (per-sample projection) does
 // not run.  out[(q * 8 + h) * V + v].
-template <int MODEL, int VB, int TEX, int FM>
+template <int MODEL, int VB, int TEX, int FM, int NEG = 0>
 __global__ __launch_bounds__(256) void k_debug_nb(const KParams kp, int n, const int* __restrict__ qx,
                                                   const int* __restrict__ qy, const float4* __restrict__ planes,
                                                   float* __restrict__ out) {
@@ -3238,14 +3288,15 @@ __global__ __launch_bounds__(256) void k_debug_nb(const KParams kp, int n, const
     const int q = blockIdx.x * kNbPix + lp;
     const bool valid = q < n;
     const int px = valid ? qx[q] : 0, py = valid ? qy[q] : 0;
-    const Patch pt = coop_patch_nb<MODEL>(kp, valid, px, py, lp, h, lds4);
+    Patch pt = coop_patch_nb<MODEL>(kp, valid, px, py, lp, h, lds4);
+    if constexpr (NEG) stage_neg_mask(kp, valid, pt, h, lds4);
     if (!valid) return;
     const long long k = static_cast<long long>(q) * kNbLanes + h;
     const float4 ph = planes[k];
     float* o = out + k * kp.V;
     const uint32_t all = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
     const uint32_t fixkey = kp.nbfix ? static_cast<uint32_t>(uniform_int(static_cast<int>(blockIdx.x * kNbPix + (t >> 6) * 8))) : kFixNone;
-    for_all_views_t<MODEL, nb_vb<MODEL, VB, FM>(), 3, FM ? kNbPipeFast : kNbPipeExact, TEX, FM, true>(
+    for_all_views_t<MODEL, nb_vb<MODEL, VB, FM>(), 3, FM ? kNbPipeFast : kNbPipeExact, TEX, FM, NEG ? 2 : 1>(
         kp, px, py, pt, ph, all, [&](int v, float c) { o[v] = c; }, fixkey);
 }
 
@@ -3261,9 +3312,12 @@ hipError_t launch_debug_nb(const KParams& kp0, int n, const int* px, const int* 
     hipError_t e0 = hipSuccess;
     if (fix && (e0 = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e0;
     const size_t lds_nb = nb_lds_bytes(kp.model, kp.S, kp.nside);
+    const size_t lds_neg = lds_nb + kNbMaskBytes;            // the masked instance: stage_neg_mask's words behind the patch
     const dim3 grd = static_cast<unsigned>(cdiv(n, kNbPix));
     if (kp.fast) {
-        if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
+        // (the masked instance where the run skips negligible samples, else the unmasked one: ACMMP_NEG_SKIP=0)
+        if (kp.tex16 && kp.neg_tau >= 0.0f) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 1, M == kSphere><<<grd, 256, lds_neg, s>>>(kp, n, px, py, planes, out)));
+        else if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
         else ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 0, 1><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
     } else {
         if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 0><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
@@ -3275,9 +3329,13 @@ hipError_t launch_debug_nb(const KParams& kp0, int n, const int* px, const int* 
 
 hipError_t launch_eval_nb_views(const KParams& kp, int colour, hipStream_t s) {
     const size_t lds_nb = nb_lds_bytes(kp.model, kp.S, kp.nside);
+    const size_t lds_neg = lds_nb + kNbMaskBytes;            // the masked instance: stage_neg_mask's words behind the patch
     const dim3 grd = static_cast<unsigned>(nb_block_count(kp.row_hi - kp.row_lo, kp.Wh, kp.nb_tile));
     if (kp.fast) {
-        if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
+        // the instance with the negligible-sample mask (stage_neg_mask) where the run skips such samples; without
+        // (ACMMP_NEG_SKIP=0, nothing interpolated) the instance that has no code for it
+        if (kp.tex16 && kp.neg_tau >= 0.0f) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1, M == kSphere><<<grd, 256, lds_neg, s>>>(kp, colour)));
+        else if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
         else ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 0, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
     } else {
         if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 0><<<grd, 256, lds_nb, s>>>(kp, colour)));
