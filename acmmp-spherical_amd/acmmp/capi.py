@@ -124,7 +124,7 @@ EXPORTS = [
     "acmmp_fusion_set_reference_cloud", "acmmp_fusion_cloud_distance", "acmmp_fusion_distance_results",
     "acmmp_fusion_distance_grid",
     "acmmp_fusion_set_cloud_transform", "acmmp_fusion_get_cloud_transform", "acmmp_fusion_cloud_align",
-    "acmmp_fusion_align_records",
+    "acmmp_fusion_align_records", "acmmp_fusion_cloud_align_plane", "acmmp_fusion_align_plane_records",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -259,6 +259,8 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_get_cloud_transform.argtypes = [vp, vp, vp]
     L.acmmp_fusion_cloud_align.argtypes = [vp, i32, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
     L.acmmp_fusion_align_records.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_cloud_align_plane.argtypes = [vp, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
+    L.acmmp_fusion_align_plane_records.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -924,11 +926,49 @@ class AlignRecord:
 
 @dataclasses.dataclass
 class CloudAlignment:
-    """What Fusion.cloud_align returns."""
+    """What Fusion.cloud_align and Fusion.cloud_align_plane return."""
     M: np.ndarray          # (3, 4) float64: data -> reference
     iterations: int
     stop_reason: str       # one of ALIGN_STOP_REASONS
-    records: list          # AlignRecord per iteration
+    records: list          # AlignRecord (AlignPlaneRecord) per iteration
+
+
+ALIGN_PLANE_RECORD_WORDS = 70     # ACMMP_ALIGN_PLANE_RECORD_WORDS
+# ACMMP_ALIGN_PLANE_RECORD_*: the offsets of the header's layout
+(ALIGN_PLANE_N_QUERY, ALIGN_PLANE_N_VALID, ALIGN_PLANE_N_MATCHED, ALIGN_PLANE_SUM_Q, ALIGN_PLANE_N_OUT_OF_RANGE,
+ ALIGN_PLANE_N_NO_NORMAL, ALIGN_PLANE_N, ALIGN_PLANE_SUM_Q3, ALIGN_PLANE_PIVOT, ALIGN_PLANE_ZERO, ALIGN_PLANE_CC,
+ ALIGN_PLANE_CR, ALIGN_PLANE_RR) = 0, 1, 2, 3, 4, 5, 6, 7, 10, 13, 14, 56, 68
+
+
+@dataclasses.dataclass
+class AlignPlaneRecord:
+    """One iteration of Fusion.cloud_align_plane (step 4 of acmmp_fusion_cloud_align_plane, include/acmmp.h)."""
+    words: np.ndarray      # (70,) int64, the header's layout
+    M: np.ndarray          # (3, 4) float64: the transform the iteration ran under
+    shift: float           # the largest displacement of a corner of the targets' box under the iteration's step
+    max_dist: float
+
+    n_query = property(lambda self: int(self.words[ALIGN_PLANE_N_QUERY]))
+    n_valid = property(lambda self: int(self.words[ALIGN_PLANE_N_VALID]))
+    n_matched = property(lambda self: int(self.words[ALIGN_PLANE_N_MATCHED]))
+    sum_q = property(lambda self: int(self.words[ALIGN_PLANE_SUM_Q]))
+    n_out_of_range = property(lambda self: int(self.words[ALIGN_PLANE_N_OUT_OF_RANGE]))
+    n_no_normal = property(lambda self: int(self.words[ALIGN_PLANE_N_NO_NORMAL]))
+    n_pairs = property(lambda self: int(self.words[ALIGN_PLANE_N]))
+    pivot = property(lambda self: [int(x) for x in self.words[ALIGN_PLANE_PIVOT:ALIGN_PLANE_PIVOT + 3]])
+
+    @property
+    def mean(self) -> float:
+        """Mean distance of the matched queries (0 with none)."""
+        k = 1048576.0 / float(np.float32(self.max_dist))
+        return self.sum_q / (self.n_matched * k) if self.n_matched else 0.0
+
+    @property
+    def rms_plane(self) -> float:
+        """sqrt(sum r^2 / N) / (kq * 4096): the RMS point-to-plane residual of the N pairs, in the clouds' unit."""
+        rr = int(self.words[ALIGN_PLANE_RR]) * (1 << 32) + int(self.words[ALIGN_PLANE_RR + 1])
+        kq = 65536.0 / float(np.float32(self.max_dist))
+        return float(np.sqrt(rr / self.n_pairs)) / (kq * 4096.0) if self.n_pairs else 0.0
 
 
 @dataclasses.dataclass
@@ -1346,6 +1386,31 @@ class Fusion:
         self._check(self.L.acmmp_fusion_align_records(self.h, first, n, _p(w), _p(M), _p(sh)), "fusion_align_records")
         return [AlignRecord(words=w[k].copy(), M=M[k].reshape(3, 4).copy(), shift=float(sh[k]),
                             max_dist=float(np.float32(max_dist))) for k in range(n)]
+
+    def cloud_align_plane(self, source: str, max_dist: float, max_iterations: int = 30, stride: int = 1,
+                          min_shift: float = 0.0, init=None) -> CloudAlignment:
+        """Refines `init` (None: the identity; usually cloud_align's result) by iterated closest points with a
+        point-to-plane residual along the data cloud's own normals (acmmp_fusion_cloud_align_plane, include/acmmp.h):
+        rigid only, otherwise cloud_align's arguments, stop reasons and lifetimes.  The records are AlignPlaneRecord."""
+        if source not in DIST_SOURCES:
+            raise ValueError('source must be one of ' + ", ".join(DIST_SOURCES))
+        m0 = None if init is None else np.ascontiguousarray(np.asarray(init, np.float64).reshape(-1)[:12])
+        if m0 is not None and m0.size != 12:
+            raise ValueError("init is a 3x4 matrix")
+        M, it, stop = np.zeros(12, np.float64), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._check(self.L.acmmp_fusion_cloud_align_plane(self.h, DIST_SOURCES[source], float(max_dist), int(max_iterations),
+                                                          int(stride), float(min_shift), None if m0 is None else _p(m0),
+                                                          _p(M), _p(it), _p(stop)), "fusion_cloud_align_plane")
+        return CloudAlignment(M=M.reshape(3, 4), iterations=int(it[0]), stop_reason=ALIGN_STOP_REASONS[int(stop[0])],
+                              records=self.align_plane_records(0, int(it[0]), max_dist))
+
+    def align_plane_records(self, first: int, n: int, max_dist: float = 1.0):
+        """AlignPlaneRecord of iterations [first, first + n) of the last cloud_align_plane (max_dist: that call's)."""
+        w, M, sh = np.zeros((max(n, 0), ALIGN_PLANE_RECORD_WORDS), np.int64), np.zeros((max(n, 0), 12)), np.zeros(max(n, 0))
+        self._check(self.L.acmmp_fusion_align_plane_records(self.h, first, n, _p(w), _p(M), _p(sh)),
+                    "fusion_align_plane_records")
+        return [AlignPlaneRecord(words=w[k].copy(), M=M[k].reshape(3, 4).copy(), shift=float(sh[k]),
+                                 max_dist=float(np.float32(max_dist))) for k in range(n)]
 
     def close(self):
         if self.h:

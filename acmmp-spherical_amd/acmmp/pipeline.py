@@ -798,7 +798,8 @@ class Pipeline:
                    render_mesh: bool = False, render_tol: float = 0.01, eval_cloud=None,
                    eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None,
                    eval_align: str | None = None, eval_align_max_dist: float | None = None,
-                   eval_align_iterations: int | None = None, eval_align_stride: int | None = None):
+                   eval_align_iterations: int | None = None, eval_align_stride: int | None = None,
+                   eval_align_plane_iterations: int | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -860,9 +861,17 @@ class Pipeline:
         include/acmmp.h) inside eval_align_max_dist (default: eval_max_dist), for at most eval_align_iterations
         iterations (default 30) over every eval_align_stride-th point (default 1); the transform is installed and
         accuracy and completeness are measured under it.  The evaluation gains "align": mode, M, stop_reason and per
-        iteration n_matched, mean and shift.  The clouds that are written are never transformed."""
+        iteration n_matched, mean and shift.  The clouds that are written are never transformed.
+
+        eval_align_plane_iterations (eval_align is then required): after that registration, up to this many
+        point-to-plane iterations (acmmp_fusion_cloud_align_plane: rigid, along the evaluated cloud's own normals) refine
+        its transform with the same cap and stride, and the refined transform is the one installed.  "align" gains
+        "plane": M, stop_reason, iterations, n_no_normal of the last iteration and rms_first / rms_last, the RMS
+        point-to-plane residual of the first and the last iteration."""
         self.fusion_info = None
         self.eval_info = None
+        if eval_align_plane_iterations is not None and eval_align is None:
+            raise ValueError("eval_align_plane_iterations needs eval_align")
         if eval_cloud is None and (eval_max_dist is not None or len(tuple(eval_thresholds)) or eval_source is not None):
             raise ValueError("the evaluation options need eval_cloud")
         if eval_cloud is not None and eval_max_dist is None:
@@ -1001,10 +1010,13 @@ class Pipeline:
                 if eval_align is not None:
                     if not hasattr(fu, "cloud_align"):
                         raise ValueError("the alignment needs a fusion object with cloud_align (capi.Fusion)")
+                    if eval_align_plane_iterations is not None and not hasattr(fu, "cloud_align_plane"):
+                        raise ValueError("the plane stage needs a fusion object with cloud_align_plane (capi.Fusion)")
                     align = align_clouds(fu, eval_source or written, eval_align,
                                          eval_max_dist if eval_align_max_dist is None else eval_align_max_dist,
                                          30 if eval_align_iterations is None else eval_align_iterations,
-                                         1 if eval_align_stride is None else eval_align_stride)
+                                         1 if eval_align_stride is None else eval_align_stride,
+                                         plane_iterations=eval_align_plane_iterations)
                 self.eval_info = evaluate_clouds(fu, eval_source or written, eval_max_dist, eval_thresholds)
                 if align is not None:
                     self.eval_info["align"] = align
@@ -1056,15 +1068,27 @@ def reference_xyz(cloud) -> np.ndarray:
     return np.ascontiguousarray(a.reshape(-1, a.shape[-1] if a.ndim > 1 else 3)[:, :3])
 
 
-def align_clouds(fu, source: str, mode: str, max_dist: float, iterations: int = 30, stride: int = 1) -> dict:
+def align_clouds(fu, source: str, mode: str, max_dist: float, iterations: int = 30, stride: int = 1,
+                 plane_iterations: int | None = None) -> dict:
     """Registers the resident cloud `source` of the fusion object to its reference cloud (cloud_align) and installs the
     transform, so that the cloud_distance calls that follow measure under it: {"mode", "max_dist", "M" (3 rows of 4),
-    "stop_reason", "iterations": [{"n_matched", "mean", "shift"}, ...]}."""
+    "stop_reason", "iterations": [{"n_matched", "mean", "shift"}, ...]}.  With plane_iterations, cloud_align_plane then
+    refines that transform with the same cap and stride, the refined one is installed, and the result gains "plane":
+    {"M", "stop_reason", "iterations" (as above), "n_no_normal" (of the last iteration), "rms_first", "rms_last"}."""
     r = fu.cloud_align(source, mode, max_dist, iterations, stride)
-    fu.set_cloud_transform(r.M)
-    return {"mode": mode, "max_dist": float(np.float32(max_dist)), "M": [[float(x) for x in row] for row in r.M],
-            "stop_reason": r.stop_reason,
-            "iterations": [{"n_matched": rec.n_matched, "mean": rec.mean, "shift": rec.shift} for rec in r.records]}
+    out = {"mode": mode, "max_dist": float(np.float32(max_dist)), "M": [[float(x) for x in row] for row in r.M],
+           "stop_reason": r.stop_reason,
+           "iterations": [{"n_matched": rec.n_matched, "mean": rec.mean, "shift": rec.shift} for rec in r.records]}
+    M = r.M
+    if plane_iterations is not None:
+        p = fu.cloud_align_plane(source, max_dist, plane_iterations, stride, 0.0, r.M)
+        M = p.M
+        out["plane"] = {"M": [[float(x) for x in row] for row in p.M], "stop_reason": p.stop_reason,
+                        "iterations": [{"n_matched": rec.n_matched, "mean": rec.mean, "shift": rec.shift} for rec in p.records],
+                        "n_no_normal": p.records[-1].n_no_normal, "rms_first": p.records[0].rms_plane,
+                        "rms_last": p.records[-1].rms_plane}
+    fu.set_cloud_transform(M)
+    return out
 
 
 def evaluate_clouds(fu, source: str, max_dist: float, thresholds=()) -> dict:
@@ -1208,6 +1232,9 @@ def arg_parser():
     ap.add_argument("--eval-align-iterations", type=int, default=None, help="with --eval-align: at most this many (default 30)")
     ap.add_argument("--eval-align-stride", type=int, default=None,
                     help="with --eval-align: register on every n-th point of the measured cloud (default 1)")
+    ap.add_argument("--eval-align-plane-iterations", type=int, default=None,
+                    help="with --eval-align: then refine the transform by at most this many rigid point-to-plane iterations "
+                         "along the measured cloud's normals; eval.json's align gains \"plane\"")
     return ap
 
 
@@ -1244,7 +1271,8 @@ def main(argv=None):
                               render_tol=a.render_tol, eval_cloud=a.eval_cloud, eval_max_dist=a.eval_max_dist,
                               eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source,
                               eval_align=a.eval_align, eval_align_max_dist=a.eval_align_max_dist,
-                              eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride)
+                              eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride,
+                              eval_align_plane_iterations=a.eval_align_plane_iterations)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

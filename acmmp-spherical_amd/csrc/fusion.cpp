@@ -153,12 +153,13 @@ struct acmmp_fusion {
     // the transform of the data cloud (acmmp_fusion_set_cloud_transform) ...
     bool xf_set = false;
     double xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    // ... and the records of the last successful acmmp_fusion_cloud_align, on the host: per iteration
-    // ACMMP_ALIGN_RECORD_WORDS words, the 12 doubles of M_k, the shift
+    // ... and the records of the last successful acmmp_fusion_cloud_align or acmmp_fusion_cloud_align_plane, on the
+    // host: per iteration ACMMP_ALIGN_RECORD_WORDS or ACMMP_ALIGN_PLANE_RECORD_WORDS words, the 12 doubles of M_k, the shift
     std::vector<int64_t> align_words;
     std::vector<double> align_M, align_shift;
     int align_source = 0;                        // ACMMP_DIST_FROM_*
     bool align_have = false;                     // an align call has succeeded on this source and reference cloud
+    bool align_plane = false;                    // ... and it was the point-to-plane call
     std::string err;
 };
 
@@ -1954,6 +1955,200 @@ acmmp_status align_run(acmmp_fusion* f, DistCloud data, DistCloud ref, int mode,
     return ACMMP_OK;
 }
 
+// ---- point-to-plane (acmmp_fusion_cloud_align_plane; kernel: k_align_plane_iter)
+
+// Step 6: floor((2 sumQ_a + N) / (2 N)) in integers, 0 when N is 0.
+void align_pivot(const int64_t* sum_q3, int64_t n, long long g[3]) {
+    for (int a = 0; a < 3; ++a) {
+        g[a] = 0;
+        if (n <= 0) continue;
+        const i128 num = 2 * static_cast<i128>(sum_q3[a]) + n, den = 2 * static_cast<i128>(n);
+        i128 q = num / den;
+        if (num % den != 0 && num < 0) --q;
+        g[a] = static_cast<long long>(q);
+    }
+}
+
+// A = sum_i lam[i] v[i] v[i]^T for a symmetric n x n A by cyclic Jacobi rotations, in the manner of align_svd.
+template <int n>
+void align_eig(double A[n][n], double lam[n], double v[n][n]) {
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) v[i][j] = i == j ? 1.0 : 0.0;      // v[j] = column j of V
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double ga = A[p][q];
+                if (ga == 0.0 || std::fabs(ga) <= 0x1p-53 * std::sqrt(std::fabs(A[p][p] * A[q][q]))) continue;
+                rotated = true;
+                const double zeta = (A[q][q] - A[p][p]) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
+                const double c = 1.0 / std::sqrt(1.0 + t * t), sn = c * t;
+                for (int i = 0; i < n; ++i) {                             // A := A J
+                    const double x = A[i][p], y = A[i][q];
+                    A[i][p] = c * x - sn * y; A[i][q] = sn * x + c * y;
+                }
+                for (int i = 0; i < n; ++i) {                             // A := J^T A
+                    const double x = A[p][i], y = A[q][i];
+                    A[p][i] = c * x - sn * y; A[q][i] = sn * x + c * y;
+                }
+                A[p][q] = A[q][p] = 0.0;
+                for (int i = 0; i < n; ++i) {
+                    const double x = v[p][i], y = v[q][i];
+                    v[p][i] = c * x - sn * y; v[q][i] = sn * x + c * y;
+                }
+            }
+        if (!rotated) break;
+    }
+    for (int i = 0; i < n; ++i) lam[i] = A[i][i];
+}
+
+// Step 5 of acmmp_fusion_cloud_align_plane: D from the record; false = degenerate.
+bool align_plane_fit(const int64_t* r, const double c[3], double kq, double D[12]) {
+    if (r[ACMMP_ALIGN_PLANE_RECORD_N] < 6) return false;
+    double S[6][6], b[6], s[6];
+    int k = ACMMP_ALIGN_PLANE_RECORD_CC;
+    for (int a = 0; a < 6; ++a)
+        for (int e = a; e < 6; ++e, k += 2) S[a][e] = S[e][a] = static_cast<double>(align_join(r + k));
+    for (int a = 0; a < 6; ++a) {
+        b[a] = -static_cast<double>(align_join(r + ACMMP_ALIGN_PLANE_RECORD_CR + 2 * a));
+        if (S[a][a] == 0.0) return false;
+        s[a] = std::sqrt(S[a][a]);
+    }
+    double A[6][6], bs[6], lam[6], v[6][6];
+    for (int a = 0; a < 6; ++a) {
+        bs[a] = b[a] / s[a];
+        for (int e = 0; e < 6; ++e) A[a][e] = S[a][e] / (s[a] * s[e]);
+    }
+    align_eig<6>(A, lam, v);
+    double lmin = lam[0], lmax = lam[0];
+    for (int i = 1; i < 6; ++i) { lmin = std::min(lmin, lam[i]); lmax = std::max(lmax, lam[i]); }
+    if (!(lmin > lmax * 0x1p-40)) return false;
+    // the noise floor: what the translation columns do not explain of the rotation columns (the Schur complement, whose
+    // inverse is the rotation block of S^-1) must exceed four times what the levers' rounding alone puts there
+    double P[3][3], mu[3], pv[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int e = 0; e < 3; ++e) {
+            double t = 0.0;
+            for (int i = 0; i < 6; ++i) t += v[i][a] * v[i][e] / lam[i];
+            P[a][e] = t / (s[a] * s[e]);
+        }
+    for (int a = 0; a < 3; ++a)
+        for (int e = a + 1; e < 3; ++e) P[e][a] = P[a][e];
+    align_eig<3>(P, mu, pv);
+    const double noise = ((S[3][3] + S[4][4]) + S[5][5]) / 18.0;
+    if (!(1.0 > 4.0 * noise * std::max(mu[0], std::max(mu[1], mu[2])))) return false;
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 6; ++i) {
+        double dot = 0.0;
+        for (int a = 0; a < 6; ++a) dot += v[i][a] * bs[a];
+        for (int a = 0; a < 6; ++a) x[a] += v[i][a] * (dot / lam[i]);
+    }
+    double om[3], tau[3], G[3];
+    for (int a = 0; a < 3; ++a) {
+        om[a] = x[a] / s[a] / 4096.0;
+        tau[a] = x[3 + a] / s[3 + a] / kq;
+        G[a] = c[a] + static_cast<double>(r[ACMMP_ALIGN_PLANE_RECORD_PIVOT + a]) / kq;
+    }
+    const double theta2 = (om[0] * om[0] + om[1] * om[1]) + om[2] * om[2];
+    double ca, cb;
+    if (theta2 >= 0x1p-40) {
+        const double theta = std::sqrt(theta2);
+        ca = std::sin(theta) / theta;
+        cb = (1.0 - std::cos(theta)) / theta2;
+    } else {
+        ca = 1.0 - theta2 / 6.0;
+        cb = 0.5 - theta2 / 24.0;
+    }
+    const double K[3][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}, {-om[1], om[0], 0.0}};
+    for (int a = 0; a < 3; ++a) {
+        double t = G[a] + tau[a];
+        for (int e = 0; e < 3; ++e) {
+            const double k2 = (K[a][0] * K[0][e] + K[a][1] * K[1][e]) + K[a][2] * K[2][e];
+            D[4 * a + e] = ((a == e ? 1.0 : 0.0) + ca * K[a][e]) + cb * k2;
+        }
+        for (int e = 0; e < 3; ++e) t -= D[4 * a + e] * G[e];
+        D[4 * a + 3] = t;
+    }
+    return true;
+}
+
+// One launch of an align kernel and its host wait: the words to h (kDistSummary + n_rec of them), checked.
+template <class Launch>
+acmmp_status align_pass(acmmp_fusion* f, const DistIndex& ix, int n_rec, unsigned long long* h, Launch launch) {
+    hipStream_t s = f->stream;
+    unsigned long long* w = f->dist_words;
+    F_HIP(f, hipMemsetAsync(w + kDistSummary, 0, sizeof(unsigned long long) * n_rec, s));
+    F_HIP(f, launch());
+    F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * (kDistSummary + n_rec), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    return distance_check(f, h, ix.valid_targets);
+}
+
+acmmp_status align_plane_run(acmmp_fusion* f, DistCloud data, DistCloud ref, float max_dist, int max_iterations,
+                             unsigned long long stride, double min_shift, AlignOut& out) {
+    hipStream_t s = f->stream;
+    DistOut scratch;
+    DistIndex ix;
+    const acmmp_status st = distance_build(f, ref, max_dist, 0, nullptr, scratch, ix);   // the one build of the call
+    if (st != ACMMP_OK) return st;
+    out.cell = scratch.cell;
+    unsigned long long* w = f->dist_words;
+    unsigned long long* rec = w + kDistSummary;            // the summary's words are free in an align call
+    static_assert(kAlignPlaneWords <= ACMMP_DIST_SUMMARY_WORDS, "the record lives in the summary's words");
+    const double kq = 65536.0 / static_cast<double>(max_dist);
+    const unsigned long long nq = (data.n + stride - 1ull) / stride;
+    data.xf = 1;
+    std::memcpy(data.M, out.last, sizeof(data.M));
+    unsigned long long h[kDistSummary + kAlignPlaneWords];
+    AlignPivot pivot;
+    {
+        // the pivot pass: the point kernel under M_0, for the mean target only; not an iteration
+        const acmmp_status ck = align_pass(f, ix, kAlignWords, h, [&] {
+            return launch_align_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, w, rec, s);
+        });
+        if (ck != ACMMP_OK) return ck;
+        int64_t r[kAlignWords];
+        for (int i = 0; i < kAlignWords; ++i) r[i] = static_cast<int64_t>(h[kDistSummary + i]);
+        align_pivot(r + ACMMP_ALIGN_RECORD_SUM_Q3, r[ACMMP_ALIGN_RECORD_N], pivot.g);
+    }
+    for (int k = 0; k < max_iterations; ++k) {
+        // the iteration's host wait: the record, from which the host fits and decides whether to stop
+        const acmmp_status ck = align_pass(f, ix, kAlignPlaneWords, h, [&] {
+            return launch_align_plane_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, pivot,
+                                           w, rec, s);
+        });
+        if (ck != ACMMP_OK) return ck;
+        out.stats[0] = h[kDistOccupied]; out.stats[1] = h[kDistMaxList]; out.stats[2] = h[kDistRings];
+        int64_t r[kAlignPlaneWords];
+        for (int i = 0; i < kAlignPlaneWords; ++i) r[i] = static_cast<int64_t>(h[kDistSummary + i]);
+        r[ACMMP_ALIGN_PLANE_RECORD_N_QUERY] = static_cast<int64_t>(nq);
+        for (int a = 0; a < 3; ++a) r[ACMMP_ALIGN_PLANE_RECORD_PIVOT + a] = pivot.g[a];
+        out.words.insert(out.words.end(), r, r + kAlignPlaneWords);
+        out.M.insert(out.M.end(), data.M, data.M + 12);
+        double D[12];
+        if (!align_plane_fit(r, ix.p.lo, kq, D)) {
+            out.shift.push_back(0.0);
+            out.stop = ACMMP_ALIGN_DEGENERATE;
+            break;
+        }
+        const double shift = align_step(D, ix.p.lo, ix.p.hi, data.M);
+        bool finite = std::isfinite(shift);
+        for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(data.M[i]);
+        if (!finite) {                                     // a fit that left float64: keep M_k
+            std::memcpy(data.M, &out.M[out.M.size() - 12], sizeof(data.M));
+            out.shift.push_back(0.0);
+            out.stop = ACMMP_ALIGN_DEGENERATE;
+            break;
+        }
+        out.shift.push_back(shift);
+        if (shift <= min_shift) { out.stop = ACMMP_ALIGN_CONVERGED; break; }
+        align_pivot(r + ACMMP_ALIGN_PLANE_RECORD_SUM_Q3, r[ACMMP_ALIGN_PLANE_RECORD_N], pivot.g);
+    }
+    std::memcpy(out.last, data.M, sizeof(out.last));
+    return ACMMP_OK;
+}
+
 bool finite12(const double* M) {
     for (int i = 0; i < 12; ++i)
         if (!std::isfinite(M[i])) return false;
@@ -2019,6 +2214,7 @@ acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, flo
     f->align_shift = std::move(out.shift);
     f->align_source = source;
     f->align_have = true;
+    f->align_plane = false;                           // the plane records, if any, went with the vectors above
     f->dist_cell = static_cast<float>(out.cell);
     for (int k = 0; k < 3; ++k) f->dist_stats[k] = static_cast<long long>(out.stats[k]);
     if (M_out) std::memcpy(M_out, out.last, sizeof(out.last));
@@ -2027,14 +2223,78 @@ acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, flo
     return ACMMP_OK;
 }
 
-acmmp_status acmmp_fusion_align_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
+}  // extern "C"
+
+namespace {
+
+// Iterations [first, first + n) of the records of the given kind (none of the other kind's are visible).
+acmmp_status align_read(acmmp_fusion* f, bool plane, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
     if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->align_shift.size())) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the align records");
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    if (words && m) std::memcpy(words, f->align_words.data() + kAlignWords * a, sizeof(int64_t) * kAlignWords * m);
+    const size_t have = f->align_plane == plane ? f->align_shift.size() : 0;
+    if (bad_range(first, n, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the align records");
+    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n), nw = plane ? kAlignPlaneWords : kAlignWords;
+    if (words && m) std::memcpy(words, f->align_words.data() + nw * a, sizeof(int64_t) * nw * m);
     if (M && m) std::memcpy(M, f->align_M.data() + 12 * a, sizeof(double) * 12 * m);
     if (shift && m) std::memcpy(shift, f->align_shift.data() + a, sizeof(double) * m);
     return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_align_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
+    return align_read(f, false, first, n, words, M, shift);
+}
+
+acmmp_status acmmp_fusion_cloud_align_plane(acmmp_fusion* f, int source, float max_dist, int max_iterations, int stride,
+                                            double min_shift, const double init[12], double M_out[12], int* n_iterations,
+                                            int* stop_reason) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    DistCloud data = {nullptr, 9, 0};
+    bool have = false;
+    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
+    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
+    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
+    if (max_iterations < 1 || max_iterations > 1024) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_iterations must be 1 to 1024");
+    if (stride < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "stride must be at least 1");
+    if (!std::isfinite(min_shift) || min_shift < 0.0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_shift must be finite and >= 0");
+    if (init && !finite12(init)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every entry of init must be finite");
+    if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
+    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
+    if (ref.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
+    F_HIP(f, hipSetDevice(f->device));
+    AlignOut out;
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::memcpy(out.last, init ? init : I, sizeof(out.last));
+    const acmmp_status st = align_plane_run(f, data, ref, max_dist, max_iterations, static_cast<unsigned long long>(stride),
+                                            min_shift, out);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(f->stream);
+        f->err = why;
+        return st;
+    }
+    f->align_words = std::move(out.words);
+    f->align_M = std::move(out.M);
+    f->align_shift = std::move(out.shift);
+    f->align_source = source;
+    f->align_have = true;
+    f->align_plane = true;                            // the point records, if any, went with the vectors above
+    f->dist_cell = static_cast<float>(out.cell);
+    for (int k = 0; k < 3; ++k) f->dist_stats[k] = static_cast<long long>(out.stats[k]);
+    if (M_out) std::memcpy(M_out, out.last, sizeof(out.last));
+    if (n_iterations) *n_iterations = static_cast<int>(f->align_shift.size());
+    if (stop_reason) *stop_reason = out.stop;
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_align_plane_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M,
+                                              double* shift) {
+    return align_read(f, true, first, n, words, M, shift);
 }
 
 }  // extern "C"

@@ -292,5 +292,13 @@ constexpr int kAlignWords = ACMMP_ALIGN_RECORD_WORDS;
 hipError_t launch_align_iter(DistCloud q, unsigned long long stride, DistCloud t, DistGrid g, DistTable fine, DistGrid cg,
                              DistTable coarse, const float4* list, DistQuery p, double kq, unsigned long long* words,
                              unsigned long long* rec, hipStream_t s);
+// One iteration of acmmp_fusion_cloud_align_plane: as launch_align_iter, with the normal of data point i at q.p[q.stride
+// * i + 3 .. + 6) (q.stride >= 6) turned by q's transform, and the pivot g of the levers.  rec: the
+// ACMMP_ALIGN_PLANE_RECORD_WORDS words, zero before the launch (n_query and the pivot are the host's).
+constexpr int kAlignPlaneWords = ACMMP_ALIGN_PLANE_RECORD_WORDS;
+struct AlignPivot { long long g[3]; };
+hipError_t launch_align_plane_iter(DistCloud q, unsigned long long stride, DistCloud t, DistGrid g, DistTable fine,
+                                   DistGrid cg, DistTable coarse, const float4* list, DistQuery p, double kq,
+                                   AlignPivot pivot, unsigned long long* words, unsigned long long* rec, hipStream_t s);
 
 }  // namespace acmmp

@@ -2220,6 +2220,142 @@ __global__ __launch_bounds__(256) void k_align_iter(const DistCloud q, unsigned 
     block_or(err, &words[kDistErr]);
 }
 
+// The sum of x over the wave to part[k] (lane 0 writes).  Every lane of the wave calls it.
+__device__ __forceinline__ void align_wave_word(unsigned long long x, unsigned long long* part, int k) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+    if ((threadIdx.x & 63) == 0) part[k] = x;
+}
+
+// The split sums of the product w over the wave: part[k] = the sum of w >> 32, part[k + 1] = the sum of w & 0xffffffff.
+__device__ __forceinline__ void align_wave_split(long long w, unsigned long long* part, int k) {
+    align_wave_word(static_cast<unsigned long long>(w >> 32), part, k);
+    align_wave_word(static_cast<unsigned long long>(w & 0xffffffffll), part, k + 1);
+}
+
+// One iteration of acmmp_fusion_cloud_align_plane (include/acmmp.h): k_align_iter's lane mapping, search and reduction,
+// with the point-to-plane row.  After the search a lane holds its flags, sum_q, Q and nine small integers -- the lever
+// L, the quantised normal Nn and D = P - Q, all zero for a lane that contributes no pair -- and every word is formed from
+// them just before its reduction, so that the 70 words are never live together.  Only integers are summed; nothing is
+// written per query.
+__global__ __launch_bounds__(256) void k_align_plane_iter(const DistCloud q, unsigned long long stride, unsigned long long nq,
+                                                          const DistCloud t, const DistGrid g, const DistTable fine,
+                                                          const DistGrid cg, const DistTable coarse,
+                                                          const float4* __restrict__ list, const DistQuery p, double kq,
+                                                          const AlignPivot pivot, unsigned long long* __restrict__ words,
+                                                          unsigned long long* __restrict__ rec) {
+    __shared__ unsigned long long part[4][kAlignPlaneWords];
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    bool valid = false, matched = false, out_of_range = false, no_normal = false, pair = false;
+    long long sum_q = 0, Qi[3] = {0, 0, 0};
+    int L[3] = {0, 0, 0}, Nn[3] = {0, 0, 0}, D[3] = {0, 0, 0};
+    unsigned long long rings = 0;
+    unsigned err = 0u;
+    if (i < nq) {
+        float v[3];
+        if (dist_load(q, i * stride, v)) {
+            valid = true;
+            unsigned long long best = ~0ull;
+            if (p.have_targets) best = dist_nearest(v, g, fine, cg, coarse, list, p, rings, err);
+            const float d2 = __uint_as_float(static_cast<uint32_t>(best >> 32));
+            const unsigned long long j = best & 0xffffffffull;
+            if (best != ~0ull && d2 <= p.m2) {
+                float tv[3];
+                if (j >= t.n || !dist_load(t, j, tv)) {
+                    err |= 8u;
+                } else {
+                    matched = true;
+                    sum_q = static_cast<long long>(rint(sqrt(static_cast<double>(d2)) * p.k));
+                    double P[3], Q[3];
+                    bool in = true;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        P[a] = rint((static_cast<double>(v[a]) - p.lo[a]) * kq);
+                        Q[a] = rint((static_cast<double>(tv[a]) - p.lo[a]) * kq);
+                        in = in && fabs(P[a]) < 0x1p30 && fabs(Q[a]) < 0x1p30;
+                    }
+                    long long lever[3] = {0, 0, 0};
+                    if (in) {
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) {
+                            lever[a] = static_cast<long long>(Q[a]) - pivot.g[a];
+                            in = in && lever[a] > -(1ll << 30) && lever[a] < (1ll << 30);
+                        }
+                    }
+                    if (!in) {
+                        out_of_range = true;
+                    } else {
+                        // the data point's own normal under the linear part of the transform, float64, no contraction
+                        const float* np = q.p + static_cast<unsigned long long>(q.stride) * (i * stride) + 3;
+                        const float nf[3] = {np[0], np[1], np[2]};
+                        const double nx = static_cast<double>(nf[0]), ny = static_cast<double>(nf[1]), nz = static_cast<double>(nf[2]);
+                        double u[3];
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) u[a] = (q.M[4 * a] * nx + q.M[4 * a + 1] * ny) + q.M[4 * a + 2] * nz;
+                        const double l2 = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+                        const bool usable = !vox_nonfinite(nf[0]) && !vox_nonfinite(nf[1]) && !vox_nonfinite(nf[2]) &&
+                                            l2 > 0.0 && l2 < __builtin_inf();
+                        if (!usable) {
+                            no_normal = true;
+                        } else {
+                            pair = true;
+                            const double len = sqrt(l2);
+#pragma unroll
+                            for (int a = 0; a < 3; ++a) {
+                                Qi[a] = static_cast<long long>(Q[a]);
+                                L[a] = static_cast<int>(lever[a] >> 12);
+                                Nn[a] = static_cast<int>(rint(u[a] / len * 4096.0));
+                                D[a] = static_cast<int>(static_cast<long long>(P[a]) - Qi[a]);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* my = part[wave];
+    const unsigned long long counts[5] = {__ballot(valid), __ballot(matched), __ballot(out_of_range), __ballot(no_normal),
+                                          __ballot(pair)};
+    if (lane == 0) {
+        my[ACMMP_ALIGN_PLANE_RECORD_N_QUERY] = 0ull;
+        my[ACMMP_ALIGN_PLANE_RECORD_N_VALID] = static_cast<unsigned long long>(__popcll(counts[0]));
+        my[ACMMP_ALIGN_PLANE_RECORD_N_MATCHED] = static_cast<unsigned long long>(__popcll(counts[1]));
+        my[ACMMP_ALIGN_PLANE_RECORD_N_OUT_OF_RANGE] = static_cast<unsigned long long>(__popcll(counts[2]));
+        my[ACMMP_ALIGN_PLANE_RECORD_N_NO_NORMAL] = static_cast<unsigned long long>(__popcll(counts[3]));
+        my[ACMMP_ALIGN_PLANE_RECORD_N] = static_cast<unsigned long long>(__popcll(counts[4]));
+#pragma unroll
+        for (int k = ACMMP_ALIGN_PLANE_RECORD_PIVOT; k < ACMMP_ALIGN_PLANE_RECORD_CC; ++k) my[k] = 0ull;   // the host's, and the 0
+    }
+    align_wave_word(static_cast<unsigned long long>(sum_q), my, ACMMP_ALIGN_PLANE_RECORD_SUM_Q);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) align_wave_word(static_cast<unsigned long long>(Qi[a]), my, ACMMP_ALIGN_PLANE_RECORD_SUM_Q3 + a);
+    // the row c = (L x Nn, Nn) and the residual r: |c_a| < 2^31, |r| < 2^31 (include/acmmp.h), so every product fits
+    long long c[6];
+    c[0] = static_cast<long long>(L[1]) * Nn[2] - static_cast<long long>(L[2]) * Nn[1];
+    c[1] = static_cast<long long>(L[2]) * Nn[0] - static_cast<long long>(L[0]) * Nn[2];
+    c[2] = static_cast<long long>(L[0]) * Nn[1] - static_cast<long long>(L[1]) * Nn[0];
+    c[3] = Nn[0]; c[4] = Nn[1]; c[5] = Nn[2];
+    const long long r = (static_cast<long long>(D[0]) * Nn[0] + static_cast<long long>(D[1]) * Nn[1]) + static_cast<long long>(D[2]) * Nn[2];
+    int k = ACMMP_ALIGN_PLANE_RECORD_CC;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b, k += 2) align_wave_split(c[a] * c[b], my, k);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) align_wave_split(c[a] * r, my, ACMMP_ALIGN_PLANE_RECORD_CR + 2 * a);
+    align_wave_split(r * r, my, ACMMP_ALIGN_PLANE_RECORD_RR);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) rings = max(rings, static_cast<unsigned long long>(__shfl_xor(rings, d)));
+    if (lane == 0 && rings) atomicMax(&words[kDistRings], rings);
+    __syncthreads();
+    if (threadIdx.x < kAlignPlaneWords) {
+        const unsigned long long x = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if (x) atomicAdd(&rec[threadIdx.x], x);
+    }
+    block_or(err, &words[kDistErr]);
+}
+
 static unsigned dist_blocks(unsigned long long n) { return static_cast<unsigned>((n + 255ull) / 256ull); }
 
 hipError_t launch_dist_bounds(DistCloud t, unsigned long long* words, hipStream_t s) {
@@ -2257,6 +2393,15 @@ hipError_t launch_align_iter(DistCloud q, unsigned long long stride, DistCloud t
     const unsigned long long nq = (q.n + stride - 1ull) / stride;
     if (nq == 0) return hipSuccess;
     k_align_iter<<<dist_blocks(nq), 256, 0, s>>>(q, stride, nq, t, g, fine, cg, coarse, list, p, kq, words, rec);
+    return hipGetLastError();
+}
+
+hipError_t launch_align_plane_iter(DistCloud q, unsigned long long stride, DistCloud t, DistGrid g, DistTable fine,
+                                   DistGrid cg, DistTable coarse, const float4* list, DistQuery p, double kq,
+                                   AlignPivot pivot, unsigned long long* words, unsigned long long* rec, hipStream_t s) {
+    const unsigned long long nq = (q.n + stride - 1ull) / stride;
+    if (nq == 0) return hipSuccess;
+    k_align_plane_iter<<<dist_blocks(nq), 256, 0, s>>>(q, stride, nq, t, g, fine, cg, coarse, list, p, kq, pivot, words, rec);
     return hipGetLastError();
 }
 

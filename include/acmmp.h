@@ -824,6 +824,98 @@ acmmp_status acmmp_fusion_cloud_align(acmmp_fusion *f, int source, int mode, flo
 acmmp_status acmmp_fusion_align_records(acmmp_fusion *f, int64_t first, int64_t n, int64_t *words, double *M,
                                         double *shift);
 
+/* ---- point-to-plane registration: the data cloud's own normals (no reference counterpart) ----
+ * acmmp_fusion_cloud_align_plane refines a transform by iterated closest points with a point-to-plane residual.  Two
+ * independent samplings of one surface never hold the same points, and the point-to-point fit above then slides along
+ * the surface; a residual measured along the normal does not.  The fit is rigid only: scale is poorly determined by
+ * plane residuals and does not fit the integer budget of step 3, so a similarity frame is found by
+ * acmmp_fusion_cloud_align first and its M_out is this call's init (NULL: the identity).  The normal of data point i is
+ * floats 3..5 of that point, which every ACMMP_DIST_FROM_* source holds; the reference cloud stays xyz only.  The call
+ * neither reads nor writes the transform that has been set.
+ * Before iteration 0 the call launches one pass of acmmp_fusion_cloud_align's iteration under M_0, which is not an
+ * iteration: it is not recorded and takes no step; the pivot g_0 is taken from its words SUM_Q3 and N as in step 6 (0
+ * when N is 0).  Iteration k = 0, 1, ... under M_k with the pivot g_k (three int64):
+ *  1. Queries and matching.  Exactly step 1 of acmmp_fusion_cloud_align: every stride-th data point read as x' under M_k,
+ *     the float32 d2, the (bits(d2) << 32 | j) key, the cap m2.
+ *  2. Normal, in float64 with no contraction.  With (nx, ny, nz) the data point's normal as doubles,
+ *     u_a = (M[4a] * nx + M[4a+1] * ny) + M[4a+2] * nz, l2 = (u0*u0 + u1*u1) + u2*u2.  The normal is usable when nx, ny, nz
+ *     are finite and l2 is finite and > 0; then Nn_a = (int64) rint(u_a / sqrt(l2) * 4096.0), so |Nn_a| <= 4096.  For a
+ *     rigid or similarity M_k this is the rotated unit normal; for any other init it is still the definition.
+ *  3. Quantisation.  c, kq, P_a and Q_a as in step 2 of acmmp_fusion_cloud_align.  The pair is in range when every |P_a|,
+ *     every |Q_a| and every |Q_a - g_a| is < 2^30; otherwise it counts in n_out_of_range.  An in-range pair whose normal
+ *     is unusable counts in n_no_normal; N counts the rest, and only those enter the moments.  The lever is
+ *     L_a = (Q_a - g_a) >> 12 (arithmetic shift), so |L_a| <= 2^18 and one lever step is max_dist / 16.  D_a = P_a - Q_a.
+ *     |D_a| < 2^17 for a matched pair: d2 <= m2 in float32 gives, per axis, |x'_a - t_a| <= max_dist (1 + 2^-22) -- m2 and
+ *     d2 are each within a few float32 roundings of the exact products, the float32 difference x'_a - t_a is within
+ *     2^-24 relative of the exact one -- so |(x'_a - t_a) kq| <= 65536 (1 + 2^-22) < 65537, and the two rint add at most
+ *     one lattice step: |D_a| <= 65538 < 2^17.  (This needs m2 to be a normal float32, max_dist >= 2^-60; below that a
+ *     product can underflow to 0 <= m2 for a pair further apart than max_dist, and the words are then sums modulo 2^64.)
+ *     Row c = (L x Nn, Nn), six int64: c_0 = L_1 Nn_2 - L_2 Nn_1, c_1 = L_2 Nn_0 - L_0 Nn_2, c_2 = L_0 Nn_1 - L_1 Nn_0,
+ *     c_{3+a} = Nn_a.  Residual r = (D_0 Nn_0 + D_1 Nn_1) + D_2 Nn_2.  |c_a| < 2^31: a quantised unit normal cannot have
+ *     two components of 4096 -- |Nn| <= 4096 + sqrt(3)/2, so |Nn_1| + |Nn_2| <= sqrt(2) |Nn| < 5795 -- and
+ *     |c_0| <= 2^18 (|Nn_1| + |Nn_2|) < 2^18 * 8192.  |r| <= |D| |Nn| < sqrt(3) * 65538 * 4097 < 2^29.  So every product
+ *     of two of c_0..c_5, r is < 2^62 in magnitude: it fits int64, its >> 32 is < 2^30 in magnitude and sums below 2^61
+ *     over up to 2^31 - 1 pairs, and its & 0xffffffff sums below 2^63.
+ *  4. Record.  ACMMP_ALIGN_PLANE_RECORD_WORDS int64 words, only integers are summed: [0..4) n_query, n_valid, n_matched,
+ *     sum_q as acmmp_fusion_cloud_align's record forms them; [4] n_out_of_range; [5] n_no_normal; [6] N; [7..10) the sums
+ *     of Q_a over the N pairs; [10..13) g_k, written by the host as n_query is; [13] 0; [14..56) for the 21 pairs a <= b of
+ *     c_a c_b in row-major order (00, 01, .., 05, 11, .., 55), the sum of w >> 32 and then the sum of w & 0xffffffff;
+ *     [56..68) the same two sums of c_a r for a = 0..5; [68..70) of r r.  The true sum of a product is hi * 2^32 + lo.
+ *  5. Fit.  The host joins the split sums in 128-bit integers, then float64.  S_ab = (double) sum(c_a c_b),
+ *     b_a = -(double) sum(c_a r).  Jacobi scaling: s_a = sqrt(S_aa), S'_ab = S_ab / (s_a s_b), b'_a = b_a / s_a (the
+ *     rotation and the translation columns differ by 2^19 in unit).  S' = sum_i lambda_i v_i v_i^T by cyclic Jacobi
+ *     rotations.  The iteration is degenerate when N < 6, any S_aa is 0, or lambda_min <= lambda_max * 2^-40 -- the rule of
+ *     acmmp_fusion_cloud_align for collinear pairs; a single plane and a cylinder along an axis are degenerate by it.
+ *     Noise floor: the lever's shift rounds (Q_a - g_a) / 4096 down by e_a in [0, 1); the mean of e x Nn is a combination
+ *     of the normal columns, which tau absorbs, and the rest has variance |Nn|^2 / 18 per rotation column, so over the
+ *     pairs the rounding alone puts F = ((S_33 + S_44) + S_55) / 18 on the rotation block's diagonal.  With P the rotation
+ *     block of S^-1, P_ab = (sum_i v_i[a] v_i[b] / lambda_i) / (s_a s_b) for a, b < 3 -- the inverse of what the
+ *     translation columns leave unexplained of the rotation columns -- and mu its largest eigenvalue (cyclic Jacobi), the
+ *     iteration is also degenerate unless 1 > 4 F mu: a rotation that rests on less than four times the levers' rounding
+ *     is not determined.  This is what makes a sphere at its correspondences degenerate: its rotation columns
+ *     (q - G) x n vanish up to that rounding, which the scaling would otherwise normalise to unit diagonal.
+ *     x' = sum_i v_i (v_i . b') / lambda_i, x_a = x'_a / s_a, omega = x_{0..2} / 4096, tau = x_{3..5} / kq: in lattice units
+ *     the linearised residual of a pair is r + c . x.  R = I + A K + B K^2 with K = [omega]x, theta2 =
+ *     |omega|^2, theta = sqrt(theta2); A = sin(theta) / theta, B = (1 - cos(theta)) / theta2 when theta2 >= 2^-40, else
+ *     A = 1 - theta2 / 6, B = 0.5 - theta2 / 24.  G_a = c_a + g_a / kq (c the lattice's corner of step 3), and
+ *     D = (R | G + tau - R G).
+ *  6. Pivot.  g_{k+1,a} = floor((2 * sumQ_a + N) / (2 * N)), a floor division in integers, from iteration k's words [7..10)
+ *     and [6].  The pivot keeps the float64 solve well conditioned when a few far targets stretch the box; it changes
+ *     only what tau means, never the exactness of the integer definition.
+ *  7. Step and stop.  Exactly step 5 of acmmp_fusion_cloud_align: M_{k+1} = D o M_k, shift over the eight corners of the
+ *     valid targets' box, ACMMP_ALIGN_CONVERGED when shift <= min_shift, ACMMP_ALIGN_MAX_ITERATIONS after max_iterations,
+ *     ACMMP_ALIGN_DEGENERATE (M_out = M_k, shift 0) for a degenerate iteration or a step that is not finite.
+ * acmmp_fusion_align_plane_records reads the iterations of the last successful plane call as acmmp_fusion_align_records
+ * does for a point call, ACMMP_ALIGN_PLANE_RECORD_WORDS words per iteration.  The object holds the records of the last
+ * successful align call of either kind: a plane call discards the point records (acmmp_fusion_align_records then refuses
+ * as with none) and a point call discards the plane records; otherwise the plane records follow the point records' rules
+ * with respect to the source, the reference cloud, the transform and acmmp_fusion_set_view.  Neither call touches the
+ * distance result or the installed transform.
+ * The argument checks (there is no mode), the stop reasons, "any error leaves the object as it was", the forced cell and
+ * acmmp_fusion_distance_grid's outputs are acmmp_fusion_cloud_align's.  An iteration is one launch that reduces its words
+ * over the wave and the workgroup and issues one integer atomic add per word per workgroup.  Device memory: a distance
+ * call's scratch (no per-query array) and the 70 words.  The host waits for the targets' bounding box, for the pivot pass
+ * and once per iteration. */
+#define ACMMP_ALIGN_PLANE_RECORD_N_QUERY 0
+#define ACMMP_ALIGN_PLANE_RECORD_N_VALID 1
+#define ACMMP_ALIGN_PLANE_RECORD_N_MATCHED 2
+#define ACMMP_ALIGN_PLANE_RECORD_SUM_Q 3
+#define ACMMP_ALIGN_PLANE_RECORD_N_OUT_OF_RANGE 4
+#define ACMMP_ALIGN_PLANE_RECORD_N_NO_NORMAL 5
+#define ACMMP_ALIGN_PLANE_RECORD_N 6
+#define ACMMP_ALIGN_PLANE_RECORD_SUM_Q3 7    /* 3 words: the sums of Q_a */
+#define ACMMP_ALIGN_PLANE_RECORD_PIVOT 10    /* 3 words: g_k, host-written */
+#define ACMMP_ALIGN_PLANE_RECORD_ZERO 13     /* 1 word: 0 */
+#define ACMMP_ALIGN_PLANE_RECORD_CC 14       /* 42 words: (hi, lo) of c_a c_b, a <= b, row-major */
+#define ACMMP_ALIGN_PLANE_RECORD_CR 56       /* 12 words: (hi, lo) of c_a r */
+#define ACMMP_ALIGN_PLANE_RECORD_RR 68       /* 2 words: (hi, lo) of r r */
+#define ACMMP_ALIGN_PLANE_RECORD_WORDS 70
+acmmp_status acmmp_fusion_cloud_align_plane(acmmp_fusion *f, int source, float max_dist, int max_iterations,
+                                            int stride, double min_shift, const double init[12], double M_out[12],
+                                            int *n_iterations, int *stop_reason);
+acmmp_status acmmp_fusion_align_plane_records(acmmp_fusion *f, int64_t first, int64_t n, int64_t *words, double *M,
+                                              double *shift);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D

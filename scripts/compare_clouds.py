@@ -3,10 +3,13 @@
 and set_reference_cloud.  For two runs of the pipeline, for example --math exact against --math fast.
 
     python scripts/compare_clouds.py A.ply B.ply --max-dist 0.02 --threshold 0.005 --threshold 0.01 [--out eval.json]
-                                     [--align rigid|similarity [--align-max-dist D] [--align-iterations K] [--align-stride S]]
+                                     [--align rigid|similarity [--align-max-dist D] [--align-iterations K] [--align-stride S]
+                                      [--align-plane-iterations N]]
 
 A is the data cloud, B the reference cloud; both are PLYs of the pipeline's layout.  With --align, A is first registered
 to B on the GPU (acmmp_fusion_cloud_align) and measured under that transform, which the output then holds under "align".
+With --align-plane-iterations, up to N rigid point-to-plane iterations along A's normals
+(acmmp_fusion_cloud_align_plane) then refine that transform, and "align" gains "plane".
 Prints the figures as one JSON line (pipeline.evaluate_clouds)."""
 import argparse
 import json
@@ -18,25 +21,30 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "acmmp-spherical_amd"))
 
-from acmmp import capi, pipeline  # noqa: E402
+from acmmp import capi, io, pipeline  # noqa: E402
 
 
 def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=None, align_max_dist=None,
-            align_iterations=30, align_stride=1):
+            align_iterations=30, align_stride=1, align_plane_iterations=None, a_normals=None):
     """evaluate_clouds of cloud A (n, 3) against cloud B, after align_clouds when align is "rigid" or "similarity";
-    make: the fusion object's factory (tests)."""
+    align_plane_iterations: its point-to-plane stage, along a_normals (n, 3).  make: the fusion object's factory
+    (tests)."""
+    if align_plane_iterations is not None and (align is None or a_normals is None):
+        raise ValueError("the plane stage needs align and A's normals")
     cam = np.zeros(1, capi.CAMERA_DTYPE)
     cam["width"], cam["height"] = 8, 8                        # the object needs a camera; no view is used
     fu = (make or (lambda c: capi.Fusion(device, c)))(cam)
     try:
         pts = np.zeros((len(a_xyz), 9), np.float32)
         pts[:, :3] = a_xyz
+        if a_normals is not None:
+            pts[:, 3:6] = a_normals
         fu.set_scene(pts)
         fu.set_reference_cloud(b_xyz)
         registered = None
         if align is not None:
             registered = pipeline.align_clouds(fu, "scene", align, max_dist if align_max_dist is None else align_max_dist,
-                                               align_iterations, align_stride)
+                                               align_iterations, align_stride, plane_iterations=align_plane_iterations)
         info = pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
         if registered is not None:
             info["align"] = registered
@@ -56,12 +64,20 @@ def main(argv=None):
     ap.add_argument("--align-max-dist", type=float, default=None, help="default: --max-dist")
     ap.add_argument("--align-iterations", type=int, default=30)
     ap.add_argument("--align-stride", type=int, default=1)
+    ap.add_argument("--align-plane-iterations", type=int, default=None,
+                    help="with --align: then at most this many point-to-plane iterations along A's normals")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
+    if a.align_plane_iterations is not None and a.align is None:
+        ap.error("--align-plane-iterations needs --align")
+    normals = None
+    if a.align_plane_iterations is not None:
+        rec = io.read_ply(a.a)
+        normals = np.stack([rec["nx"], rec["ny"], rec["nz"]], 1)
     info = compare(pipeline.reference_xyz(a.a), pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device,
                    align=a.align, align_max_dist=a.align_max_dist, align_iterations=a.align_iterations,
-                   align_stride=a.align_stride)
+                   align_stride=a.align_stride, align_plane_iterations=a.align_plane_iterations, a_normals=normals)
     info.update(a=a.a, b=a.b)
     if a.out:
         with open(a.out, "w") as f:
