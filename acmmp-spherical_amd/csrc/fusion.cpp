@@ -42,11 +42,49 @@ struct SceneBuf {
     size_t cap = 0;                              // points allocated
 };
 
-// The arrays of the voxel hash table; VoxTable holds their addresses for the device.
+int log2_ceil(unsigned long long x) {
+    int l = 0;
+    while ((1ull << l) < x) ++l;
+    return l;
+}
+
+// The arrays of the voxel hash table; view() holds their addresses for the device.
 struct VoxTableBuf {
     DevBuf<unsigned long long> keys, first, oid;
     DevBuf<uint32_t> cnt;
     unsigned long long slots = 0;
+    VoxTable view() const { return {keys, first, oid, cnt, slots, log2_ceil(slots)}; }
+    // every slot empty
+    hipError_t reset_async(hipStream_t s) const {
+        hipError_t e = hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * slots, s);
+        if (e == hipSuccess) e = hipMemsetAsync(first, 0xff, sizeof(unsigned long long) * slots, s);
+        if (e == hipSuccess) e = hipMemsetAsync(oid, 0xff, sizeof(unsigned long long) * slots, s);
+        if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(uint32_t) * slots, s);
+        return e;
+    }
+};
+
+// The scratch of the ordered compactions (Compaction, fusion.h), one segment's worth: every stage's passes borrow it.
+struct SegScratch {
+    DevBuf<int> flags;                           // per item of a segment
+    DevBuf<int> counts, offsets;                 // per 256-item chunk of a segment
+    DevBuf<int> seg_count;
+    DevBuf<unsigned long long> words;            // running, seg_base
+    size_t cap = 0;                              // items of a segment allocated
+    // room for segments of n items (exact size: contents are not kept)
+    hipError_t reserve(size_t n) {
+        hipError_t e = hipSuccess;
+        if (!seg_count) e = seg_count.alloc(1);
+        if (e == hipSuccess && !words) e = words.alloc(2);
+        if (e != hipSuccess || cap >= n) return e;
+        cap = 0;
+        e = flags.alloc(n);
+        if (e == hipSuccess) e = counts.alloc((n + 255) / 256);
+        if (e == hipSuccess) e = offsets.alloc((n + 255) / 256);
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+    Compaction view(unsigned long long out_cap) const { return {flags, counts, offsets, seg_count, words, words + 1, out_cap}; }
 };
 
 }  // namespace
@@ -74,7 +112,7 @@ struct acmmp_fusion {
     DevBuf<int> d_view_counts;                   // per reference view
     DevBuf<unsigned long long> d_view_base;      // per reference view: scene offset of its first point
     size_t cap_refs = 0;
-    DevBuf<unsigned long long> d_running;        // running scene offset
+    DevBuf<unsigned long long> d_running;        // running scene offset of a scene pass
     PinnedBuf<int> h_count;                      // the one word the host reads per view
     bool s_have = false;                         // a run_scene has succeeded
     // voxel-grid reduction of the scene result (acmmp_fusion_voxelize): its resident result ...
@@ -89,11 +127,8 @@ struct acmmp_fusion {
     VoxGrid v_grid = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // origin and size of the voxel result held
     // ... and its scratch, kept between runs and dropped with the scene result it was sized for
     VoxTableBuf v_tab, v_tab_spare;              // v_tab_spare: filled by a voxelize while v_tab belongs to a result
-    DevBuf<int> v_flags;                         // per point of a segment
-    DevBuf<int> v_counts, v_offsets;             // per 256-point chunk of a segment
-    size_t v_cap_seg = 0;
-    DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the segment base, then 3 minima (as 2 words)
-    DevBuf<int> v_seg_count;
+    SegScratch seg;                              // of voxelize's compaction and of every later stage's
+    DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the 3 minima (32-bit each, in 2 words)
     // cleaning of the voxel result (acmmp_fusion_voxel_clean): its resident result
     DevBuf<float> c_pts;                         // 9 floats per kept voxel
     DevBuf<int32_t> c_cnt;                       // points per kept voxel
@@ -318,8 +353,7 @@ void voxel_scratch_release(acmmp_fusion* f) {
     f->v_tab = VoxTableBuf();
     f->v_tab_spare = VoxTableBuf();
     f->v_tab_live = false;
-    f->v_flags.reset(); f->v_counts.reset(); f->v_offsets.reset();
-    f->v_cap_seg = 0;
+    f->seg = SegScratch();
 }
 
 // m_source of a mesh that acmmp_fusion_set_mesh installed: no result is its source.
@@ -636,28 +670,43 @@ struct VoxelOut {
     DevBuf<unsigned long long> vslot;        // scratch: table slot per kept voxel
 };
 
-// The per-segment scratch of the compactions (voxelize's per point, clean's per voxel).
-acmmp_status segment_scratch(acmmp_fusion* f, size_t seg_pts) {
-    if (!f->v_seg_count) F_HIP(f, alloc(f->v_seg_count, 1));
-    if (f->v_cap_seg < seg_pts) {
-        const size_t seg_chunks = (seg_pts + 255) / 256;
-        f->v_cap_seg = 0;
-        F_HIP(f, alloc(f->v_flags, seg_pts));
-        F_HIP(f, alloc(f->v_counts, seg_chunks));
-        F_HIP(f, alloc(f->v_offsets, seg_chunks));
-        f->v_cap_seg = seg_pts;
+// fn(i0, n) over the items [0, N) in segments of voxel_segment_points(), in ascending order; the first error ends it.
+template <class Fn>
+hipError_t for_segments(unsigned long long N, Fn fn) {
+    const unsigned long long seg = voxel_segment_points();
+    for (unsigned long long i0 = 0; i0 < N; i0 += seg) {
+        const hipError_t e = fn(i0, static_cast<int>(std::min(seg, N - i0)));
+        if (e != hipSuccess) return e;
     }
-    return ACMMP_OK;
+    return hipSuccess;
+}
+
+// The scratch for compaction passes over up to N items.
+hipError_t segment_reserve(acmmp_fusion* f, unsigned long long N) {
+    return f->seg.reserve(static_cast<size_t>(std::min(N, voxel_segment_points())));
+}
+
+// One ordered compaction of the items [0, N) into at most `cap` outputs, all in stream order: launch(i0, n, c) per
+// segment (a stage's launcher, see Compaction), then the copy of the number compacted to *done, which holds it after
+// the caller's next wait for the stream.
+template <class Launch>
+hipError_t compact_pass(acmmp_fusion* f, unsigned long long N, unsigned long long cap, unsigned long long* done,
+                        Launch launch) {
+    const Compaction c = f->seg.view(cap);
+    hipError_t e = hipMemsetAsync(c.running, 0, sizeof(unsigned long long), f->stream);
+    if (e == hipSuccess) e = for_segments(N, [&](unsigned long long i0, int n) { return launch(i0, n, c); });
+    if (e == hipSuccess) e = hipMemcpyAsync(done, c.running, sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream);
+    return e;
 }
 
 // `tab`: the table the run fills -- the object's scratch table, or a new one while the object's belongs to the
 // voxel result held, which a failed run must leave usable.
 acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_points, unsigned long long slots,
-                       int log2_slots, VoxTableBuf& tab, VoxelOut& out, unsigned long long words[kVoxWords]) {
+                       VoxTableBuf& tab, VoxelOut& out, unsigned long long words[kVoxWords]) {
     hipStream_t s = f->stream;
-    const unsigned long long N = f->s_total, seg = voxel_segment_points();
+    const unsigned long long N = f->s_total;
     // scratch
-    if (!f->v_words) F_HIP(f, alloc(f->v_words, kVoxWords + 3));
+    if (!f->v_words) F_HIP(f, alloc(f->v_words, kVoxWords + 2));
     if (tab.slots != slots) {
         tab.slots = 0;
         F_HIP(f, alloc(tab.keys, slots));
@@ -666,24 +715,15 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
         F_HIP(f, alloc(tab.cnt, slots));
         tab.slots = slots;
     }
-    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(N, seg)));
-    if (scratch != ACMMP_OK) return scratch;
-    const VoxTable t = {tab.keys, tab.first, tab.oid, tab.cnt, slots, log2_slots};
+    F_HIP(f, segment_reserve(f, N));
+    const VoxTable t = tab.view();
     unsigned long long* st = f->v_words;
-    unsigned long long* seg_base = f->v_words + kVoxWords;
-    uint32_t* mn = reinterpret_cast<uint32_t*>(f->v_words + kVoxWords + 1);
-    F_HIP(f, hipMemsetAsync(st, 0, sizeof(unsigned long long) * (kVoxWords + 1), s));
-    auto segments = [&](auto&& fn) -> hipError_t {
-        for (unsigned long long i0 = 0; i0 < N; i0 += seg) {
-            const hipError_t e = fn(i0, static_cast<int>(std::min(seg, N - i0)));
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    };
+    uint32_t* mn = reinterpret_cast<uint32_t*>(f->v_words + kVoxWords);
+    F_HIP(f, hipMemsetAsync(st, 0, sizeof(unsigned long long) * kVoxWords, s));
     if (find_origin) {
         uint32_t h_mn[3];
         F_HIP(f, hipMemsetAsync(mn, 0xff, sizeof(uint32_t) * 4, s));
-        F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_min(f->scene.pts, i0, n, mn, s); }));
+        F_HIP(f, for_segments(N, [&](unsigned long long i0, int n) { return launch_voxel_min(f->scene.pts, i0, n, mn, s); }));
         F_HIP(f, hipMemcpyAsync(h_mn, mn, sizeof(h_mn), hipMemcpyDeviceToHost, s));
         F_HIP(f, hipStreamSynchronize(s));
         // no point passed the finiteness test: the origin is (0, 0, 0), and every point is rejected below
@@ -693,11 +733,8 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
         g.oz = any ? vox_decode_ordered(h_mn[2]) : 0.0f;
     }
     // insert pass, then the table's counts
-    F_HIP(f, hipMemsetAsync(t.keys, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(t.first, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(t.oid, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(t.cnt, 0, sizeof(uint32_t) * slots, s));
-    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_insert(f->scene.pts, i0, n, g, t, st, s); }));
+    F_HIP(f, tab.reset_async(s));
+    F_HIP(f, for_segments(N, [&](unsigned long long i0, int n) { return launch_voxel_insert(f->scene.pts, i0, n, g, t, st, s); }));
     F_HIP(f, launch_voxel_stats(t, min_points, st, s));
     F_HIP(f, hipMemcpyAsync(words, st, sizeof(unsigned long long) * kVoxWords, hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
@@ -709,18 +746,15 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
     F_HIP(f, alloc(out.vslot, static_cast<size_t>(kept)));
     if (kept == 0) return ACMMP_OK;
     // compaction in order of first appearance, the sums, the means
-    F_HIP(f, hipMemsetAsync(f->d_running, 0, sizeof(unsigned long long), s));
+    unsigned long long end[2] = {0, 0};                                  // error word, voxels compacted
     F_HIP(f, hipMemsetAsync(out.sums, 0, sizeof(unsigned long long) * 9 * kept, s));
     F_HIP(f, hipMemsetAsync(out.vslot, 0xff, sizeof(unsigned long long) * kept, s));
-    F_HIP(f, segments([&](unsigned long long i0, int n) {
-        return launch_voxel_compact(f->scene.pts, i0, n, g, t, min_points, f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count,
-                                    f->d_running, seg_base, kept, out.vslot, st, s);
+    F_HIP(f, compact_pass(f, N, kept, &end[1], [&](unsigned long long i0, int n, Compaction c) {
+        return launch_voxel_compact(f->scene.pts, i0, n, g, t, min_points, c, out.vslot, st, s);
     }));
-    F_HIP(f, segments([&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->scene.pts, i0, n, g, t, out.sums, st, s); }));
+    F_HIP(f, for_segments(N, [&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->scene.pts, i0, n, g, t, out.sums, st, s); }));
     F_HIP(f, launch_voxel_finalise(kept, out.vslot, t, out.sums, g, out.pts, out.cnt, s));
-    unsigned long long end[2] = {0, 0};                                  // error word, voxels compacted
     F_HIP(f, hipMemcpyAsync(&end[0], st + kVoxErr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    F_HIP(f, hipMemcpyAsync(&end[1], f->d_running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
     if (end[0] || end[1] != kept)
         return ffail(f, ACMMP_ERR_HIP, "voxel table: lookup failed (flags " + std::to_string(end[0]) + ", compacted " +
@@ -751,8 +785,6 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
         if (N > (1ull << 61)) return ffail(f, ACMMP_ERR_UNSUPPORTED, "scene too large for the voxel table");
         while (slots < 2 * N) slots <<= 1;
     }
-    int log2_slots = 0;
-    while ((1ull << log2_slots) < slots) ++log2_slots;
     F_HIP(f, hipSetDevice(f->device));
     VoxGrid g;
     g.ox = origin ? origin[0] : 0.0f;
@@ -768,7 +800,7 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     VoxTableBuf tab = std::move(from);
     from = VoxTableBuf();
     if (N > 0) {
-        const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, log2_slots, tab, out, words);
+        const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, tab, out, words);
         if (st != ACMMP_OK) {
             const std::string why = f->err;
             (void)hipGetLastError();
@@ -846,17 +878,14 @@ struct CleanOut {
 acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, unsigned long long min_voxels,
                        unsigned long long min_points, CleanOut& out) {
     hipStream_t s = f->stream;
-    const unsigned long long nv = f->v_total, seg = voxel_segment_points();
+    const unsigned long long nv = f->v_total;
     const size_t n = static_cast<size_t>(nv);
     if (!f->c_words) F_HIP(f, alloc(f->c_words, kCleanWords));
-    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(nv, seg)));
-    if (scratch != ACMMP_OK) return scratch;
+    F_HIP(f, segment_reserve(f, nv));
     F_HIP(f, alloc(out.lab, n));
     F_HIP(f, alloc(out.mask, n));
     F_HIP(f, alloc(out.scratch, 3 * n));
-    int log2_slots = 0;
-    while ((1ull << log2_slots) < f->v_tab.slots) ++log2_slots;
-    const VoxTable t = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, f->v_tab.slots, log2_slots};
+    const VoxTable t = f->v_tab.view();
     unsigned long long* w = f->c_words;
     const CleanComp c = {out.scratch, out.scratch + n, out.scratch + 2 * n, min_voxels, min_points};
     unsigned long long h[kCleanWords] = {0};
@@ -890,20 +919,13 @@ acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, un
     F_HIP(f, alloc(out.comp, nk));
     F_HIP(f, alloc(out.vox, nk));
     // the roots, then the kept voxels, each compacted in voxel order, segment after segment
-    unsigned long long* running = w + kCleanRunning;
-    unsigned long long* seg_base = w + kCleanSegBase;
     unsigned long long done[2] = {0, 0};
-    for (unsigned long long i0 = 0; i0 < nv; i0 += seg)
-        F_HIP(f, launch_clean_compact_roots(nv, i0, static_cast<int>(std::min(seg, nv - i0)), out.lab, c, f->v_flags,
-                                            f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.comps,
-                                            out.table, out.table + nc, out.table + 2 * nc, s));
-    F_HIP(f, hipMemcpyAsync(&done[0], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
-    for (unsigned long long i0 = 0; i0 < nv; i0 += seg)
-        F_HIP(f, launch_clean_compact_kept(nv, i0, static_cast<int>(std::min(seg, nv - i0)), out.lab, c, f->v_flags,
-                                           f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
-                                           f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, out.vox, s));
-    F_HIP(f, hipMemcpyAsync(&done[1], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, compact_pass(f, nv, out.comps, &done[0], [&](unsigned long long i0, int m, Compaction k) {
+        return launch_clean_compact_roots(nv, i0, m, out.lab, c, k, out.table, out.table + nc, out.table + 2 * nc, s);
+    }));
+    F_HIP(f, compact_pass(f, nv, out.kept, &done[1], [&](unsigned long long i0, int m, Compaction k) {
+        return launch_clean_compact_kept(nv, i0, m, out.lab, c, k, f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, out.vox, s);
+    }));
     F_HIP(f, hipStreamSynchronize(s));
     if (done[0] != out.comps || done[1] != out.kept)
         return ffail(f, ACMMP_ERR_HIP, "voxel clean: compacted " + std::to_string(done[0]) + " of " + std::to_string(out.comps) +
@@ -1031,11 +1053,9 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
                             int n_list, const int* views, float rel_tol, int radius, int min_support, int max_conflicts,
                             VisOut& out) {
     hipStream_t s = f->stream;
-    const unsigned long long seg = voxel_segment_points();
     if (!f->vis_words) F_HIP(f, alloc(f->vis_words, kVisWords));
     if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
-    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(N, seg)));
-    if (scratch != ACMMP_OK) return scratch;
+    F_HIP(f, segment_reserve(f, N));
     F_HIP(f, alloc(out.tal, 3 * static_cast<size_t>(N)));
     unsigned long long* w = f->vis_words;
     unsigned long long h[kVisWords] = {0};
@@ -1057,14 +1077,11 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
     F_HIP(f, alloc(out.kept_tal, 3 * nk));
     F_HIP(f, alloc(out.vox, nk));
     // the kept entries, compacted in entry order, segment after segment
-    unsigned long long* running = w + kVisRunning;
-    unsigned long long* seg_base = w + kVisSegBase;
     unsigned long long done = 0;
-    for (unsigned long long i0 = 0; i0 < N; i0 += seg)
-        F_HIP(f, launch_vis_compact(i0, static_cast<int>(std::min(seg, N - i0)), out.tal, min_support, max_conflicts,
-                                    f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.kept,
-                                    src_pts, src_cnt, out.pts, out.cnt, out.kept_tal, src_vox, out.vox, s));
-    F_HIP(f, hipMemcpyAsync(&done, running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, compact_pass(f, N, out.kept, &done, [&](unsigned long long i0, int n, Compaction c) {
+        return launch_vis_compact(i0, n, out.tal, min_support, max_conflicts, c, src_pts, src_cnt, out.pts, out.cnt,
+                                  out.kept_tal, src_vox, out.vox, s);
+    }));
     F_HIP(f, hipStreamSynchronize(s));
     if (done != out.kept)
         return ffail(f, ACMMP_ERR_HIP, "voxel visibility: compacted " + std::to_string(done) + " of " +
@@ -1161,7 +1178,8 @@ namespace {
 
 // The sample table of one mesh call (scratch) and the new result, swapped in only when the whole call succeeded.
 struct MeshOut {
-    DevBuf<unsigned long long> keys, rank, ent, sid;       // the table
+    DevBuf<unsigned long long> keys, rank, ent, sid;       // the table, `slots` of each
+    unsigned long long slots = 0;
     DevBuf<unsigned long long> ekey;                       // per entry
     DevBuf<uint8_t> cflag, fbits;                          // per sample
     DevBuf<int32_t> vid;                                   // per sample
@@ -1171,40 +1189,39 @@ struct MeshOut {
     DevBuf<long long> sent;
     unsigned long long nv = 0, nf = 0, ns = 0, valid = 0, cubes = 0, uncoloured = 0;
     long long stats[4] = {0, 0, 0, 0};
+    MeshTable table() const { return {keys, rank, ent, sid, slots, log2_ceil(slots)}; }
+    // every slot empty
+    hipError_t table_reset_async(hipStream_t s) const {
+        hipError_t e = hipSuccess;
+        for (unsigned long long* a : {keys.get(), rank.get(), ent.get(), sid.get()})
+            if (e == hipSuccess) e = hipMemsetAsync(a, 0xff, sizeof(unsigned long long) * slots, s);
+        return e;
+    }
 };
 
 acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long long* src_vox, unsigned long long ne,
                       int n_list, const int* views, float trunc, int min_weight, unsigned long long slots, MeshOut& out) {
     hipStream_t s = f->stream;
-    const unsigned long long seg = voxel_segment_points(), pairs = 27ull * ne;
+    const unsigned long long pairs = 27ull * ne;
     if (!f->m_words) F_HIP(f, alloc(f->m_words, kMeshWords));
     if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
-    const acmmp_status scratch = segment_scratch(f, static_cast<size_t>(std::min(pairs, seg)));
-    if (scratch != ACMMP_OK) return scratch;
-    int log2_slots = 0, v_log2 = 0;
-    while ((1ull << log2_slots) < slots) ++log2_slots;
-    while ((1ull << v_log2) < f->v_tab.slots) ++v_log2;
+    F_HIP(f, segment_reserve(f, pairs));
     F_HIP(f, alloc(out.keys, slots));
     F_HIP(f, alloc(out.rank, slots));
     F_HIP(f, alloc(out.ent, slots));
     F_HIP(f, alloc(out.sid, slots));
+    out.slots = slots;
     F_HIP(f, alloc(out.ekey, static_cast<size_t>(ne)));
-    const VoxTable vt = {f->v_tab.keys, f->v_tab.first, f->v_tab.oid, f->v_tab.cnt, f->v_tab.slots, v_log2};
-    const MeshTable m = {out.keys, out.rank, out.ent, out.sid, slots, log2_slots};
+    const VoxTable vt = f->v_tab.view();
+    const MeshTable m = out.table();
     unsigned long long* w = f->m_words;
-    unsigned long long* running = w + kMeshRunning;
-    unsigned long long* seg_base = w + kMeshSegBase;
     unsigned long long h[kMeshWords] = {0};
     F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kMeshWords, s));
-    F_HIP(f, hipMemsetAsync(m.keys, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(m.rank, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(m.ent, 0xff, sizeof(unsigned long long) * slots, s));
-    F_HIP(f, hipMemsetAsync(m.sid, 0xff, sizeof(unsigned long long) * slots, s));
+    F_HIP(f, out.table_reset_async(s));
     F_HIP(f, hipMemcpyAsync(f->vis_list, views, sizeof(int) * n_list, hipMemcpyHostToDevice, s));
     // the samples: insert, then the table's counts
     F_HIP(f, launch_mesh_keys(ne, src_vox, f->v_total, f->v_slot, vt, out.ekey, w, s));
-    for (unsigned long long p0 = 0; p0 < pairs; p0 += seg)
-        F_HIP(f, launch_mesh_insert(p0, static_cast<int>(std::min(seg, pairs - p0)), out.ekey, m, w, s));
+    F_HIP(f, for_segments(pairs, [&](unsigned long long p0, int n) { return launch_mesh_insert(p0, n, out.ekey, m, w, s); }));
     F_HIP(f, launch_mesh_stats(m, w, s));
     // the first host wait: the sample count, to size the per-sample arrays
     F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
@@ -1219,8 +1236,7 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
     if (out.ns > pairs) return ffail(f, ACMMP_ERR_HIP, "voxel mesh: more samples than (entry, offset) pairs");
     const size_t ns = static_cast<size_t>(out.ns);
     // the compactions run over the 27 ne pairs, the ns samples and the 3 ns (sample, axis) pairs
-    const acmmp_status scratch2 = segment_scratch(f, static_cast<size_t>(std::min(std::max(pairs, 3ull * out.ns), seg)));
-    if (scratch2 != ACMMP_OK) return scratch2;
+    F_HIP(f, segment_reserve(f, std::max(pairs, 3ull * out.ns)));
     F_HIP(f, alloc(out.skey, ns));
     F_HIP(f, alloc(out.tsdf, 2 * ns));
     F_HIP(f, alloc(out.sent, ns));
@@ -1228,12 +1244,10 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
     F_HIP(f, alloc(out.fbits, ns));
     F_HIP(f, alloc(out.vid, ns));
     const MeshSamples smp = {out.skey, out.tsdf, out.sent, out.ns};
-    for (unsigned long long p0 = 0; p0 < pairs; p0 += seg)
-        F_HIP(f, launch_mesh_number(p0, static_cast<int>(std::min(seg, pairs - p0)), out.ekey, m, f->v_flags, f->v_counts,
-                                    f->v_offsets, f->v_seg_count, running, seg_base, smp, w, s));
     unsigned long long done[3] = {0, 0, 0};
-    F_HIP(f, hipMemcpyAsync(&done[0], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
+    F_HIP(f, compact_pass(f, pairs, out.ns, &done[0], [&](unsigned long long p0, int n, Compaction c) {
+        return launch_mesh_number(p0, n, out.ekey, m, c, smp, w, s);
+    }));
     // the distances, the cubes, the pairs that emit faces
     F_HIP(f, launch_mesh_tsdf(f->model, f->d_cams, f->d_views, f->vis_list, n_list, smp, f->v_grid, trunc, s));
     F_HIP(f, launch_mesh_cubes(smp, m, min_weight, out.cflag, out.fbits, w, s));
@@ -1253,18 +1267,12 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
     F_HIP(f, alloc(out.verts, 9 * static_cast<size_t>(out.nv)));
     F_HIP(f, alloc(out.faces, 6 * static_cast<size_t>(n_pairs)));
     F_HIP(f, hipMemsetAsync(out.vid, 0xff, sizeof(int32_t) * ns, s));
-    for (unsigned long long i0 = 0; i0 < out.ns; i0 += seg)
-        F_HIP(f, launch_mesh_vertices(i0, static_cast<int>(std::min(seg, out.ns - i0)), smp, m, f->v_grid, out.cflag, src_pts,
-                                      f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, out.nv,
-                                      out.verts, out.vid, w, s));
-    F_HIP(f, hipMemcpyAsync(&done[1], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    F_HIP(f, hipMemsetAsync(running, 0, sizeof(unsigned long long), s));
-    const unsigned long long fp = 3ull * out.ns;
-    for (unsigned long long p0 = 0; p0 < fp; p0 += seg)
-        F_HIP(f, launch_mesh_faces(p0, static_cast<int>(std::min(seg, fp - p0)), smp, m, out.cflag, out.fbits, out.vid,
-                                   f->v_flags, f->v_counts, f->v_offsets, f->v_seg_count, running, seg_base, n_pairs,
-                                   out.faces, w, s));
-    F_HIP(f, hipMemcpyAsync(&done[2], running, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    F_HIP(f, compact_pass(f, out.ns, out.nv, &done[1], [&](unsigned long long i0, int n, Compaction c) {
+        return launch_mesh_vertices(i0, n, smp, m, f->v_grid, out.cflag, src_pts, c, out.verts, out.vid, w, s);
+    }));
+    F_HIP(f, compact_pass(f, 3ull * out.ns, n_pairs, &done[2], [&](unsigned long long p0, int n, Compaction c) {
+        return launch_mesh_faces(p0, n, smp, m, out.cflag, out.fbits, out.vid, c, out.faces, w, s);
+    }));
     // the third host wait: the end
     F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
@@ -1611,8 +1619,7 @@ acmmp_status distance_build(acmmp_fusion* f, DistCloud t, float max_dist, int n_
             out.cell = cell;
             unsigned long long slots = 1024;
             while (slots < 2 * t.n) slots <<= 1;
-            int log2_slots = 0;
-            while ((1ull << log2_slots) < slots) ++log2_slots;
+            const int log2_slots = log2_ceil(slots);
             F_HIP(f, alloc(out.keys, slots));
             F_HIP(f, alloc(out.start, slots));
             F_HIP(f, alloc(out.cnt, slots));

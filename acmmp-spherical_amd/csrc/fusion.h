@@ -41,6 +41,22 @@ hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const
                                      unsigned long long cap, float* out, int* out_ref, int* out_pix, uint32_t* out_mask,
                                      hipStream_t s);
 
+// Ordered compaction of one segment of a stage's items (points, voxels, entries, pairs, samples), in stream order with
+// no host step.  A mark kernel writes flags[i] = item i0 + i is kept and counts[chunk] per 256 items; k_fuse_scan turns
+// the counts into offsets and sets *seg_count = the segment's kept items, *seg_base = *running, *running += *seg_count;
+// a scatter kernel gives kept item i the output position *seg_base + offsets[chunk] + its rank in the chunk and writes
+// it there.  Nothing is written at or past `cap` outputs.  A pass zeroes *running, runs its segments (n <= 2^30 each:
+// the offsets are 32-bit) in ascending order and ends with *running = the kept items of the whole pass.
+struct Compaction {
+    int* flags;                        // per item of a segment
+    int* counts;                       // per 256-item chunk of a segment
+    int* offsets;
+    int* seg_count;
+    unsigned long long* running;
+    unsigned long long* seg_base;
+    unsigned long long cap;
+};
+
 // Voxel-grid reduction of a scene cloud (acmmp_fusion_voxelize, include/acmmp.h).  Every launcher
 // covers points [i0, i0 + n) of `pts` (9 floats each, n <= 2^30: one segment), one lane per point.
 struct VoxGrid {
@@ -76,13 +92,10 @@ hipError_t launch_voxel_insert(const float* pts, unsigned long long i0, int n, V
 // Over the slots: st[kVoxOccupied], st[kVoxKept] (cnt >= min_points), st[kVoxWrapped] (stored below the home slot),
 // st[kVoxMaxProbe] (largest distance from the home slot + 1).
 hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st, hipStream_t s);
-// Compaction of one segment, in stream order: flags[i] = point i0 + i is the first of a kept voxel, the chunk
-// counts, their scan (k_fuse_scan: *seg_base = *running, *running += the segment's count), then per flagged
-// point oid[slot] = *seg_base + rank and vslot[that id] = slot; nothing is written at or past `cap` ids.
+// One segment, see Compaction: the points that are the first of a kept voxel; per kept point oid[slot] = its position
+// and vslot[that id] = slot.  st[kVoxErr] |= 2 (mark) or 4 (scatter) for a failed lookup.
 hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
-                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
-                                unsigned long long* st, hipStream_t s);
+                                Compaction c, unsigned long long* vslot, unsigned long long* st, hipStream_t s);
 // sums[9 * oid + k] += the point's quantised channel k (64-bit integer adds), for points of kept voxels.
 hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
                                    unsigned long long* sums, unsigned long long* st, hipStream_t s);
@@ -94,7 +107,7 @@ hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long
 // voxel result, vslot[v] their slots in the table `t` that voxelize filled, one lane per voxel.
 // Device words of a clean run (all zero before it; kCleanChanged is zeroed before every round).
 enum { kCleanErr = 0, kCleanChanged = 1, kCleanUnsupported = 2, kCleanComps = 3, kCleanCompsKept = 4, kCleanKept = 5,
-       kCleanRunning = 6, kCleanSegBase = 7, kCleanWords = 8 };
+       kCleanWords = 6 };
 // Per-voxel scratch of the component table, meaningful at a component's root (its smallest voxel): voxels, points
 // (both zero before the run), dense id; and the two thresholds of step 5.
 struct CleanComp {
@@ -116,17 +129,14 @@ hipError_t launch_clean_round(unsigned long long nv, const unsigned long long* v
 // After the last round: c.voxels / c.points at every root, then words[kCleanComps], [kCleanCompsKept], [kCleanKept].
 hipError_t launch_clean_sizes(unsigned long long nv, const unsigned long long* lab, const int32_t* cnt, CleanComp c,
                               unsigned long long* words, hipStream_t s);
-// Compaction of voxels [i0, i0 + n) (one segment, as launch_voxel_compact): the roots to the component table and
-// c.id[root]; then, once every segment's roots are through, the kept voxels to the clean cloud (out_vox: their
-// voxel index).  Nothing is written at or past `cap` entries.
+// Voxels [i0, i0 + n), one segment, see Compaction: the roots to the component table and c.id[root]; then, once every
+// segment's roots are through, the kept voxels to the clean cloud (out_vox: their voxel index).
 hipError_t launch_clean_compact_roots(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
-                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
-                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                      long long* out_root, long long* out_voxels, long long* out_points, hipStream_t s);
+                                      CleanComp c, Compaction k, long long* out_root, long long* out_voxels,
+                                      long long* out_points, hipStream_t s);
 hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
-                                     CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
-                                     unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                     const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
+                                     CleanComp c, Compaction k, const float* v_pts, const int32_t* v_cnt, float* out,
+                                     int32_t* out_cnt,
                                      long long* out_comp, unsigned long long* out_vox, hipStream_t s);
 
 // Visibility check of the voxel or clean cloud (acmmp_fusion_voxel_visibility, include/acmmp.h): over
@@ -135,7 +145,7 @@ hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i
 constexpr int kVisChunk = 32;
 // Device words of a visibility run (all zero before it).
 enum { kVisSupport = 0, kVisConflict = 1, kVisOccluded = 2, kVisUnobserved = 3, kVisKept = 4, kVisNoSupport = 5,
-       kVisConflicting = 6, kVisRunning = 7, kVisSegBase = 8, kVisWords = 9 };
+       kVisConflicting = 6, kVisWords = 7 };
 // tallies[3 e ..] = (support, conflict, occluded) of entry e over the views list[0 .. n_list) (indices into cams /
 // views, every one set), the entry classed per view by its projection against the view's raw depth in the window
 // of `radius` pixels.  More than kVisChunk positions: the tallies are zeroed and added to, else stored.
@@ -147,14 +157,12 @@ hipError_t launch_vis_tally(int model, const DevCam* cams, const FuseView* views
 // failing the first, those failing the second.
 hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_list, int min_support, int max_conflicts,
                             unsigned long long* words, hipStream_t s);
-// Compaction of entries [i0, i0 + n) (one segment, as launch_voxel_compact): the kept entries' floats, counts and
-// tallies in ascending order, and out_vox = their voxel index (src_vox[e], or e itself when src_vox is NULL).  Nothing
-// is written at or past `cap` entries.
+// Entries [i0, i0 + n), one segment, see Compaction: the kept entries' floats, counts and tallies in ascending order,
+// and out_vox = their voxel index (src_vox[e], or e itself when src_vox is NULL).
 hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
-                              int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                              unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
-                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal,
-                              const unsigned long long* src_vox, unsigned long long* out_vox, hipStream_t s);
+                              Compaction c, const float* src_pts, const int32_t* src_cnt, float* out, int32_t* out_cnt,
+                              int32_t* out_tal, const unsigned long long* src_vox, unsigned long long* out_vox,
+                              hipStream_t s);
 
 // Surface mesh of the voxel, clean or visible result (acmmp_fusion_voxel_mesh, include/acmmp.h).
 // The sample table: open addressing as VoxTable.  keys (~0 = empty), rank (smallest e * 27 + offset index), ent (the
@@ -169,7 +177,7 @@ struct MeshTable {
 };
 // Device words of a mesh run (all zero before it).
 enum { kMeshErr = 0, kMeshOccupied = 1, kMeshWrapped = 2, kMeshMaxProbe = 3, kMeshValid = 4, kMeshCubes = 5, kMeshActive = 6,
-       kMeshPairs = 7, kMeshUncoloured = 8, kMeshRunning = 9, kMeshSegBase = 10, kMeshWords = 11 };
+       kMeshPairs = 7, kMeshUncoloured = 8, kMeshWords = 9 };
 // Bits of a sample's flag byte (launch_mesh_cubes).
 enum { kMeshCubeExists = 1, kMeshCubeActive = 2, kMeshSampleValid = 4, kMeshSampleInside = 8 };
 // The per-sample arrays of a mesh result: packed cell, (S, n), remembered entry (-1 = none).
@@ -189,11 +197,10 @@ hipError_t launch_mesh_insert(unsigned long long p0, int n, const unsigned long 
                               unsigned long long* words, hipStream_t s);
 // Over the slots: words[kMeshOccupied], [kMeshWrapped], [kMeshMaxProbe] as launch_voxel_stats.
 hipError_t launch_mesh_stats(MeshTable m, unsigned long long* words, hipStream_t s);
-// Compaction of pairs [p0, p0 + n) (one segment, as launch_voxel_compact): the pairs that own their cell's rank, in
-// ascending order, number the samples: sid[slot], out.key, out.ent.  Nothing is written at or past out.n samples.
-hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, int* flags,
-                              int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                              unsigned long long* seg_base, MeshSamples out, unsigned long long* words, hipStream_t s);
+// Pairs [p0, p0 + n), one segment, see Compaction (c.cap = out.n): the pairs that own their cell's rank, in ascending
+// order, number the samples: sid[slot], out.key, out.ent.
+hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, Compaction c,
+                              MeshSamples out, unsigned long long* words, hipStream_t s);
 // out.tsdf[2 s ..] = (S, n) of every sample over the views list[0 .. n_list), as launch_vis_tally.
 hipError_t launch_mesh_tsdf(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
                             MeshSamples smp, VoxGrid g, float trunc, hipStream_t s);
@@ -201,18 +208,16 @@ hipError_t launch_mesh_tsdf(int model, const DevCam* cams, const FuseView* views
 // [kMeshCubes], [kMeshActive], [kMeshPairs] += their numbers, words[kMeshErr] |= 4 for a failed lookup.
 hipError_t launch_mesh_cubes(MeshSamples smp, MeshTable m, int min_weight, uint8_t* cflag, uint8_t* fbits,
                              unsigned long long* words, hipStream_t s);
-// Compaction of samples [i0, i0 + n): the active cubes' vertices (9 floats each) in ascending s, vid[s] = their number
-// (all-ones before); src_pts: the entries' 9 floats.  Nothing is written at or past `cap` vertices.
+// Samples [i0, i0 + n), one segment, see Compaction: the active cubes' vertices (9 floats each) in ascending s, vid[s] =
+// their number (all-ones before); src_pts: the entries' 9 floats.
 hipError_t launch_mesh_vertices(unsigned long long i0, int n, MeshSamples smp, MeshTable m, VoxGrid g, const uint8_t* cflag,
-                                const float* src_pts, int* flags, int* counts, int* offsets, int* seg_count,
-                                unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                float* verts, int32_t* vid, unsigned long long* words, hipStream_t s);
-// Compaction of the (sample, axis) pairs [p0, p0 + n) of 3 ns: two triangles (6 indices) per flagged pair, in ascending
-// order.  Nothing is written at or past `cap` pairs.
+                                const float* src_pts, Compaction c, float* verts, int32_t* vid, unsigned long long* words,
+                                hipStream_t s);
+// The (sample, axis) pairs [p0, p0 + n) of 3 ns, one segment, see Compaction: two triangles (6 indices) per flagged
+// pair, in ascending order.
 hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, MeshTable m, const uint8_t* cflag,
-                             const uint8_t* fbits, const int32_t* vid, int* flags, int* counts, int* offsets,
-                             int* seg_count, unsigned long long* running, unsigned long long* seg_base,
-                             unsigned long long cap, int32_t* faces, unsigned long long* words, hipStream_t s);
+                             const uint8_t* fbits, const int32_t* vid, Compaction c, int32_t* faces,
+                             unsigned long long* words, hipStream_t s);
 
 // The mesh result rendered into one camera (acmmp_fusion_mesh_render, include/acmmp.h).
 // Device words of a render (all zero before it): kRenderLarge is also the queue's counter, kRenderCounts the first of

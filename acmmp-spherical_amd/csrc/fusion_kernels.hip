@@ -311,6 +311,58 @@ hipError_t launch_fuse_scatter_scene(int W, int H, const float* out_dense, const
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ ordered compaction of a segment
+//
+// Compaction (fusion.h) for the stages below.  A stage is an Op, a small struct passed by value: keep(idx, lane) says
+// whether item idx is kept, emit(idx, pos, lane) writes kept item idx as output pos.  `lane` is the Op's per-lane state
+// (Op::Lane); once the items are through, every lane of the workgroup hands it to mark_end / scatter_end, where an Op
+// folds it into its run words (block_or, wave_add).  CompactOp holds the defaults: no state, nothing to fold.
+struct CompactOp {
+    struct Lane {};
+    template <class L> __device__ void mark_end(const L&) const {}
+    template <class L> __device__ void scatter_end(const L&) const {}
+};
+
+// flags[i] = item i0 + i is kept; counts[chunk] as k_fuse_count
+template <class Op>
+__global__ __launch_bounds__(256) void k_compact_mark(const Op op, unsigned long long i0, int n, int* __restrict__ flags,
+                                                      int* __restrict__ counts) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    typename Op::Lane lane{};
+    int f = 0;
+    if (i < n) {
+        f = op.keep(i0 + static_cast<unsigned long long>(i), lane) ? 1 : 0;
+        flags[i] = f;
+    }
+    const int c = __syncthreads_count(f);
+    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+    op.mark_end(lane);
+}
+
+// the flagged items of each chunk in order: output position = *seg_base + offsets[chunk] + rank
+template <class Op>
+__global__ __launch_bounds__(256) void k_compact_scatter(const Op op, unsigned long long i0, int n,
+                                                         const int* __restrict__ flags, const int* __restrict__ offsets,
+                                                         const unsigned long long* __restrict__ seg_base,
+                                                         unsigned long long cap) {
+    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
+    const int f = i < n ? flags[i] : 0;
+    const int rank = chunk_rank(f, offsets);
+    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
+    typename Op::Lane lane{};
+    if (f && pos < cap) op.emit(i0 + static_cast<unsigned long long>(i), pos, lane);
+    op.scatter_end(lane);
+}
+
+template <class Op>
+static hipError_t compact_segment(const Op& op, unsigned long long i0, int n, const Compaction& c, hipStream_t s) {
+    const int n_chunks = cdiv(n, 256);
+    k_compact_mark<Op><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(op, i0, n, c.flags, c.counts);
+    k_fuse_scan<<<1, 1024, 0, s>>>(c.counts, n_chunks, c.offsets, c.seg_count, c.running, c.seg_base);
+    k_compact_scatter<Op><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(op, i0, n, c.flags, c.offsets, c.seg_base, c.cap);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ voxel-grid reduction of the scene cloud
 //
 // acmmp_fusion_voxelize (include/acmmp.h).  Everything a result depends on is an integer: the
@@ -361,17 +413,45 @@ __device__ __forceinline__ unsigned long long vox_home(unsigned long long key, i
     return z >> (64 - log2_slots);
 }
 
-// The slot of a key that is in the table (after the insert pass); at most `slots` steps.
-__device__ __forceinline__ bool vox_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        const unsigned long long k = t.keys[s];
-        if (k == key) { slot = s; return true; }
-        if (k == kVoxEmpty) return false;
+// The probe of every table here (VoxTable, MeshTable, DistTable): linear from the key's home slot, at most `slots`
+// steps.  The lookup of a key after the insert pass: 0 = found (its slot), 1 = absent, 2 = the probe sequence covered
+// every slot.
+__device__ __forceinline__ int table_find(const unsigned long long* keys, unsigned long long slots, int log2_slots,
+                                          unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = slots - 1ull;
+    unsigned long long s = vox_home(key, log2_slots);
+    for (unsigned long long probe = 0; probe < slots; ++probe) {
+        const unsigned long long k = keys[s];
+        if (k == key) { slot = s; return 0; }
+        if (k == kVoxEmpty) return 1;
+        s = (s + 1ull) & mask;
+    }
+    return 2;
+}
+
+// The slot of `key` in the insert pass, claimed when the key is new; false = the probe sequence covered every slot.
+__device__ __forceinline__ bool table_claim(unsigned long long* keys, unsigned long long slots, int log2_slots,
+                                            unsigned long long key, unsigned long long& slot) {
+    const unsigned long long mask = slots - 1ull;
+    unsigned long long s = vox_home(key, log2_slots);
+    for (unsigned long long probe = 0; probe < slots; ++probe) {
+        // a slot's key changes once, from empty: a plain read that shows a key is final, one that shows
+        // empty (stale or not) is settled by the CAS
+        unsigned long long k = keys[s];
+        if (k == kVoxEmpty) k = atomicCAS(&keys[s], kVoxEmpty, key);
+        if (k == kVoxEmpty || k == key) { slot = s; return true; }
         s = (s + 1ull) & mask;
     }
     return false;
+}
+
+template <class Table>
+__device__ __forceinline__ int table_find(const Table& t, unsigned long long key, unsigned long long& slot) {
+    return table_find(t.keys, t.slots, t.log2_slots, key, slot);
+}
+template <class Table>
+__device__ __forceinline__ bool table_claim(const Table& t, unsigned long long key, unsigned long long& slot) {
+    return table_claim(t.keys, t.slots, t.log2_slots, key, slot);
 }
 
 __device__ __forceinline__ uint32_t vox_ordered(float f) {
@@ -416,18 +496,8 @@ __global__ __launch_bounds__(256) void k_voxel_insert(const float* __restrict__ 
     const int rejected = __syncthreads_count(i < n && !ok);
     if (threadIdx.x == 0 && rejected) atomicAdd(&st[kVoxRejected], static_cast<unsigned long long>(rejected));
     if (!ok) return;
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    bool found = false;
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        // a slot's key changes once, from empty: a plain read that shows a key is final, one that shows
-        // empty (stale or not) is settled by the CAS
-        unsigned long long k = t.keys[s];
-        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
-        if (k == kVoxEmpty || k == key) { found = true; break; }
-        s = (s + 1ull) & mask;
-    }
-    if (!found) { atomicOr(&st[kVoxErr], 1ull); return; }
+    unsigned long long s;
+    if (!table_claim(t, key, s)) { atomicOr(&st[kVoxErr], 1ull); return; }
     atomicAdd(&t.cnt[s], 1u);
     atomicMin(&t.first[s], idx);
 }
@@ -460,50 +530,32 @@ __global__ __launch_bounds__(256) void k_voxel_stats(const VoxTable t, int min_p
     }
 }
 
-// flags[i] = point i0 + i is the first point of a voxel that is kept; counts[chunk] as k_fuse_count
-__global__ __launch_bounds__(256) void k_voxel_mark(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                    const VoxGrid g, const VoxTable t, int min_points,
-                                                    int* __restrict__ flags, int* __restrict__ counts,
-                                                    unsigned long long* __restrict__ st) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const unsigned long long idx = i0 + static_cast<unsigned long long>(i);
-    int f = 0;
-    if (i < n) {
+// kept: the first point of a voxel that is kept; its position is the voxel's output id
+struct VoxelCompact : CompactOp {
+    const float* pts;
+    VoxGrid g;
+    VoxTable t;
+    int min_points;
+    unsigned long long* vslot;
+    unsigned long long* st;
+    __device__ bool keep(unsigned long long idx, Lane&) const {
         float v[9], frac[3];
         unsigned long long key, s;
-        if (vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac)) {
-            if (vox_find(t, key, s)) f = (t.first[s] == idx && t.cnt[s] >= static_cast<uint32_t>(min_points)) ? 1 : 0;
-            else atomicOr(&st[kVoxErr], 2ull);
-        }
-        flags[i] = f;
+        if (!(vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac))) return false;
+        if (table_find(t, key, s) != 0) { atomicOr(&st[kVoxErr], 2ull); return false; }
+        return t.first[s] == idx && t.cnt[s] >= static_cast<uint32_t>(min_points);
     }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// the flagged points of each chunk in order: output id = *seg_base + offsets[chunk] + rank
-__global__ __launch_bounds__(256) void k_voxel_scatter(const float* __restrict__ pts, unsigned long long i0, int n,
-                                                       const VoxGrid g, const VoxTable t, const int* __restrict__ flags,
-                                                       const int* __restrict__ offsets,
-                                                       const unsigned long long* __restrict__ seg_base, unsigned long long cap,
-                                                       unsigned long long* __restrict__ vslot,
-                                                       unsigned long long* __restrict__ st) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    if (f && pos < cap) {
+    __device__ void emit(unsigned long long idx, unsigned long long pos, Lane&) const {
         float v[9], frac[3];
         unsigned long long key, s;
-        if (vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac) &&
-            vox_find(t, key, s)) {
+        if (vox_load(pts + 9ull * idx, v) && vox_cell(v, g, key, frac) && table_find(t, key, s) == 0) {
             t.oid[s] = pos;
             vslot[pos] = s;
         } else {
             atomicOr(&st[kVoxErr], 4ull);
         }
     }
-}
+};
 
 __global__ __launch_bounds__(256) void k_voxel_accumulate(const float* __restrict__ pts, unsigned long long i0, int n,
                                                           const VoxGrid g, const VoxTable t,
@@ -514,7 +566,7 @@ __global__ __launch_bounds__(256) void k_voxel_accumulate(const float* __restric
     float v[9], frac[3];
     unsigned long long key, s;
     if (!(vox_load(pts + 9ull * (i0 + static_cast<unsigned long long>(i)), v) && vox_cell(v, g, key, frac))) return;
-    if (!vox_find(t, key, s)) { atomicOr(&st[kVoxErr], 8ull); return; }
+    if (table_find(t, key, s) != 0) { atomicOr(&st[kVoxErr], 8ull); return; }
     const unsigned long long o = t.oid[s];
     if (o == kVoxEmpty) return;                      // fewer than min_points
     unsigned long long* acc = sums + 9ull * o;
@@ -571,14 +623,8 @@ hipError_t launch_voxel_stats(VoxTable t, int min_points, unsigned long long* st
 }
 
 hipError_t launch_voxel_compact(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t, int min_points,
-                                int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                                unsigned long long* seg_base, unsigned long long cap, unsigned long long* vslot,
-                                unsigned long long* st, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_voxel_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, min_points, flags, counts, st);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_voxel_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(pts, i0, n, g, t, flags, offsets, seg_base, cap, vslot, st);
-    return hipGetLastError();
+                                Compaction c, unsigned long long* vslot, unsigned long long* st, hipStream_t s) {
+    return compact_segment(VoxelCompact{{}, pts, g, t, min_points, vslot, st}, i0, n, c, s);
 }
 
 hipError_t launch_voxel_accumulate(const float* pts, unsigned long long i0, int n, VoxGrid g, VoxTable t,
@@ -600,19 +646,6 @@ hipError_t launch_voxel_finalise(unsigned long long nv, const unsigned long long
 // voxels of the resident voxel result, through the table that voxelize left (cell -> slot -> oid).  Everything
 // is an integer, and every atomic is a minimum, an or or an integer add: no result depends on the order they land in.
 
-// The lookup of a cell that may be absent: 0 = found, 1 = absent, 2 = the probe sequence covered every slot.
-__device__ __forceinline__ int clean_find(const VoxTable& t, unsigned long long key, unsigned long long& slot) {
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        const unsigned long long k = t.keys[s];
-        if (k == key) { slot = s; return 0; }
-        if (k == kVoxEmpty) return 1;
-        s = (s + 1ull) & mask;
-    }
-    return 2;
-}
-
 // Neighbour `b` (0 .. 27, b = (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1)) of the cell `key`, offsets applied per axis
 // on the unpacked 21-bit indices; false = that cell does not exist.
 __device__ __forceinline__ bool clean_neighbour(unsigned long long key, int b, unsigned long long& nkey) {
@@ -626,6 +659,12 @@ __device__ __forceinline__ bool clean_neighbour(unsigned long long key, int b, u
         nkey |= static_cast<unsigned long long>(ok ? g : 0) << (21 * a);
     }
     return ok;
+}
+
+// dst[0 .. 9) = src[0 .. 9) of another array: the nine loads go out ahead of the stores.
+__device__ __forceinline__ void copy9(float* __restrict__ dst, const float* __restrict__ src) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dst[k] = src[k];
 }
 
 // *word |= the or of `bits` over the workgroup, one atomic per workgroup.  Every lane calls it.
@@ -665,7 +704,7 @@ __global__ __launch_bounds__(256) void k_clean_support(unsigned long long nv, co
                 const int l1 = abs(b % 3 - 1) + abs((b / 3) % 3 - 1) + abs(b / 9 - 1);
                 unsigned long long nkey, ns;
                 if (l1 == 0 || l1 > max_l1 || !clean_neighbour(key, b, nkey)) continue;
-                const int r = clean_find(t, nkey, ns);
+                const int r = table_find(t, nkey, ns);
                 if (r == 2) err |= 2u;
                 if (r == 0 && t.oid[ns] < nv) m |= 1u << b;          // a cell below min_points has no oid
             }
@@ -700,7 +739,7 @@ __global__ __launch_bounds__(256) void k_clean_round(unsigned long long nv, cons
         const unsigned long long key = t.keys[slot];
         for (uint32_t left = nbmask[v]; left; left &= left - 1u) {
             unsigned long long nkey, ns;
-            if (!clean_neighbour(key, __ffs(static_cast<int>(left)) - 1, nkey) || clean_find(t, nkey, ns) != 0) { err |= 4u; continue; }
+            if (!clean_neighbour(key, __ffs(static_cast<int>(left)) - 1, nkey) || table_find(t, nkey, ns) != 0) { err |= 4u; continue; }
             const unsigned long long o = t.oid[ns];
             if (o >= nv) { err |= 4u; continue; }
             m = min(m, lab[o]);                                      // ~0 (unsupported) never wins
@@ -769,72 +808,50 @@ __global__ __launch_bounds__(256) void k_clean_count(unsigned long long nv, cons
     wave_add(kept ? 1ull : 0ull, &words[kCleanKept]);
 }
 
-// flags[i] of voxel i0 + i: KEPT = false, it labels itself (the root of a component); KEPT = true, it is kept.
-template <bool KEPT>
-__global__ __launch_bounds__(256) void k_clean_mark(unsigned long long nv, unsigned long long i0, int n,
-                                                    const unsigned long long* __restrict__ lab,
-                                                    const unsigned long long* __restrict__ cvox,
-                                                    const unsigned long long* __restrict__ cpts, unsigned long long min_voxels,
-                                                    unsigned long long min_points, int* __restrict__ flags,
-                                                    int* __restrict__ counts) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const unsigned long long v = i0 + static_cast<unsigned long long>(i);
-    int f = 0;
-    if (i < n) {
+// kept: the voxels that label themselves (the roots of the components), in ascending order; a root's position is its
+// component's id: its table entry, c.id[root] = id
+struct CleanRoots : CompactOp {
+    unsigned long long nv;
+    const unsigned long long* lab;
+    CleanComp c;
+    long long* out_root;
+    long long* out_voxels;
+    long long* out_points;
+    __device__ bool keep(unsigned long long v, Lane&) const {
         const unsigned long long L = lab[v];
-        if (L < nv) f = KEPT ? (clean_component_kept(L, cvox, cpts, min_voxels, min_points) ? 1 : 0) : (L == v ? 1 : 0);
-        flags[i] = f;
+        return L < nv && L == v;
     }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// the roots in ascending order: component id = *seg_base + offsets[chunk] + rank, its table entry, cid[root] = id
-__global__ __launch_bounds__(256) void k_clean_scatter_roots(unsigned long long i0, int n, const int* __restrict__ flags,
-                                                             const int* __restrict__ offsets,
-                                                             const unsigned long long* __restrict__ seg_base,
-                                                             unsigned long long cap, const unsigned long long* __restrict__ cvox,
-                                                             const unsigned long long* __restrict__ cpts,
-                                                             unsigned long long* __restrict__ cid, long long* __restrict__ out_root,
-                                                             long long* __restrict__ out_voxels, long long* __restrict__ out_points) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    if (f && pos < cap) {
-        const unsigned long long v = i0 + static_cast<unsigned long long>(i);
-        cid[v] = pos;
+    __device__ void emit(unsigned long long v, unsigned long long pos, Lane&) const {
+        c.id[v] = pos;
         out_root[pos] = static_cast<long long>(v);
-        out_voxels[pos] = static_cast<long long>(cvox[v]);
-        out_points[pos] = static_cast<long long>(cpts[v]);
+        out_voxels[pos] = static_cast<long long>(c.voxels[v]);
+        out_points[pos] = static_cast<long long>(c.points[v]);
     }
-}
+};
 
-// the kept voxels in ascending order: the voxel's 9 floats and count as they are, and its component's id
-__global__ __launch_bounds__(256) void k_clean_scatter_kept(unsigned long long i0, int n, const int* __restrict__ flags,
-                                                            const int* __restrict__ offsets,
-                                                            const unsigned long long* __restrict__ seg_base,
-                                                            unsigned long long cap, const unsigned long long* __restrict__ lab,
-                                                            const unsigned long long* __restrict__ cid,
-                                                            const float* __restrict__ v_pts, const int32_t* __restrict__ v_cnt,
-                                                            float* __restrict__ out, int32_t* __restrict__ out_cnt,
-                                                            long long* __restrict__ out_comp,
-                                                            unsigned long long* __restrict__ out_vox) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    if (f && pos < cap) {
-        const unsigned long long v = i0 + static_cast<unsigned long long>(i);
-        const float* src = v_pts + 9ull * v;
-        float* dst = out + 9ull * pos;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) dst[k] = src[k];
+// kept: the voxels of kept components, in ascending order: the voxel's 9 floats and count as they are, and its
+// component's id
+struct CleanKept : CompactOp {
+    unsigned long long nv;
+    const unsigned long long* lab;
+    CleanComp c;
+    const float* v_pts;
+    const int32_t* v_cnt;
+    float* out;
+    int32_t* out_cnt;
+    long long* out_comp;
+    unsigned long long* out_vox;
+    __device__ bool keep(unsigned long long v, Lane&) const {
+        const unsigned long long L = lab[v];
+        return L < nv && clean_component_kept(L, c.voxels, c.points, c.min_voxels, c.min_points);
+    }
+    __device__ void emit(unsigned long long v, unsigned long long pos, Lane&) const {
+        copy9(out + 9ull * pos, v_pts + 9ull * v);
         out_cnt[pos] = v_cnt[v];
-        out_comp[pos] = static_cast<long long>(cid[lab[v]]);
+        out_comp[pos] = static_cast<long long>(c.id[lab[v]]);
         out_vox[pos] = v;
     }
-}
+};
 
 static unsigned clean_blocks(unsigned long long nv) { return static_cast<unsigned>((nv + 255ull) / 256ull); }
 
@@ -860,30 +877,15 @@ hipError_t launch_clean_sizes(unsigned long long nv, const unsigned long long* l
 }
 
 hipError_t launch_clean_compact_roots(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
-                                      CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
-                                      unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                      long long* out_root, long long* out_voxels, long long* out_points, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_clean_mark<false><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(nv, i0, n, lab, c.voxels, c.points, c.min_voxels,
-                                                                        c.min_points, flags, counts);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_clean_scatter_roots<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, c.voxels,
-                                                                          c.points, c.id, out_root, out_voxels, out_points);
-    return hipGetLastError();
+                                      CleanComp c, Compaction k, long long* out_root, long long* out_voxels,
+                                      long long* out_points, hipStream_t s) {
+    return compact_segment(CleanRoots{{}, nv, lab, c, out_root, out_voxels, out_points}, i0, n, k, s);
 }
 
 hipError_t launch_clean_compact_kept(unsigned long long nv, unsigned long long i0, int n, const unsigned long long* lab,
-                                     CleanComp c, int* flags, int* counts, int* offsets, int* seg_count,
-                                     unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                     const float* v_pts, const int32_t* v_cnt, float* out, int32_t* out_cnt,
-                                     long long* out_comp, unsigned long long* out_vox, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_clean_mark<true><<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(nv, i0, n, lab, c.voxels, c.points, c.min_voxels,
-                                                                       c.min_points, flags, counts);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_clean_scatter_kept<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, lab, c.id,
-                                                                         v_pts, v_cnt, out, out_cnt, out_comp, out_vox);
-    return hipGetLastError();
+                                     CleanComp c, Compaction k, const float* v_pts, const int32_t* v_cnt, float* out,
+                                     int32_t* out_cnt, long long* out_comp, unsigned long long* out_vox, hipStream_t s) {
+    return compact_segment(CleanKept{{}, nv, lab, c, v_pts, v_cnt, out, out_cnt, out_comp, out_vox}, i0, n, k, s);
 }
 
 // ------------------------------------------------------------------ visibility check of the voxel cloud
@@ -979,45 +981,26 @@ __global__ __launch_bounds__(256) void k_vis_count(unsigned long long n, const i
     wave_add(in && t[1] > max_conflicts ? 1ull : 0ull, &words[kVisConflicting]);
 }
 
-// flags[i] = entry i0 + i is kept; counts[chunk] as k_fuse_count
-__global__ __launch_bounds__(256) void k_vis_mark(unsigned long long i0, int n, const int32_t* __restrict__ tallies,
-                                                  int min_support, int max_conflicts, int* __restrict__ flags,
-                                                  int* __restrict__ counts) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    int f = 0;
-    if (i < n) {
-        f = vis_kept(tallies + 3ull * (i0 + static_cast<unsigned long long>(i)), min_support, max_conflicts) ? 1 : 0;
-        flags[i] = f;
-    }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// the kept entries in ascending order: the entry's 9 floats and count as they are, and its tallies
-__global__ __launch_bounds__(256) void k_vis_scatter(unsigned long long i0, int n, const int* __restrict__ flags,
-                                                     const int* __restrict__ offsets,
-                                                     const unsigned long long* __restrict__ seg_base, unsigned long long cap,
-                                                     const float* __restrict__ src_pts, const int32_t* __restrict__ src_cnt,
-                                                     const int32_t* __restrict__ tallies, float* __restrict__ out,
-                                                     int32_t* __restrict__ out_cnt, int32_t* __restrict__ out_tal,
-                                                     const unsigned long long* __restrict__ src_vox,
-                                                     unsigned long long* __restrict__ out_vox) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    if (f && pos < cap) {
-        const unsigned long long e = i0 + static_cast<unsigned long long>(i);
-        const float* src = src_pts + 9ull * e;
-        float* dst = out + 9ull * pos;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) dst[k] = src[k];
+// kept: the kept entries, in ascending order: the entry's 9 floats and count as they are, and its tallies
+struct VisCompact : CompactOp {
+    const int32_t* tallies;
+    int min_support, max_conflicts;
+    const float* src_pts;
+    const int32_t* src_cnt;
+    float* out;
+    int32_t* out_cnt;
+    int32_t* out_tal;
+    const unsigned long long* src_vox;
+    unsigned long long* out_vox;
+    __device__ bool keep(unsigned long long e, Lane&) const { return vis_kept(tallies + 3ull * e, min_support, max_conflicts); }
+    __device__ void emit(unsigned long long e, unsigned long long pos, Lane&) const {
+        copy9(out + 9ull * pos, src_pts + 9ull * e);
         out_cnt[pos] = src_cnt[e];
 #pragma unroll
         for (int k = 0; k < 3; ++k) out_tal[3ull * pos + k] = tallies[3ull * e + k];
         out_vox[pos] = src_vox ? src_vox[e] : e;
     }
-}
+};
 
 hipError_t launch_vis_tally(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
                             const float* pts, unsigned long long n, float rel_tol, int radius, int32_t* tallies,
@@ -1043,16 +1026,11 @@ hipError_t launch_vis_count(unsigned long long n, const int32_t* tallies, int n_
 }
 
 hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* tallies, int min_support, int max_conflicts,
-                              int* flags, int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                              unsigned long long* seg_base, unsigned long long cap, const float* src_pts,
-                              const int32_t* src_cnt, float* out, int32_t* out_cnt, int32_t* out_tal,
-                              const unsigned long long* src_vox, unsigned long long* out_vox, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_vis_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, tallies, min_support, max_conflicts, flags, counts);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_vis_scatter<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, flags, offsets, seg_base, cap, src_pts, src_cnt,
-                                                                   tallies, out, out_cnt, out_tal, src_vox, out_vox);
-    return hipGetLastError();
+                              Compaction c, const float* src_pts, const int32_t* src_cnt, float* out, int32_t* out_cnt,
+                              int32_t* out_tal, const unsigned long long* src_vox, unsigned long long* out_vox,
+                              hipStream_t s) {
+    return compact_segment(VisCompact{{}, tallies, min_support, max_conflicts, src_pts, src_cnt, out, out_cnt, out_tal,
+                                      src_vox, out_vox}, i0, n, c, s);
 }
 
 // ------------------------------------------------------------------ surface mesh of the voxel cloud
@@ -1067,20 +1045,12 @@ hipError_t launch_vis_compact(unsigned long long i0, int n, const int32_t* talli
 // 2 = the probe sequence covered every slot or the slot holds no number.
 __device__ __forceinline__ int mesh_sample(const MeshTable& m, unsigned long long ns, unsigned long long key, int b,
                                            unsigned long long& sid) {
-    unsigned long long nkey;
+    unsigned long long nkey, s;
     if (!clean_neighbour(key, b, nkey)) return 1;
-    const unsigned long long mask = m.slots - 1ull;
-    unsigned long long s = vox_home(nkey, m.log2_slots);
-    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
-        const unsigned long long k = m.keys[s];
-        if (k == nkey) {
-            sid = m.sid[s];
-            return sid < ns ? 0 : 2;
-        }
-        if (k == kVoxEmpty) return 1;
-        s = (s + 1ull) & mask;
-    }
-    return 2;
+    const int r = table_find(m, nkey, s);
+    if (r != 0) return r;
+    sid = m.sid[s];
+    return sid < ns ? 0 : 2;
 }
 
 // clean_neighbour's index of the offset (dx, dy, dz)
@@ -1111,16 +1081,8 @@ __global__ __launch_bounds__(256) void k_mesh_insert(unsigned long long p0, int 
     const unsigned long long key = ekey[e];
     unsigned long long nkey;
     if (key == kVoxEmpty || !clean_neighbour(key, b, nkey)) return;
-    const unsigned long long mask = m.slots - 1ull;
-    unsigned long long s = vox_home(nkey, m.log2_slots);
-    bool found = false;
-    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
-        unsigned long long k = m.keys[s];                 // (a key changes once, from empty: see k_voxel_insert)
-        if (k == kVoxEmpty) k = atomicCAS(&m.keys[s], kVoxEmpty, nkey);
-        if (k == kVoxEmpty || k == nkey) { found = true; break; }
-        s = (s + 1ull) & mask;
-    }
-    if (!found) { atomicOr(&words[kMeshErr], 2ull); return; }
+    unsigned long long s;
+    if (!table_claim(m, nkey, s)) { atomicOr(&words[kMeshErr], 2ull); return; }
     atomicMin(&m.rank[s], p);
     if (b == 13) m.ent[s] = e;                            // one entry at most has this cell
 }
@@ -1156,54 +1118,37 @@ __device__ __forceinline__ bool mesh_owner(const MeshTable& m, const unsigned lo
                                            unsigned& err) {
     const unsigned long long key = ekey[p / 27ull];
     if (key == kVoxEmpty || !clean_neighbour(key, static_cast<int>(p % 27ull), nkey)) return false;
-    const unsigned long long mask = m.slots - 1ull;
-    unsigned long long s = vox_home(nkey, m.log2_slots);
-    for (unsigned long long probe = 0; probe < m.slots; ++probe) {
-        const unsigned long long k = m.keys[s];
-        if (k == nkey) { slot = s; return m.rank[s] == p; }
-        if (k == kVoxEmpty) break;
-        s = (s + 1ull) & mask;
-    }
+    if (table_find(m, nkey, slot) == 0) return m.rank[slot] == p;
     err |= 4u;                                            // the insert pass put every pair's cell there
     return false;
 }
 
-__global__ __launch_bounds__(256) void k_mesh_mark_samples(unsigned long long p0, int n,
-                                                           const unsigned long long* __restrict__ ekey, const MeshTable m,
-                                                           int* __restrict__ flags, int* __restrict__ counts,
-                                                           unsigned long long* __restrict__ words) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    int f = 0;
+// The per-lane error bits of a mesh compaction, one block_or per workgroup into words[kMeshErr].
+struct MeshLane {
     unsigned err = 0u;
-    if (i < n) {
-        unsigned long long nkey, slot;
-        f = mesh_owner(m, ekey, p0 + static_cast<unsigned long long>(i), nkey, slot, err) ? 1 : 0;
-        flags[i] = f;
-    }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
-    block_or(err, &words[kMeshErr]);
-}
+};
 
-__global__ __launch_bounds__(256) void k_mesh_scatter_samples(unsigned long long p0, int n,
-                                                              const unsigned long long* __restrict__ ekey, const MeshTable m,
-                                                              const int* __restrict__ flags, const int* __restrict__ offsets,
-                                                              const unsigned long long* __restrict__ seg_base,
-                                                              const MeshSamples out) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    if (f && pos < out.n) {
+// kept: the pairs that own their cell's rank, in ascending order; a pair's position is the sample's number
+struct MeshNumber : CompactOp {
+    using Lane = MeshLane;
+    const unsigned long long* ekey;
+    MeshTable m;
+    MeshSamples out;
+    unsigned long long* words;
+    __device__ bool keep(unsigned long long p, Lane& lane) const {
         unsigned long long nkey, slot;
-        unsigned err = 0u;
-        if (mesh_owner(m, ekey, p0 + static_cast<unsigned long long>(i), nkey, slot, err)) {
+        return mesh_owner(m, ekey, p, nkey, slot, lane.err);
+    }
+    __device__ void mark_end(const Lane& lane) const { block_or(lane.err, &words[kMeshErr]); }
+    __device__ void emit(unsigned long long p, unsigned long long pos, Lane& lane) const {
+        unsigned long long nkey, slot;
+        if (mesh_owner(m, ekey, p, nkey, slot, lane.err)) {              // (the mark pass has reported a failure)
             m.sid[slot] = pos;
             out.key[pos] = nkey;
             out.ent[pos] = static_cast<long long>(m.ent[slot]);          // ~0 reads as -1
         }
     }
-}
+};
 
 // One lane per sample, blockIdx.y = a chunk of kVisChunk list positions, as k_vis_tally.
 template <int MODEL, bool ATOMIC>
@@ -1317,36 +1262,30 @@ __global__ __launch_bounds__(256) void k_mesh_pairs(const MeshSamples smp, const
     block_or(err, &words[kMeshErr]);
 }
 
-// flags[i] = bit `bit` of bytes[(i0 + i) / per] shifted by (i0 + i) % per: the active cubes (per 1) or the face pairs (per 3)
-__global__ __launch_bounds__(256) void k_mesh_mark(unsigned long long i0, int n, const uint8_t* __restrict__ bytes, int per,
-                                                   int bit, int* __restrict__ flags, int* __restrict__ counts) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    int f = 0;
-    if (i < n) {
-        const unsigned long long p = i0 + static_cast<unsigned long long>(i);
-        f = (bytes[p / static_cast<unsigned>(per)] >> (bit + static_cast<int>(p % static_cast<unsigned>(per)))) & 1;
-        flags[i] = f;
-    }
-    const int c = __syncthreads_count(f);
-    if (threadIdx.x == 0) counts[blockIdx.x] = c;
+// Bit `bit` of bytes[p / per] shifted by p % per: the active cubes (per 1) or the face pairs (per 3).
+__device__ __forceinline__ bool mesh_flag(const uint8_t* __restrict__ bytes, int per, int bit, unsigned long long p) {
+    return (bytes[p / static_cast<unsigned>(per)] >> (bit + static_cast<int>(p % static_cast<unsigned>(per)))) & 1;
 }
 
-// Step 3 for the active cubes of samples [i0, i0 + n), in ascending order: position, normal, colour.
-__global__ __launch_bounds__(256) void k_mesh_scatter_vertices(unsigned long long i0, int n, const MeshSamples smp,
-                                                               const MeshTable m, const VoxGrid g,
-                                                               const float* __restrict__ src_pts, const int* __restrict__ flags,
-                                                               const int* __restrict__ offsets,
-                                                               const unsigned long long* __restrict__ seg_base,
-                                                               unsigned long long cap, float* __restrict__ verts,
-                                                               int32_t* __restrict__ vid, unsigned long long* __restrict__ words) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    unsigned err = 0u;
-    unsigned long long uncoloured = 0;
-    if (f && pos < cap) {
-        const unsigned long long s = i0 + static_cast<unsigned long long>(i);
+// kept: the active cubes, in ascending sample order; step 3 for each: position, normal, colour.
+struct MeshVertices : CompactOp {
+    struct Lane : MeshLane {
+        unsigned long long uncoloured = 0;
+    };
+    MeshSamples smp;
+    MeshTable m;
+    VoxGrid g;
+    const uint8_t* cflag;
+    const float* src_pts;
+    float* verts;
+    int32_t* vid;
+    unsigned long long* words;
+    __device__ bool keep(unsigned long long s, Lane&) const { return mesh_flag(cflag, 1, 1, s); }       // kMeshCubeActive
+    __device__ void scatter_end(const Lane& lane) const {
+        wave_add(lane.uncoloured, &words[kMeshUncoloured]);
+        block_or(lane.err, &words[kMeshErr]);
+    }
+    __device__ void emit(unsigned long long s, unsigned long long pos, Lane& lane) const {
         const unsigned long long key = smp.key[s];
         long long S[8], N[8], ent[8];
         bool ok = true;
@@ -1358,7 +1297,7 @@ __global__ __launch_bounds__(256) void k_mesh_scatter_vertices(unsigned long lon
             ent[c] = smp.ent[q];
         }
         if (!ok) {
-            err |= 8u;
+            lane.err |= 8u;
         } else {
             double L[3] = {0.0, 0.0, 0.0}, G[3] = {0.0, 0.0, 0.0};
             int crossings = 0;
@@ -1397,28 +1336,25 @@ __global__ __launch_bounds__(256) void k_mesh_scatter_vertices(unsigned long lon
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) dst[6 + a] = coloured ? static_cast<float>(col[a] / static_cast<double>(coloured)) : 128.0f;
-            uncoloured = coloured ? 0ull : 1ull;
+            lane.uncoloured = coloured ? 0ull : 1ull;
             vid[s] = static_cast<int32_t>(pos);
         }
     }
-    wave_add(uncoloured, &words[kMeshUncoloured]);
-    block_or(err, &words[kMeshErr]);
-}
+};
 
-// Step 4 for the flagged pairs of [p0, p0 + n), in ascending order: two triangles each.
-__global__ __launch_bounds__(256) void k_mesh_scatter_faces(unsigned long long p0, int n, const MeshSamples smp, const MeshTable m,
-                                                            const uint8_t* __restrict__ cflag, const int32_t* __restrict__ vid,
-                                                            const int* __restrict__ flags, const int* __restrict__ offsets,
-                                                            const unsigned long long* __restrict__ seg_base,
-                                                            unsigned long long cap, int32_t* __restrict__ faces,
-                                                            unsigned long long* __restrict__ words) {
-    const int i = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
-    const int f = i < n ? flags[i] : 0;
-    const int rank = chunk_rank(f, offsets);
-    const unsigned long long pos = *seg_base + static_cast<unsigned long long>(rank);
-    unsigned err = 0u;
-    if (f && pos < cap) {
-        const unsigned long long p = p0 + static_cast<unsigned long long>(i);
+// kept: the (sample, axis) pairs flagged in fbits, in ascending order; step 4 for each: two triangles.
+struct MeshFaces : CompactOp {
+    using Lane = MeshLane;
+    MeshSamples smp;
+    MeshTable m;
+    const uint8_t* cflag;
+    const uint8_t* fbits;
+    const int32_t* vid;
+    int32_t* faces;
+    unsigned long long* words;
+    __device__ bool keep(unsigned long long p, Lane&) const { return mesh_flag(fbits, 3, 0, p); }
+    __device__ void scatter_end(const Lane& lane) const { block_or(lane.err, &words[kMeshErr]); }
+    __device__ void emit(unsigned long long p, unsigned long long pos, Lane& lane) const {
         const unsigned long long s = p / 3ull;
         unsigned long long q[4];
         int32_t v[4] = {-1, -1, -1, -1};
@@ -1426,7 +1362,7 @@ __global__ __launch_bounds__(256) void k_mesh_scatter_faces(unsigned long long p
             for (int k = 0; k < 4; ++k) v[k] = vid[q[k]];
         int32_t* dst = faces + 6ull * pos;
         if (v[0] < 0 || v[1] < 0 || v[2] < 0 || v[3] < 0) {
-            err |= 16u;
+            lane.err |= 16u;
         } else if (cflag[s] & kMeshSampleInside) {
             dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2];
             dst[3] = v[0]; dst[4] = v[2]; dst[5] = v[3];
@@ -1435,8 +1371,7 @@ __global__ __launch_bounds__(256) void k_mesh_scatter_faces(unsigned long long p
             dst[3] = v[0]; dst[4] = v[2]; dst[5] = v[1];
         }
     }
-    block_or(err, &words[kMeshErr]);
-}
+};
 
 hipError_t launch_mesh_keys(unsigned long long ne, const unsigned long long* vox, unsigned long long nv,
                             const unsigned long long* vslot, VoxTable t, unsigned long long* ekey,
@@ -1457,14 +1392,9 @@ hipError_t launch_mesh_stats(MeshTable m, unsigned long long* words, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, int* flags,
-                              int* counts, int* offsets, int* seg_count, unsigned long long* running,
-                              unsigned long long* seg_base, MeshSamples out, unsigned long long* words, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_mesh_mark_samples<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, ekey, m, flags, counts, words);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_mesh_scatter_samples<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, ekey, m, flags, offsets, seg_base, out);
-    return hipGetLastError();
+hipError_t launch_mesh_number(unsigned long long p0, int n, const unsigned long long* ekey, MeshTable m, Compaction c,
+                              MeshSamples out, unsigned long long* words, hipStream_t s) {
+    return compact_segment(MeshNumber{{}, ekey, m, out, words}, p0, n, c, s);
 }
 
 hipError_t launch_mesh_tsdf(int model, const DevCam* cams, const FuseView* views, const int* list, int n_list,
@@ -1492,27 +1422,15 @@ hipError_t launch_mesh_cubes(MeshSamples smp, MeshTable m, int min_weight, uint8
 }
 
 hipError_t launch_mesh_vertices(unsigned long long i0, int n, MeshSamples smp, MeshTable m, VoxGrid g, const uint8_t* cflag,
-                                const float* src_pts, int* flags, int* counts, int* offsets, int* seg_count,
-                                unsigned long long* running, unsigned long long* seg_base, unsigned long long cap,
-                                float* verts, int32_t* vid, unsigned long long* words, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_mesh_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, cflag, 1, 1, flags, counts);     // kMeshCubeActive
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_mesh_scatter_vertices<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(i0, n, smp, m, g, src_pts, flags, offsets, seg_base,
-                                                                             cap, verts, vid, words);
-    return hipGetLastError();
+                                const float* src_pts, Compaction c, float* verts, int32_t* vid, unsigned long long* words,
+                                hipStream_t s) {
+    return compact_segment(MeshVertices{{}, smp, m, g, cflag, src_pts, verts, vid, words}, i0, n, c, s);
 }
 
 hipError_t launch_mesh_faces(unsigned long long p0, int n, MeshSamples smp, MeshTable m, const uint8_t* cflag,
-                             const uint8_t* fbits, const int32_t* vid, int* flags, int* counts, int* offsets,
-                             int* seg_count, unsigned long long* running, unsigned long long* seg_base,
-                             unsigned long long cap, int32_t* faces, unsigned long long* words, hipStream_t s) {
-    const int n_chunks = cdiv(n, 256);
-    k_mesh_mark<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, fbits, 3, 0, flags, counts);
-    k_fuse_scan<<<1, 1024, 0, s>>>(counts, n_chunks, offsets, seg_count, running, seg_base);
-    k_mesh_scatter_faces<<<static_cast<unsigned>(n_chunks), 256, 0, s>>>(p0, n, smp, m, cflag, vid, flags, offsets, seg_base, cap,
-                                                                          faces, words);
-    return hipGetLastError();
+                             const uint8_t* fbits, const int32_t* vid, Compaction c, int32_t* faces,
+                             unsigned long long* words, hipStream_t s) {
+    return compact_segment(MeshFaces{{}, smp, m, cflag, fbits, vid, faces, words}, p0, n, c, s);
 }
 
 // ------------------------------------------------------------------ the mesh rendered into a view
@@ -1867,32 +1785,6 @@ __device__ __forceinline__ unsigned long long dist_cell_key(const DistGrid& g, c
     return dist_key(cx, cy, cz);
 }
 
-// The slot of `key`, claimed when the key is new (as k_voxel_insert); false = the probe sequence covered every slot.
-__device__ __forceinline__ bool dist_claim(const DistTable& t, unsigned long long key, unsigned long long& slot) {
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        unsigned long long k = t.keys[s];
-        if (k == kVoxEmpty) k = atomicCAS(&t.keys[s], kVoxEmpty, key);
-        if (k == kVoxEmpty || k == key) { slot = s; return true; }
-        s = (s + 1ull) & mask;
-    }
-    return false;
-}
-
-// The lookup of a cell that may be absent, after the insert pass: 0 = found, 1 = absent, 2 = every slot covered.
-__device__ __forceinline__ int dist_find(const DistTable& t, unsigned long long key, unsigned long long& slot) {
-    const unsigned long long mask = t.slots - 1ull;
-    unsigned long long s = vox_home(key, t.log2_slots);
-    for (unsigned long long probe = 0; probe < t.slots; ++probe) {
-        const unsigned long long k = t.keys[s];
-        if (k == key) { slot = s; return 0; }
-        if (k == kVoxEmpty) return 1;
-        s = (s + 1ull) & mask;
-    }
-    return 2;
-}
-
 __global__ __launch_bounds__(256) void k_dist_bounds(const DistCloud t, unsigned long long* __restrict__ words) {
     const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
     uint32_t m[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
@@ -1923,9 +1815,9 @@ __global__ __launch_bounds__(256) void k_dist_insert(const DistCloud t, const Di
         float v[3];
         if (dist_load(t, i, v)) {
             unsigned long long s;
-            if (dist_claim(fine, dist_cell_key(g, v), s)) atomicAdd(&fine.cnt[s], 1u);
+            if (table_claim(fine, dist_cell_key(g, v), s)) atomicAdd(&fine.cnt[s], 1u);
             else err = 1u;
-            if (coarse.keys && !dist_claim(coarse, dist_cell_key(cg, v), s)) err = 1u;
+            if (coarse.keys && !table_claim(coarse, dist_cell_key(cg, v), s)) err = 1u;
         }
     }
     block_or(err, &words[kDistErr]);
@@ -1978,7 +1870,7 @@ __global__ __launch_bounds__(256) void k_dist_scatter(const DistCloud t, const D
         float v[3];
         if (dist_load(t, i, v)) {
             unsigned long long s;
-            if (dist_find(fine, dist_cell_key(g, v), s) == 0) {
+            if (table_find(fine, dist_cell_key(g, v), s) == 0) {
                 const uint32_t pos = atomicAdd(&fine.cnt[s], 1u);
                 if (pos < t.n) list[pos] = make_float4(v[0], v[1], v[2], __uint_as_float(static_cast<uint32_t>(i)));
                 else err = 2u;
@@ -2001,7 +1893,7 @@ __device__ __forceinline__ double dist_floor2(double L) {
 __device__ __forceinline__ void dist_visit(const DistTable& fine, const float4* __restrict__ list, const float v[3], int cx,
                                            int cy, int cz, unsigned long long& best, unsigned& err) {
     unsigned long long s;
-    const int r = dist_find(fine, dist_key(cx, cy, cz), s);
+    const int r = table_find(fine, dist_key(cx, cy, cz), s);
     if (r == 2) err |= 4u;
     if (r != 0) return;
     const uint32_t a = fine.start[s], b = fine.cnt[s];
@@ -2041,7 +1933,7 @@ __device__ __forceinline__ unsigned long long dist_nearest(const float v[3], con
             for (int y = max(c[1] - 1, 0); y <= min(c[1] + 1, cg.cmax[1]) && !any; ++y)
                 for (int x = max(c[0] - 1, 0); x <= min(c[0] + 1, cg.cmax[0]) && !any; ++x) {
                     unsigned long long s;
-                    const int r = dist_find(coarse, dist_key(x, y, z), s);
+                    const int r = table_find(coarse, dist_key(x, y, z), s);
                     if (r == 2) err |= 4u;
                     any = r != 1;
                 }

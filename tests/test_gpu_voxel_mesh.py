@@ -127,6 +127,36 @@ def test_segments(source, monkeypatch):
     assert plain[2][:2] == (0, 0) and plain[2][2]["valid"] == 0 and plain[2][2]["samples"] == info["samples"]
 
 
+def test_one_chunk_segments_across_stages(monkeypatch):
+    """The compaction primitive every stage shares, at one 256-item chunk per segment: the carry of the output position
+    from segment to segment is taken at every boundary of the voxel, root, clean, visible, sample, vertex and face
+    passes.  The device against itself at the default segment size, array for array."""
+    def run():
+        cams, depths, normals, colours, cloud, size, trunc, _ = ms.base_case("pinhole")
+        views = list(range(len(cams)))
+        gf = fill(capi.Fusion(0, cams), cams, depths, normals, colours)
+        gf.set_scene(cloud)
+        n = gf.voxelize(size, None, 1)[0]
+        kept, info = gf.voxel_clean(*CLEAN)
+        tol, radius, sup, con = VISIBILITY
+        seen = gf.voxel_visibility(views, tol, radius, sup, con, source="clean")[0]
+        nv, nf, mesh = gf.voxel_mesh(views, trunc, 1, source="visible")
+        out = [*gf.voxel_points(0, n, counts=True), *gf.component_table(0, info["components"]),
+               *gf.clean_points(0, kept, counts=True, component=True), *gf.visible_points(0, seen, counts=True, tallies=True),
+               *_read(gf, nv, nf, mesh["samples"])]
+        gf.close()
+        return (n, kept, info, seen, nv, nf, mesh), out
+    plain, want = run()
+    monkeypatch.setenv("ACMMP_VOXEL_SEGMENT_POINTS", "256")
+    split, got = run()
+    assert split == plain
+    n, kept, info, seen, nv, nf, mesh = plain
+    assert min(n, kept, seen, mesh["samples"], nv, nf // 2) > 256                      # more than one segment each
+    assert len(got) == len(want) == 16
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), k
+
+
 def test_collisions_and_a_full_table():
     """The visible source of the sphere rig: at the smallest table above its samples the restatement counts cells
     stored below their home slot (test_voxel_mesh_restatement.py asserts > 0)."""
