@@ -973,6 +973,21 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     // of 65 px; scripts/interp_feasibility.py, tests/test_interp_design.py).  patch_size 21 / increment 4
     // also gives 6x6 samples but spans twice the angle: it projects every sample below 4000x2000.
     kp.interp = c->model == kSphere && nside == 6 && 2000LL * R <= 5LL * c->W && 1000LL * R <= 5LL * c->H;
+    // The per-sample refinement loops' negligible-sample threshold (ncc_chunk's PNEG instances):
+    // fast SPHERE with binary16 texels, V <= 4, in k_eval_ref, k_eval_ref_tail and k_select's cache misses (k_init,
+    // whose cost vectors are always complete, keeps every sample; without the binary16 images the refinement runs the
+    // TF = 0 instances, which have no masked form).  A sample whose weight is at most tau x its own pixel's patch sum
+    // adds nothing to the source sums: a function of the pixel alone, so whichever kernel and wave evaluates a
+    // (pixel, plane, view) forms the same bits.  Gated by the geometry above only, before ACMMP_INTERP is applied, and by none of
+    // ACMMP_SPREAD_MAX / ACMMP_NBFIX_MAX_PC / ACMMP_NEG_*: the runs the tests compare across those knobs share
+    // one refinement.  ACMMP_REF_NEG_TAU overrides tau (tests), ACMMP_REF_NEG_SKIP=0 launches the instances
+    // without the mask; both read per run.
+    kp.ref_neg_tau = -1.0f;
+    if (kp.interp && c->math == ACMMP_MATH_FAST && c->tex16 && kp.V <= 4) {
+        kp.ref_neg_tau = 0x1p-35f;
+        if (const char* e = std::getenv("ACMMP_REF_NEG_TAU")) kp.ref_neg_tau = std::strtof(e, nullptr);
+        if (const char* e = std::getenv("ACMMP_REF_NEG_SKIP")) if (std::atoi(e) == 0) kp.ref_neg_tau = -1.0f;
+    }
     // ACMMP_INTERP=0 projects every sample in the fast mode too (the per-sample fast arithmetic the
     // interpolation is gated against, tests/test_gpu_fastmath.py T2); read per run
     if (const char* e = std::getenv("ACMMP_INTERP")) kp.interp = kp.interp && std::atoi(e) != 0;

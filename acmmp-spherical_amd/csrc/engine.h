@@ -145,6 +145,10 @@ struct KParams {
     // drops the ones whose partial aggregate already cannot beat cost_now, and queues the rest
     // (ci * 8 + candidate) for k_eval_ref_tail, which adds views [ref_split, V).  0 = no split.
     int ref_split;
+    // (in the 4 bytes of padding before the next pointer: no field moves, so every kernel's argument offsets stay)
+    float ref_neg_tau;              // the per-sample refinement loops (k_eval_ref, its tail, k_select's cache misses) drop a
+                                    // sample whose weight is <= ref_neg_tau x its own pixel's patch sum
+                                    // (ACMMP_REF_NEG_TAU, 2^-35); < 0: none (ACMMP_REF_NEG_SKIP=0, or outside the gate)
     uint32_t* surv;                 // queued candidates: kRefSlots (255) slots per k_eval_ref block
     unsigned* surv_count;           // [k_eval_ref blocks] slots used (zeroed before each k_eval_ref)
     unsigned* surv_pre;             // [k_eval_ref blocks + 1] their exclusive prefix (k_tail_scan)

@@ -605,7 +605,7 @@ __device__ __forceinline__ int lane_id_here() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, int NB = 0>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, int NB = 0, bool PNEG = false>
 __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                           const int (&vlist)[VB], int nv_rt, float (&cost)[VB],
                                           uint32_t fixkey = kFixNone) {
@@ -688,9 +688,9 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
 // Pinhole: a sample outside the source image (ok false) adds nothing (ACMMP.cu:470-473); instead of a
 // branch per view-sample its weight and texel are selected to zero -- fma(0, 0, s) and s + 0 return s
 // for the non-negative sums, so the same bits as skipping it
-#define ACMMP_ACCUMULATE_T(v, T, W_, WWR_, R_, OK_)                          \
+#define ACMMP_ACCUMULATE_Z(v, T, W_, WWR_, R_, OK_, ZERO_)                   \
     do {                                                             \
-        const float sp = lerp_tap<TEX>(T);                           \
+        const float sp = (ZERO_) ? 0.f : lerp_tap<TEX>(T);           \
         if (MODEL == kPinhole) {                                     \
             const bool ok_ = (OK_);                                  \
             const f32x2 wwr_ = ok_ ? (WWR_) : splat2(0.f);           \
@@ -706,6 +706,7 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
             sss[v] = fmaf(ws, sp, sss[v]);                           \
         }                                                            \
     } while (0)
+#define ACMMP_ACCUMULATE_T(v, T, W_, WWR_, R_, OK_) ACMMP_ACCUMULATE_Z(v, T, W_, WWR_, R_, OK_, false)
 #define ACMMP_ACCUMULATE(v) ACMMP_ACCUMULATE_T(v, tap[v], w, wwr, r, ok[v])
     // Fast SPHERE k_eval_nb chunks with 6x6 samples: per view, the source coordinates come from 16 exact
     // projections at the samples of patch columns / rows {0, 2, 3, 5} and, for the others, the 4-point
@@ -1112,6 +1113,23 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
         }
     }
     if (!interp_done) {
+        // PNEG (fast SPHERE refinement, V <= 4: k_eval_ref, its tail, k_select's cache misses; DESIGN.md
+        // §2.4): a sample whose weight is at most ref_neg_tau x its own pixel's patch sum adds nothing to the
+        // source sums of any view.  `mine` is a function of the pixel alone, so a cost does not depend on which
+        // kernel, wave or strip evaluates it: w is patch_sample's value in all three (k_eval_ref reads back what
+        // coop_patch_sep staged from it, the tail and k_select recompute it with the same centre texel);
+        // pt.sbw is coop_patch_sep's sum in k_eval_ref, the same word handed on through kp.psum in the tail, and
+        // make_patch's in k_select -- the one place that relies on patch_sums and coop_patch_sep folding the 36
+        // weights in the same order, as the unmasked cost's own bits (sbw is its divisor) already do.  The test is
+        // one ballot per sample, not a mask reduced before the loop: nothing is held across the views for it.  Where every active lane of the wave drops the
+        // sample (lanes of dead pixels returned above) a scalar branch skips its ray, depth, point, projections,
+        // fetches and sums; in a sample the wave keeps, a dropping lane runs the body with w = 0 and its source
+        // texel selected to 0: fma(+0, +0, s) = s and s + +0 = s for the sums, which are never -0 (they start
+        // at +0 and take products of non-negative weights and texels), so its bits are the skipped form's --
+        // also where its own projection is NaN (a point on the source's vertical axis), which w = 0 alone
+        // would let into the sums.  The reference-side sums (pt.sbw, sref, srr) keep all samples.
+        const float neg_lim = PNEG ? kp.ref_neg_tau * pt.sbw : 0.f;
+#define ACMMP_ACCUMULATE_N(v) ACMMP_ACCUMULATE_Z(v, tap[v], w, wwr, r, ok[v], PNEG && mine)
         int s = 0, ii = 0;
         for (int i = -R; i <= R; i += inc, ++ii) {
             int jj = 0;                                      // s % nside without a division per sample
@@ -1136,7 +1154,9 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                 } else {
                     rw = patch_sample<MODEL>(kp, px, py, s, i, j, pt.center, r);
                 }
-                const float w = rw.w;
+                const bool mine = PNEG && rw.w <= neg_lim;
+                if constexpr (PNEG) if (__all(mine)) continue;
+                const float w = mine ? 0.f : rw.w;
                 // reference camera through the constant address space too: scalar loads per sample
                 // instead of 12 wave-uniform VGPRs held across the loop
                 float3 P;
@@ -1172,7 +1192,7 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                             ok[v] = pin_in_image(c, ix, iy);
                             tap[v] = fetch_tap_pin<TEX>(rs, c, sx, sy, ix, iy);
                         }
-                        if (G == 1) ACMMP_ACCUMULATE(v);
+                        if (G == 1) ACMMP_ACCUMULATE_N(v);
                     }
                     // a full SPHERE chunk has no per-view branches; keep its views' code in view order
                     // (interleaved, their live ranges overlap and the 7-wave register budget spills)
@@ -1182,14 +1202,16 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                     if (G > 1 && ((v + 1) % G == 0 || v == VB - 1)) {
 #pragma unroll
                         for (int u = v - (v % G); u <= v; ++u)
-                            if (has(u)) ACMMP_ACCUMULATE(u);
+                            if (has(u)) ACMMP_ACCUMULATE_N(u);
                     }
                 }
             }
         }
     }
 #undef ACMMP_ACCUMULATE
+#undef ACMMP_ACCUMULATE_N
 #undef ACMMP_ACCUMULATE_T
+#undef ACMMP_ACCUMULATE_Z
 #pragma unroll
     for (int v = 0; v < VB; ++v) {
         cost[v] = cval[v] ? ncc_cost(sbw[v], srrr[v], ssrs[v], sss[v]) : 2.0f;
@@ -1282,7 +1304,7 @@ __device__ __forceinline__ float4 perturbed_normal(float4 v, float4 n, Rng& rs, 
 // ------------------------------------------------------------------ cost-vector helpers
 
 // Evaluate all source views of plane `ph` and hand each cost to f(view0, cost) in view order.
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, int NOFULL = 0, typename F>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, int NOFULL = 0, bool PNEG = false, typename F>
 __device__ __forceinline__ void for_all_views_t(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                                 uint32_t wave_mask, F&& f, uint32_t fixkey = kFixNone) {
     int v = 0;
@@ -1309,9 +1331,9 @@ __device__ __forceinline__ void for_all_views_t(const KParams& kp, int px, int p
         constexpr bool kFullCopy = (MODEL == kSphere ? VB <= 2 : true) && VB > 1 &&
                                    !(NOFULL && MODEL == kSphere && STAGED == 3 && FM && TEX == 1);
         if (kFullCopy && nv == VB)
-            ncc_chunk<MODEL, VB, STAGED, PIPE, TEX, FM, true, NOFULL>(kp, px, py, pt, ph, vlist, nv, cost, fixkey);
+            ncc_chunk<MODEL, VB, STAGED, PIPE, TEX, FM, true, NOFULL, PNEG>(kp, px, py, pt, ph, vlist, nv, cost, fixkey);
         else
-            ncc_chunk<MODEL, VB, STAGED, PIPE, TEX, FM, false, NOFULL>(kp, px, py, pt, ph, vlist, nv, cost, fixkey);
+            ncc_chunk<MODEL, VB, STAGED, PIPE, TEX, FM, false, NOFULL, PNEG>(kp, px, py, pt, ph, vlist, nv, cost, fixkey);
 #pragma unroll
         for (int k = 0; k < VB; ++k)
             if (k < nv) f(vlist[k] - 1, cost[k]);
@@ -1337,15 +1359,16 @@ __device__ __forceinline__ void for_all_views(const KParams& kp, int px, int py,
 // register allocation (k_eval_nb's r02 A/B: a run-time branch between them sized every path for the
 // largest).  0 = fp32 texels, math mode at run time (images that are not binary16-exact); 1 = binary16
 // texels, exact; 2 = binary16 texels, fast math.
-template <int MODEL, int VB, int STAGED, bool PIPE, int TF, bool PIPE_FM = PIPE, typename F>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TF, bool PIPE_FM = PIPE, bool PNEG = false, typename F>
 __device__ __forceinline__ void for_all_views_tf(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                                  uint32_t wave_mask, F&& f, uint32_t fixkey = kFixNone) {
     if constexpr (TF == 0) {
         if (kp.fast) for_all_views_t<MODEL, VB, STAGED, PIPE_FM, 0, 1>(kp, px, py, pt, ph, wave_mask, f);
         else for_all_views_t<MODEL, VB, STAGED, PIPE, 0, 0>(kp, px, py, pt, ph, wave_mask, f);
     } else {
-        for_all_views_t<MODEL, VB, STAGED, TF == 2 ? PIPE_FM : PIPE, 1, TF == 2 ? 1 : 0>(kp, px, py, pt, ph, wave_mask, f,
-                                                                                       fixkey);
+        // (PNEG: the per-pixel negligible-sample mask of the fast SPHERE per-sample loop, ncc_chunk)
+        for_all_views_t<MODEL, VB, STAGED, TF == 2 ? PIPE_FM : PIPE, 1, TF == 2 ? 1 : 0, 0, PNEG && TF == 2 && MODEL == kSphere>(
+            kp, px, py, pt, ph, wave_mask, f, fixkey);
     }
 }
 static inline int tf_of(const KParams& kp) { return kp.tex16 ? (kp.fast ? 2 : 1) : 0; }
@@ -2102,7 +2125,7 @@ __global__ __launch_bounds__(256) void k_nb_fix(const KParams kp, const int colo
 #ifndef ACMMP_SELECT_WAVES
 #define ACMMP_SELECT_WAVES 5
 #endif
-template <int MODEL, int VB, bool GEOM>
+template <int MODEL, int VB, bool GEOM, bool PNEG = false>
 __global__ __launch_bounds__(256, ACMMP_SELECT_WAVES) void k_select(const KParams kp, const int colour, const int iter) {
     const long long q = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     // k_eval_ref's per-block survivor counters, emptied here for the launch that follows (launch_eval_ref's grid:
@@ -2357,9 +2380,13 @@ __global__ __launch_bounds__(256, ACMMP_SELECT_WAVES) void k_select(const KParam
     }
     if (miss) {
         const Patch pt = make_patch<MODEL>(kp, px, py);
-        for_all_views<MODEL, 1, 0, true>(kp, px, py, pt, cur_plane, wave_or(miss, V), [&](int v, float c) {
+        auto put = [&](int v, float c) {
             if ((miss >> v) & 1u) cvec[v * Pc] = c;
-        });
+        };
+        // (PNEG: launched only in the fast mode with binary16 texels -- the refinement's masked per-sample loop, so a
+        // view evaluated here has the bits k_eval_ref or its tail would have formed for it)
+        if constexpr (PNEG) for_all_views_t<MODEL, 1, 0, true, 1, 1, 0, true>(kp, px, py, pt, cur_plane, wave_or(miss, V), put);
+        else for_all_views<MODEL, 1, 0, true>(kp, px, py, pt, cur_plane, wave_or(miss, V), put);
     }
     if (kCvecLoop || miss) {
         cost_now = 0.0f;
@@ -2559,7 +2586,7 @@ __global__ __launch_bounds__(256, ACMMP_SELECT_WAVES) void k_select(const KParam
 #ifndef ACMMP_REF_INTERP_WAVES
 #define ACMMP_REF_INTERP_WAVES 4
 #endif
-template <int MODEL, int VB, bool GEOM, int TF>
+template <int MODEL, int VB, bool GEOM, int TF, bool PNEG = false>
 __global__ __launch_bounds__(256, (MODEL == kSphere && VB > 4 && TF == 2) ? ACMMP_REF_INTERP_WAVES : 1) void k_eval_ref(const KParams kp, const int colour) {
     extern __shared__ float4 lds4[];
     const int t = threadIdx.x;
@@ -2612,7 +2639,7 @@ __global__ __launch_bounds__(256, (MODEL == kSphere && VB > 4 && TF == 2) ? ACMM
     // pruning stays exact; a survivor with rough selected views restarts its chain in the tail.
     constexpr bool kRefInterp = MODEL == kSphere && kStaged == 3 && TF == 2;
     uint32_t rough = 0u;
-    for_all_views_tf<MODEL, VBA, kStaged, kRefPipe, TF>(kp, px, py, pt, tp, amask, [&](int v, float c) {
+    for_all_views_tf<MODEL, VBA, kStaged, kRefPipe, TF, kRefPipe, PNEG>(kp, px, py, pt, tp, amask, [&](int v, float c) {
         vcost[v * Pc] = c;
         const bool r = kRefInterp && c != c;
         if (r) rough |= 1u << v;
@@ -2738,7 +2765,7 @@ __global__ __launch_bounds__(256) void k_tail_compact(const KParams kp) {
 // wave completion order, gave C3 a 58% L2 hit rate and 36 GB per launch), and every lane has a survivor
 // (per-k_eval_ref-block tail blocks left half their lanes idle; a binary search of surv_pre per 256 survivors
 // serialised each block: the metric's tail 0.34 -> 1.2 ms).
-template <int MODEL, int VB, bool GEOM, int TF>
+template <int MODEL, int VB, bool GEOM, int TF, bool PNEG = false>
 __global__ __launch_bounds__(256) void k_eval_ref_tail(const KParams kp, const int colour, const int nref) {
     const unsigned total = kp.surv_pre[nref];
     const unsigned x = blockIdx.x & 7u, k = blockIdx.x >> 3, nk = gridDim.x >> 3;
@@ -2793,7 +2820,7 @@ __global__ __launch_bounds__(256) void k_eval_ref_tail(const KParams kp, const i
 #endif
         constexpr int VBT = (MODEL == kSphere && VB > 4) ? ACMMP_TAIL_SPH_VB
                           : (MODEL == kPinhole && VB > 4) ? ACMMP_TAIL_PIN_VB : ref_vb<MODEL, VB>();
-        for_all_views_tf<MODEL, VBT, 0, kRefPipe, TF>(kp, px, py, pt, tp, umask, [&](int v, float c) {
+        for_all_views_tf<MODEL, VBT, 0, kRefPipe, TF, kRefPipe, PNEG>(kp, px, py, pt, tp, umask, [&](int v, float c) {
             vcost[v * Pc] = c;
             add_term(v, c);
         });
@@ -3354,7 +3381,11 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
 #define ACMMP_SELECT(MV)                                                                                              \
     do {                                                                                                              \
         if (kp.model == kSphere) {                                                                                    \
-            if (kp.geom) k_select<kSphere, MV, true><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);               \
+            constexpr bool N = MV <= 4;       /* the masked per-sample loop (ref_neg_tau: fast, binary16, V <= 4) */  \
+            if (kp.ref_neg_tau >= 0.0f && N) {                                                                        \
+                if (kp.geom) k_select<kSphere, MV, true, N><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);        \
+                else k_select<kSphere, MV, false, N><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);               \
+            } else if (kp.geom) k_select<kSphere, MV, true><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);        \
             else k_select<kSphere, MV, false><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);                      \
         } else {                                                                                                      \
             if (kp.geom) k_select<kPinhole, MV, true><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);              \
@@ -3375,6 +3406,32 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
 #endif  // ACMMP_IN_TU(3)
 
 #if ACMMP_IN_TU(4)
+// The refinement's instances with the per-pixel negligible-sample mask (ncc_chunk's PNEG) exist for fast SPHERE with
+// binary16 texels up to 4 views, and are launched where the run has the mask (ref_neg_tau >= 0); every other
+// launch, and ACMMP_REF_NEG_SKIP=0, takes the instance that has no code for it.
+template <int M, int VBC, int TF>
+constexpr bool ref_neg_inst() { return M == kSphere && VBC <= 4 && TF == 2; }
+template <int M, int VBC, bool GEOM, int TF>
+static void launch_ref_inst(const KParams& kp, int colour, dim3 grd, size_t lds, hipStream_t s) {
+    if constexpr (ref_neg_inst<M, VBC, TF>()) {
+        if (kp.ref_neg_tau >= 0.0f) {
+            k_eval_ref<M, VBC, GEOM, TF, true><<<grd, 256, lds, s>>>(kp, colour);
+            return;
+        }
+    }
+    k_eval_ref<M, VBC, GEOM, TF><<<grd, 256, lds, s>>>(kp, colour);
+}
+template <int M, int VBC, bool GEOM, int TF>
+static void launch_tail_inst(const KParams& kp, int colour, int nref, dim3 grd, hipStream_t s) {
+    if constexpr (ref_neg_inst<M, VBC, TF>()) {
+        if (kp.ref_neg_tau >= 0.0f) {
+            k_eval_ref_tail<M, VBC, GEOM, TF, true><<<grd, 256, 0, s>>>(kp, colour, nref);
+            return;
+        }
+    }
+    k_eval_ref_tail<M, VBC, GEOM, TF><<<grd, 256, 0, s>>>(kp, colour, nref);
+}
+
 // Precondition: kp.surv_count[0 .. ref_block_count(kp)) is zero -- k_select, the kernel launch_propagate runs
 // right before, empties it.
 hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
@@ -3390,8 +3447,8 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
     // k_eval_nb's Pc x chunk / 32, S <= chunk)
     const bool ref_fix = uses_fix_queue(kp, true);
     if (ref_fix && (e = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e;
-    if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref<M, VBC, true, TF><<<grd_ref, 256, lds_ref, s>>>(kp, colour))));
-    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref<M, VBC, false, TF><<<grd_ref, 256, lds_ref, s>>>(kp, colour))));
+    if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, true, TF>(kp, colour, grd_ref, lds_ref, s))));
+    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, false, TF>(kp, colour, grd_ref, lds_ref, s))));
     if (ref_fix) k_nb_fix<1, true><<<16 * kNbFixRegions, 256, 0, s>>>(kp, colour);
     if (kp.ref_split > 0) {
         // the survivors' prefix over k_eval_ref blocks, then 8 x nk tail blocks (the queue's length is
@@ -3405,8 +3462,8 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
         k_tail_scan<<<1, 1024, 0, s>>>(kp, nref);
         k_tail_compact<<<static_cast<unsigned>(nref), 256, 0, s>>>(kp);
         const unsigned grd = 8u * static_cast<unsigned>(std::min<long long>(ACMMP_TAIL_NK, std::max<long long>(1, cdiv(static_cast<long long>(nref) * kRefSlots, 8 * 256))));
-        if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref_tail<M, VBC, true, TF><<<grd, 256, 0, s>>>(kp, colour, nref))));
-        else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_eval_ref_tail<M, VBC, false, TF><<<grd, 256, 0, s>>>(kp, colour, nref))));
+        if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, true, TF>(kp, colour, nref, grd, s))));
+        else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, false, TF>(kp, colour, nref, grd, s))));
     }
     return hipGetLastError();
 }
@@ -3416,7 +3473,7 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
 // all views; the views whose interpolation fell back (fast SPHERE, V > 4) are queued as k_eval_ref queues a
 // survivor's (candidate << 5 | view keys on the fallback queue) and recomputed by k_debug_nb_fix<1, 5>, whose
 // per-entry code (fix_row, fix_fold) is k_nb_fix<1, true>'s.  out[(q * 5 + h) * V + v].
-template <int MODEL, int VB, int TF>
+template <int MODEL, int VB, int TF, bool PNEG = false>
 __global__ __launch_bounds__(256) void k_debug_ref(const KParams kp, int n, const int* __restrict__ qx,
                                                    const int* __restrict__ qy, const float4* __restrict__ planes,
                                                    float* __restrict__ out) {
@@ -3438,7 +3495,7 @@ __global__ __launch_bounds__(256) void k_debug_ref(const KParams kp, int n, cons
     const uint32_t all = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
     constexpr bool kRefInterp = MODEL == kSphere && kStaged == 3 && TF == 2;
     uint32_t rough = 0u;
-    for_all_views_tf<MODEL, VBA, kStaged, kRefPipe, TF>(kp, px, py, pt, ph, all, [&](int v, float c) {
+    for_all_views_tf<MODEL, VBA, kStaged, kRefPipe, TF, kRefPipe, PNEG>(kp, px, py, pt, ph, all, [&](int v, float c) {
         o[v] = c;
         if (kRefInterp && c != c) rough |= 1u << v;
     }, kRefInterp && kp.nbfix ? kFixNan : kFixNone);
@@ -3464,6 +3521,19 @@ __global__ __launch_bounds__(256) void k_debug_ref(const KParams kp, int n, cons
     }
 }
 
+// (the masked instance where the run's refinement takes it: launch_ref_inst's rule)
+template <int M, int VBC, int TF>
+static void launch_debug_ref_inst(const KParams& kp, int n, const int* px, const int* py, const float4* planes, float* out,
+                                  dim3 grd, size_t lds, hipStream_t s) {
+    if constexpr (ref_neg_inst<M, VBC, TF>()) {
+        if (kp.ref_neg_tau >= 0.0f) {
+            k_debug_ref<M, VBC, TF, true><<<grd, 256, lds, s>>>(kp, n, px, py, planes, out);
+            return;
+        }
+    }
+    k_debug_ref<M, VBC, TF><<<grd, 256, lds, s>>>(kp, n, px, py, planes, out);
+}
+
 hipError_t launch_debug_ref(const KParams& kp0, int n, const int* px, const int* py, const float4* planes, float* out,
                             hipStream_t s) {
     KParams kp = kp0;
@@ -3477,7 +3547,7 @@ hipError_t launch_debug_ref(const KParams& kp0, int n, const int* px, const int*
     if (fix && static_cast<long long>(cdiv(grd.x, kNbFixRegions)) * kRefSlots * kp.V > kp.nbfix_cap) return hipErrorInvalidValue;
     hipError_t e0 = hipSuccess;
     if (fix && (e0 = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e0;
-    ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_debug_ref<M, VBC, TF><<<grd, 256, lds_ref, s>>>(kp, n, px, py, planes, out))));
+    ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_debug_ref_inst<M, VBC, TF>(kp, n, px, py, planes, out, grd, lds_ref, s))));
     if (fix) k_debug_nb_fix<1, kRefLanes><<<kNbFixRegions, 256, 0, s>>>(kp, px, py, planes, out);
     return hipGetLastError();
 }
