@@ -102,7 +102,7 @@ EXPORTS = [
     "acmmp_set_scaled_state", "acmmp_set_planar_prior", "acmmp_run_patchmatch", "acmmp_run_patchmatch_ex",
     "acmmp_download", "acmmp_download_aux", "acmmp_device_outputs", "acmmp_synchronize", "acmmp_last_timing",
     "acmmp_last_kernel_timing", "acmmp_last_work", "acmmp_last_planar_timing", "acmmp_texel_bytes", "acmmp_set_math", "acmmp_get_math", "acmmp_jbu",
-    "acmmp_debug_ncc", "acmmp_debug_geom", "acmmp_debug_ncc_nb", "acmmp_debug_ncc_ref",
+    "acmmp_debug_ncc", "acmmp_debug_geom", "acmmp_debug_ncc_nb", "acmmp_debug_ncc_ref", "acmmp_debug_band_cvec",
     "acmmp_support_points", "acmmp_delaunay", "acmmp_prior_plane_params", "acmmp_depth_from_plane_param",
     "acmmp_planar_prior_host", "acmmp_set_planar_prior_from_maps", "acmmp_set_planar_prior_from_state",
     "acmmp_download_planar_prior",
@@ -221,6 +221,7 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_band_copy_rows.argtypes = [vp, vp, i32, i32, i32]
     L.acmmp_band_get_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.acmmp_band_set_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.acmmp_debug_band_cvec.argtypes = [vp, i32, i32, i32, vp]
     L.acmmp_band_end.argtypes = [vp, i32]
     L.acmmp_fusion_create.argtypes = [i32, i32, vp, C.POINTER(vp)]
     L.acmmp_fusion_set_view.argtypes = [vp, i32, vp, vp, vp]
@@ -635,6 +636,13 @@ class Context:
         sel = np.empty(n, np.uint32)
         self._check(self.L.acmmp_band_get_rows(self.h, colour, row_a, row_b, _p(pl), _p(co), _p(sel)), "band_get_rows")
         return np.concatenate([pl.view(np.uint32), co.view(np.uint32)[:, None], sel[:, None]], axis=1)
+
+    def debug_band_cvec(self, colour: int, row_a: int, row_b: int) -> np.ndarray:
+        """The cached NCC cost vectors of rows [row_a, row_b) of `colour` in a band run -> (V, n) float32, n the rows'
+        colour-grid pixels in band_get_rows' order; straight after band_begin, k_init's vectors of its planes."""
+        out = np.empty((self.N - 1, (row_b - row_a) * ((self.W + 1) // 2)), np.float32)
+        self._check(self.L.acmmp_debug_band_cvec(self.h, colour, row_a, row_b, _p(out)), "debug_band_cvec")
+        return out
 
     def band_set_rows(self, colour: int, row_a: int, row_b: int, rows: np.ndarray):
         """Inverse of band_get_rows: write the (n, 6) words into `colour`'s current band state."""

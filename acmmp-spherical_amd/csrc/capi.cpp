@@ -974,9 +974,9 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     // also gives 6x6 samples but spans twice the angle: it projects every sample below 4000x2000.
     kp.interp = c->model == kSphere && nside == 6 && 2000LL * R <= 5LL * c->W && 1000LL * R <= 5LL * c->H;
     // The per-sample refinement loops' negligible-sample threshold (ncc_chunk's PNEG instances):
-    // fast SPHERE with binary16 texels, V <= 4, in k_eval_ref, k_eval_ref_tail and k_select's cache misses (k_init,
-    // whose cost vectors are always complete, keeps every sample; without the binary16 images the refinement runs the
-    // TF = 0 instances, which have no masked form).  A sample whose weight is at most tau x its own pixel's patch sum
+    // fast SPHERE with binary16 texels, V <= 4, in k_init, k_eval_ref, k_eval_ref_tail and k_select's cache misses
+    // (without the binary16 images these run the TF = 0 instances, which have no masked form), so the cost cache holds
+    // one arithmetic from the first vector on.  A sample whose weight is at most tau x its own pixel's patch sum
     // adds nothing to the source sums: a function of the pixel alone, so whichever kernel and wave evaluates a
     // (pixel, plane, view) forms the same bits.  Gated by the geometry above only, before ACMMP_INTERP is applied, and by none of
     // ACMMP_SPREAD_MAX / ACMMP_NBFIX_MAX_PC / ACMMP_NEG_*: the runs the tests compare across those knobs share
@@ -1453,6 +1453,24 @@ acmmp_status acmmp_band_get_rows(acmmp_ctx* c, int colour, int row_a, int row_b,
     HIP_TRY(c, d2h(planes, b.plane + off, sizeof(float4) * n));
     HIP_TRY(c, d2h(costs, b.cost + off, sizeof(float) * n));
     HIP_TRY(c, d2h(sel, b.sel + off, sizeof(uint32_t) * n));
+    return ACMMP_OK;
+}
+
+// Test hook: the cost cache (KParams::cvec) of rows [row_a, row_b) of `colour` in a band run, out[v * n + k] for view v
+// and colour-grid pixel k of the n = (row_b - row_a) * Wh -- after acmmp_band_begin, k_init's vectors of its planes.
+acmmp_status acmmp_debug_band_cvec(acmmp_ctx* c, int colour, int row_a, int row_b, float* out) {
+    if (!c || !out) return ACMMP_ERR_INVALID_ARGUMENT;
+    BandBuffers b{};
+    const acmmp_status st = band_buffers(c, colour, &b);
+    if (st != ACMMP_OK) return st;
+    if (row_a < 0 || row_b > c->H || row_a > row_b) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "rows out of range");
+    if (row_a == row_b) return ACMMP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const KParams& kp = c->band_kp;
+    const size_t off = static_cast<size_t>(row_a) * b.Wh, n = static_cast<size_t>(row_b - row_a) * b.Wh;
+    for (int v = 0; v < kp.V; ++v)
+        HIP_TRY(c, d2h(out + static_cast<size_t>(v) * n, kp.cvec[colour] + static_cast<size_t>(v) * kp.Pc + off, sizeof(float) * n));
     return ACMMP_OK;
 }
 

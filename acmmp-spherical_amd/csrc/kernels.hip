@@ -1113,13 +1113,13 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
         }
     }
     if (!interp_done) {
-        // PNEG (fast SPHERE refinement, V <= 4: k_eval_ref, its tail, k_select's cache misses; DESIGN.md
+        // PNEG (fast SPHERE, V <= 4: k_init, k_eval_ref, its tail, k_select's cache misses; DESIGN.md
         // §2.4): a sample whose weight is at most ref_neg_tau x its own pixel's patch sum adds nothing to the
         // source sums of any view.  `mine` is a function of the pixel alone, so a cost does not depend on which
-        // kernel, wave or strip evaluates it: w is patch_sample's value in all three (k_eval_ref reads back what
-        // coop_patch_sep staged from it, the tail and k_select recompute it with the same centre texel);
+        // kernel, wave or strip evaluates it: w is patch_sample's value in all four (k_eval_ref reads back what
+        // coop_patch_sep staged from it, the tail, k_select and k_init recompute it with the same centre texel);
         // pt.sbw is coop_patch_sep's sum in k_eval_ref, the same word handed on through kp.psum in the tail, and
-        // make_patch's in k_select -- the one place that relies on patch_sums and coop_patch_sep folding the 36
+        // make_patch's in k_select and k_init -- the one place that relies on patch_sums and coop_patch_sep folding the 36
         // weights in the same order, as the unmasked cost's own bits (sbw is its divisor) already do.  The test is
         // one ballot per sample, not a mask reduced before the loop: nothing is held across the views for it.  Where every active lane of the wave drops the
         // sample (lanes of dead pixels returned above) a scalar branch skips its ray, depth, point, projections,
@@ -1495,14 +1495,16 @@ __device__ __forceinline__ void sort_small(float* d, int n) {
 }
 
 // ComputeMultiViewInitialCostandSelectedViews, ACMMP.cu:519-556
-template <int MODEL, int VB, int VMAXB, int TF>
+// (PNEG: k_init's masked instances -- the per-pixel negligible-sample mask of ncc_chunk's per-sample loop, so the
+// cached vector holds the bits the masked k_select / k_eval_ref form for the same pixel, plane and view)
+template <int MODEL, int VB, int VMAXB, int TF, bool PNEG = false>
 __device__ float initial_cost(const KParams& kp, int px, int py, const Patch& pt, float4 ph, uint32_t* sel,
                               float* cvec = nullptr) {
     constexpr int VMAX = VMAXB < 8 ? VMAXB : kMaxViews;      // pick_vb: V <= VMAXB when VMAXB < 8
     float cv[VMAX], cvc[VMAX];
     int nvalid = 0;
     const uint32_t all = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
-    for_all_views_tf<MODEL, VB, 0, true, TF>(kp, px, py, pt, ph, all, [&](int v, float c) {
+    for_all_views_tf<MODEL, VB, 0, true, TF, true, PNEG>(kp, px, py, pt, ph, all, [&](int v, float c) {
         cv[v] = c;
         cvc[v] = c;
         if (c < 2.0f) nvalid++;
@@ -1547,7 +1549,7 @@ enum InitBranch { kInitRandom = 0, kInitPlanar = 1, kInitUpsample = 2, kInitReus
 // exact mode only: 1 view 1.55, 2 views 1.36, 4 views 1.41 ms at the metric).
 [[maybe_unused]] constexpr int kInitVB = 4;
 
-template <int MODEL, int VB, int BR, int VMAXB, int TF>
+template <int MODEL, int VB, int BR, int VMAXB, int TF, bool PNEG = false>
 __global__ __launch_bounds__(256) void k_init(const KParams kp) {
     // 16x16 tiles in XCD-aware order (xcd_block) over a row-major grid of ceil(W/16) tiles per row
     const long long tile = xcd_block(blockIdx.x);
@@ -1577,7 +1579,7 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
         const float depth = fmaf(rs.uniform(), kp.depth_max - kp.depth_min, kp.depth_min);
         ph = random_normal(dc, rs);
         ph.w = dist_to_origin(dc, depth, ph);
-        cost = initial_cost<MODEL, VB, VMAXB, TF>(kp, x, y, pt, ph, &sel, cvec);
+        cost = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, ph, &sel, cvec);
     } else if (BR == kInitPlanar) {
         if (kp.mask[center] > 0 && kp.costs_rm[center] >= 0.1f) {
             const float perturbation = 0.02f;
@@ -1593,7 +1595,7 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
             const float depth = ph.w;
             ph.w = dist_to_origin(dc, depth, ph);
         }
-        cost = initial_cost<MODEL, VB, VMAXB, TF>(kp, x, y, pt, ph, &sel, cvec);
+        cost = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, ph, &sel, cvec);
     } else if (BR == kInitUpsample) {
         const float scale = static_cast<float>(1.0 * static_cast<double>(kp.scaled_cols) / static_cast<double>(kp.W));
         const float sigmad = 0.50f, sigmar = 25.5f;
@@ -1627,16 +1629,16 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
         normalize3(nx, ny, nz);
         const float4 cur = kp.planes_rm[center];
         uint32_t sel0;
-        kp.pre_rm[center] = initial_cost<MODEL, VB, VMAXB, TF>(kp, x, y, pt, cur, &sel0);
+        kp.pre_rm[center] = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, cur, &sel0);
         ph = to_ref(rc, make_float4(nx, ny, nz, 0.0f));
         ph.w = dist_to_origin(dc, cur.w, ph);
-        cost = initial_cost<MODEL, VB, VMAXB, TF>(kp, x, y, pt, ph, &sel, cvec);
+        cost = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, ph, &sel, cvec);
     } else {
         ph = kp.hier ? kp.scaled[center] : kp.planes_rm[center];
         ph = to_ref(rc, ph);
         const float depth = ph.w;
         ph.w = dist_to_origin(dc, depth, ph);
-        cost = initial_cost<MODEL, VB, VMAXB, TF>(kp, x, y, pt, ph, &sel, cvec);
+        cost = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, ph, &sel, cvec);
     }
     kp.plane_cs[colour][ci] = ph;
     kp.cost_cs[colour][ci] = cost;
@@ -3185,19 +3187,36 @@ static inline int ref_block_count(const KParams& kp) {
         else { constexpr int TF = 0; BODY; }                                            \
     } while (0)
 
+// The instances with the per-pixel negligible-sample mask (ncc_chunk's PNEG; k_init and the refinement's kernels)
+// exist for fast SPHERE with binary16 texels up to 4 views, and are launched where the run has the mask
+// (ref_neg_tau >= 0); every other launch, and ACMMP_REF_NEG_SKIP=0, takes the instance that has no code for it.
+template <int M, int VBC, int TF>
+constexpr bool ref_neg_inst() { return M == kSphere && VBC <= 4 && TF == 2; }
+
 #if ACMMP_IN_TU(1)
+template <int M, int BR, int VBC, int TF>
+static void launch_init_inst(const KParams& kp, dim3 grd, dim3 blk, hipStream_t s) {
+    if constexpr (ref_neg_inst<M, VBC, TF>()) {
+        if (kp.ref_neg_tau >= 0.0f) {
+            k_init<M, kInitVB, BR, VBC, TF, true><<<grd, blk, 0, s>>>(kp);
+            return;
+        }
+    }
+    k_init<M, kInitVB, BR, VBC, TF><<<grd, blk, 0, s>>>(kp);
+}
+
 hipError_t launch_init(const KParams& kp, hipStream_t s) {
     if (kp.init_hi <= kp.init_lo) return hipSuccess;
     dim3 blk(16, 16), grd(xcd_grid(static_cast<long long>(cdiv(kp.W, 16)) * cdiv(kp.init_hi - kp.init_lo, 16)));
     // branch order of ACMMP.cu:686-793
     const int br = (!kp.geom && !kp.hier) ? kInitRandom : kp.planar ? kInitPlanar : kp.upsample ? kInitUpsample
                                                                                                  : kInitReuse;
-    if (br == kInitRandom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_init<M, kInitVB, kInitRandom, VBC, TF><<<grd, blk, 0, s>>>(kp))));
+    if (br == kInitRandom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitRandom, VBC, TF>(kp, grd, blk, s))));
     else if (br == kInitPlanar)
-        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_init<M, kInitVB, kInitPlanar, VBC, TF><<<grd, blk, 0, s>>>(kp))));
+        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitPlanar, VBC, TF>(kp, grd, blk, s))));
     else if (br == kInitUpsample)
-        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_init<M, kInitVB, kInitUpsample, VBC, TF><<<grd, blk, 0, s>>>(kp))));
-    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (k_init<M, kInitVB, kInitReuse, VBC, TF><<<grd, blk, 0, s>>>(kp))));
+        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitUpsample, VBC, TF>(kp, grd, blk, s))));
+    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitReuse, VBC, TF>(kp, grd, blk, s))));
     return hipGetLastError();
 }
 
@@ -3406,11 +3425,6 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
 #endif  // ACMMP_IN_TU(3)
 
 #if ACMMP_IN_TU(4)
-// The refinement's instances with the per-pixel negligible-sample mask (ncc_chunk's PNEG) exist for fast SPHERE with
-// binary16 texels up to 4 views, and are launched where the run has the mask (ref_neg_tau >= 0); every other
-// launch, and ACMMP_REF_NEG_SKIP=0, takes the instance that has no code for it.
-template <int M, int VBC, int TF>
-constexpr bool ref_neg_inst() { return M == kSphere && VBC <= 4 && TF == 2; }
 template <int M, int VBC, bool GEOM, int TF>
 static void launch_ref_inst(const KParams& kp, int colour, dim3 grd, size_t lds, hipStream_t s) {
     if constexpr (ref_neg_inst<M, VBC, TF>()) {

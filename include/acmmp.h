@@ -268,6 +268,10 @@ acmmp_status acmmp_band_get_rows(acmmp_ctx *ctx, int colour, int row_a, int row_
                                  uint32_t *selected_views);
 acmmp_status acmmp_band_set_rows(acmmp_ctx *ctx, int colour, int row_a, int row_b, const float *planes,
                                  const float *costs, const uint32_t *selected_views);
+/* Test hook: the cached NCC cost vectors of rows [row_a, row_b) of `colour` in a band run, out[v * n + k] for
+ * source view v and colour-grid pixel k of the n = (row_b - row_a) * ceil(W / 2) -- straight after acmmp_band_begin,
+ * what the initialisation evaluated for the planes acmmp_band_get_rows returns.  Waits for the context's stream. */
+acmmp_status acmmp_debug_band_cvec(acmmp_ctx *ctx, int colour, int row_a, int row_b, float *out);
 /* GetDepthandNormal + the two filters on band +- 10 / 5 rows; synchronous.  Rows [row0, row1) of the
  * row-major outputs (acmmp_download / acmmp_device_outputs) are then final. */
 acmmp_status acmmp_band_end(acmmp_ctx *ctx, int do_post);

@@ -3,8 +3,11 @@
 (DESIGN.md §2.4): the float64 restatement of stage_neg_mask (tests/np_neg_skip.py) over every wave of the
 reference view -- 8 consecutive pixels of one colour in one row, aligned to the 8 x 4 tile.  CPU only.
 
-  python scripts/neg_skip_share.py [--width 2000 --height 1500 --n-src 4 --seed 1234] [--json OUT]
+  python scripts/neg_skip_share.py [--width 2000 --height 1500 --n-src 4 --seed 1234] [--json OUT] [--nodes]
 (the defaults are bench.py's metric scene; bench.py --width 2000 --height 1000 is the other recorded shape)
+
+--nodes adds the count of interpolation nodes a live wave still needs once its masked samples are gone (nodes_needed):
+why dropping node rows / columns 0 and 5 with the mask does not pay.
 """
 import argparse
 import json
@@ -45,7 +48,36 @@ def all_weights(sc, p):
     return out
 
 
-def share(W, H, n_src, seed):
+NODE, MID = (0, 2, 3, 5), (1, 4)
+
+
+def nodes_needed(kept):
+    """kept: (..., 36) bool, the samples a wave keeps (sample ci * 6 + cj: patch column ci, row cj) -> (..., 4, 4) bool,
+    the nodes (columns x rows {0, 2, 3, 5}) its kept samples depend on by ncc_chunk's node-column loop: a node sample
+    on itself; rows 1 and 4 of a node column on that column's four nodes; a node row's samples in columns 1 and 4 on
+    that row's four nodes; a sample in both an interpolated column and row on all sixteen.  (The four corners are
+    read by the spread test whatever is kept; the caller adds them.)"""
+    k = kept.reshape(kept.shape[:-1] + (6, 6))
+    need = np.zeros(k.shape, bool)
+    for a in NODE:
+        for b in NODE:
+            need[..., a, b] |= k[..., a, b]
+    for a in NODE:
+        mid = k[..., a, MID[0]] | k[..., a, MID[1]]
+        for b in NODE:
+            need[..., a, b] |= mid
+    for b in NODE:
+        mid = k[..., MID[0], b] | k[..., MID[1], b]
+        for a in NODE:
+            need[..., a, b] |= mid
+    both = k[..., MID[0], MID[0]] | k[..., MID[0], MID[1]] | k[..., MID[1], MID[0]] | k[..., MID[1], MID[1]]
+    for a in NODE:
+        for b in NODE:
+            need[..., a, b] |= both
+    return need[..., NODE, :][..., :, NODE]
+
+
+def share(W, H, n_src, seed, nodes=False):
     sc = scene.sphere_scene(W, H, n_src=n_src, seed=seed)
     c0 = sc.cameras[0]
     p = types.default_params(num_images=n_src + 1, depth_min=float(c0["depth_min"]) * 0.6,
@@ -61,6 +93,7 @@ def share(W, H, n_src, seed):
     waves = live_waves = masked = 0
     hist = np.zeros(37, np.int64)
     rows5 = cols5 = 0
+    all16 = node_sum = 0
     for colour in (0, 1):
         for par in (0, 1):                                   # rows with (py + colour) & 1 == par start at px = par
             rows = np.arange(H)[((np.arange(H) + colour) & 1) == par]
@@ -81,8 +114,15 @@ def share(W, H, n_src, seed):
             i5 = np.array([k // 6 in (0, 5) for k in range(36)])
             rows5 += int(m[:, j5].all(-1).sum())
             cols5 += int(m[:, i5].all(-1).sum())
+            if nodes:
+                nd = nodes_needed(~m)                        # (live waves, 4, 4)
+                node_sum += int(nd.sum())
+                nd[:, ::3, ::3] = True                       # the corners stay for the spread test
+                all16 += int(nd.all((-1, -2)).sum())
     assert Wh >= n
-    return {"width": W, "height": H, "n_src": n_src, "seed": seed, "tau": ns.TAU, "waves": waves,
+    extra = {"live_waves_needing_all_16_nodes": round(all16 / live_waves, 4),
+             "mean_nodes_needed_without_the_corner_rule": round(node_sum / live_waves, 2)} if nodes else {}
+    return {**extra, "width": W, "height": H, "n_src": n_src, "seed": seed, "tau": ns.TAU, "waves": waves,
             "live_waves": live_waves, "live_wave_share": round(live_waves / waves, 4),
             "masked_pair_share_of_live_waves": round(masked / (36.0 * live_waves), 4),
             "mean_masked_samples_per_live_wave": round(masked / live_waves, 2),
@@ -98,8 +138,9 @@ if __name__ == "__main__":
     ap.add_argument("--n-src", type=int, default=4)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--nodes", action="store_true", help="also count the interpolation nodes the live waves still need")
     a = ap.parse_args()
-    out = share(a.width, a.height, a.n_src, a.seed)
+    out = share(a.width, a.height, a.n_src, a.seed, nodes=a.nodes)
     print(json.dumps(out))
     if a.json:
         json.dump(out, open(a.json, "w"), indent=1)
