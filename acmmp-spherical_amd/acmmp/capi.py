@@ -123,6 +123,8 @@ EXPORTS = [
     "acmmp_fusion_render_plan",
     "acmmp_fusion_set_reference_cloud", "acmmp_fusion_cloud_distance", "acmmp_fusion_distance_results",
     "acmmp_fusion_distance_grid",
+    "acmmp_fusion_surface_distance", "acmmp_fusion_surface_results", "acmmp_fusion_surface_plan",
+    "acmmp_fusion_surface_grid",
     "acmmp_fusion_set_cloud_transform", "acmmp_fusion_get_cloud_transform", "acmmp_fusion_cloud_align",
     "acmmp_fusion_align_records", "acmmp_fusion_cloud_align_plane", "acmmp_fusion_align_plane_records",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
@@ -256,6 +258,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_cloud_distance.argtypes = [vp, i32, i32, C.c_float, i32, vp, vp]
     L.acmmp_fusion_distance_results.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_distance_grid.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.acmmp_fusion_surface_distance.argtypes = [vp, i32, C.c_float, i32, vp, vp]
+    L.acmmp_fusion_surface_results.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
+    L.acmmp_fusion_surface_plan.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.acmmp_fusion_surface_grid.argtypes = [vp, C.c_float, vp, vp, vp, vp]
     L.acmmp_fusion_set_cloud_transform.argtypes = [vp, vp]
     L.acmmp_fusion_get_cloud_transform.argtypes = [vp, vp, vp]
     L.acmmp_fusion_cloud_align.argtypes = [vp, i32, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
@@ -904,6 +910,7 @@ MESH_SOURCES = {"voxel": 0, "clean": 1, "visible": 2}     # ACMMP_MESH_FROM_VOXE
 RENDER_COUNTS = ("agree", "mesh_in_front", "mesh_behind", "mesh_only", "raw_only", "neither", "back_facing")
 DIST_SOURCES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "mesh": 4}     # ACMMP_DIST_FROM_*
 DIST_DIRECTIONS = {"data_to_ref": 0, "ref_to_data": 1}     # ACMMP_DIST_DATA_TO_REF (accuracy), _REF_TO_DATA (completeness)
+SURF_QUERIES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "reference": 5}     # ACMMP_SURF_FROM_*
 DIST_SUMMARY_WORDS = 268     # ACMMP_DIST_SUMMARY_WORDS: n_query, n_valid, n_matched, sum_q, within[8], hist[256]
 ALIGN_MODES = {"rigid": 0, "similarity": 1}     # ACMMP_ALIGN_RIGID, ACMMP_ALIGN_SIMILARITY
 ALIGN_STOP_REASONS = ("max_iterations", "converged", "degenerate")     # ACMMP_ALIGN_MAX_ITERATIONS, _CONVERGED, _DEGENERATE
@@ -1346,6 +1353,61 @@ class Fusion:
         cell, st = np.zeros(1, np.float32), np.zeros(3, np.int64)
         self._check(self.L.acmmp_fusion_distance_grid(self.h, float(force_cell), _p(cell), _p(st[0:1]), _p(st[1:2]),
                                                       _p(st[2:3])), "fusion_distance_grid")
+        return {"cell": float(cell[0]), "cells": int(st[0]), "max_list": int(st[1]), "rings": int(st[2])}
+
+    def surface_distance(self, query: str = "reference", max_dist: float = 1.0, thresholds=()) -> CloudDistance:
+        """Point-to-triangle distances from the cloud `query` ("reference": completeness against the surface; "scene",
+        "voxels", "clean", "visible": the mesh's fidelity to that cloud) to the faces of the mesh result, capped at
+        max_dist.  Exhaustive by definition, bit for bit (acmmp_fusion_surface_distance, include/acmmp.h); at most 8
+        thresholds, each in [0, max_dist].  The per-query results stay on the GPU (surface_results) until the mesh or
+        the query cloud goes."""
+        if query not in SURF_QUERIES:
+            raise ValueError('query must be one of ' + ", ".join(SURF_QUERIES))
+        md = float(max_dist)
+        if not (np.isfinite(md) and md > 0.0):
+            raise ValueError("max_dist must be finite and > 0")
+        tau = np.ascontiguousarray(thresholds, np.float32).reshape(-1)
+        if tau.size > 8:
+            raise ValueError("at most 8 thresholds")
+        if not np.all(np.isfinite(tau) & (tau >= 0) & (tau <= np.float32(md))):
+            raise ValueError("every threshold must be finite and in [0, max_dist]")
+        out = np.zeros(DIST_SUMMARY_WORDS, np.int64)
+        self._check(self.L.acmmp_fusion_surface_distance(self.h, SURF_QUERIES[query], md, tau.size,
+                                                         _p(tau) if tau.size else None, _p(out)), "fusion_surface_distance")
+        self._surf_queries = int(out[0])
+        return CloudDistance(n_query=int(out[0]), n_valid=int(out[1]), n_matched=int(out[2]), sum_q=int(out[3]),
+                             max_dist=float(np.float32(max_dist)), within=[int(x) for x in out[4:4 + tau.size]],
+                             hist=out[12:268].copy())
+
+    def surface_results(self, first: int = 0, n: int | None = None, squared: bool = False):
+        """(dist (n,) float32, nearest_face (n,) int32) of queries [first, first + n) of the last surface_distance (n
+        None: to the end): dist = sqrt(d2), inf for a query that is unmatched or invalid, nearest_face -1 then.
+        squared: d2 itself, the quantity the result is defined in."""
+        if first < 0 or (n is not None and n < 0):
+            raise ValueError("first and n must be >= 0")
+        if n is None:
+            n = max(getattr(self, "_surf_queries", 0) - first, 0)
+        d2, nn = np.empty(n, np.float32), np.empty(n, np.int32)
+        self._check(self.L.acmmp_fusion_surface_results(self.h, first, n, _p(d2), _p(nn)), "fusion_surface_results")
+        return (d2 if squared else np.sqrt(d2)), nn
+
+    def surface_plan(self, small_max: int = 0):
+        """Test hook: sets the number of cells above which a face goes to the overflow list instead of the grid (0 = the
+        default, below 0 = every face) and returns the last surface_distance's {"small", "large", "registrations",
+        "skipped"}."""
+        if not -2 ** 31 <= int(small_max) < 2 ** 31:
+            raise ValueError("small_max must fit an int32")
+        st = np.zeros(4, np.int64)
+        self._check(self.L.acmmp_fusion_surface_plan(self.h, int(small_max), _p(st[0:1]), _p(st[1:2]), _p(st[2:3]),
+                                                     _p(st[3:4])), "fusion_surface_plan")
+        return {"small": int(st[0]), "large": int(st[1]), "registrations": int(st[2]), "skipped": int(st[3])}
+
+    def surface_grid(self, force_cell: float = 0.0):
+        """Test hook: sets the cell of the face grid of the next surface_distance calls (0 = automatic) and returns the
+        last successful call's {"cell", "cells", "max_list", "rings"}.  Apart from distance_grid."""
+        cell, st = np.zeros(1, np.float32), np.zeros(3, np.int64)
+        self._check(self.L.acmmp_fusion_surface_grid(self.h, float(force_cell), _p(cell), _p(st[0:1]), _p(st[1:2]),
+                                                     _p(st[2:3])), "fusion_surface_grid")
         return {"cell": float(cell[0]), "cells": int(st[0]), "max_list": int(st[1]), "rings": int(st[2])}
 
     def set_cloud_transform(self, M):

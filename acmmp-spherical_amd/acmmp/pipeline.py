@@ -799,7 +799,7 @@ class Pipeline:
                    eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None,
                    eval_align: str | None = None, eval_align_max_dist: float | None = None,
                    eval_align_iterations: int | None = None, eval_align_stride: int | None = None,
-                   eval_align_plane_iterations: int | None = None):
+                   eval_align_plane_iterations: int | None = None, eval_surface: bool = False):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -867,9 +867,18 @@ class Pipeline:
         point-to-plane iterations (acmmp_fusion_cloud_align_plane: rigid, along the evaluated cloud's own normals) refine
         its transform with the same cap and stride, and the refined transform is the one installed.  "align" gains
         "plane": M, stop_reason, iterations, n_no_normal of the last iteration and rms_first / rms_last, the RMS
-        point-to-plane residual of the first and the last iteration."""
+        point-to-plane residual of the first and the last iteration.
+
+        eval_surface (eval_cloud and mesh_trunc are then required): after the measurement, and under the transform an
+        alignment installed, the reference cloud and the cloud that is written are measured against the faces of the
+        mesh, point to triangle (acmmp_fusion_surface_distance, include/acmmp.h); eval_info and eval.json gain "surface":
+        {"completeness", "fidelity", "thresholds"} (evaluate_surface), precision from the accuracy pass above, recall
+        from the surface.
+        """
         self.fusion_info = None
         self.eval_info = None
+        if eval_surface and (eval_cloud is None or mesh_trunc is None):
+            raise ValueError("eval_surface needs eval_cloud and the mesh (mesh_trunc)")
         if eval_align_plane_iterations is not None and eval_align is None:
             raise ValueError("eval_align_plane_iterations needs eval_align")
         if eval_cloud is None and (eval_max_dist is not None or len(tuple(eval_thresholds)) or eval_source is not None):
@@ -1020,6 +1029,11 @@ class Pipeline:
                 self.eval_info = evaluate_clouds(fu, eval_source or written, eval_max_dist, eval_thresholds)
                 if align is not None:
                     self.eval_info["align"] = align
+                if eval_surface:
+                    if not hasattr(fu, "surface_distance"):
+                        raise ValueError("the surface evaluation needs a fusion object with surface_distance (capi.Fusion)")
+                    self.eval_info["surface"] = evaluate_surface(fu, written, eval_max_dist, eval_thresholds,
+                                                                 self.eval_info["accuracy"])
                 if path:
                     with open(os.path.join(os.path.dirname(os.path.abspath(path)), "eval.json"), "w") as f:
                         json.dump(self.eval_info, f, indent=1)
@@ -1111,6 +1125,30 @@ def evaluate_clouds(fu, source: str, max_dist: float, thresholds=()) -> dict:
         p = a.within[i] / a.n_valid if a.n_valid else 0.0
         r = c.within[i] / c.n_valid if c.n_valid else 0.0
         rows.append({"threshold": t, "precision": p, "recall": r, "f_score": 2 * p * r / (p + r) if p + r > 0 else 0.0})
+    out["thresholds"] = rows
+    return out
+
+
+def evaluate_surface(fu, cloud: str, max_dist: float, thresholds=(), accuracy: dict | None = None) -> dict:
+    """The fusion object's reference cloud and its resident cloud `cloud` against the faces of its mesh result
+    (surface_distance), under the installed transform: {"completeness": the reference points to the surface,
+    "fidelity": the cloud's own points to the surface, "thresholds": [...]}, the two passes with evaluate_clouds' fields.
+    Each threshold holds recall = the surface completeness within it, precision from `accuracy` (an accuracy pass of
+    evaluate_clouds over the same thresholds; without one precision and f_score are left out) and their f_score."""
+    taus = [float(np.float32(t)) for t in thresholds]
+    out, runs = {}, {}
+    for name, query in (("completeness", "reference"), ("fidelity", cloud)):
+        r = runs[name] = fu.surface_distance(query, max_dist, taus)
+        out[name] = {"n_query": r.n_query, "n_valid": r.n_valid, "n_matched": r.n_matched, "mean": r.mean,
+                     "median_upper": r.median_upper, "within": list(r.within)}
+    rows = []
+    for i, t in enumerate(taus):
+        c = runs["completeness"]
+        row = {"threshold": t, "recall": c.within[i] / c.n_valid if c.n_valid else 0.0}
+        if accuracy is not None:
+            p, r = (accuracy["within"][i] / accuracy["n_valid"] if accuracy["n_valid"] else 0.0), row["recall"]
+            row.update(precision=p, f_score=2 * p * r / (p + r) if p + r > 0 else 0.0)
+        rows.append(row)
     out["thresholds"] = rows
     return out
 
@@ -1235,6 +1273,9 @@ def arg_parser():
     ap.add_argument("--eval-align-plane-iterations", type=int, default=None,
                     help="with --eval-align: then refine the transform by at most this many rigid point-to-plane iterations "
                          "along the measured cloud's normals; eval.json's align gains \"plane\"")
+    ap.add_argument("--eval-surface", action="store_true",
+                    help="with --eval-cloud and a mesh: also measure the reference cloud and the written cloud against the "
+                         "mesh's faces (point-to-triangle); eval.json gains \"surface\"")
     return ap
 
 
@@ -1272,7 +1313,7 @@ def main(argv=None):
                               eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source,
                               eval_align=a.eval_align, eval_align_max_dist=a.eval_align_max_dist,
                               eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride,
-                              eval_align_plane_iterations=a.eval_align_plane_iterations)
+                              eval_align_plane_iterations=a.eval_align_plane_iterations, eval_surface=a.eval_surface)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

@@ -185,6 +185,18 @@ struct acmmp_fusion {
     float dist_cell = 0.0f;                      // the cell of the last successful call ...
     long long dist_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
     DevBuf<unsigned long long> dist_words;       // kDistWords device words
+    // point-to-triangle distances to the mesh result (acmmp_fusion_surface_distance): the resident result
+    DevBuf<float> surf_d2;                       // per query
+    DevBuf<int32_t> surf_nn;                     // per query: the nearest face, -1 = none
+    unsigned long long surf_n = 0;               // queries
+    int surf_query = 0;                          // ACMMP_SURF_FROM_*
+    bool surf_have = false;                      // a surface call has succeeded on this mesh and query cloud
+    long long surf_small_max = 0;                // test hook: the small / large threshold, 0 = kSurfSmallMax
+    long long surf_plan[4] = {0, 0, 0, 0};       // small faces, large faces, registrations, skipped of the last successful call
+    float surf_force_cell = 0.0f;                // test hook: the cell of the next calls' face grid, 0 = automatic
+    float surf_cell = 0.0f;                      // the cell of the last successful call ...
+    long long surf_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
+    DevBuf<unsigned long long> surf_words;       // kSurfWords device words
     // the transform of the data cloud (acmmp_fusion_set_cloud_transform) ...
     bool xf_set = false;
     double xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -370,11 +382,24 @@ void align_release(acmmp_fusion* f) {
     f->align_have = false;
 }
 
+void surface_release(acmmp_fusion* f) {
+    f->surf_d2.reset(); f->surf_nn.reset();
+    f->surf_n = 0;
+    f->surf_have = false;
+}
+
+// The surface result's queries were the reference cloud, which has been replaced or is read in another frame now.
+void surface_reference_gone(acmmp_fusion* f) {
+    if (f->surf_have && f->surf_query == ACMMP_SURF_FROM_REFERENCE) surface_release(f);
+}
+
 // The data cloud `source` (ACMMP_DIST_FROM_*) has been replaced or discarded: a distance result measured on it goes,
-// and so do the records of an align call on it.
+// and so do the records of an align call on it.  The surface result goes with the mesh and with its query cloud
+// (ACMMP_SURF_FROM_* of a data cloud is its ACMMP_DIST_FROM_*).
 void distance_source_gone(acmmp_fusion* f, int source) {
     if (f->dist_have && f->dist_source == source) distance_release(f);
     if (f->align_have && f->align_source == source) align_release(f);
+    if (f->surf_have && (source == ACMMP_DIST_FROM_MESH || f->surf_query == source)) surface_release(f);
 }
 
 void render_release(acmmp_fusion* f) {
@@ -1702,6 +1727,7 @@ acmmp_status acmmp_fusion_set_reference_cloud(acmmp_fusion* f, int64_t n, const 
     f->ref_have = true;
     distance_release(f);                              // it was measured against the previous reference cloud
     align_release(f);                                 // and these were aligned to it
+    surface_reference_gone(f);
     return ACMMP_OK;
 }
 
@@ -1773,6 +1799,210 @@ acmmp_status acmmp_fusion_distance_grid(acmmp_fusion* f, float force_cell, float
     if (cells) *cells = f->dist_stats[0];
     if (max_list) *max_list = f->dist_stats[1];
     if (rings) *rings = f->dist_stats[2];
+    return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- point-to-triangle distances from a cloud to the mesh result (include/acmmp.h; kernels: k_surf_*) ---------
+
+namespace {
+
+// The new result of a surface call and its scratch, swapped in only when the whole call succeeded.
+struct SurfOut {
+    DevBuf<float> d2;
+    DevBuf<int32_t> nn;
+    DevBuf<unsigned long long> keys;                       // scratch: the cell table
+    DevBuf<uint32_t> start, cnt;
+    DevBuf<float4> list, large;                            // scratch: the cells' lists and the overflow list
+    double cell = 0.0;
+    unsigned long long valid_faces = 0;
+    unsigned long long words[kSurfWords] = {0};
+};
+
+// The cell of the face grid: the edge of the mean face of a closed surface that fills its box.  Half the box's area
+// is A = ex ey + ey ez + ez ex; F triangles of edge s cover about F s^2 / 2, so s = 2 sqrt(A / F).  A face then overlaps
+// a handful of cells and a cell lists a handful of faces.  Unlike the cloud grid the cell is not capped by max_dist: a
+// cell narrower than the faces would turn every face into a large one, and a wider one costs the capped search only the
+// lists of the 27 cells around the query.  A box without area falls back to the cloud rule; never more than 2^20 cells
+// on an axis.
+double surface_cell(const double lo[3], const double hi[3], unsigned long long faces, float forced) {
+    const double e[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    const double ext = std::max(e[0], std::max(e[1], e[2])), n = static_cast<double>(faces);
+    double cell = 2.0 * std::sqrt(((e[0] * e[1] + e[1] * e[2]) + e[2] * e[0]) / n);
+    if (!(cell > 0.0) || !std::isfinite(cell)) cell = ext / std::cbrt(n);
+    if (forced != 0.0f) cell = static_cast<double>(forced);
+    cell = std::max(cell, ext / 1048576.0);
+    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
+    return cell;
+}
+
+acmmp_status surface_run(acmmp_fusion* f, DistCloud q, SurfMesh m, float max_dist, int n_tau, const float* tau, SurfOut& out) {
+    hipStream_t s = f->stream;
+    F_HIP(f, alloc(out.d2, static_cast<size_t>(q.n)));
+    F_HIP(f, alloc(out.nn, static_cast<size_t>(q.n)));
+    if (!f->surf_words) F_HIP(f, alloc(f->surf_words, kSurfWords));
+    unsigned long long* w = f->surf_words;
+    F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kSurfWords, s));
+    F_HIP(f, hipMemsetAsync(w + kDistMin, 0xff, sizeof(unsigned long long) * 3, s));
+    DistQuery p;
+    p.m2 = max_dist * max_dist;
+    p.k = 1048576.0 / static_cast<double>(max_dist);
+    p.n_tau = n_tau;
+    for (int i = 0; i < 8; ++i) p.tau2[i] = i < n_tau ? tau[i] * tau[i] : 0.0f;
+    for (int a = 0; a < 3; ++a) p.lo[a] = p.hi[a] = 0.0;
+    p.have_targets = 0;
+    DistGrid g = {{0.0, 0.0, 0.0}, 1.0, 1.0, {0, 0, 0}};
+    DistTable fine = {nullptr, nullptr, nullptr, 0, 0};
+    unsigned long long regs = 0, n_large = 0;
+    unsigned long long h[kDistSummary] = {0};
+    if (m.nf > 0) {
+        // the first host wait: the valid faces' bounding box and number, from which the cell is chosen
+        F_HIP(f, launch_surf_bounds(m, w, s));
+        F_HIP(f, hipMemcpyAsync(h, w, sizeof(h), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        out.valid_faces = h[kDistValidTargets];
+        if (out.valid_faces > m.nf) return ffail(f, ACMMP_ERR_HIP, "surface distance: more valid faces than faces");
+    }
+    if (out.valid_faces > 0) {
+        uint32_t mn[6];
+        std::memcpy(mn, h + kDistMin, sizeof(mn));
+        for (int a = 0; a < 3; ++a) {
+            p.lo[a] = static_cast<double>(vox_decode_ordered(mn[a]));
+            p.hi[a] = -static_cast<double>(vox_decode_ordered(mn[3 + a]));
+        }
+        out.cell = surface_cell(p.lo, p.hi, out.valid_faces, f->surf_force_cell);
+        g = dist_grid(p.lo, p.hi, out.cell);
+        const long long small_max = f->surf_small_max != 0 ? f->surf_small_max : kSurfSmallMax;
+        // the second host wait: the plan, from which the table and the two lists are sized
+        unsigned long long plan[kSurfWords] = {0};
+        F_HIP(f, launch_surf_plan(m, g, small_max, w, s));
+        F_HIP(f, hipMemcpyAsync(plan, w, sizeof(plan), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        regs = plan[kSurfRegs];
+        n_large = plan[kSurfLarge];
+        if (plan[kSurfSmall] + n_large != out.valid_faces)
+            return ffail(f, ACMMP_ERR_HIP, "surface distance: the plan does not add up to the valid faces");
+        if (regs > 0xffffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^32 - 1 registrations: a larger cell or a smaller small_max");
+        // no more cells can be occupied than the grid has or than there are registrations
+        const double grid_cells = (g.cmax[0] + 1.0) * (g.cmax[1] + 1.0) * (g.cmax[2] + 1.0);
+        const unsigned long long most = grid_cells < static_cast<double>(regs) ? static_cast<unsigned long long>(grid_cells) : regs;
+        unsigned long long slots = 1024;
+        while (slots < 2 * most) slots <<= 1;
+        F_HIP(f, alloc(out.keys, slots));
+        F_HIP(f, alloc(out.start, slots));
+        F_HIP(f, alloc(out.cnt, slots));
+        F_HIP(f, alloc(out.list, kSurfEntryWords * static_cast<size_t>(regs)));
+        F_HIP(f, alloc(out.large, kSurfEntryWords * static_cast<size_t>(n_large)));
+        fine = DistTable{out.keys, out.start, out.cnt, slots, log2_ceil(slots)};
+        F_HIP(f, hipMemsetAsync(out.keys, 0xff, sizeof(unsigned long long) * slots, s));
+        F_HIP(f, hipMemsetAsync(out.cnt, 0, sizeof(uint32_t) * slots, s));
+        F_HIP(f, launch_surf_lists(m, g, fine, small_max, out.list, regs, out.large, n_large, w, s));
+        p.have_targets = 1;
+    }
+    F_HIP(f, launch_surf_query(q, g, fine, out.list, out.large, static_cast<unsigned>(n_large), p, out.d2, out.nn, w, s));
+    // the last host wait: the end
+    F_HIP(f, hipMemcpyAsync(out.words, w, sizeof(out.words), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    if (out.words[kDistErr] || out.words[kDistCursor] != regs || out.words[kSurfLargeCursor] != n_large)
+        return ffail(f, ACMMP_ERR_HIP, "surface distance: the cell table failed (flags " + std::to_string(out.words[kDistErr]) +
+                                           ", listed " + std::to_string(out.words[kDistCursor]) + " of " + std::to_string(regs) +
+                                           " registrations, " + std::to_string(out.words[kSurfLargeCursor]) + " of " +
+                                           std::to_string(n_large) + " large faces)");
+    out.words[kDistSummary + ACMMP_DIST_SUMMARY_N_QUERY] = q.n;
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_surface_distance(acmmp_fusion* f, int query, float max_dist, int n_tau, const float* tau,
+                                           int64_t* summary) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    DistCloud q = {nullptr, 9, 0};
+    bool have = false;
+    if (query == ACMMP_SURF_FROM_REFERENCE) {
+        have = f->ref_have;
+        q = DistCloud{f->ref_pts, 3, f->ref_n};
+    } else if (query < ACMMP_SURF_FROM_SCENE || query > ACMMP_SURF_FROM_VISIBLE || !distance_data(f, query, q, have)) {
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "query must be one of ACMMP_SURF_FROM_*");
+    }
+    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such query result");
+    if (!f->m_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
+    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
+    if (n_tau < 0 || n_tau > ACMMP_DIST_MAX_TAU || (n_tau > 0 && !tau))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "n_tau must be 0 to 8");
+    for (int i = 0; i < n_tau; ++i)
+        if (!finite32(tau[i]) || !(tau[i] >= 0.0f) || tau[i] > max_dist)
+            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every tau must be finite and in [0, max_dist]");
+    if (f->surf_force_cell != 0.0f && (!finite32(f->surf_force_cell) || !(f->surf_force_cell > 0.0f)))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
+    if (f->m_nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
+    if (q.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 queries");
+    // the frames: reference queries see the mesh under the transform, data queries share its frame
+    SurfMesh m = {DistCloud{f->m_verts, 9, f->m_nv}, f->m_faces, static_cast<unsigned>(f->m_nf)};
+    if (query == ACMMP_SURF_FROM_REFERENCE && f->xf_set) {
+        m.v.xf = 1;
+        std::memcpy(m.v.M, f->xf, sizeof(m.v.M));
+    }
+    F_HIP(f, hipSetDevice(f->device));
+    SurfOut out;
+    const acmmp_status st = surface_run(f, q, m, max_dist, n_tau, tau, out);
+    if (st != ACMMP_OK) {
+        const std::string why = f->err;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(f->stream);
+        f->err = why;
+        return st;
+    }
+    f->surf_d2 = std::move(out.d2);
+    f->surf_nn = std::move(out.nn);
+    f->surf_n = q.n;
+    f->surf_query = query;
+    f->surf_have = true;
+    f->surf_plan[0] = static_cast<long long>(out.words[kSurfSmall]);
+    f->surf_plan[1] = static_cast<long long>(out.words[kSurfLarge]);
+    f->surf_plan[2] = static_cast<long long>(out.words[kSurfRegs]);
+    f->surf_plan[3] = static_cast<long long>(f->m_nf - out.valid_faces);
+    f->surf_cell = static_cast<float>(out.cell);
+    f->surf_stats[0] = static_cast<long long>(out.words[kDistOccupied]);
+    f->surf_stats[1] = static_cast<long long>(out.words[kDistMaxList]);
+    f->surf_stats[2] = static_cast<long long>(out.words[kDistRings]);
+    if (summary)
+        for (int k = 0; k < ACMMP_DIST_SUMMARY_WORDS; ++k) summary[k] = static_cast<int64_t>(out.words[kDistSummary + k]);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_surface_results(acmmp_fusion* f, int64_t first, int64_t n, float* d2, int32_t* nearest_face) {
+    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, f->surf_n)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the surface result");
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    F_HIP(f, read_range<float>(d2, f->surf_d2, static_cast<size_t>(first), static_cast<size_t>(n)));
+    F_HIP(f, read_range<int32_t>(nearest_face, f->surf_nn, static_cast<size_t>(first), static_cast<size_t>(n)));
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_surface_plan(acmmp_fusion* f, int small_max, int64_t* n_small, int64_t* n_large,
+                                       int64_t* n_registrations, int64_t* n_skipped) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->surf_small_max = small_max;
+    if (n_small) *n_small = f->surf_plan[0];
+    if (n_large) *n_large = f->surf_plan[1];
+    if (n_registrations) *n_registrations = f->surf_plan[2];
+    if (n_skipped) *n_skipped = f->surf_plan[3];
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_surface_grid(acmmp_fusion* f, float force_cell, float* cell, int64_t* cells, int64_t* max_list,
+                                       int64_t* rings) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    f->surf_force_cell = force_cell;                  // checked by the next surface call
+    if (cell) *cell = f->surf_cell;
+    if (cells) *cells = f->surf_stats[0];
+    if (max_list) *max_list = f->surf_stats[1];
+    if (rings) *rings = f->surf_stats[2];
     return ACMMP_OK;
 }
 
@@ -2173,6 +2403,7 @@ acmmp_status acmmp_fusion_set_cloud_transform(acmmp_fusion* f, const double M[12
     std::memcpy(f->xf, M ? M : I, sizeof(f->xf));
     f->xf_set = M != nullptr;
     distance_release(f);                              // it was measured under the previous transform
+    surface_reference_gone(f);                        // and so were the faces that reference queries saw
     return ACMMP_OK;
 }
 

@@ -306,4 +306,32 @@ hipError_t launch_align_plane_iter(DistCloud q, unsigned long long stride, DistC
                                    DistGrid cg, DistTable coarse, const float4* list, DistQuery p, double kq,
                                    AlignPivot pivot, unsigned long long* words, unsigned long long* rec, hipStream_t s);
 
+// Point-to-triangle distances from a cloud to the mesh result (acmmp_fusion_surface_distance, include/acmmp.h;
+// DESIGN.md §8).  The mesh for the device: face j is the vertices faces[3 j .. + 3) of v, read as dist_load reads a point.
+struct SurfMesh {
+    DistCloud v;
+    const int32_t* faces;
+    unsigned nf;
+};
+// Device words of a surface call: a distance call's (kDistValidTargets counts the valid faces, kDistCursor the
+// registrations listed), then the plan and the overflow list's cursor.
+enum { kSurfSmall = kDistWords, kSurfLarge, kSurfRegs, kSurfLargeCursor, kSurfWords };
+constexpr int kSurfSmallMax = 64;            // cells up to which a face is registered in the grid
+constexpr size_t kSurfEntryWords = 3;        // a list entry in float4s: (A, bits of j), (B, 0), (C, 0) -- 48 bytes
+// words[kDistMin ..] over the vertices of the valid faces and words[kDistValidTargets] = their number.
+hipError_t launch_surf_bounds(SurfMesh m, unsigned long long* words, hipStream_t s);
+// words[kSurfSmall], [kSurfLarge], [kSurfRegs]: the faces registered, the large faces (small_max < 0: every face) and
+// the (face, cell) registrations of grid g.
+hipError_t launch_surf_plan(SurfMesh m, DistGrid g, long long small_max, unsigned long long* words, hipStream_t s);
+// The count pass, the cells' runs and the scatter: every small face into the list of every cell its box overlaps, every
+// large face into `large` (cap_large entries).  list holds cap_list entries.  words[kDistErr] |= 1 a full table, |= 2 a
+// failed lookup or a list overrun; words[kDistCursor] and [kSurfLargeCursor] end at the two lists' lengths.
+hipError_t launch_surf_lists(SurfMesh m, DistGrid g, DistTable fine, long long small_max, float4* list,
+                             unsigned long long cap_list, float4* large, unsigned long long cap_large,
+                             unsigned long long* words, hipStream_t s);
+// One lane per query, as launch_dist_query: the box reject, the n_large overflow entries, the rings.
+hipError_t launch_surf_query(DistCloud q, DistGrid g, DistTable fine, const float4* list, const float4* large,
+                             unsigned n_large, DistQuery p, float* d2, int32_t* nearest, unsigned long long* words,
+                             hipStream_t s);
+
 }  // namespace acmmp

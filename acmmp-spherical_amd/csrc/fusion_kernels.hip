@@ -1907,6 +1907,48 @@ __device__ __forceinline__ void dist_visit(const DistTable& fine, const float4* 
     }
 }
 
+// The ring walk around a query v whose box reject has let it through: visit(x, y, z, best) for every cell of the rings
+// 0, 1, ... of Chebyshev radius r, clipped to the grid, until the stop rule of DESIGN.md §8 fires.  The rule needs of
+// `visit` only that what it has not been shown after rings 0 .. r lies at least (r + m - 2^-20) h from v on one axis.
+template <class Visit>
+__device__ __forceinline__ void dist_walk(const float v[3], const DistGrid& g, double m2d, unsigned long long& best,
+                                          unsigned long long& rings, Visit visit) {
+    int c[3], rmax = 0;
+    double mfrac = 0.5;
+    bool clamped = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        double fr;
+        c[a] = dist_axis(g, a, v[a], fr, clamped);
+        mfrac = fmin(mfrac, fmin(fr, 1.0 - fr));
+        rmax = max(rmax, max(c[a], g.cmax[a] - c[a]));
+    }
+    if (clamped) mfrac = 0.0;
+    for (int r = 0;; ++r) {
+        rings = static_cast<unsigned long long>(r);
+        // the shell of Chebyshev radius r, clipped to the grid
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.cmax[0]);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.cmax[1]);
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.cmax[2]);
+        for (int z = z0; z <= z1; ++z) {
+            const bool zface = z == c[2] - r || z == c[2] + r;
+            for (int y = y0; y <= y1; ++y) {
+                if (zface || y == c[1] - r || y == c[1] + r) {
+                    for (int x = x0; x <= x1; ++x) visit(x, y, z, best);
+                } else {
+                    if (c[0] - r >= 0) visit(c[0] - r, y, z, best);
+                    if (c[0] + r <= g.cmax[0]) visit(c[0] + r, y, z, best);
+                }
+            }
+        }
+        if (r >= rmax) break;                       // every cell of the grid has been searched
+        // a target not yet searched lies more than L from the query on one axis
+        const double lb = dist_floor2((static_cast<double>(r) + mfrac - 0x1p-20) * g.cell);
+        if (lb > m2d) break;                        // it is unmatched
+        if (best != ~0ull && static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) < lb) break;   // it loses
+    }
+}
+
 // Steps 2 and 3 for one valid query v: the smallest (bits(d2) << 32 | j) key over the valid targets that the bounds of
 // DESIGN.md §8 cannot rule out, ~0 with none.  Shared by k_dist_query and k_align_iter.  rings = the largest ring searched.
 __device__ __forceinline__ unsigned long long dist_nearest(const float v[3], const DistGrid& g, const DistTable& fine,
@@ -1939,43 +1981,35 @@ __device__ __forceinline__ unsigned long long dist_nearest(const float v[3], con
                 }
         search = any;
     }
-    if (search) {
-        int c[3], rmax = 0;
-        double mfrac = 0.5;
-        bool clamped = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            double fr;
-            c[a] = dist_axis(g, a, v[a], fr, clamped);
-            mfrac = fmin(mfrac, fmin(fr, 1.0 - fr));
-            rmax = max(rmax, max(c[a], g.cmax[a] - c[a]));
-        }
-        if (clamped) mfrac = 0.0;
-        for (int r = 0;; ++r) {
-            rings = static_cast<unsigned long long>(r);
-            // the shell of Chebyshev radius r, clipped to the grid
-            const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.cmax[0]);
-            const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.cmax[1]);
-            const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.cmax[2]);
-            for (int z = z0; z <= z1; ++z) {
-                const bool zface = z == c[2] - r || z == c[2] + r;
-                for (int y = y0; y <= y1; ++y) {
-                    if (zface || y == c[1] - r || y == c[1] + r) {
-                        for (int x = x0; x <= x1; ++x) dist_visit(fine, list, v, x, y, z, best, err);
-                    } else {
-                        if (c[0] - r >= 0) dist_visit(fine, list, v, c[0] - r, y, z, best, err);
-                        if (c[0] + r <= g.cmax[0]) dist_visit(fine, list, v, c[0] + r, y, z, best, err);
-                    }
-                }
-            }
-            if (r >= rmax) break;                       // every cell of the grid has been searched
-            // a target not yet searched lies more than L from the query on one axis
-            const double lb = dist_floor2((static_cast<double>(r) + mfrac - 0x1p-20) * g.cell);
-            if (lb > m2d) break;                        // it is unmatched
-            if (best != ~0ull && static_cast<double>(__uint_as_float(static_cast<uint32_t>(best >> 32))) < lb) break;   // it loses
-        }
-    }
+    if (search)
+        dist_walk(v, g, m2d, best, rings, [&](int x, int y, int z, unsigned long long& b) {
+            dist_visit(fine, list, v, x, y, z, b, err);
+        });
     return best;
+}
+
+// The summary of step 5 from one lane per query: integers only, reduced per wave or per workgroup (hist: 256 words of
+// LDS, zero, with a barrier behind them) before any global atomic.  Every lane of the workgroup calls it.  It repeats
+// k_dist_query's tail, which stays inline there: called from that kernel it costs nine scalar registers.
+__device__ __forceinline__ void dist_summarise(bool valid, bool matched, float d2, unsigned long long rings, unsigned err,
+                                               const DistQuery& p, unsigned* hist, unsigned long long* __restrict__ words) {
+    unsigned long long* sm = words + kDistSummary;
+    long long qv = 0;
+    if (matched) {
+        qv = static_cast<long long>(rint(sqrt(static_cast<double>(d2)) * p.k));
+        const long long b = qv >> 12;
+        atomicAdd(&hist[b < 255 ? (b < 0 ? 0 : b) : 255], 1u);
+    }
+    wave_count(valid, &sm[1]);
+    wave_count(matched, &sm[2]);
+    wave_add(static_cast<unsigned long long>(qv), &sm[3]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wave_count(matched && k < p.n_tau && d2 <= p.tau2[k], &sm[4 + k]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) rings = max(rings, static_cast<unsigned long long>(__shfl_xor(rings, d)));
+    if ((threadIdx.x & 63) == 0 && rings) atomicMax(&words[kDistRings], rings);
+    block_or(err, &words[kDistErr]);
+    if (hist[threadIdx.x]) atomicAdd(&sm[12 + threadIdx.x], static_cast<unsigned long long>(hist[threadIdx.x]));
 }
 
 __global__ __launch_bounds__(256) void k_dist_query(const DistCloud q, const DistGrid g, const DistTable fine, const DistGrid cg,
@@ -2294,6 +2328,253 @@ hipError_t launch_align_plane_iter(DistCloud q, unsigned long long stride, DistC
     const unsigned long long nq = (q.n + stride - 1ull) / stride;
     if (nq == 0) return hipSuccess;
     k_align_plane_iter<<<dist_blocks(nq), 256, 0, s>>>(q, stride, nq, t, g, fine, cg, coarse, list, p, kq, pivot, words, rec);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ point-to-triangle distances to the mesh
+//
+// acmmp_fusion_surface_distance (include/acmmp.h).  As above the result is defined over all (query, face)
+// pairs and the grid only decides which are looked at.  A face is listed in every cell its vertex box overlaps, so a
+// face not yet met after rings 0 .. r has a box that misses the cube of those rings; the clamp of step 3 keeps the
+// closest point inside that box, which is what turns the cell gap into a bound on D2.
+
+// Step 3: the float32 D2 of query p and face (A, B, C); NaN for a pair that is no candidate.
+__device__ __forceinline__ float surf_pair_d2(const float p[3], const float A[3], const float B[3], const float C[3]) {
+    double ap[3], bp[3], cp[3], ab[3], ac[3], bc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double pk = static_cast<double>(p[k]), a = static_cast<double>(A[k]), b = static_cast<double>(B[k]),
+                     c = static_cast<double>(C[k]);
+        ap[k] = pk - a; bp[k] = pk - b; cp[k] = pk - c;
+        ab[k] = b - a; ac[k] = c - a; bc[k] = c - b;
+    }
+    const double d1 = (ab[0] * ap[0] + ab[1] * ap[1]) + ab[2] * ap[2];
+    const double d2 = (ac[0] * ap[0] + ac[1] * ap[1]) + ac[2] * ap[2];
+    const double d3 = (ab[0] * bp[0] + ab[1] * bp[1]) + ab[2] * bp[2];
+    const double d4 = (ac[0] * bp[0] + ac[1] * bp[1]) + ac[2] * bp[2];
+    const double d5 = (ab[0] * cp[0] + ab[1] * cp[1]) + ab[2] * cp[2];
+    const double d6 = (ac[0] * cp[0] + ac[1] * cp[1]) + ac[2] * cp[2];
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    double e[3];
+    if (d1 <= 0.0 && d2 <= 0.0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = -ap[k];
+    } else if (d3 >= 0.0 && d4 <= d3) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = -bp[k];
+    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        const double v = d1 / (d1 - d3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = v * ab[k] - ap[k];
+    } else if (d6 >= 0.0 && d5 <= d6) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = -cp[k];
+    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        const double w = d2 / (d2 - d6);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = w * ac[k] - ap[k];
+    } else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
+        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = w * bc[k] - bp[k];
+    } else {
+        const double s = (va + vb) + vc, v = vb / s, w = vc / s;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) e[k] = (v * ab[k] + w * ac[k]) - ap[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double lo = fmin(-ap[k], fmin(-bp[k], -cp[k])), hi = fmax(-ap[k], fmax(-bp[k], -cp[k]));
+        e[k] = e[k] < lo ? lo : (e[k] > hi ? hi : e[k]);
+    }
+    return static_cast<float>((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+}
+
+// Steps 1 and 2 for face j: its vertices as dist_load reads them; false = not a valid face.
+__device__ __forceinline__ bool surf_face(const SurfMesh& m, unsigned j, float A[3], float B[3], float C[3]) {
+    const int32_t* t = m.faces + 3ull * j;
+    const unsigned long long ia = static_cast<uint32_t>(t[0]), ib = static_cast<uint32_t>(t[1]), ic = static_cast<uint32_t>(t[2]);
+    if (ia >= m.v.n || ib >= m.v.n || ic >= m.v.n) return false;
+    const bool oa = dist_load(m.v, ia, A), ob = dist_load(m.v, ib, B), oc = dist_load(m.v, ic, C);
+    return oa && ob && oc;
+}
+
+__global__ __launch_bounds__(256) void k_surf_bounds(const SurfMesh m, unsigned long long* __restrict__ words) {
+    const unsigned long long j = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    uint32_t mm[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    bool ok = false;
+    if (j < m.nf) {
+        float A[3], B[3], C[3];
+        ok = surf_face(m, static_cast<unsigned>(j), A, B, C);
+        if (ok) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                mm[a] = vox_ordered(fminf(A[a], fminf(B[a], C[a])));
+                mm[3 + a] = vox_ordered(-fmaxf(A[a], fmaxf(B[a], C[a])));
+            }
+        }
+    }
+    uint32_t* mn = reinterpret_cast<uint32_t*>(words + kDistMin);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mm[a] = min(mm[a], static_cast<uint32_t>(__shfl_xor(static_cast<int>(mm[a]), d)));
+        if ((threadIdx.x & 63) == 0 && mm[a] != 0xffffffffu) atomicMin(&mn[a], mm[a]);
+    }
+    wave_count(ok, &words[kDistValidTargets]);
+}
+
+// The three passes over the faces.  kSurfPlan: the counts of the plan.  kSurfCount: a small face claims its cells and
+// adds 1 to each count, a large face goes to the overflow list.  kSurfScatter: a small face goes to its cells' lists.
+enum { kSurfPlan = 0, kSurfCount = 1, kSurfScatter = 2 };
+template <int PASS>
+__global__ __launch_bounds__(256) void k_surf_faces(const SurfMesh m, const DistGrid g, const DistTable fine, long long small_max,
+                                                    float4* __restrict__ list, unsigned long long cap_list,
+                                                    float4* __restrict__ large, unsigned long long cap_large,
+                                                    unsigned long long* __restrict__ words) {
+    const unsigned long long j = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned err = 0u;
+    bool is_small = false, is_large = false;
+    unsigned long long cells = 0;
+    if (j < m.nf) {
+        float A[3], B[3], C[3];
+        if (surf_face(m, static_cast<unsigned>(j), A, B, C)) {
+            int c0[3], c1[3];
+            cells = 1;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                double fr;
+                bool cl = false;
+                c0[a] = dist_axis(g, a, fminf(A[a], fminf(B[a], C[a])), fr, cl);
+                c1[a] = dist_axis(g, a, fmaxf(A[a], fmaxf(B[a], C[a])), fr, cl);
+                cells *= static_cast<unsigned long long>(c1[a] - c0[a] + 1);
+            }
+            is_large = small_max < 0 || cells > static_cast<unsigned long long>(small_max);
+            is_small = !is_large;
+            const float4 ea = make_float4(A[0], A[1], A[2], __uint_as_float(static_cast<uint32_t>(j)));
+            const float4 eb = make_float4(B[0], B[1], B[2], 0.0f), ec = make_float4(C[0], C[1], C[2], 0.0f);
+            if (PASS == kSurfCount && is_large) {
+                const unsigned long long pos = atomicAdd(&words[kSurfLargeCursor], 1ull);
+                if (pos < cap_large) { large[3 * pos] = ea; large[3 * pos + 1] = eb; large[3 * pos + 2] = ec; }
+                else err = 2u;
+            }
+            if (PASS != kSurfPlan && is_small) {
+                for (int z = c0[2]; z <= c1[2]; ++z)
+                    for (int y = c0[1]; y <= c1[1]; ++y)
+                        for (int x = c0[0]; x <= c1[0]; ++x) {
+                            unsigned long long s;
+                            if (PASS == kSurfCount) {
+                                if (table_claim(fine, dist_key(x, y, z), s)) atomicAdd(&fine.cnt[s], 1u);
+                                else err = 1u;
+                            } else if (table_find(fine, dist_key(x, y, z), s) == 0) {
+                                const unsigned long long pos = atomicAdd(&fine.cnt[s], 1u);
+                                if (pos < cap_list) { list[3 * pos] = ea; list[3 * pos + 1] = eb; list[3 * pos + 2] = ec; }
+                                else err = 2u;
+                            } else {
+                                err = 2u;
+                            }
+                        }
+            }
+        }
+    }
+    if (PASS == kSurfPlan) {
+        wave_count(is_small, &words[kSurfSmall]);
+        wave_count(is_large, &words[kSurfLarge]);
+        wave_add(is_small ? cells : 0ull, &words[kSurfRegs]);
+    } else {
+        block_or(err, &words[kDistErr]);
+    }
+}
+
+// One listed face against the query: best = min(best, key) unless D2 is NaN.
+__device__ __forceinline__ void surf_entry(const float4* __restrict__ e, const float v[3], unsigned long long& best) {
+    const float4 a = e[0], b = e[1], c = e[2];
+    const float A[3] = {a.x, a.y, a.z}, B[3] = {b.x, b.y, b.z}, C[3] = {c.x, c.y, c.z};
+    const float d2 = surf_pair_d2(v, A, B, C);
+    const unsigned long long key =
+        static_cast<unsigned long long>(__float_as_uint(d2)) << 32 | static_cast<unsigned long long>(__float_as_uint(a.w));
+    if (d2 == d2) best = min(best, key);
+}
+
+__global__ __launch_bounds__(256) void k_surf_query(const DistCloud q, const DistGrid g, const DistTable fine,
+                                                    const float4* __restrict__ list, const float4* __restrict__ large,
+                                                    unsigned n_large, const DistQuery p, float* __restrict__ d2out,
+                                                    int32_t* __restrict__ nnout, unsigned long long* __restrict__ words) {
+    __shared__ unsigned hist[256];
+    hist[threadIdx.x] = 0u;
+    __syncthreads();
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    bool valid = false, matched = false;
+    float d2 = __builtin_inff();
+    int32_t nn = -1;
+    unsigned long long rings = 0;
+    unsigned err = 0u;
+    if (i < q.n) {
+        float v[3];
+        valid = dist_load(q, i, v);
+        if (valid && p.have_targets) {
+            const double m2d = static_cast<double>(p.m2);
+            // the bounding box of the faces: the closest point of every face lies in it
+            double gap = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+                gap = fmax(gap, fmax(p.lo[a] - static_cast<double>(v[a]), static_cast<double>(v[a]) - p.hi[a]));
+            unsigned long long best = ~0ull;
+            if (!(dist_floor2(gap) > m2d)) {
+                for (unsigned l = 0; l < n_large; ++l) surf_entry(large + 3ull * l, v, best);
+                dist_walk(v, g, m2d, best, rings, [&](int x, int y, int z, unsigned long long& b) {
+                    unsigned long long s;
+                    const int r = table_find(fine, dist_key(x, y, z), s);
+                    if (r == 2) err |= 4u;
+                    if (r != 0) return;
+                    const uint32_t e0 = fine.start[s], e1 = fine.cnt[s];
+                    for (uint32_t pos = e0; pos < e1; ++pos) surf_entry(list + 3ull * pos, v, b);
+                });
+            }
+            if (best != ~0ull) {
+                const float w = __uint_as_float(static_cast<uint32_t>(best >> 32));
+                if (w <= p.m2) {
+                    matched = true;
+                    d2 = w;
+                    nn = static_cast<int32_t>(static_cast<uint32_t>(best & 0xffffffffull));
+                }
+            }
+        }
+        d2out[i] = d2;
+        nnout[i] = nn;
+    }
+    dist_summarise(valid, matched, d2, rings, err, p, hist, words);
+}
+
+hipError_t launch_surf_bounds(SurfMesh m, unsigned long long* words, hipStream_t s) {
+    if (m.nf == 0) return hipSuccess;
+    k_surf_bounds<<<dist_blocks(m.nf), 256, 0, s>>>(m, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_surf_plan(SurfMesh m, DistGrid g, long long small_max, unsigned long long* words, hipStream_t s) {
+    if (m.nf == 0) return hipSuccess;
+    const DistTable none = {nullptr, nullptr, nullptr, 0, 0};
+    k_surf_faces<kSurfPlan><<<dist_blocks(m.nf), 256, 0, s>>>(m, g, none, small_max, nullptr, 0, nullptr, 0, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_surf_lists(SurfMesh m, DistGrid g, DistTable fine, long long small_max, float4* list,
+                             unsigned long long cap_list, float4* large, unsigned long long cap_large,
+                             unsigned long long* words, hipStream_t s) {
+    if (m.nf == 0) return hipSuccess;
+    const unsigned long long blocks = std::min<unsigned long long>((fine.slots + 255ull) / 256ull, 4096ull);
+    k_surf_faces<kSurfCount><<<dist_blocks(m.nf), 256, 0, s>>>(m, g, fine, small_max, list, cap_list, large, cap_large, words);
+    k_dist_starts<<<static_cast<unsigned>(blocks), 256, 0, s>>>(fine, words);
+    k_surf_faces<kSurfScatter><<<dist_blocks(m.nf), 256, 0, s>>>(m, g, fine, small_max, list, cap_list, large, cap_large, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_surf_query(DistCloud q, DistGrid g, DistTable fine, const float4* list, const float4* large,
+                             unsigned n_large, DistQuery p, float* d2, int32_t* nearest, unsigned long long* words,
+                             hipStream_t s) {
+    if (q.n == 0) return hipSuccess;
+    k_surf_query<<<dist_blocks(q.n), 256, 0, s>>>(q, g, fine, list, large, n_large, p, d2, nearest, words);
     return hipGetLastError();
 }
 

@@ -920,6 +920,92 @@ acmmp_status acmmp_fusion_cloud_align_plane(acmmp_fusion *f, int source, float m
 acmmp_status acmmp_fusion_align_plane_records(acmmp_fusion *f, int64_t first, int64_t n, int64_t *words, double *M,
                                               double *shift);
 
+/* ---- point-to-triangle distances from a cloud to the mesh result's surface (no reference counterpart) ----
+ * acmmp_fusion_surface_distance measures the points of the cloud `query` against the faces of the mesh result
+ * (acmmp_fusion_voxel_mesh, acmmp_fusion_set_mesh).  ACMMP_SURF_FROM_REFERENCE: the queries are the reference cloud -- how
+ * much of it lies within tau of the surface, which acmmp_fusion_cloud_distance with ACMMP_DIST_FROM_MESH can only say of the
+ * vertices.  ACMMP_SURF_FROM_SCENE, _VOXELS, _CLEAN, _VISIBLE: the queries are the first three floats of each point of that
+ * resident data cloud -- how far the mesh strays from the cloud it was extracted from.  The definition is exhaustive over
+ * the (query, face) pairs, in plain IEEE arithmetic with no contraction:
+ *  1. Frames.  With a reference query and a cloud transform set (acmmp_fusion_set_cloud_transform), every mesh vertex is
+ *     read under M exactly as a data point of acmmp_fusion_cloud_distance is: float64, rounded once to float32.  With a
+ *     data-cloud query neither side is transformed: both live in the data frame.  The reference cloud is never
+ *     transformed.  The call never modifies the transform, the mesh or any source.
+ *  2. Validity.  A query is valid when its three floats are finite; a face when its three vertices, after step 1, are
+ *     finite.  Invalid queries are neither matched nor counted as valid; invalid faces do not exist, and
+ *     acmmp_fusion_surface_plan's *n_skipped counts them.
+ *  3. Pair distance of query p and face (A, B, C), in float64 on the float32 inputs widened, with
+ *     dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z: ap = p - A, bp = p - B, cp = p - C, ab = B - A, ac = C - A, bc = C - B;
+ *     d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+ *     vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4.  The offset e from the query to the closest point is,
+ *     per component k, that of the first case that applies, in this order:
+ *       d1 <= 0 && d2 <= 0:                               e = -ap
+ *       d3 >= 0 && d4 <= d3:                              e = -bp
+ *       vc <= 0 && d1 >= 0 && d3 <= 0:                    v = d1 / (d1 - d3), e_k = v*ab_k - ap_k
+ *       d6 >= 0 && d5 <= d6:                              e = -cp
+ *       vb <= 0 && d2 >= 0 && d6 <= 0:                    w = d2 / (d2 - d6), e_k = w*ac_k - ap_k
+ *       va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0:      w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), e_k = w*bc_k - bp_k
+ *       otherwise:                                        s = (va + vb) + vc, v = vb / s, w = vc / s,
+ *                                                         e_k = (v*ab_k + w*ac_k) - ap_k
+ *     Then the clamp: lo_k = min(-ap_k, -bp_k, -cp_k), hi_k the maximum of the same three,
+ *     e_k = e_k < lo_k ? lo_k : (e_k > hi_k ? hi_k : e_k); a NaN passes through.  The clamp is the identity in exact
+ *     arithmetic; it keeps the closest point inside the face's bounding box, which the device's skips rest on.  Finally
+ *     D2 = (float)((e_x*e_x + e_y*e_y) + e_z*e_z).  A pair whose D2 is NaN is not a candidate (only a degenerate face
+ *     produces one); D2 may be +inf.
+ *  4. Nearest.  A valid query takes the smallest key (bits(D2) << 32) | j over the valid faces j that are candidates:
+ *     equal distances go to the lower face index.
+ *  5. Match, per-query results and summary: steps 4 and 5 of acmmp_fusion_cloud_distance with D2 for d2 -- m2, k, q,
+ *     within, the histogram, the ACMMP_DIST_SUMMARY_* offsets and ACMMP_DIST_MAX_TAU.  nearest_face is -1 and d2 is +inf when
+ *     the query is unmatched, invalid or has no candidate.
+ * The device lists every valid face in every cell of a uniform grid that its vertex bounding box overlaps, except faces
+ * that overlap more than small_max cells (64; acmmp_fusion_surface_plan), which go to one overflow list that every query
+ * past the box reject tests in full.  A query walks the grid ring by ring and skips a face only where the bounds of
+ * DESIGN.md §8 prove that it loses or is unmatched; a face met in several cells is evaluated again, which a key minimum
+ * does not notice.  No result depends on the grid, on small_max or on the order the atomics land in.
+ *
+ * ACMMP_ERR_INVALID_ARGUMENT: a query that is none of the constants, no such query result (an empty one is valid; for
+ * ACMMP_SURF_FROM_REFERENCE: no reference cloud), no mesh result (an empty one is valid), max_dist not finite or <= 0, n_tau
+ * outside [0, 8], a NULL tau with n_tau > 0, a tau[i] that is not finite, < 0 or > max_dist, a forced cell that is not finite
+ * and > 0 (acmmp_fusion_surface_grid).  ACMMP_ERR_UNSUPPORTED: more than
+ * 2^31 - 1 faces or queries, more than 2^32 - 1 registrations.  No query gives zeros; no valid face leaves every query
+ * unmatched.  One surface result is resident, separate from the distance result (acmmp_fusion_surface_results reads it); it
+ * is built beside the previous one, and any error -- an out-of-memory part-way included -- leaves the object as it was.
+ * It is discarded when the mesh result is replaced or discarded, when its query source is replaced or discarded, and, for
+ * a reference query only, when the reference cloud is replaced or the transform is set or cleared.
+ * acmmp_fusion_set_view, the align calls and acmmp_fusion_cloud_distance do not touch it, and this call touches neither
+ * the distance result nor the align records.
+ * Device memory: 8 bytes per query held with the result (d2, nearest_face); while the call runs, 48 bytes per
+ * registration and per large face (the three vertices after step 1 and the face index, so that a query never gathers
+ * vertices), and 16 bytes per slot of the cell table, S = the smallest power of two >= max(2 min(R, cells of the grid),
+ * 1024) slots for R registrations.  The host waits three times: for the faces' bounding box and valid count, from which it
+ * chooses the cell; for the plan (small faces, large faces, registrations), from which it sizes the table and the lists
+ * exactly; and at the end. */
+#define ACMMP_SURF_FROM_SCENE 0       /* queries = the scene result's points (the values of ACMMP_DIST_FROM_*) */
+#define ACMMP_SURF_FROM_VOXELS 1      /* the voxel result */
+#define ACMMP_SURF_FROM_CLEAN 2       /* the clean result's kept voxels */
+#define ACMMP_SURF_FROM_VISIBLE 3     /* the visible result's kept entries */
+#define ACMMP_SURF_FROM_REFERENCE 5   /* the reference cloud */
+acmmp_status acmmp_fusion_surface_distance(acmmp_fusion *f, int query, float max_dist, int n_tau, const float *tau,
+                                           int64_t *summary);
+/* Results of queries [first, first + n) of the surface result to host arrays, either of which may be NULL: d2 n floats,
+ * nearest_face n int32.  Ranges as acmmp_fusion_distance_results. */
+acmmp_status acmmp_fusion_surface_results(acmmp_fusion *f, int64_t first, int64_t n, float *d2, int32_t *nearest_face);
+/* Test hook, in the spirit of acmmp_fusion_render_plan.  small_max = 0: a face that overlaps more than 64 cells is a large
+ * face; small_max > 0: more than small_max cells; small_max < 0: every face is large.  It holds for the surface calls
+ * that follow.  The outputs, each of which may be NULL, describe the last successful surface call: the faces registered
+ * in the grid, the large faces, the (face, cell) registrations, the invalid faces. */
+acmmp_status acmmp_fusion_surface_plan(acmmp_fusion *f, int small_max, int64_t *n_small, int64_t *n_large,
+                                       int64_t *n_registrations, int64_t *n_skipped);
+/* Test hook: acmmp_fusion_distance_grid for the face grid of the surface calls, apart from it -- neither hook's forced
+ * cell reaches the other's calls, and neither call changes what the other's hook reports.  force_cell = 0: the cell is
+ * chosen from the valid faces' bounding box and number; otherwise it is the cell of the surface calls that follow
+ * (enlarged where the extent would need more than 2^20 cells on an axis), and one that is not finite and > 0 makes the
+ * next surface call return ACMMP_ERR_INVALID_ARGUMENT.  The outputs, each of which may be NULL, describe the last
+ * successful surface call: the cell used, the occupied cells, the longest cell list and the largest ring a query
+ * searched.  They are informational: no result depends on them. */
+acmmp_status acmmp_fusion_surface_grid(acmmp_fusion *f, float force_cell, float *cell, int64_t *cells, int64_t *max_list,
+                                       int64_t *rings);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D
