@@ -103,6 +103,7 @@ EXPORTS = [
     "acmmp_download", "acmmp_download_aux", "acmmp_device_outputs", "acmmp_synchronize", "acmmp_last_timing",
     "acmmp_last_kernel_timing", "acmmp_last_work", "acmmp_last_planar_timing", "acmmp_texel_bytes", "acmmp_set_math", "acmmp_get_math", "acmmp_jbu",
     "acmmp_debug_ncc", "acmmp_debug_geom", "acmmp_debug_ncc_nb", "acmmp_debug_ncc_ref", "acmmp_debug_band_cvec",
+    "acmmp_debug_band_keep_mask", "acmmp_keep_mask_bytes",
     "acmmp_support_points", "acmmp_delaunay", "acmmp_prior_plane_params", "acmmp_depth_from_plane_param",
     "acmmp_planar_prior_host", "acmmp_set_planar_prior_from_maps", "acmmp_set_planar_prior_from_state",
     "acmmp_download_planar_prior",
@@ -134,6 +135,17 @@ EXPORTS = [
 
 class AcmmpError(RuntimeError):
     pass
+
+
+def keep_mask_bytes(W: int, H: int, model: int = 11, patch_size: int = 11, radius_increment: int = 2, fast: bool = True,
+                    tex16: bool = True, n_src: int = 4, geom: bool = False) -> int:
+    """Bytes the kept-sample mask adds to the scratch slab of such a run under the current environment
+    (acmmp_keep_mask_bytes: the run's own gates; no GPU needed); 0 where the run publishes none."""
+    n = int(load_library().acmmp_keep_mask_bytes(int(W), int(H), int(model), int(patch_size), int(radius_increment),
+                                                 int(bool(fast)), int(bool(tex16)), int(n_src), int(bool(geom))))
+    if n < 0:
+        raise AcmmpError(f"keep_mask_bytes: invalid arguments ({W} x {H})")
+    return n
 
 
 def strip_plan(rows: int, want_strips: int):
@@ -224,6 +236,9 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_band_get_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.acmmp_band_set_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.acmmp_debug_band_cvec.argtypes = [vp, i32, i32, i32, vp]
+    L.acmmp_debug_band_keep_mask.argtypes = [vp, i32, i32, i32, vp]
+    L.acmmp_keep_mask_bytes.argtypes = [i32] * 9
+    L.acmmp_keep_mask_bytes.restype = C.c_longlong
     L.acmmp_band_end.argtypes = [vp, i32]
     L.acmmp_fusion_create.argtypes = [i32, i32, vp, C.POINTER(vp)]
     L.acmmp_fusion_set_view.argtypes = [vp, i32, vp, vp, vp]
@@ -648,6 +663,13 @@ class Context:
         colour-grid pixels in band_get_rows' order; straight after band_begin, k_init's vectors of its planes."""
         out = np.empty((self.N - 1, (row_b - row_a) * ((self.W + 1) // 2)), np.float32)
         self._check(self.L.acmmp_debug_band_cvec(self.h, colour, row_a, row_b, _p(out)), "debug_band_cvec")
+        return out
+
+    def debug_band_keep_mask(self, colour: int, row_a: int, row_b: int) -> np.ndarray:
+        """The kept-sample mask words of rows [row_a, row_b) of `colour` in a band run -> (n,) uint64 in
+        band_get_rows' order (bit s set: sample s dropped); AcmmpError when the run publishes no mask."""
+        out = np.empty((row_b - row_a) * ((self.W + 1) // 2), np.uint64)
+        self._check(self.L.acmmp_debug_band_keep_mask(self.h, colour, row_a, row_b, _p(out)), "debug_band_keep_mask")
         return out
 
     def band_set_rows(self, colour: int, row_a: int, row_b: int, rows: np.ndarray):

@@ -944,6 +944,29 @@ int acmmp_strip_plan(int rows, int want_strips, int* bounds, int* waits) {
 
 // want_strips: the strip schedule's strip count before clamping (strip_plan); the queues a half-sweep indexes by
 // block number get one slice per strip (c->strips), and kp's own queue pointers are strip 0's.
+// The run-time gates build_kparams and the host-side size query (acmmp_keep_mask_bytes) share; the environment is read
+// at every call.  interp_geometry: the geometric part of the interpolation gate (see build_kparams).
+static bool interp_geometry(int model, int nside, int R, int W, int H) {
+    return model == kSphere && nside == 6 && 2000LL * R <= 5LL * W && 1000LL * R <= 5LL * H;
+}
+static float ref_neg_tau_of(bool interp_geom, bool fast, bool tex16, int V) {
+    float tau = -1.0f;
+    if (interp_geom && fast && tex16 && V <= 4) {
+        tau = 0x1p-35f;
+        if (const char* e = std::getenv("ACMMP_REF_NEG_TAU")) tau = std::strtof(e, nullptr);
+        if (const char* e = std::getenv("ACMMP_REF_NEG_SKIP")) if (std::atoi(e) == 0) tau = -1.0f;
+    }
+    return tau;
+}
+// ACMMP_KEEP_MASK=0 (read per run) launches the instances that recompute the test, with the same bits (A/B,
+// tests/test_gpu_keep_mask.py); without the mask there is nothing to publish.  Not in a geom run: k_eval_ref's geom
+// form would go from 80 to 81 VGPRs and from 6 waves to 5 with the word, and it and the tail must agree on who fills psum.
+static bool keep_mask_of(float ref_neg_tau, bool geom) {
+    bool keep = ref_neg_tau >= 0.0f && !geom;
+    if (const char* e = std::getenv("ACMMP_KEEP_MASK")) if (std::atoi(e) == 0) keep = false;
+    return keep;
+}
+
 static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int want_strips = 1) {
     const acmmp_params& p = c->params;
     if (!c->has_params) return fail(c, ACMMP_ERR_STATE, "set_params first");
@@ -972,7 +995,7 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     // poles, where the 256-pixel corner-spread fallback no longer catches it (1600x800: 3.7e-3 at a spread
     // of 65 px; scripts/interp_feasibility.py, tests/test_interp_design.py).  patch_size 21 / increment 4
     // also gives 6x6 samples but spans twice the angle: it projects every sample below 4000x2000.
-    kp.interp = c->model == kSphere && nside == 6 && 2000LL * R <= 5LL * c->W && 1000LL * R <= 5LL * c->H;
+    kp.interp = interp_geometry(c->model, nside, R, c->W, c->H);
     // The per-sample refinement loops' negligible-sample threshold (ncc_chunk's PNEG instances):
     // fast SPHERE with binary16 texels, V <= 4, in k_init, k_eval_ref, k_eval_ref_tail and k_select's cache misses
     // (without the binary16 images these run the TF = 0 instances, which have no masked form), so the cost cache holds
@@ -982,12 +1005,12 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     // ACMMP_SPREAD_MAX / ACMMP_NBFIX_MAX_PC / ACMMP_NEG_*: the runs the tests compare across those knobs share
     // one refinement.  ACMMP_REF_NEG_TAU overrides tau (tests), ACMMP_REF_NEG_SKIP=0 launches the instances
     // without the mask; both read per run.
-    kp.ref_neg_tau = -1.0f;
-    if (kp.interp && c->math == ACMMP_MATH_FAST && c->tex16 && kp.V <= 4) {
-        kp.ref_neg_tau = 0x1p-35f;
-        if (const char* e = std::getenv("ACMMP_REF_NEG_TAU")) kp.ref_neg_tau = std::strtof(e, nullptr);
-        if (const char* e = std::getenv("ACMMP_REF_NEG_SKIP")) if (std::atoi(e) == 0) kp.ref_neg_tau = -1.0f;
-    }
+    kp.ref_neg_tau = ref_neg_tau_of(kp.interp, c->math == ACMMP_MATH_FAST, c->tex16, kp.V);
+    // The kept-sample mask (KParams::keep, keep_mask_of): the drop test above is the same in every half-sweep of a
+    // run, so a masked run's k_init publishes it once per pixel, with the patch sums, and k_eval_ref and its tail
+    // read it instead of forming every weight again to test it.
+    const bool keep = keep_mask_of(kp.ref_neg_tau, p.geom_consistency != 0);
+    kp.keep = keep ? 1 : 0;
     // ACMMP_INTERP=0 projects every sample in the fast mode too (the per-sample fast arithmetic the
     // interpolation is gated against, tests/test_gpu_fastmath.py T2); read per run
     if (const char* e = std::getenv("ACMMP_INTERP")) kp.interp = kp.interp && std::atoi(e) != 0;
@@ -1123,7 +1146,7 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         piece(kp.cand_vcost, 5 * VP);
         piece(kp.surv, surv_n);
         piece(kp.surv_count, std::max(Pc / 51 + 2, ref_total));
-        piece(kp.psum, Pc);
+        piece(kp.psum, psum_count(Pc, keep));
         piece(kp.nbfix, kNbFixRegions * fix_total);              // (empty without a fallback queue)
         piece(kp.nbfix_count, static_cast<size_t>(kNbFixRegions) * ns);
         piece(kp.surv_pre, std::max(Pc / 51 + 3, ref_total + ns));
@@ -1472,6 +1495,38 @@ acmmp_status acmmp_debug_band_cvec(acmmp_ctx* c, int colour, int row_a, int row_
     for (int v = 0; v < kp.V; ++v)
         HIP_TRY(c, d2h(out + static_cast<size_t>(v) * n, kp.cvec[colour] + static_cast<size_t>(v) * kp.Pc + off, sizeof(float) * n));
     return ACMMP_OK;
+}
+
+// Test hook: the kept-sample mask words (keep_words) of rows [row_a, row_b) of `colour` in a band run, one per
+// colour-grid pixel in acmmp_band_get_rows' order.  ACMMP_ERR_STATE when the run has no mask.
+acmmp_status acmmp_debug_band_keep_mask(acmmp_ctx* c, int colour, int row_a, int row_b, uint64_t* out) {
+    if (!c || !out) return ACMMP_ERR_INVALID_ARGUMENT;
+    BandBuffers b{};
+    const acmmp_status st = band_buffers(c, colour, &b);
+    if (st != ACMMP_OK) return st;
+    if (row_a < 0 || row_b > c->H || row_a > row_b) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "rows out of range");
+    const KParams& kp = c->band_kp;
+    if (!kp.keep) return fail(c, ACMMP_ERR_STATE, "the run has no kept-sample mask");
+    if (row_a == row_b) return ACMMP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t off = static_cast<size_t>(row_a) * b.Wh, n = static_cast<size_t>(row_b - row_a) * b.Wh;
+    HIP_TRY(c, d2h(out, keep_words(kp) + static_cast<size_t>(colour) * kp.Pc + off, sizeof(uint64_t) * n));
+    return ACMMP_OK;
+}
+
+// The bytes the kept-sample mask adds to the scratch slab of a run of the given view and settings, before the piece's
+// 256-byte rounding: build_kparams' own gates (with the environment as it is now) and piece count.  No GPU needed.
+long long acmmp_keep_mask_bytes(int W, int H, int model, int patch_size, int radius_increment, int fast, int tex16,
+                                int n_src, int geom) {
+    if (W < 1 || H < 1 || patch_size < 1 || radius_increment < 1 || n_src < 1) return -1;
+    const int R = patch_size / 2;
+    int nside = 0;
+    for (int i = -R; i <= R; i += radius_increment) ++nside;
+    const float tau = ref_neg_tau_of(interp_geometry(model, nside, R, W, H), fast != 0, tex16 != 0, n_src);
+    const bool keep = keep_mask_of(tau, geom != 0);
+    const size_t Pc = static_cast<size_t>(H) * ((W + 1) / 2);
+    return static_cast<long long>(sizeof(float4) * (psum_count(Pc, keep) - psum_count(Pc, false)));
 }
 
 acmmp_status acmmp_band_set_rows(acmmp_ctx* c, int colour, int row_a, int row_b, const float* planes, const float* costs,

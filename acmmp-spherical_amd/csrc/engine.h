@@ -153,12 +153,22 @@ struct KParams {
     unsigned* surv_count;           // [k_eval_ref blocks] slots used (zeroed before each k_eval_ref)
     unsigned* surv_pre;             // [k_eval_ref blocks + 1] their exclusive prefix (k_tail_scan)
     uint32_t* surv_dense;           // the survivors in block order (k_tail_compact)
-    float4* psum;                   // [Pc] (patch sum w, sum w r, sum w r^2, centre texel) for the tail
+    float4* psum;                   // [Pc] (patch sum w, sum w r, sum w r^2, centre texel) for the tail ([2][Pc] from
+                                    // k_init with `keep`, below)
     // k_eval_nb's deferred interpolation fallbacks (ncc_chunk, k_nb_fix): pixel << 8 | hypothesis << 5 |
     // view; null = none (no interpolation, or ACMMP_SPREAD_MAX off)
     uint32_t* nbfix;                // kNbFixRegions regions of nbfix_cap entries (every entry a launch can queue)
     unsigned* nbfix_count;          // [kNbFixRegions]
     unsigned nbfix_cap;             // entries per region
+    // (in the 4 bytes of padding before the next pointer: no field moves and the struct keeps its size, so every
+    // kernel's argument offsets stay, the arguments behind the struct included)
+    int keep;                       // 1: the run publishes the per-pixel kept-sample mask of the masked per-sample loops
+                                    // (ref_neg_tau >= 0).  k_init then writes, for every pixel it
+                                    // initialises, the patch sums into psum -- both colours, [2][Pc] colour-major -- and
+                                    // behind them one 64-bit word per pixel (keep_words: bit s set = sample s is dropped,
+                                    // its weight is <= ref_neg_tau x the pixel's patch sum), also [2][Pc]; k_eval_ref and
+                                    // its tail read both and form no dropped weight again.  0: every kernel recomputes the
+                                    // test from the weights (ACMMP_KEEP_MASK=0, a geom run, or outside the gate)
     // k_eval_ref's interpolated instance (SPHERE V > 4): per queued candidate, its selected views of
     // [0, ref_split) whose interpolation fell back -- k_eval_ref_tail recomputes them and restarts the chain
     uint32_t* cand_rough;           // [5][Pc]
@@ -171,6 +181,15 @@ struct KParams {
                                     // without one reads this word (a scalar load) and no mask byte
     unsigned* status;               // run status bits (kStatus*), zeroed per run, checked after it
 };
+static_assert(sizeof(KParams) == 568, "KParams is every kernel's first argument: a size change moves the ones behind it");
+
+// The psum piece of the scratch slab (build_kparams), in float4 entries: one colour's sums, or with the kept-sample
+// mask both colours' and behind them the 2 Pc mask words (two words per entry).
+inline size_t psum_count(size_t Pc, bool keep) { return keep ? 3 * Pc : Pc; }
+// The kept-sample words of a run with kp.keep, [2][Pc] colour-major.
+__host__ __device__ inline unsigned long long* keep_words(const KParams& kp) {
+    return reinterpret_cast<unsigned long long*>(kp.psum + 2 * kp.Pc);
+}
 
 // Per-half-sweep output buffers of the colour being updated.
 struct SweepOut {

@@ -334,7 +334,16 @@ struct Patch {
     float sbw, sref, srr;
     // k_eval_nb's fast SPHERE instance: the wave's mask of negligible samples, two words in LDS (stage_neg_mask)
     const uint32_t* neg = nullptr;
+    // the masked per-sample loops' kept-sample word (KParams::keep, keep_words; ncc_chunk's PNEG): the pixel's word where
+    // the loop reads it (kNegWord), and where k_init's loop leaves the word it forms (kNegPublish)
+    unsigned long long keep = 0ull;
+    unsigned long long* keep_out = nullptr;
 };
+
+// ncc_chunk's PNEG, the per-pixel negligible-sample mask of the per-sample loop: none; the test
+// formed from each recomputed weight; the test read from the pixel's published word (pt.keep: no weight is formed
+// for a sample the wave drops); and k_init's form, the recomputed test with its 36 bits left in *pt.keep_out.
+enum NegMode { kNegNone = 0, kNegTest = 1, kNegWord = 2, kNegPublish = 3 };
 
 typedef float float2u __attribute__((ext_vector_type(2), aligned(4)));
 
@@ -605,7 +614,7 @@ __device__ __forceinline__ int lane_id_here() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, int NB = 0, bool PNEG = false>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM = 0, bool FULL = false, int NB = 0, int PNEG = kNegNone>
 __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                           const int (&vlist)[VB], int nv_rt, float (&cost)[VB],
                                           uint32_t fixkey = kFixNone) {
@@ -1128,7 +1137,10 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
         // at +0 and take products of non-negative weights and texels), so its bits are the skipped form's --
         // also where its own projection is NaN (a point on the source's vertical axis), which w = 0 alone
         // would let into the sums.  The reference-side sums (pt.sbw, sref, srr) keep all samples.
-        const float neg_lim = PNEG ? kp.ref_neg_tau * pt.sbw : 0.f;
+        // kNegWord: `mine` is the pixel's bit of the word k_init published from this very test (pt.keep), read before
+        // anything of the sample is formed: a sample the wave drops costs a shift and a ballot.
+        const float neg_lim = (PNEG == kNegTest || PNEG == kNegPublish) ? kp.ref_neg_tau * pt.sbw : 0.f;
+        [[maybe_unused]] unsigned long long published = 0ull;
 #define ACMMP_ACCUMULATE_N(v) ACMMP_ACCUMULATE_Z(v, tap[v], w, wwr, r, ok[v], PNEG && mine)
         int s = 0, ii = 0;
         for (int i = -R; i <= R; i += inc, ++ii) {
@@ -1137,6 +1149,11 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
             for (int j = -R; j <= R; j += inc, ++s, ++jj) {
                 float r;
                 float4 rw;
+                bool mine = false;
+                if constexpr (PNEG == kNegWord) {
+                    mine = ((pt.keep >> s) & 1ull) != 0ull;
+                    if (__all(mine)) continue;
+                }
                 if (STAGED == 4) {                           // coop_patch_sep layout (SPHERE): ray_at's products
                     const float2 rs = pt.row[jj];
                     const float2 q = pt.wr[s];
@@ -1154,8 +1171,11 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                 } else {
                     rw = patch_sample<MODEL>(kp, px, py, s, i, j, pt.center, r);
                 }
-                const bool mine = PNEG && rw.w <= neg_lim;
-                if constexpr (PNEG) if (__all(mine)) continue;
+                if constexpr (PNEG == kNegTest || PNEG == kNegPublish) {
+                    mine = rw.w <= neg_lim;
+                    if constexpr (PNEG == kNegPublish) published |= static_cast<unsigned long long>(mine) << s;
+                    if (__all(mine)) continue;
+                }
                 const float w = mine ? 0.f : rw.w;
                 // reference camera through the constant address space too: scalar loads per sample
                 // instead of 12 wave-uniform VGPRs held across the loop
@@ -1207,6 +1227,7 @@ __device__ __forceinline__ void ncc_chunk(const KParams& kp, int px, int py, con
                 }
             }
         }
+        if constexpr (PNEG == kNegPublish) *pt.keep_out = published;
     }
 #undef ACMMP_ACCUMULATE
 #undef ACMMP_ACCUMULATE_N
@@ -1304,7 +1325,7 @@ __device__ __forceinline__ float4 perturbed_normal(float4 v, float4 n, Rng& rs, 
 // ------------------------------------------------------------------ cost-vector helpers
 
 // Evaluate all source views of plane `ph` and hand each cost to f(view0, cost) in view order.
-template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, int NOFULL = 0, bool PNEG = false, typename F>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TEX, int FM, int NOFULL = 0, int PNEG = kNegNone, typename F>
 __device__ __forceinline__ void for_all_views_t(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                                 uint32_t wave_mask, F&& f, uint32_t fixkey = kFixNone) {
     int v = 0;
@@ -1359,7 +1380,7 @@ __device__ __forceinline__ void for_all_views(const KParams& kp, int px, int py,
 // register allocation (k_eval_nb's r02 A/B: a run-time branch between them sized every path for the
 // largest).  0 = fp32 texels, math mode at run time (images that are not binary16-exact); 1 = binary16
 // texels, exact; 2 = binary16 texels, fast math.
-template <int MODEL, int VB, int STAGED, bool PIPE, int TF, bool PIPE_FM = PIPE, bool PNEG = false, typename F>
+template <int MODEL, int VB, int STAGED, bool PIPE, int TF, bool PIPE_FM = PIPE, int PNEG = kNegNone, typename F>
 __device__ __forceinline__ void for_all_views_tf(const KParams& kp, int px, int py, const Patch& pt, float4 ph,
                                                  uint32_t wave_mask, F&& f, uint32_t fixkey = kFixNone) {
     if constexpr (TF == 0) {
@@ -1367,7 +1388,7 @@ __device__ __forceinline__ void for_all_views_tf(const KParams& kp, int px, int 
         else for_all_views_t<MODEL, VB, STAGED, PIPE, 0, 0>(kp, px, py, pt, ph, wave_mask, f);
     } else {
         // (PNEG: the per-pixel negligible-sample mask of the fast SPHERE per-sample loop, ncc_chunk)
-        for_all_views_t<MODEL, VB, STAGED, TF == 2 ? PIPE_FM : PIPE, 1, TF == 2 ? 1 : 0, 0, PNEG && TF == 2 && MODEL == kSphere>(
+        for_all_views_t<MODEL, VB, STAGED, TF == 2 ? PIPE_FM : PIPE, 1, TF == 2 ? 1 : 0, 0, (TF == 2 && MODEL == kSphere) ? PNEG : kNegNone>(
             kp, px, py, pt, ph, wave_mask, f, fixkey);
     }
 }
@@ -1497,7 +1518,7 @@ __device__ __forceinline__ void sort_small(float* d, int n) {
 // ComputeMultiViewInitialCostandSelectedViews, ACMMP.cu:519-556
 // (PNEG: k_init's masked instances -- the per-pixel negligible-sample mask of ncc_chunk's per-sample loop, so the
 // cached vector holds the bits the masked k_select / k_eval_ref form for the same pixel, plane and view)
-template <int MODEL, int VB, int VMAXB, int TF, bool PNEG = false>
+template <int MODEL, int VB, int VMAXB, int TF, int PNEG = kNegNone>
 __device__ float initial_cost(const KParams& kp, int px, int py, const Patch& pt, float4 ph, uint32_t* sel,
                               float* cvec = nullptr) {
     constexpr int VMAX = VMAXB < 8 ? VMAXB : kMaxViews;      // pick_vb: V <= VMAXB when VMAXB < 8
@@ -1549,7 +1570,7 @@ enum InitBranch { kInitRandom = 0, kInitPlanar = 1, kInitUpsample = 2, kInitReus
 // exact mode only: 1 view 1.55, 2 views 1.36, 4 views 1.41 ms at the metric).
 [[maybe_unused]] constexpr int kInitVB = 4;
 
-template <int MODEL, int VB, int BR, int VMAXB, int TF, bool PNEG = false>
+template <int MODEL, int VB, int BR, int VMAXB, int TF, int PNEG = kNegNone>
 __global__ __launch_bounds__(256) void k_init(const KParams kp) {
     // 16x16 tiles in XCD-aware order (xcd_block) over a row-major grid of ceil(W/16) tiles per row
     const long long tile = xcd_block(blockIdx.x);
@@ -1561,7 +1582,12 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
     const long long center = static_cast<long long>(y) * kp.W + x;
     const int colour = (x + y) & 1;
     const long long ci = cs_index(kp, x, y);
-    const Patch pt = make_patch<MODEL>(kp, x, y);
+    Patch pt = make_patch<MODEL>(kp, x, y);
+    // kNegPublish: the kept-sample word of the pixel, from the loop's own per-lane test (every branch below evaluates
+    // its plane's vector through initial_cost, so every initialised pixel gets one; a dead pixel's loop does not
+    // run and its word stays 0, never read where the dead mask skips it and unused where ncc_chunk returns 2.0)
+    [[maybe_unused]] unsigned long long kept = 0ull;
+    if constexpr (PNEG == kNegPublish) pt.keep_out = &kept;
     // the dead mask: ncc_chunk's own test on the sum the staged layouts form too (patch_sums)
     if (MODEL == kSphere && kp.dead[0]) {
         const bool dead = pt.sbw < 1e-6f;
@@ -1629,7 +1655,8 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
         normalize3(nx, ny, nz);
         const float4 cur = kp.planes_rm[center];
         uint32_t sel0;
-        kp.pre_rm[center] = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, cur, &sel0);
+        // (the word is published by the second evaluation alone)
+        kp.pre_rm[center] = initial_cost<MODEL, VB, VMAXB, TF, PNEG == kNegPublish ? kNegTest : PNEG>(kp, x, y, pt, cur, &sel0);
         ph = to_ref(rc, make_float4(nx, ny, nz, 0.0f));
         ph.w = dist_to_origin(dc, cur.w, ph);
         cost = initial_cost<MODEL, VB, VMAXB, TF, PNEG>(kp, x, y, pt, ph, &sel, cvec);
@@ -1644,6 +1671,12 @@ __global__ __launch_bounds__(256) void k_init(const KParams kp) {
     kp.cost_cs[colour][ci] = cost;
     kp.sel_cs[colour][ci] = sel;
     kp.rng_cs[colour][ci] = rs.n;
+    if constexpr (PNEG == kNegPublish) {
+        // what k_eval_ref and its tail read instead of forming it again: the word, and make_patch's sums and centre
+        // texel (the words coop_patch_sep's fold gives); both colours, colour-major
+        keep_words(kp)[colour * kp.Pc + ci] = kept;
+        kp.psum[colour * kp.Pc + ci] = make_float4(pt.sbw, pt.sref, pt.srr, pt.center);
+    }
 }
 
 // ------------------------------------------------------------------ kernels: CheckerboardPropagation
@@ -1894,17 +1927,24 @@ __device__ __forceinline__ void stage_neg_mask(const KParams& kp, bool valid, Pa
 // k_eval_ref's 51-pixel block fits 8 times in a CU's LDS instead of 5.
 static inline size_t sep_lds_bytes(int S, int nside, int npix) { return (8 * static_cast<size_t>(S) + 16 * nside) * npix; }
 
-template <int NPIX, int NLANES>
+// KEEP (k_eval_ref's kNegWord instance): the pixel's kept-sample word and patch sums come from k_init (entry pi of
+// keep_words / kp.psum): a dropped sample is staged as (0, 0) without its texel, division and exponential -- the
+// loop selects its weight and source texel to 0 whatever is staged -- and the sums, which keep all 36 terms, are
+// k_init's words instead of a fold over the staged weights.
+template <int NPIX, int NLANES, bool KEEP = false>
 __device__ __forceinline__ Patch coop_patch_sep(const KParams& kp, bool valid, int px, int py, int lp, int h,
-                                                float4* lds) {
+                                                float4* lds, long long pi = 0) {
     float2* base = reinterpret_cast<float2*>(lds);
     float2* wr = base + lp * kp.S;
     float2* row = base + NPIX * kp.S + lp * 2 * kp.nside;
     float2* col = row + kp.nside;
+    [[maybe_unused]] unsigned long long keep = 0ull;
     if (valid) {
         const DevCam& rc = kp.cams[0];
         const float center = texel_padded(rc.img_base, rc.img_pitch, rc.W, rc.H, px, py);
+        if constexpr (KEEP) keep = keep_words(kp)[pi];
         for (int s = h; s < kp.S; s += NLANES) {
+            if (KEEP && ((keep >> s) & 1ull)) { wr[s] = make_float2(0.f, 0.f); continue; }
             const int i = -kp.R + (s / kp.nside) * kp.inc, j = -kp.R + (s % kp.nside) * kp.inc;
             float r;
             const float4 q = patch_sample<kSphere>(kp, px, py, s, i, j, center, r);
@@ -1920,7 +1960,13 @@ __device__ __forceinline__ Patch coop_patch_sep(const KParams& kp, bool valid, i
     pt.rw = nullptr; pt.rr = nullptr; pt.wr = wr; pt.row = row; pt.col = col; pt.stride = 1;
     pt.center = 0.f;
     pt.sbw = 0.f; pt.sref = 0.f; pt.srr = 0.f;
-    if (valid) {
+    if (KEEP) {
+        pt.keep = keep;
+        if (valid) {
+            const float4 ps = kp.psum[pi];
+            pt.sbw = ps.x; pt.sref = ps.y; pt.srr = ps.z;
+        }
+    } else if (valid) {
         for (int s = 0; s < kp.S; ++s) {                // patch_sums order (ACMMP.cu:482-486)
             patch_fold_sample(wr[s].x, wr[s].y, pt);
         }
@@ -2588,7 +2634,7 @@ __global__ __launch_bounds__(256, ACMMP_SELECT_WAVES) void k_select(const KParam
 #ifndef ACMMP_REF_INTERP_WAVES
 #define ACMMP_REF_INTERP_WAVES 4
 #endif
-template <int MODEL, int VB, bool GEOM, int TF, bool PNEG = false>
+template <int MODEL, int VB, bool GEOM, int TF, int PNEG = kNegNone>
 __global__ __launch_bounds__(256, (MODEL == kSphere && VB > 4 && TF == 2) ? ACMMP_REF_INTERP_WAVES : 1) void k_eval_ref(const KParams kp, const int colour) {
     extern __shared__ float4 lds4[];
     const int t = threadIdx.x;
@@ -2608,11 +2654,12 @@ __global__ __launch_bounds__(256, (MODEL == kSphere && VB > 4 && TF == 2) ? ACMM
     }
     constexpr int kStaged = (MODEL == kSphere && VB <= 4) ? 4 : 3;
     Patch pt;
-    if constexpr (kStaged == 4) pt = coop_patch_sep<kRefPix, kRefLanes>(kp, valid, px, py, lp, h, lds4);
+    if constexpr (kStaged == 4) pt = coop_patch_sep<kRefPix, kRefLanes, PNEG == kNegWord>(kp, valid, px, py, lp, h, lds4, colour * Pc + ci);
     else pt = coop_patch_nb<MODEL, kRefPix, kRefLanes>(kp, valid, px, py, lp, h, lds4);
     constexpr int VBA = ref_vb_eval<MODEL, VB, TF>();
     if (!valid) return;
-    if (kp.ref_split > 0 && h == 0) {                        // the tail's patch, without re-summing it
+    // (kNegWord: k_init left the sums there for both colours)
+    if (PNEG != kNegWord && kp.ref_split > 0 && h == 0) {    // the tail's patch, without re-summing it
         const DevCam& rc = kp.cams[0];
         kp.psum[ci] = make_float4(pt.sbw, pt.sref, pt.srr,
                                   texel_padded(rc.img_base, rc.img_pitch, rc.W, rc.H, px, py));
@@ -2767,7 +2814,7 @@ __global__ __launch_bounds__(256) void k_tail_compact(const KParams kp) {
 // wave completion order, gave C3 a 58% L2 hit rate and 36 GB per launch), and every lane has a survivor
 // (per-k_eval_ref-block tail blocks left half their lanes idle; a binary search of surv_pre per 256 survivors
 // serialised each block: the metric's tail 0.34 -> 1.2 ms).
-template <int MODEL, int VB, bool GEOM, int TF, bool PNEG = false>
+template <int MODEL, int VB, bool GEOM, int TF, int PNEG = kNegNone>
 __global__ __launch_bounds__(256) void k_eval_ref_tail(const KParams kp, const int colour, const int nref) {
     const unsigned total = kp.surv_pre[nref];
     const unsigned x = blockIdx.x & 7u, k = blockIdx.x >> 3, nk = gridDim.x >> 3;
@@ -2797,7 +2844,10 @@ __global__ __launch_bounds__(256) void k_eval_ref_tail(const KParams kp, const i
         const float4 dc = ray_at<MODEL>(kp, px, py);
         const float4 tp = kp.cand[h * Pc + ci];
         Patch pt;                                            // make_patch's values, from k_eval_ref
-        const float4 ps = kp.psum[ci];
+        // (kNegWord: k_init's sums and kept-sample word of the pixel, colour-major)
+        const long long pi = PNEG == kNegWord ? colour * Pc + ci : ci;
+        const float4 ps = kp.psum[pi];
+        if constexpr (PNEG == kNegWord) pt.keep = keep_words(kp)[pi];
         pt.rw = nullptr; pt.rr = nullptr; pt.wr = nullptr; pt.row = pt.col = nullptr; pt.stride = 0;
         pt.sbw = ps.x; pt.sref = ps.y; pt.srr = ps.z; pt.center = ps.w;
         float temp_cost = need ? 0.0f : kp.cand_cost[h * Pc + ci];
@@ -3198,7 +3248,8 @@ template <int M, int BR, int VBC, int TF>
 static void launch_init_inst(const KParams& kp, dim3 grd, dim3 blk, hipStream_t s) {
     if constexpr (ref_neg_inst<M, VBC, TF>()) {
         if (kp.ref_neg_tau >= 0.0f) {
-            k_init<M, kInitVB, BR, VBC, TF, true><<<grd, blk, 0, s>>>(kp);
+            if (kp.keep) k_init<M, kInitVB, BR, VBC, TF, kNegPublish><<<grd, blk, 0, s>>>(kp);
+            else k_init<M, kInitVB, BR, VBC, TF, kNegTest><<<grd, blk, 0, s>>>(kp);
             return;
         }
     }
@@ -3429,7 +3480,14 @@ template <int M, int VBC, bool GEOM, int TF>
 static void launch_ref_inst(const KParams& kp, int colour, dim3 grd, size_t lds, hipStream_t s) {
     if constexpr (ref_neg_inst<M, VBC, TF>()) {
         if (kp.ref_neg_tau >= 0.0f) {
-            k_eval_ref<M, VBC, GEOM, TF, true><<<grd, 256, lds, s>>>(kp, colour);
+            // (a geom run publishes no word, build_kparams: this kernel's GEOM form would lose a wave to it)
+            if constexpr (!GEOM) {
+                if (kp.keep) {
+                    k_eval_ref<M, VBC, GEOM, TF, kNegWord><<<grd, 256, lds, s>>>(kp, colour);
+                    return;
+                }
+            }
+            k_eval_ref<M, VBC, GEOM, TF, kNegTest><<<grd, 256, lds, s>>>(kp, colour);
             return;
         }
     }
@@ -3439,7 +3497,13 @@ template <int M, int VBC, bool GEOM, int TF>
 static void launch_tail_inst(const KParams& kp, int colour, int nref, dim3 grd, hipStream_t s) {
     if constexpr (ref_neg_inst<M, VBC, TF>()) {
         if (kp.ref_neg_tau >= 0.0f) {
-            k_eval_ref_tail<M, VBC, GEOM, TF, true><<<grd, 256, 0, s>>>(kp, colour, nref);
+            if constexpr (!GEOM) {
+                if (kp.keep) {
+                    k_eval_ref_tail<M, VBC, GEOM, TF, kNegWord><<<grd, 256, 0, s>>>(kp, colour, nref);
+                    return;
+                }
+            }
+            k_eval_ref_tail<M, VBC, GEOM, TF, kNegTest><<<grd, 256, 0, s>>>(kp, colour, nref);
             return;
         }
     }

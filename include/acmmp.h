@@ -272,6 +272,15 @@ acmmp_status acmmp_band_set_rows(acmmp_ctx *ctx, int colour, int row_a, int row_
  * source view v and colour-grid pixel k of the n = (row_b - row_a) * ceil(W / 2) -- straight after acmmp_band_begin,
  * what the initialisation evaluated for the planes acmmp_band_get_rows returns.  Waits for the context's stream. */
 acmmp_status acmmp_debug_band_cvec(acmmp_ctx *ctx, int colour, int row_a, int row_b, float *out);
+/* Test hook: the kept-sample mask words of the same rows, one per colour-grid pixel (bit s set: the initialisation
+ * found patch sample s negligible for that pixel, and the refinement's per-sample loops skip it).  ACMMP_ERR_STATE
+ * when the run publishes no mask (outside the fast SPHERE V <= 4 gate, ACMMP_REF_NEG_SKIP=0 or ACMMP_KEEP_MASK=0). */
+acmmp_status acmmp_debug_band_keep_mask(acmmp_ctx *ctx, int colour, int row_a, int row_b, uint64_t *out);
+/* Test hook: device memory the kept-sample mask adds to a run of a W x H view with these settings (model 0 pinhole / 11 sphere,
+ * fast math, binary16 texels, source views, geom pass) under the environment as it is now: the run's own gates, no GPU
+ * needed.  0 where the run publishes no mask, -1 on bad arguments. */
+long long acmmp_keep_mask_bytes(int W, int H, int model, int patch_size, int radius_increment, int fast, int tex16,
+                                int n_src, int geom);
 /* GetDepthandNormal + the two filters on band +- 10 / 5 rows; synchronous.  Rows [row0, row1) of the
  * row-major outputs (acmmp_download / acmmp_device_outputs) are then final. */
 acmmp_status acmmp_band_end(acmmp_ctx *ctx, int do_post);
