@@ -22,6 +22,7 @@
 #include "acmmp.h"
 #include "devbuf.h"
 #include "fusion.h"
+#include "fusion_results.h"
 
 using namespace acmmp;
 
@@ -87,6 +88,81 @@ struct SegScratch {
     Compaction view(unsigned long long out_cap) const { return {flags, counts, offsets, seg_count, words, words + 1, out_cap}; }
 };
 
+// The resident results.  A record owns its buffers and holds its counts, `source`, the cloud it was computed from (what
+// goes_with reads), and `have`; a default-constructed record is the absent result, so releasing one is rec = {}.  A
+// stage's *Out type is its record plus the call's scratch and statistics, built beside the result held: a successful
+// call installs it with f->rec = std::move(out), which takes the record and leaves the rest to end with the call.
+struct VoxelRec {
+    DevBuf<float> pts;                           // 9 floats per voxel
+    DevBuf<int32_t> cnt;                         // points per voxel
+    DevBuf<unsigned long long> slot;             // table slot per voxel (for acmmp_fusion_voxel_clean)
+    unsigned long long total = 0;                // voxels held
+    VoxGrid grid = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // origin and size
+    Res source = R_SCENE;
+    bool have = false;
+};
+struct CleanRec {
+    DevBuf<float> pts;                           // 9 floats per kept voxel
+    DevBuf<int32_t> cnt;                         // points per kept voxel
+    DevBuf<long long> comp;                      // component id per kept voxel
+    DevBuf<unsigned long long> vox;              // voxel index per kept voxel
+    DevBuf<unsigned long long> lab;              // per voxel of the voxel result: label, ~0 = unsupported
+    DevBuf<uint32_t> mask;                       // per voxel: its neighbours, one bit each
+    DevBuf<long long> table;                     // roots, then voxels, then points, comps of each
+    unsigned long long kept = 0, comps = 0;      // kept voxels, components
+    Res source = R_VOXELS;
+    bool have = false;
+};
+struct VisRec {
+    DevBuf<float> pts;                           // 9 floats per kept entry
+    DevBuf<int32_t> cnt;                         // points per kept entry
+    DevBuf<int32_t> kept_tal;                    // 3 per kept entry
+    DevBuf<int32_t> tal;                         // 3 per entry of the source
+    DevBuf<unsigned long long> vox;              // voxel index per kept entry
+    unsigned long long kept = 0, entries = 0;    // kept entries, entries of the source
+    Res source = R_NONE;
+    bool have = false;
+};
+struct MeshRec {
+    DevBuf<float> verts;                         // 9 floats per vertex
+    DevBuf<int32_t> faces;                       // 3 per triangle
+    DevBuf<unsigned long long> skey;             // packed cell per sample
+    DevBuf<int32_t> tsdf;                        // (S, n) per sample
+    DevBuf<long long> sent;                      // remembered entry per sample, -1 = none
+    unsigned long long nv = 0, nf = 0, ns = 0;   // vertices, triangles, samples
+    Res source = R_NONE;                         // stays R_NONE for a mesh that acmmp_fusion_set_mesh installed
+    bool have = false;
+};
+struct RenderRec {
+    DevBuf<float> depth, normal, colour;         // 1, 3 and 3 floats per pixel
+    DevBuf<int32_t> face;                        // the winner per pixel, -1 = none
+    int W = 0, H = 0;
+    Res source = R_MESH;
+    bool have = false;
+};
+struct RefRec {
+    DevBuf<float> pts;                           // 3 floats per point
+    unsigned long long n = 0;
+    bool have = false;
+};
+// A distance result, and a surface result: `source` is the data cloud, and the query cloud.
+struct DistRec {
+    DevBuf<float> d2;                            // per query
+    DevBuf<int32_t> nn;                          // per query: the nearest target or face, -1 = none
+    unsigned long long n = 0;                    // queries
+    Res source = R_NONE;
+    bool have = false;
+};
+// The records of the last successful align call of either kind, on the host: per iteration ACMMP_ALIGN_RECORD_WORDS or
+// ACMMP_ALIGN_PLANE_RECORD_WORDS words, the 12 doubles of M_k, the shift.
+struct AlignRec {
+    std::vector<int64_t> words;
+    std::vector<double> M, shift;
+    bool plane = false;                          // it was the point-to-plane call
+    Res source = R_NONE;
+    bool have = false;
+};
+
 }  // namespace
 
 struct acmmp_fusion {
@@ -115,98 +191,35 @@ struct acmmp_fusion {
     DevBuf<unsigned long long> d_running;        // running scene offset of a scene pass
     PinnedBuf<int> h_count;                      // the one word the host reads per view
     bool s_have = false;                         // a run_scene has succeeded
-    // voxel-grid reduction of the scene result (acmmp_fusion_voxelize): its resident result ...
-    DevBuf<float> v_pts;                         // 9 floats per voxel
-    DevBuf<int32_t> v_cnt;                       // points per voxel
-    DevBuf<unsigned long long> v_slot;           // table slot per voxel (for acmmp_fusion_voxel_clean)
-    unsigned long long v_total = 0;              // voxels held
-    bool v_have = false;                         // a voxelize has succeeded on this scene result
-    bool v_tab_live = false;                     // v_tab is the table of the voxel result held (else scratch)
-    long long v_force_slots = 0;                 // test hook: table size of the next run, 0 = automatic
-    long long v_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful run
-    VoxGrid v_grid = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // origin and size of the voxel result held
-    // ... and its scratch, kept between runs and dropped with the scene result it was sized for
-    VoxTableBuf v_tab, v_tab_spare;              // v_tab_spare: filled by a voxelize while v_tab belongs to a result
-    SegScratch seg;                              // of voxelize's compaction and of every later stage's
-    DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the 3 minima (32-bit each, in 2 words)
-    // cleaning of the voxel result (acmmp_fusion_voxel_clean): its resident result
-    DevBuf<float> c_pts;                         // 9 floats per kept voxel
-    DevBuf<int32_t> c_cnt;                       // points per kept voxel
-    DevBuf<long long> c_comp;                    // component id per kept voxel
-    DevBuf<unsigned long long> c_vox;            // voxel index per kept voxel
-    DevBuf<unsigned long long> c_lab;            // per voxel of the voxel result: label, ~0 = unsupported
-    DevBuf<uint32_t> c_mask;                     // per voxel: its neighbours, one bit each
-    DevBuf<long long> c_table;                   // roots, then voxels, then points, c_comps of each
-    unsigned long long c_total = 0, c_comps = 0; // kept voxels, components
-    bool c_have = false;                         // a clean has succeeded on this voxel result
-    DevBuf<unsigned long long> c_words;          // kCleanWords device words
-    // visibility check of the voxel or clean result (acmmp_fusion_voxel_visibility): its resident result
-    DevBuf<float> vis_pts;                       // 9 floats per kept entry
-    DevBuf<int32_t> vis_cnt;                     // points per kept entry
-    DevBuf<int32_t> vis_kept_tal;                // 3 per kept entry
-    DevBuf<int32_t> vis_tal;                     // 3 per entry of the source
-    DevBuf<unsigned long long> vis_vox;          // voxel index per kept entry
-    unsigned long long vis_total = 0, vis_entries = 0;   // kept entries, entries of the source
-    int vis_source = 0;                          // ACMMP_VIS_FROM_*
-    bool vis_have = false;                       // a visibility call has succeeded on this source
-    DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
-    DevBuf<unsigned long long> vis_words;        // kVisWords device words
-    // surface mesh of the voxel, clean or visible result (acmmp_fusion_voxel_mesh): its resident result
-    DevBuf<float> m_verts;                       // 9 floats per vertex
-    DevBuf<int32_t> m_faces;                     // 3 per triangle
-    DevBuf<unsigned long long> m_skey;           // packed cell per sample
-    DevBuf<int32_t> m_tsdf;                      // (S, n) per sample
-    DevBuf<long long> m_sent;                    // remembered entry per sample, -1 = none
-    unsigned long long m_nv = 0, m_nf = 0, m_ns = 0;   // vertices, triangles, samples
-    int m_source = 0;                            // ACMMP_MESH_FROM_*
-    bool m_have = false;                         // a mesh call has succeeded on this source
-    long long m_force_slots = 0;                 // test hook: sample table size of the next call, 0 = automatic
-    long long m_stats[4] = {0, 0, 0, 0};         // slots, occupied, max_probe, wrapped of the last successful call
-    DevBuf<unsigned long long> m_words;          // kMeshWords device words
-    // the mesh result rendered into one camera (acmmp_fusion_mesh_render): its resident result
-    DevBuf<float> r_depth, r_normal, r_colour;   // 1, 3 and 3 floats per pixel
-    DevBuf<int32_t> r_face;                      // the winner per pixel, -1 = none
-    int r_W = 0, r_H = 0;
-    bool r_have = false;                         // a render has succeeded on this mesh result
-    long long r_small_max = 0;                   // test hook: the small / large threshold, 0 = kRenderSmallMax
-    long long r_plan[3] = {0, 0, 0};             // small faces, large faces, candidates of the last successful render
-    DevBuf<unsigned long long> r_words;          // kRenderWords device words
-    // nearest-neighbour distances (acmmp_fusion_cloud_distance): the reference cloud ...
-    DevBuf<float> ref_pts;                       // 3 floats per point
-    unsigned long long ref_n = 0;
-    bool ref_have = false;                       // a set_reference_cloud has succeeded
-    // ... and the resident result
-    DevBuf<float> dist_d2;                       // per query
-    DevBuf<int32_t> dist_nn;                     // per query, -1 = none
-    unsigned long long dist_n = 0;               // queries
-    int dist_source = 0;                         // ACMMP_DIST_FROM_*
-    bool dist_have = false;                      // a distance call has succeeded on this source and reference cloud
-    float dist_force_cell = 0.0f;                // test hook: the cell of the next calls, 0 = automatic
-    float dist_cell = 0.0f;                      // the cell of the last successful call ...
-    long long dist_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
-    DevBuf<unsigned long long> dist_words;       // kDistWords device words
-    // point-to-triangle distances to the mesh result (acmmp_fusion_surface_distance): the resident result
-    DevBuf<float> surf_d2;                       // per query
-    DevBuf<int32_t> surf_nn;                     // per query: the nearest face, -1 = none
-    unsigned long long surf_n = 0;               // queries
-    int surf_query = 0;                          // ACMMP_SURF_FROM_*
-    bool surf_have = false;                      // a surface call has succeeded on this mesh and query cloud
-    long long surf_small_max = 0;                // test hook: the small / large threshold, 0 = kSurfSmallMax
-    long long surf_plan[4] = {0, 0, 0, 0};       // small faces, large faces, registrations, skipped of the last successful call
-    float surf_force_cell = 0.0f;                // test hook: the cell of the next calls' face grid, 0 = automatic
-    float surf_cell = 0.0f;                      // the cell of the last successful call ...
-    long long surf_stats[3] = {0, 0, 0};         // ... its occupied cells, longest list, largest ring
-    DevBuf<unsigned long long> surf_words;       // kSurfWords device words
-    // the transform of the data cloud (acmmp_fusion_set_cloud_transform) ...
+    // the resident results, one record each (absent when default-constructed); invalidate() knows which goes with which
+    VoxelRec voxels;                             // acmmp_fusion_voxelize
+    CleanRec clean;                              // acmmp_fusion_voxel_clean
+    VisRec visible;                              // acmmp_fusion_voxel_visibility
+    MeshRec mesh;                                // acmmp_fusion_voxel_mesh, acmmp_fusion_set_mesh
+    RenderRec render;                            // acmmp_fusion_mesh_render
+    RefRec ref;                                  // acmmp_fusion_set_reference_cloud
+    DistRec dist, surf;                          // acmmp_fusion_cloud_distance, acmmp_fusion_surface_distance
+    AlignRec align;                              // acmmp_fusion_cloud_align, acmmp_fusion_cloud_align_plane
+    // the transform of the data cloud (acmmp_fusion_set_cloud_transform)
     bool xf_set = false;
     double xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    // ... and the records of the last successful acmmp_fusion_cloud_align or acmmp_fusion_cloud_align_plane, on the
-    // host: per iteration ACMMP_ALIGN_RECORD_WORDS or ACMMP_ALIGN_PLANE_RECORD_WORDS words, the 12 doubles of M_k, the shift
-    std::vector<int64_t> align_words;
-    std::vector<double> align_M, align_shift;
-    int align_source = 0;                        // ACMMP_DIST_FROM_*
-    bool align_have = false;                     // an align call has succeeded on this source and reference cloud
-    bool align_plane = false;                    // ... and it was the point-to-plane call
+    // what outlives the results: the test hooks' knobs (0 = automatic) ...
+    long long v_force_slots = 0, m_force_slots = 0;   // table size of the next voxelize / mesh call
+    long long r_small_max = 0, surf_small_max = 0;    // the small / large threshold of a render / surface call
+    float dist_force_cell = 0.0f, surf_force_cell = 0.0f;   // the cell of the next distance and align / surface calls
+    // ... and what they report of the last successful call
+    long long v_stats[4] = {0, 0, 0, 0}, m_stats[4] = {0, 0, 0, 0};   // slots, occupied, max_probe, wrapped
+    long long r_plan[3] = {0, 0, 0};             // small faces, large faces, candidates
+    long long surf_plan[4] = {0, 0, 0, 0};       // small faces, large faces, registrations, skipped
+    float dist_cell = 0.0f, surf_cell = 0.0f;    // the cell ...
+    long long dist_stats[3] = {0, 0, 0}, surf_stats[3] = {0, 0, 0};   // ... its occupied cells, longest list, largest ring
+    // the scratch, kept between calls; the tables and seg are dropped with the scene result they were sized for
+    VoxTableBuf v_tab, v_tab_spare;              // v_tab_spare: filled by a voxelize while v_tab belongs to a result
+    bool v_tab_live = false;                     // v_tab is the table of the voxel result held (else scratch)
+    SegScratch seg;                              // of voxelize's compaction and of every later stage's
+    DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
+    DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the 3 minima (32-bit each, in 2 words)
+    DevBuf<unsigned long long> c_words, vis_words, m_words, r_words, dist_words, surf_words;   // k*Words device words each
     std::string err;
 };
 
@@ -361,92 +374,111 @@ acmmp_status acmmp_fusion_run(acmmp_fusion* f, int ref, int n_src, const int* sr
 
 namespace {
 
-void voxel_scratch_release(acmmp_fusion* f) {
-    f->v_tab = VoxTableBuf();
-    f->v_tab_spare = VoxTableBuf();
-    f->v_tab_live = false;
-    f->seg = SegScratch();
+// `what` has been replaced or discarded: every held result that goes with it (goes_with, fusion_results.h) is released,
+// and in turn what goes with that one.  The one place where results are released: an entry point installs its record
+// and calls this.  The scratch sized for a scene goes with the scene.
+void invalidate(acmmp_fusion* f, Res what) {
+    const auto drop = [&](auto& rec, Res r) {
+        if (!rec.have || !goes_with(r, rec.source, what)) return;
+        rec = {};
+        invalidate(f, r);
+    };
+    drop(f->voxels, R_VOXELS);
+    drop(f->clean, R_CLEAN);
+    drop(f->visible, R_VISIBLE);
+    drop(f->mesh, R_MESH);
+    drop(f->render, R_RENDER);
+    drop(f->dist, R_DIST);
+    drop(f->surf, R_SURF);
+    drop(f->align, R_ALIGN);
+    if (what == R_SCENE) {
+        f->v_tab = VoxTableBuf();
+        f->v_tab_spare = VoxTableBuf();
+        f->v_tab_live = false;
+        f->seg = SegScratch();
+    }
 }
 
-// m_source of a mesh that acmmp_fusion_set_mesh installed: no result is its source.
-constexpr int kMeshNoSource = -1;
+// A resident cloud as a stage reads it: 9 floats per point (3 for the reference cloud), and where the cloud has them
+// the points per entry and the entries' voxel indices.
+struct Cloud {
+    bool have = false;
+    const float* pts = nullptr;
+    int stride = 9;
+    unsigned long long n = 0;
+    const int32_t* cnt = nullptr;
+    const unsigned long long* vox = nullptr;
+    DistCloud dist() const { return DistCloud{pts, stride, n}; }
+};
 
-void distance_release(acmmp_fusion* f) {
-    f->dist_d2.reset(); f->dist_nn.reset();
-    f->dist_n = 0;
-    f->dist_have = false;
+Cloud cloud(const acmmp_fusion* f, Res id) {
+    switch (id) {
+        case R_SCENE: return {f->s_have, f->scene.pts, 9, f->s_total};
+        case R_VOXELS: return {f->voxels.have, f->voxels.pts, 9, f->voxels.total, f->voxels.cnt};
+        case R_CLEAN: return {f->clean.have, f->clean.pts, 9, f->clean.kept, f->clean.cnt, f->clean.vox};
+        case R_VISIBLE: return {f->visible.have, f->visible.pts, 9, f->visible.kept, f->visible.cnt, f->visible.vox};
+        case R_MESH: return {f->mesh.have, f->mesh.verts, 9, f->mesh.nv};
+        case R_REFERENCE: return {f->ref.have, f->ref.pts, 3, f->ref.n};
+        default: return {};
+    }
 }
 
-void align_release(acmmp_fusion* f) {
-    f->align_words.clear(); f->align_M.clear(); f->align_shift.clear();
-    f->align_have = false;
+// After a failed *_run: the device's error cleared and the stream drained, the run's message kept.
+acmmp_status run_failed(acmmp_fusion* f, acmmp_status st) {
+    const std::string why = f->err;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(f->stream);
+    f->err = why;
+    return st;
 }
 
-void surface_release(acmmp_fusion* f) {
-    f->surf_d2.reset(); f->surf_nn.reset();
-    f->surf_n = 0;
-    f->surf_have = false;
+bool finite32(float x) {
+    uint32_t b;
+    std::memcpy(&b, &x, 4);
+    return (b & 0x7f800000u) != 0x7f800000u;
 }
 
-// The surface result's queries were the reference cloud, which has been replaced or is read in another frame now.
-void surface_reference_gone(acmmp_fusion* f) {
-    if (f->surf_have && f->surf_query == ACMMP_SURF_FROM_REFERENCE) surface_release(f);
+constexpr int kVisMaxList = 4096;
+
+acmmp_status check_view_list(acmmp_fusion* f, int n_list, const int* views) {
+    if (n_list < 1 || n_list > kVisMaxList || !views)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the view list must hold 1 to 4096 views");
+    for (int j = 0; j < n_list; ++j) {
+        if (views[j] < 0 || views[j] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
+        if (!f->views[views[j]].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for every view listed");
+    }
+    return ACMMP_OK;
 }
 
-// The data cloud `source` (ACMMP_DIST_FROM_*) has been replaced or discarded: a distance result measured on it goes,
-// and so do the records of an align call on it.  The surface result goes with the mesh and with its query cloud
-// (ACMMP_SURF_FROM_* of a data cloud is its ACMMP_DIST_FROM_*).
-void distance_source_gone(acmmp_fusion* f, int source) {
-    if (f->dist_have && f->dist_source == source) distance_release(f);
-    if (f->align_have && f->align_source == source) align_release(f);
-    if (f->surf_have && (source == ACMMP_DIST_FROM_MESH || f->surf_query == source)) surface_release(f);
+acmmp_status check_tau_list(acmmp_fusion* f, float max_dist, int n_tau, const float* tau) {
+    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
+    if (n_tau < 0 || n_tau > ACMMP_DIST_MAX_TAU || (n_tau > 0 && !tau))
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "n_tau must be 0 to 8");
+    for (int i = 0; i < n_tau; ++i)
+        if (!finite32(tau[i]) || !(tau[i] >= 0.0f) || tau[i] > max_dist)
+            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every tau must be finite and in [0, max_dist]");
+    return ACMMP_OK;
 }
 
-void render_release(acmmp_fusion* f) {
-    f->r_depth.reset(); f->r_normal.reset(); f->r_colour.reset(); f->r_face.reset();
-    f->r_W = f->r_H = 0;
-    f->r_have = false;
+// Copies [first, first + n) of `count`-element device arrays to the host ones that are not NULL.
+template <typename T>
+hipError_t read_range(T* dst, const T* src, size_t first, size_t n, size_t per = 1) {
+    return dst ? hipMemcpy(dst, src + per * first, sizeof(T) * per * n, hipMemcpyDeviceToHost) : hipSuccess;
 }
 
-// The render result goes with the mesh result it shows.
-void mesh_release(acmmp_fusion* f) {
-    render_release(f);
-    f->m_verts.reset(); f->m_faces.reset(); f->m_skey.reset(); f->m_tsdf.reset(); f->m_sent.reset();
-    f->m_nv = f->m_nf = f->m_ns = 0;
-    f->m_have = false;
-    distance_source_gone(f, ACMMP_DIST_FROM_MESH);
+bool bad_range(int64_t first, int64_t n, unsigned long long total) {
+    return static_cast<unsigned long long>(first) > total || static_cast<unsigned long long>(n) > total - first;
 }
 
-// The clean result and the visible result go with a mesh result built from them.
-void clean_release(acmmp_fusion* f) {
-    f->c_pts.reset(); f->c_cnt.reset(); f->c_comp.reset(); f->c_vox.reset(); f->c_lab.reset(); f->c_mask.reset();
-    f->c_table.reset();
-    f->c_total = f->c_comps = 0;
-    f->c_have = false;
-    if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
-    distance_source_gone(f, ACMMP_DIST_FROM_CLEAN);
-}
-
-void visibility_release(acmmp_fusion* f) {
-    f->vis_pts.reset(); f->vis_cnt.reset(); f->vis_kept_tal.reset(); f->vis_tal.reset(); f->vis_vox.reset();
-    f->vis_total = f->vis_entries = 0;
-    f->vis_have = false;
-    if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);
-    distance_source_gone(f, ACMMP_DIST_FROM_VISIBLE);
-}
-
-// A new scene result is in place: the voxel result, the clean result and the visible result described the previous
-// one and go, with the scratch sized for that scene.
-void scene_replaced(acmmp_fusion* f) {
-    f->v_pts.reset(); f->v_cnt.reset(); f->v_slot.reset();
-    f->v_total = 0;
-    f->v_have = false;
-    clean_release(f);
-    visibility_release(f);
-    if (f->m_source != kMeshNoSource) mesh_release(f);
-    distance_source_gone(f, ACMMP_DIST_FROM_SCENE);
-    distance_source_gone(f, ACMMP_DIST_FROM_VOXELS);
-    voxel_scratch_release(f);
+// A range reader: [first, first + n) checked against the `total` elements the record holds (`beyond` is the refusal's
+// message), then, unless the range is empty, reads(first, n) on the object's device.  f is not NULL.
+template <class Reads>
+acmmp_status read_result(acmmp_fusion* f, int64_t first, int64_t n, unsigned long long total, const char* beyond, Reads reads) {
+    if (first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
+    if (bad_range(first, n, total)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, beyond);
+    if (n == 0) return ACMMP_OK;
+    F_HIP(f, hipSetDevice(f->device));
+    return reads(static_cast<size_t>(first), static_cast<size_t>(n));
 }
 
 // b := arrays of at least `need` points (geometric growth) holding b's first `live` points.  b is unchanged
@@ -573,7 +605,7 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
     std::vector<int> view_counts(n_refs, 0);
     unsigned long long total = 0;
     const acmmp_status st = scene_views(f, n_refs, refs, n_src, unique, out, view_counts, total);
-    if (st != ACMMP_OK) {
+    if (st != ACMMP_OK) {                               // (not run_failed: the masks go back between the two waits)
         const std::string why = f->err;
         (void)hipStreamSynchronize(s);
         for (size_t v = 0; v < saved.size(); ++v)
@@ -587,7 +619,7 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
     f->scene = std::move(out);
     f->s_total = total;
     f->s_have = true;
-    scene_replaced(f);
+    invalidate(f, R_SCENE);                           // it described the previous scene, or was sized for it
     if (counts) std::copy(view_counts.begin(), view_counts.end(), counts);
     *n_points = static_cast<int64_t>(total);
     return ACMMP_OK;
@@ -595,17 +627,14 @@ acmmp_status acmmp_fusion_run_scene(acmmp_fusion* f, int n_refs, const int* refs
 
 acmmp_status acmmp_fusion_scene_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* ref_index,
                                        int32_t* pixel, uint32_t* src_mask) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (static_cast<unsigned long long>(first) > f->s_total || static_cast<unsigned long long>(n) > f->s_total - first)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the scene result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    if (points) F_HIP(f, hipMemcpy(points, f->scene.pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
-    if (ref_index) F_HIP(f, hipMemcpy(ref_index, f->scene.ref + a, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (pixel) F_HIP(f, hipMemcpy(pixel, f->scene.pix + a, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (src_mask) F_HIP(f, hipMemcpy(src_mask, f->scene.mask + a, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->s_total, "range beyond the scene result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(points, f->scene.pts, a, m, 9));
+        F_HIP(f, read_range<int>(ref_index, f->scene.ref, a, m));
+        F_HIP(f, read_range<int>(pixel, f->scene.pix, a, m));
+        F_HIP(f, read_range<uint32_t>(src_mask, f->scene.mask, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_set_scene(acmmp_fusion* f, int64_t n, const float* points, const int32_t* ref_index,
@@ -642,7 +671,7 @@ acmmp_status acmmp_fusion_set_scene(acmmp_fusion* f, int64_t n, const float* poi
     f->scene = std::move(out);
     f->s_total = static_cast<unsigned long long>(n);
     f->s_have = true;
-    scene_replaced(f);
+    invalidate(f, R_SCENE);                           // it described the previous scene, or was sized for it
     return ACMMP_OK;
 }
 
@@ -681,18 +710,9 @@ unsigned long long voxel_segment_points() {
     return (v >= 256 && v % 256 == 0 && static_cast<unsigned long long>(v) <= dflt) ? static_cast<unsigned long long>(v) : dflt;
 }
 
-bool finite32(float x) {
-    uint32_t b;
-    std::memcpy(&b, &x, 4);
-    return (b & 0x7f800000u) != 0x7f800000u;
-}
-
-// The new result of a voxel run, swapped in only when the whole run succeeded.
-struct VoxelOut {
-    DevBuf<float> pts;
-    DevBuf<int32_t> cnt;
+// The new result of a voxel run.
+struct VoxelOut : VoxelRec {
     DevBuf<unsigned long long> sums;         // scratch: 9 int64 per kept voxel
-    DevBuf<unsigned long long> vslot;        // scratch: table slot per kept voxel
 };
 
 // fn(i0, n) over the items [0, N) in segments of voxel_segment_points(), in ascending order; the first error ends it.
@@ -768,17 +788,17 @@ acmmp_status voxel_run(acmmp_fusion* f, VoxGrid& g, bool find_origin, int min_po
     F_HIP(f, alloc(out.pts, 9 * static_cast<size_t>(kept)));
     F_HIP(f, alloc(out.cnt, static_cast<size_t>(kept)));
     F_HIP(f, alloc(out.sums, 9 * static_cast<size_t>(kept)));
-    F_HIP(f, alloc(out.vslot, static_cast<size_t>(kept)));
+    F_HIP(f, alloc(out.slot, static_cast<size_t>(kept)));
     if (kept == 0) return ACMMP_OK;
     // compaction in order of first appearance, the sums, the means
     unsigned long long end[2] = {0, 0};                                  // error word, voxels compacted
     F_HIP(f, hipMemsetAsync(out.sums, 0, sizeof(unsigned long long) * 9 * kept, s));
-    F_HIP(f, hipMemsetAsync(out.vslot, 0xff, sizeof(unsigned long long) * kept, s));
+    F_HIP(f, hipMemsetAsync(out.slot, 0xff, sizeof(unsigned long long) * kept, s));
     F_HIP(f, compact_pass(f, N, kept, &end[1], [&](unsigned long long i0, int n, Compaction c) {
-        return launch_voxel_compact(f->scene.pts, i0, n, g, t, min_points, c, out.vslot, st, s);
+        return launch_voxel_compact(f->scene.pts, i0, n, g, t, min_points, c, out.slot, st, s);
     }));
     F_HIP(f, for_segments(N, [&](unsigned long long i0, int n) { return launch_voxel_accumulate(f->scene.pts, i0, n, g, t, out.sums, st, s); }));
-    F_HIP(f, launch_voxel_finalise(kept, out.vslot, t, out.sums, g, out.pts, out.cnt, s));
+    F_HIP(f, launch_voxel_finalise(kept, out.slot, t, out.sums, g, out.pts, out.cnt, s));
     F_HIP(f, hipMemcpyAsync(&end[0], st + kVoxErr, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
     if (end[0] || end[1] != kept)
@@ -827,11 +847,8 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     if (N > 0) {
         const acmmp_status st = voxel_run(f, g, origin == nullptr, min_points, slots, tab, out, words);
         if (st != ACMMP_OK) {
-            const std::string why = f->err;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(f->stream);
-            from = std::move(tab);
-            f->err = why;
+            (void)run_failed(f, st);
+            from = std::move(tab);                    // after the stream has drained
             return st;
         }
     }
@@ -839,16 +856,11 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
     if (f->v_tab_live) f->v_tab_spare = std::move(f->v_tab);
     f->v_tab = std::move(tab);
     f->v_tab_live = N > 0;
-    f->v_pts = std::move(out.pts);
-    f->v_cnt = std::move(out.cnt);
-    f->v_slot = std::move(out.vslot);
-    f->v_total = words[kVoxKept];
-    f->v_have = true;
-    clean_release(f);                                 // it described the previous voxel result
-    visibility_release(f);                            // and so did this one, from either source
-    if (f->m_source != kMeshNoSource) mesh_release(f);   // and this one, from any source
-    distance_source_gone(f, ACMMP_DIST_FROM_VOXELS);  // and a distance result measured on it
-    f->v_grid = g;
+    out.total = words[kVoxKept];
+    out.grid = g;
+    out.have = true;
+    f->voxels = std::move(out);
+    invalidate(f, R_VOXELS);                          // whatever described the previous voxel result
     f->v_stats[0] = static_cast<long long>(slots);
     f->v_stats[1] = static_cast<long long>(words[kVoxOccupied]);
     f->v_stats[2] = static_cast<long long>(words[kVoxMaxProbe]);
@@ -861,15 +873,12 @@ acmmp_status acmmp_fusion_voxelize(acmmp_fusion* f, float voxel_size, const floa
 }
 
 acmmp_status acmmp_fusion_voxel_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (static_cast<unsigned long long>(first) > f->v_total || static_cast<unsigned long long>(n) > f->v_total - first)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the voxel result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    if (points) F_HIP(f, hipMemcpy(points, f->v_pts + 9 * a, sizeof(float) * 9 * m, hipMemcpyDeviceToHost));
-    if (counts) F_HIP(f, hipMemcpy(counts, f->v_cnt + a, sizeof(int32_t) * m, hipMemcpyDeviceToHost));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->voxels.total, "range beyond the voxel result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(points, f->voxels.pts, a, m, 9));
+        F_HIP(f, read_range<int32_t>(counts, f->voxels.cnt, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_voxel_table(acmmp_fusion* f, int64_t force_slots, int64_t* slots, int64_t* occupied,
@@ -889,21 +898,16 @@ acmmp_status acmmp_fusion_voxel_table(acmmp_fusion* f, int64_t force_slots, int6
 
 namespace {
 
-// The new result of a clean run, swapped in only when the whole run succeeded.
-struct CleanOut {
-    DevBuf<float> pts;
-    DevBuf<int32_t> cnt;
-    DevBuf<long long> comp, table;
-    DevBuf<unsigned long long> lab, vox;
-    DevBuf<uint32_t> mask;
+// The new result of a clean run.
+struct CleanOut : CleanRec {
     DevBuf<unsigned long long> scratch;      // per voxel: component voxels, points, dense id
-    unsigned long long kept = 0, comps = 0, comps_kept = 0, unsupported = 0, rounds = 0;
+    unsigned long long comps_kept = 0, unsupported = 0, rounds = 0;
 };
 
 acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, unsigned long long min_voxels,
                        unsigned long long min_points, CleanOut& out) {
     hipStream_t s = f->stream;
-    const unsigned long long nv = f->v_total;
+    const unsigned long long nv = f->voxels.total;
     const size_t n = static_cast<size_t>(nv);
     if (!f->c_words) F_HIP(f, alloc(f->c_words, kCleanWords));
     F_HIP(f, segment_reserve(f, nv));
@@ -916,20 +920,20 @@ acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, un
     unsigned long long h[kCleanWords] = {0};
     F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kCleanWords, s));
     F_HIP(f, hipMemsetAsync(out.scratch, 0, sizeof(unsigned long long) * 2 * n, s));
-    F_HIP(f, launch_clean_support(nv, f->v_slot, t, connectivity, min_neighbours, out.mask, out.lab, w, s));
+    F_HIP(f, launch_clean_support(nv, f->voxels.slot, t, connectivity, min_neighbours, out.mask, out.lab, w, s));
     // Rounds until one lowers no label.  After k rounds a label is at most the smallest index within k edges, so
     // nv rounds settle every label and one more sees no change: a run past that bound has gone wrong.
     for (;;) {
         if (out.rounds > nv + 1) return ffail(f, ACMMP_ERR_HIP, "voxel clean: the labelling did not settle in nv + 2 rounds");
         ++out.rounds;
         F_HIP(f, hipMemsetAsync(w + kCleanChanged, 0, sizeof(unsigned long long), s));
-        F_HIP(f, launch_clean_round(nv, f->v_slot, t, out.mask, out.lab, w, s));
+        F_HIP(f, launch_clean_round(nv, f->voxels.slot, t, out.mask, out.lab, w, s));
         F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, s));
         F_HIP(f, hipStreamSynchronize(s));
         if (h[kCleanErr]) return ffail(f, ACMMP_ERR_HIP, "voxel clean: lookup failed (flags " + std::to_string(h[kCleanErr]) + ")");
         if (!h[kCleanChanged]) break;
     }
-    F_HIP(f, launch_clean_sizes(nv, out.lab, f->v_cnt, c, w, s));
+    F_HIP(f, launch_clean_sizes(nv, out.lab, f->voxels.cnt, c, w, s));
     F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kCleanWords, hipMemcpyDeviceToHost, s));
     F_HIP(f, hipStreamSynchronize(s));
     out.unsupported = h[kCleanUnsupported];
@@ -949,23 +953,13 @@ acmmp_status clean_run(acmmp_fusion* f, int connectivity, int min_neighbours, un
         return launch_clean_compact_roots(nv, i0, m, out.lab, c, k, out.table, out.table + nc, out.table + 2 * nc, s);
     }));
     F_HIP(f, compact_pass(f, nv, out.kept, &done[1], [&](unsigned long long i0, int m, Compaction k) {
-        return launch_clean_compact_kept(nv, i0, m, out.lab, c, k, f->v_pts, f->v_cnt, out.pts, out.cnt, out.comp, out.vox, s);
+        return launch_clean_compact_kept(nv, i0, m, out.lab, c, k, f->voxels.pts, f->voxels.cnt, out.pts, out.cnt, out.comp, out.vox, s);
     }));
     F_HIP(f, hipStreamSynchronize(s));
     if (done[0] != out.comps || done[1] != out.kept)
         return ffail(f, ACMMP_ERR_HIP, "voxel clean: compacted " + std::to_string(done[0]) + " of " + std::to_string(out.comps) +
                                            " components, " + std::to_string(done[1]) + " of " + std::to_string(out.kept) + " voxels");
     return ACMMP_OK;
-}
-
-// Copies [first, first + n) of `count`-element device arrays to the host ones that are not NULL.
-template <typename T>
-hipError_t read_range(T* dst, const T* src, size_t first, size_t n, size_t per = 1) {
-    return dst ? hipMemcpy(dst, src + per * first, sizeof(T) * per * n, hipMemcpyDeviceToHost) : hipSuccess;
-}
-
-bool bad_range(int64_t first, int64_t n, unsigned long long total) {
-    return static_cast<unsigned long long>(first) > total || static_cast<unsigned long long>(n) > total - first;
 }
 
 }  // namespace
@@ -981,33 +975,17 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
     if (min_neighbours < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_neighbours must not be negative");
     if (min_component_voxels < 1 || min_component_points < 1)
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "component thresholds must be at least 1");
-    if (!f->v_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no voxel result: acmmp_fusion_voxelize first");
+    if (!f->voxels.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no voxel result: acmmp_fusion_voxelize first");
     F_HIP(f, hipSetDevice(f->device));
     CleanOut out;
-    if (f->v_total > 0) {
+    if (f->voxels.total > 0) {
         const acmmp_status st = clean_run(f, connectivity, min_neighbours, static_cast<unsigned long long>(min_component_voxels),
                                           static_cast<unsigned long long>(min_component_points), out);
-        if (st != ACMMP_OK) {
-            const std::string why = f->err;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(f->stream);
-            f->err = why;
-            return st;
-        }
+        if (st != ACMMP_OK) return run_failed(f, st);
     }
-    f->c_pts = std::move(out.pts);
-    f->c_cnt = std::move(out.cnt);
-    f->c_comp = std::move(out.comp);
-    f->c_vox = std::move(out.vox);
-    f->c_lab = std::move(out.lab);
-    f->c_mask = std::move(out.mask);
-    f->c_table = std::move(out.table);
-    f->c_total = out.kept;
-    f->c_comps = out.comps;
-    f->c_have = true;
-    if (f->vis_have && f->vis_source == ACMMP_VIS_FROM_CLEAN) visibility_release(f);   // its source is replaced
-    if (f->m_have && f->m_source == ACMMP_MESH_FROM_CLEAN) mesh_release(f);
-    distance_source_gone(f, ACMMP_DIST_FROM_CLEAN);
+    out.have = true;
+    f->clean = std::move(out);
+    invalidate(f, R_CLEAN);                           // whatever was computed from the previous clean result
     if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
     if (n_components) *n_components = static_cast<int64_t>(out.comps);
     if (n_components_kept) *n_components_kept = static_cast<int64_t>(out.comps_kept);
@@ -1018,43 +996,38 @@ acmmp_status acmmp_fusion_voxel_clean(acmmp_fusion* f, int connectivity, int min
 
 acmmp_status acmmp_fusion_clean_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts,
                                        int64_t* component) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->c_total)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the clean result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    F_HIP(f, read_range<float>(points, f->c_pts, a, m, 9));
-    F_HIP(f, read_range<int32_t>(counts, f->c_cnt, a, m));
-    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(component), f->c_comp, a, m));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->clean.kept, "range beyond the clean result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(points, f->clean.pts, a, m, 9));
+        F_HIP(f, read_range<int32_t>(counts, f->clean.cnt, a, m));
+        F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(component), f->clean.comp, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_voxel_labels(acmmp_fusion* f, int64_t first, int64_t n, int64_t* label, int32_t* support) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->c_have ? f->v_total : 0ull))
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the labelled voxel result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    // the device holds ~0 for an unsupported voxel, which reads as -1, and the neighbours as one bit each
-    F_HIP(f, read_range<unsigned long long>(reinterpret_cast<unsigned long long*>(label), f->c_lab, a, m));
-    F_HIP(f, read_range<uint32_t>(reinterpret_cast<uint32_t*>(support), f->c_mask, a, m));
-    if (support)
-        for (size_t i = 0; i < m; ++i) support[i] = __builtin_popcount(static_cast<uint32_t>(support[i]));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->clean.have ? f->voxels.total : 0ull, "range beyond the labelled voxel result",
+                       [&](size_t a, size_t m) -> acmmp_status {
+        // the device holds ~0 for an unsupported voxel, which reads as -1, and the neighbours as one bit each
+        F_HIP(f, read_range<unsigned long long>(reinterpret_cast<unsigned long long*>(label), f->clean.lab, a, m));
+        F_HIP(f, read_range<uint32_t>(reinterpret_cast<uint32_t*>(support), f->clean.mask, a, m));
+        if (support)
+            for (size_t i = 0; i < m; ++i) support[i] = __builtin_popcount(static_cast<uint32_t>(support[i]));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_component_table(acmmp_fusion* f, int64_t first, int64_t n, int64_t* root, int64_t* voxels,
                                           int64_t* points) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->c_comps)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the component table");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n), nc = static_cast<size_t>(f->c_comps);
-    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(root), f->c_table, a, m));
-    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(voxels), f->c_table + nc, a, m));
-    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(points), f->c_table + 2 * nc, a, m));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->clean.comps, "range beyond the component table", [&](size_t a, size_t m) -> acmmp_status {
+        const size_t nc = static_cast<size_t>(f->clean.comps);
+        F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(root), f->clean.table, a, m));
+        F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(voxels), f->clean.table + nc, a, m));
+        F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(points), f->clean.table + 2 * nc, a, m));
+        return ACMMP_OK;
+    });
 }
 
 }  // extern "C"
@@ -1063,21 +1036,15 @@ acmmp_status acmmp_fusion_component_table(acmmp_fusion* f, int64_t first, int64_
 
 namespace {
 
-constexpr int kVisMaxList = 4096;
-
-// The new result of a visibility run, swapped in only when the whole run succeeded.
-struct VisOut {
-    DevBuf<float> pts;
-    DevBuf<int32_t> cnt, kept_tal, tal;
-    DevBuf<unsigned long long> vox;
-    unsigned long long kept = 0, no_support = 0, conflicting = 0, classes[4] = {0, 0, 0, 0};
+// The new result of a visibility run.
+struct VisOut : VisRec {
+    unsigned long long no_support = 0, conflicting = 0, classes[4] = {0, 0, 0, 0};
 };
 
-acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t* src_cnt,
-                            const unsigned long long* src_vox, unsigned long long N,
-                            int n_list, const int* views, float rel_tol, int radius, int min_support, int max_conflicts,
-                            VisOut& out) {
+acmmp_status visibility_run(acmmp_fusion* f, const Cloud& src, int n_list, const int* views, float rel_tol, int radius,
+                            int min_support, int max_conflicts, VisOut& out) {
     hipStream_t s = f->stream;
+    const unsigned long long N = src.n;
     if (!f->vis_words) F_HIP(f, alloc(f->vis_words, kVisWords));
     if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
     F_HIP(f, segment_reserve(f, N));
@@ -1086,7 +1053,7 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
     unsigned long long h[kVisWords] = {0};
     F_HIP(f, hipMemsetAsync(w, 0, sizeof(unsigned long long) * kVisWords, s));
     F_HIP(f, hipMemcpyAsync(f->vis_list, views, sizeof(int) * n_list, hipMemcpyHostToDevice, s));
-    F_HIP(f, launch_vis_tally(f->model, f->d_cams, f->d_views, f->vis_list, n_list, src_pts, N, rel_tol, radius, out.tal, s));
+    F_HIP(f, launch_vis_tally(f->model, f->d_cams, f->d_views, f->vis_list, n_list, src.pts, N, rel_tol, radius, out.tal, s));
     F_HIP(f, launch_vis_count(N, out.tal, n_list, min_support, max_conflicts, w, s));
     // the first host wait: the kept count, to size the result before anything is written there
     F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kVisWords, hipMemcpyDeviceToHost, s));
@@ -1104,8 +1071,8 @@ acmmp_status visibility_run(acmmp_fusion* f, const float* src_pts, const int32_t
     // the kept entries, compacted in entry order, segment after segment
     unsigned long long done = 0;
     F_HIP(f, compact_pass(f, N, out.kept, &done, [&](unsigned long long i0, int n, Compaction c) {
-        return launch_vis_compact(i0, n, out.tal, min_support, max_conflicts, c, src_pts, src_cnt, out.pts, out.cnt,
-                                  out.kept_tal, src_vox, out.vox, s);
+        return launch_vis_compact(i0, n, out.tal, min_support, max_conflicts, c, src.pts, src.cnt, out.pts, out.cnt,
+                                  out.kept_tal, src.vox, out.vox, s);
     }));
     F_HIP(f, hipStreamSynchronize(s));
     if (done != out.kept)
@@ -1122,49 +1089,29 @@ acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_li
                                            int radius, int min_support, int max_conflicts, int64_t* n_kept,
                                            int64_t* n_unsupported, int64_t* n_conflicting, int64_t class_totals[4]) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    if (source != ACMMP_VIS_FROM_VOXELS && source != ACMMP_VIS_FROM_CLEAN)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be ACMMP_VIS_FROM_VOXELS or ACMMP_VIS_FROM_CLEAN");
-    if (source == ACMMP_VIS_FROM_VOXELS ? !f->v_have : !f->c_have)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, source == ACMMP_VIS_FROM_VOXELS
-                                                        ? "no voxel result: acmmp_fusion_voxelize first"
-                                                        : "no clean result: acmmp_fusion_voxel_clean first");
-    if (n_list < 1 || n_list > kVisMaxList || !views)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the view list must hold 1 to 4096 views");
-    for (int j = 0; j < n_list; ++j) {
-        if (views[j] < 0 || views[j] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
-        if (!f->views[views[j]].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for every view listed");
-    }
+    const Res id = vis_source(source);
+    if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be ACMMP_VIS_FROM_VOXELS or ACMMP_VIS_FROM_CLEAN");
+    const Cloud src = cloud(f, id);
+    if (!src.have)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, id == R_VOXELS ? "no voxel result: acmmp_fusion_voxelize first"
+                                                                   : "no clean result: acmmp_fusion_voxel_clean first");
+    const acmmp_status listed = check_view_list(f, n_list, views);
+    if (listed != ACMMP_OK) return listed;
     if (!finite32(rel_tol) || !(rel_tol >= 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "rel_tol must be finite and >= 0");
     if (radius != 0 && radius != 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "radius must be 0 or 1");
     if (min_support < 0 || max_conflicts < 0)
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_support and max_conflicts must not be negative");
     F_HIP(f, hipSetDevice(f->device));
-    const bool clean = source == ACMMP_VIS_FROM_CLEAN;
-    const unsigned long long N = clean ? f->c_total : f->v_total;
     VisOut out;
-    if (N > 0) {
-        const acmmp_status st = visibility_run(f, clean ? f->c_pts : f->v_pts, clean ? f->c_cnt : f->v_cnt,
-                                               clean ? f->c_vox.get() : nullptr, N, n_list, views, rel_tol, radius,
-                                               min_support, max_conflicts, out);
-        if (st != ACMMP_OK) {
-            const std::string why = f->err;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(f->stream);
-            f->err = why;
-            return st;
-        }
+    if (src.n > 0) {
+        const acmmp_status st = visibility_run(f, src, n_list, views, rel_tol, radius, min_support, max_conflicts, out);
+        if (st != ACMMP_OK) return run_failed(f, st);
     }
-    f->vis_pts = std::move(out.pts);
-    f->vis_cnt = std::move(out.cnt);
-    f->vis_kept_tal = std::move(out.kept_tal);
-    f->vis_tal = std::move(out.tal);
-    f->vis_vox = std::move(out.vox);
-    if (f->m_have && f->m_source == ACMMP_MESH_FROM_VISIBLE) mesh_release(f);          // its source is replaced
-    distance_source_gone(f, ACMMP_DIST_FROM_VISIBLE);
-    f->vis_total = out.kept;
-    f->vis_entries = N;
-    f->vis_source = source;
-    f->vis_have = true;
+    out.entries = src.n;
+    out.source = id;
+    out.have = true;
+    f->visible = std::move(out);
+    invalidate(f, R_VISIBLE);                         // whatever was computed from the previous visible result
     if (n_kept) *n_kept = static_cast<int64_t>(out.kept);
     if (n_unsupported) *n_unsupported = static_cast<int64_t>(out.no_support);
     if (n_conflicting) *n_conflicting = static_cast<int64_t>(out.conflicting);
@@ -1175,24 +1122,21 @@ acmmp_status acmmp_fusion_voxel_visibility(acmmp_fusion* f, int source, int n_li
 
 acmmp_status acmmp_fusion_visible_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* counts,
                                          int32_t* tallies) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->vis_total)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the visible result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    F_HIP(f, read_range<float>(points, f->vis_pts, a, m, 9));
-    F_HIP(f, read_range<int32_t>(counts, f->vis_cnt, a, m));
-    F_HIP(f, read_range<int32_t>(tallies, f->vis_kept_tal, a, m, 3));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->visible.kept, "range beyond the visible result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(points, f->visible.pts, a, m, 9));
+        F_HIP(f, read_range<int32_t>(counts, f->visible.cnt, a, m));
+        F_HIP(f, read_range<int32_t>(tallies, f->visible.kept_tal, a, m, 3));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion* f, int64_t first, int64_t n, int32_t* tallies) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->vis_entries)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the tallied source");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    F_HIP(f, read_range<int32_t>(tallies, f->vis_tal, static_cast<size_t>(first), static_cast<size_t>(n), 3));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->visible.entries, "range beyond the tallied source", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<int32_t>(tallies, f->visible.tal, a, m, 3));
+        return ACMMP_OK;
+    });
 }
 
 }  // extern "C"
@@ -1201,18 +1145,14 @@ acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion* f, int64_t first, int
 
 namespace {
 
-// The sample table of one mesh call (scratch) and the new result, swapped in only when the whole call succeeded.
-struct MeshOut {
+// The new result of a mesh call and the call's sample table (scratch).
+struct MeshOut : MeshRec {
     DevBuf<unsigned long long> keys, rank, ent, sid;       // the table, `slots` of each
     unsigned long long slots = 0;
     DevBuf<unsigned long long> ekey;                       // per entry
     DevBuf<uint8_t> cflag, fbits;                          // per sample
     DevBuf<int32_t> vid;                                   // per sample
-    DevBuf<float> verts;
-    DevBuf<int32_t> faces, tsdf;
-    DevBuf<unsigned long long> skey;
-    DevBuf<long long> sent;
-    unsigned long long nv = 0, nf = 0, ns = 0, valid = 0, cubes = 0, uncoloured = 0;
+    unsigned long long valid = 0, cubes = 0, uncoloured = 0;
     long long stats[4] = {0, 0, 0, 0};
     MeshTable table() const { return {keys, rank, ent, sid, slots, log2_ceil(slots)}; }
     // every slot empty
@@ -1224,10 +1164,10 @@ struct MeshOut {
     }
 };
 
-acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long long* src_vox, unsigned long long ne,
-                      int n_list, const int* views, float trunc, int min_weight, unsigned long long slots, MeshOut& out) {
+acmmp_status mesh_run(acmmp_fusion* f, const Cloud& src, int n_list, const int* views, float trunc, int min_weight,
+                      unsigned long long slots, MeshOut& out) {
     hipStream_t s = f->stream;
-    const unsigned long long pairs = 27ull * ne;
+    const unsigned long long ne = src.n, pairs = 27ull * ne;
     if (!f->m_words) F_HIP(f, alloc(f->m_words, kMeshWords));
     if (!f->vis_list) F_HIP(f, alloc(f->vis_list, kVisMaxList));
     F_HIP(f, segment_reserve(f, pairs));
@@ -1245,7 +1185,7 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
     F_HIP(f, out.table_reset_async(s));
     F_HIP(f, hipMemcpyAsync(f->vis_list, views, sizeof(int) * n_list, hipMemcpyHostToDevice, s));
     // the samples: insert, then the table's counts
-    F_HIP(f, launch_mesh_keys(ne, src_vox, f->v_total, f->v_slot, vt, out.ekey, w, s));
+    F_HIP(f, launch_mesh_keys(ne, src.vox, f->voxels.total, f->voxels.slot, vt, out.ekey, w, s));
     F_HIP(f, for_segments(pairs, [&](unsigned long long p0, int n) { return launch_mesh_insert(p0, n, out.ekey, m, w, s); }));
     F_HIP(f, launch_mesh_stats(m, w, s));
     // the first host wait: the sample count, to size the per-sample arrays
@@ -1274,7 +1214,7 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
         return launch_mesh_number(p0, n, out.ekey, m, c, smp, w, s);
     }));
     // the distances, the cubes, the pairs that emit faces
-    F_HIP(f, launch_mesh_tsdf(f->model, f->d_cams, f->d_views, f->vis_list, n_list, smp, f->v_grid, trunc, s));
+    F_HIP(f, launch_mesh_tsdf(f->model, f->d_cams, f->d_views, f->vis_list, n_list, smp, f->voxels.grid, trunc, s));
     F_HIP(f, launch_mesh_cubes(smp, m, min_weight, out.cflag, out.fbits, w, s));
     // the second host wait: the vertex and face counts, to size the result
     F_HIP(f, hipMemcpyAsync(h, w, sizeof(unsigned long long) * kMeshWords, hipMemcpyDeviceToHost, s));
@@ -1293,7 +1233,7 @@ acmmp_status mesh_run(acmmp_fusion* f, const float* src_pts, const unsigned long
     F_HIP(f, alloc(out.faces, 6 * static_cast<size_t>(n_pairs)));
     F_HIP(f, hipMemsetAsync(out.vid, 0xff, sizeof(int32_t) * ns, s));
     F_HIP(f, compact_pass(f, out.ns, out.nv, &done[1], [&](unsigned long long i0, int n, Compaction c) {
-        return launch_mesh_vertices(i0, n, smp, m, f->v_grid, out.cflag, src_pts, c, out.verts, out.vid, w, s);
+        return launch_mesh_vertices(i0, n, smp, m, f->voxels.grid, out.cflag, src.pts, c, out.verts, out.vid, w, s);
     }));
     F_HIP(f, compact_pass(f, 3ull * out.ns, n_pairs, &done[2], [&](unsigned long long p0, int n, Compaction c) {
         return launch_mesh_faces(p0, n, smp, m, out.cflag, out.fbits, out.vid, c, out.faces, w, s);
@@ -1317,22 +1257,15 @@ acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, co
                                      int64_t* n_vertices, int64_t* n_faces, int64_t* n_samples, int64_t* n_valid,
                                      int64_t* n_cubes, int64_t* n_uncoloured) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    if (source != ACMMP_MESH_FROM_VOXELS && source != ACMMP_MESH_FROM_CLEAN && source != ACMMP_MESH_FROM_VISIBLE)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_MESH_FROM_*");
-    const bool have = source == ACMMP_MESH_FROM_VOXELS ? f->v_have : source == ACMMP_MESH_FROM_CLEAN ? f->c_have : f->vis_have;
-    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such source result");
-    if (n_list < 1 || n_list > kVisMaxList || !views)
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the view list must hold 1 to 4096 views");
-    for (int j = 0; j < n_list; ++j) {
-        if (views[j] < 0 || views[j] >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
-        if (!f->views[views[j]].depth) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "set_view first for every view listed");
-    }
+    const Res id = mesh_source(source);
+    if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_MESH_FROM_*");
+    const Cloud src = cloud(f, id);
+    if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such source result");
+    const acmmp_status listed = check_view_list(f, n_list, views);
+    if (listed != ACMMP_OK) return listed;
     if (!finite32(trunc) || !(trunc > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "trunc must be finite and > 0");
     if (min_weight < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_weight must be at least 1");
-    const float* src_pts = source == ACMMP_MESH_FROM_VOXELS ? f->v_pts : source == ACMMP_MESH_FROM_CLEAN ? f->c_pts : f->vis_pts;
-    const unsigned long long* src_vox =
-        source == ACMMP_MESH_FROM_VOXELS ? nullptr : source == ACMMP_MESH_FROM_CLEAN ? f->c_vox.get() : f->vis_vox.get();
-    const unsigned long long ne = source == ACMMP_MESH_FROM_VOXELS ? f->v_total : source == ACMMP_MESH_FROM_CLEAN ? f->c_total : f->vis_total;
+    const unsigned long long ne = src.n;
     unsigned long long slots = 1024;
     if (f->m_force_slots != 0) {
         const long long v = f->m_force_slots;
@@ -1345,29 +1278,15 @@ acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, co
     F_HIP(f, hipSetDevice(f->device));
     MeshOut out;
     if (ne > 0) {
-        const acmmp_status st = mesh_run(f, src_pts, src_vox, ne, n_list, views, trunc, min_weight, slots, out);
-        if (st != ACMMP_OK) {
-            const std::string why = f->err;
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(f->stream);
-            f->err = why;
-            return st;
-        }
+        const acmmp_status st = mesh_run(f, src, n_list, views, trunc, min_weight, slots, out);
+        if (st != ACMMP_OK) return run_failed(f, st);
     } else {
         out.stats[0] = static_cast<long long>(slots);
     }
-    render_release(f);                                // it showed the previous mesh result
-    distance_source_gone(f, ACMMP_DIST_FROM_MESH);    // and this one was measured on it
-    f->m_verts = std::move(out.verts);
-    f->m_faces = std::move(out.faces);
-    f->m_skey = std::move(out.skey);
-    f->m_tsdf = std::move(out.tsdf);
-    f->m_sent = std::move(out.sent);
-    f->m_nv = out.nv;
-    f->m_nf = out.nf;
-    f->m_ns = out.ns;
-    f->m_source = source;
-    f->m_have = true;
+    out.source = id;
+    out.have = true;
+    invalidate(f, R_MESH);                            // what showed the previous mesh result or was measured on it
+    f->mesh = std::move(out);
     std::copy(out.stats, out.stats + 4, f->m_stats);
     if (n_vertices) *n_vertices = static_cast<int64_t>(out.nv);
     if (n_faces) *n_faces = static_cast<int64_t>(out.nf);
@@ -1379,38 +1298,34 @@ acmmp_status acmmp_fusion_voxel_mesh(acmmp_fusion* f, int source, int n_list, co
 }
 
 acmmp_status acmmp_fusion_mesh_vertices(acmmp_fusion* f, int64_t first, int64_t n, float* vertices) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->m_nv)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's vertices");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    F_HIP(f, read_range<float>(vertices, f->m_verts, static_cast<size_t>(first), static_cast<size_t>(n), 9));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->mesh.nv, "range beyond the mesh result's vertices", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(vertices, f->mesh.verts, a, m, 9));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_mesh_faces(acmmp_fusion* f, int64_t first, int64_t n, int32_t* faces) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->m_nf)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's faces");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    F_HIP(f, read_range<int32_t>(faces, f->m_faces, static_cast<size_t>(first), static_cast<size_t>(n), 3));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->mesh.nf, "range beyond the mesh result's faces", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<int32_t>(faces, f->mesh.faces, a, m, 3));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_mesh_samples(acmmp_fusion* f, int64_t first, int64_t n, int32_t* cells, int32_t* tsdf, int64_t* entry) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->m_ns)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the mesh result's samples");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n);
-    if (cells) {
-        std::vector<unsigned long long> keys(m);
-        F_HIP(f, read_range<unsigned long long>(keys.data(), f->m_skey, a, m));
-        for (size_t i = 0; i < m; ++i)
-            for (int k = 0; k < 3; ++k) cells[3 * i + k] = static_cast<int32_t>((keys[i] >> (21 * k)) & 0x1fffffull);
-    }
-    F_HIP(f, read_range<int32_t>(tsdf, f->m_tsdf, a, m, 2));
-    F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(entry), f->m_sent, a, m));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->mesh.ns, "range beyond the mesh result's samples", [&](size_t a, size_t m) -> acmmp_status {
+        if (cells) {
+            std::vector<unsigned long long> keys(m);
+            F_HIP(f, read_range<unsigned long long>(keys.data(), f->mesh.skey, a, m));
+            for (size_t i = 0; i < m; ++i)
+                for (int k = 0; k < 3; ++k) cells[3 * i + k] = static_cast<int32_t>((keys[i] >> (21 * k)) & 0x1fffffull);
+        }
+        F_HIP(f, read_range<int32_t>(tsdf, f->mesh.tsdf, a, m, 2));
+        F_HIP(f, read_range<long long>(reinterpret_cast<long long*>(entry), f->mesh.sent, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_mesh_table(acmmp_fusion* f, int64_t force_slots, int64_t* slots, int64_t* occupied,
@@ -1431,21 +1346,18 @@ acmmp_status acmmp_fusion_set_mesh(acmmp_fusion* f, int64_t nv, const float* ver
     for (int64_t i = 0; i < 3 * nf; ++i)
         if (faces[i] < 0 || faces[i] >= nv) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "vertex index out of range");
     F_HIP(f, hipSetDevice(f->device));
-    // built beside the present mesh result, installed when both copies have succeeded
-    DevBuf<float> v;
-    DevBuf<int32_t> t;
+    // built beside the present mesh result, installed when both copies have succeeded; no result is its source
+    MeshRec out;
     const size_t n = static_cast<size_t>(nv), m = static_cast<size_t>(nf);
-    F_HIP(f, alloc(v, 9 * n));
-    F_HIP(f, alloc(t, 3 * m));
-    if (n > 0) F_HIP(f, hipMemcpy(v, vertices, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
-    if (m > 0) F_HIP(f, hipMemcpy(t, faces, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice));
-    mesh_release(f);
-    f->m_verts = std::move(v);
-    f->m_faces = std::move(t);
-    f->m_nv = static_cast<unsigned long long>(nv);
-    f->m_nf = static_cast<unsigned long long>(nf);
-    f->m_source = kMeshNoSource;
-    f->m_have = true;
+    F_HIP(f, alloc(out.verts, 9 * n));
+    F_HIP(f, alloc(out.faces, 3 * m));
+    if (n > 0) F_HIP(f, hipMemcpy(out.verts, vertices, sizeof(float) * 9 * n, hipMemcpyHostToDevice));
+    if (m > 0) F_HIP(f, hipMemcpy(out.faces, faces, sizeof(int32_t) * 3 * m, hipMemcpyHostToDevice));
+    out.nv = static_cast<unsigned long long>(nv);
+    out.nf = static_cast<unsigned long long>(nf);
+    out.have = true;
+    invalidate(f, R_MESH);
+    f->mesh = std::move(out);
     return ACMMP_OK;
 }
 
@@ -1455,10 +1367,8 @@ acmmp_status acmmp_fusion_set_mesh(acmmp_fusion* f, int64_t nv, const float* ver
 
 namespace {
 
-// The new result of a render, swapped in only when the whole call succeeded.
-struct RenderOut {
-    DevBuf<float> depth, normal, colour;
-    DevBuf<int32_t> face;
+// The new result of a render.
+struct RenderOut : RenderRec {
     DevBuf<unsigned long long> keys;                       // scratch: the z-buffer
     DevBuf<uint8_t> queue;                                 // scratch: the large faces
     unsigned long long words[kRenderWords] = {0};
@@ -1467,7 +1377,7 @@ struct RenderOut {
 acmmp_status render_run(acmmp_fusion* f, const DevCam& cam, const float* raw, float rel_tol, RenderOut& out) {
     hipStream_t s = f->stream;
     const size_t P = static_cast<size_t>(cam.W) * cam.H;
-    const unsigned nf = static_cast<unsigned>(f->m_nf);
+    const unsigned nf = static_cast<unsigned>(f->mesh.nf);
     if (!f->r_words) F_HIP(f, alloc(f->r_words, kRenderWords));
     F_HIP(f, alloc(out.depth, P));
     F_HIP(f, alloc(out.face, P));
@@ -1478,7 +1388,7 @@ acmmp_status render_run(acmmp_fusion* f, const DevCam& cam, const float* raw, fl
     F_HIP(f, hipMemsetAsync(f->r_words, 0, sizeof(unsigned long long) * kRenderWords, s));
     F_HIP(f, hipMemsetAsync(out.keys, 0xff, sizeof(unsigned long long) * P, s));
     const long long small_max = f->r_small_max != 0 ? f->r_small_max : kRenderSmallMax;
-    F_HIP(f, launch_render(f->model, cam, f->m_verts, f->m_nv, f->m_faces, nf, small_max, out.keys, out.queue.get(), raw, rel_tol,
+    F_HIP(f, launch_render(f->model, cam, f->mesh.verts, f->mesh.nv, f->mesh.faces, nf, small_max, out.keys, out.queue.get(), raw, rel_tol,
                            out.depth, out.face, out.normal, out.colour, f->r_words, s));
     // the one host wait: the counts
     F_HIP(f, hipMemcpyAsync(out.words, f->r_words, sizeof(out.words), hipMemcpyDeviceToHost, s));
@@ -1493,7 +1403,7 @@ extern "C" {
 acmmp_status acmmp_fusion_mesh_render(acmmp_fusion* f, int view, const acmmp_camera* cam, float rel_tol, int64_t counts[7],
                                       int64_t* n_skipped) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    if (!f->m_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
+    if (!f->mesh.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
     if (!finite32(rel_tol) || !(rel_tol >= 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "rel_tol must be finite and >= 0");
     if (view < -1 || view >= f->n) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "view index out of range");
     DevCam dc;
@@ -1509,24 +1419,15 @@ acmmp_status acmmp_fusion_mesh_render(acmmp_fusion* f, int view, const acmmp_cam
         dc = make_devcam(*cam);
     }
     if (static_cast<long long>(dc.W) * dc.H > 0x7fffffffll) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels");
-    if (f->m_nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
+    if (f->mesh.nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
     F_HIP(f, hipSetDevice(f->device));
     RenderOut out;
     const acmmp_status st = render_run(f, dc, raw, rel_tol, out);
-    if (st != ACMMP_OK) {
-        const std::string why = f->err;
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(f->stream);
-        f->err = why;
-        return st;
-    }
-    f->r_depth = std::move(out.depth);
-    f->r_face = std::move(out.face);
-    f->r_normal = std::move(out.normal);
-    f->r_colour = std::move(out.colour);
-    f->r_W = dc.W;
-    f->r_H = dc.H;
-    f->r_have = true;
+    if (st != ACMMP_OK) return run_failed(f, st);
+    out.W = dc.W;
+    out.H = dc.H;
+    out.have = true;
+    f->render = std::move(out);
     f->r_plan[0] = static_cast<long long>(out.words[kRenderSmall]);
     f->r_plan[1] = static_cast<long long>(out.words[kRenderLarge]);
     f->r_plan[2] = static_cast<long long>(out.words[kRenderCandidates]);
@@ -1538,13 +1439,14 @@ acmmp_status acmmp_fusion_mesh_render(acmmp_fusion* f, int view, const acmmp_cam
 
 acmmp_status acmmp_fusion_render_maps(acmmp_fusion* f, float* depth, int32_t* face, float* normal, float* colour) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    if (!f->r_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no render result: acmmp_fusion_mesh_render first");
+    if (!f->render.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no render result: acmmp_fusion_mesh_render first");
     F_HIP(f, hipSetDevice(f->device));
-    const size_t P = static_cast<size_t>(f->r_W) * f->r_H;
-    F_HIP(f, read_range<float>(depth, f->r_depth, 0, P));
-    F_HIP(f, read_range<int32_t>(face, f->r_face, 0, P));
-    F_HIP(f, read_range<float>(normal, f->r_normal, 0, P, 3));
-    F_HIP(f, read_range<float>(colour, f->r_colour, 0, P, 3));
+    const RenderRec& r = f->render;
+    const size_t P = static_cast<size_t>(r.W) * r.H;
+    F_HIP(f, read_range<float>(depth, r.depth, 0, P));
+    F_HIP(f, read_range<int32_t>(face, r.face, 0, P));
+    F_HIP(f, read_range<float>(normal, r.normal, 0, P, 3));
+    F_HIP(f, read_range<float>(colour, r.colour, 0, P, 3));
     return ACMMP_OK;
 }
 
@@ -1563,10 +1465,8 @@ acmmp_status acmmp_fusion_render_plan(acmmp_fusion* f, int small_max, int64_t* n
 
 namespace {
 
-// The new result of a distance call and its scratch, swapped in only when the whole call succeeded.
-struct DistOut {
-    DevBuf<float> d2;
-    DevBuf<int32_t> nn;
+// The new result of a distance call and the call's scratch.
+struct DistOut : DistRec {
     DevBuf<unsigned long long> keys, ckeys;                // scratch: the cell table and the coarse table
     DevBuf<uint32_t> start, cnt;
     DevBuf<float4> list;                                   // scratch: the cells' lists
@@ -1696,19 +1596,6 @@ acmmp_status distance_run(acmmp_fusion* f, DistCloud q, DistCloud t, float max_d
     return ACMMP_OK;
 }
 
-// The data cloud `source` without a transform; false = no such constant.
-bool distance_data(acmmp_fusion* f, int source, DistCloud& data, bool& have) {
-    switch (source) {
-        case ACMMP_DIST_FROM_SCENE: have = f->s_have; data.p = f->scene.pts; data.n = f->s_total; break;
-        case ACMMP_DIST_FROM_VOXELS: have = f->v_have; data.p = f->v_pts; data.n = f->v_total; break;
-        case ACMMP_DIST_FROM_CLEAN: have = f->c_have; data.p = f->c_pts; data.n = f->c_total; break;
-        case ACMMP_DIST_FROM_VISIBLE: have = f->vis_have; data.p = f->vis_pts; data.n = f->vis_total; break;
-        case ACMMP_DIST_FROM_MESH: have = f->m_have; data.p = f->m_verts; data.n = f->m_nv; break;
-        default: return false;
-    }
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1718,60 +1605,48 @@ acmmp_status acmmp_fusion_set_reference_cloud(acmmp_fusion* f, int64_t n, const 
     if (n < 0 || n > 0x7fffffffll || (n > 0 && !xyz)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
     F_HIP(f, hipSetDevice(f->device));
     // built beside the present reference cloud, installed when the copy has succeeded
-    DevBuf<float> pts;
+    RefRec out;
     const size_t m = static_cast<size_t>(n);
-    F_HIP(f, alloc(pts, 3 * m));
-    if (m > 0) F_HIP(f, hipMemcpy(pts, xyz, sizeof(float) * 3 * m, hipMemcpyHostToDevice));
-    f->ref_pts = std::move(pts);
-    f->ref_n = static_cast<unsigned long long>(n);
-    f->ref_have = true;
-    distance_release(f);                              // it was measured against the previous reference cloud
-    align_release(f);                                 // and these were aligned to it
-    surface_reference_gone(f);
+    F_HIP(f, alloc(out.pts, 3 * m));
+    if (m > 0) F_HIP(f, hipMemcpy(out.pts, xyz, sizeof(float) * 3 * m, hipMemcpyHostToDevice));
+    out.n = static_cast<unsigned long long>(n);
+    out.have = true;
+    f->ref = std::move(out);
+    invalidate(f, R_REFERENCE);                       // what was measured against the previous one or aligned to it
     return ACMMP_OK;
 }
 
 acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion* f, int source, int direction, float max_dist, int n_tau,
                                          const float* tau, int64_t* summary) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    DistCloud data = {nullptr, 9, 0};
-    bool have = false;
-    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    const Res id = dist_source(source);
+    if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    const Cloud src = cloud(f, id);
+    DistCloud data = src.dist();
     if (f->xf_set) {
         data.xf = 1;
         std::memcpy(data.M, f->xf, sizeof(data.M));
     }
     if (direction != ACMMP_DIST_DATA_TO_REF && direction != ACMMP_DIST_REF_TO_DATA)
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "direction must be ACMMP_DIST_DATA_TO_REF or ACMMP_DIST_REF_TO_DATA");
-    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
-    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
-    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
-    if (n_tau < 0 || n_tau > ACMMP_DIST_MAX_TAU || (n_tau > 0 && !tau))
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "n_tau must be 0 to 8");
-    for (int i = 0; i < n_tau; ++i)
-        if (!finite32(tau[i]) || !(tau[i] >= 0.0f) || tau[i] > max_dist)
-            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every tau must be finite and in [0, max_dist]");
+    if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
+    if (!f->ref.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
+    const acmmp_status taus = check_tau_list(f, max_dist, n_tau, tau);
+    if (taus != ACMMP_OK) return taus;
     if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
-    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
+    const DistCloud ref = cloud(f, R_REFERENCE).dist();
     const DistCloud q = direction == ACMMP_DIST_DATA_TO_REF ? data : ref;
     const DistCloud t = direction == ACMMP_DIST_DATA_TO_REF ? ref : data;
     if (t.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
     F_HIP(f, hipSetDevice(f->device));
     DistOut out;
     const acmmp_status st = distance_run(f, q, t, max_dist, n_tau, tau, out);
-    if (st != ACMMP_OK) {
-        const std::string why = f->err;
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(f->stream);
-        f->err = why;
-        return st;
-    }
-    f->dist_d2 = std::move(out.d2);
-    f->dist_nn = std::move(out.nn);
-    f->dist_n = q.n;
-    f->dist_source = source;
-    f->dist_have = true;
+    if (st != ACMMP_OK) return run_failed(f, st);
+    out.n = q.n;
+    out.source = id;
+    out.have = true;
+    f->dist = std::move(out);
     f->dist_cell = static_cast<float>(out.cell);
     f->dist_stats[0] = static_cast<long long>(out.words[kDistOccupied]);
     f->dist_stats[1] = static_cast<long long>(out.words[kDistMaxList]);
@@ -1782,13 +1657,12 @@ acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion* f, int source, int direct
 }
 
 acmmp_status acmmp_fusion_distance_results(acmmp_fusion* f, int64_t first, int64_t n, float* d2, int32_t* nearest) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->dist_n)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the distance result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    F_HIP(f, read_range<float>(d2, f->dist_d2, static_cast<size_t>(first), static_cast<size_t>(n)));
-    F_HIP(f, read_range<int32_t>(nearest, f->dist_nn, static_cast<size_t>(first), static_cast<size_t>(n)));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->dist.n, "range beyond the distance result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(d2, f->dist.d2, a, m));
+        F_HIP(f, read_range<int32_t>(nearest, f->dist.nn, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_distance_grid(acmmp_fusion* f, float force_cell, float* cell, int64_t* cells, int64_t* max_list,
@@ -1808,10 +1682,8 @@ acmmp_status acmmp_fusion_distance_grid(acmmp_fusion* f, float force_cell, float
 
 namespace {
 
-// The new result of a surface call and its scratch, swapped in only when the whole call succeeded.
-struct SurfOut {
-    DevBuf<float> d2;
-    DevBuf<int32_t> nn;
+// The new result of a surface call and the call's scratch.
+struct SurfOut : DistRec {
     DevBuf<unsigned long long> keys;                       // scratch: the cell table
     DevBuf<uint32_t> start, cnt;
     DevBuf<float4> list, large;                            // scratch: the cells' lists and the overflow list
@@ -1920,51 +1792,36 @@ extern "C" {
 acmmp_status acmmp_fusion_surface_distance(acmmp_fusion* f, int query, float max_dist, int n_tau, const float* tau,
                                            int64_t* summary) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    DistCloud q = {nullptr, 9, 0};
-    bool have = false;
-    if (query == ACMMP_SURF_FROM_REFERENCE) {
-        have = f->ref_have;
-        q = DistCloud{f->ref_pts, 3, f->ref_n};
-    } else if (query < ACMMP_SURF_FROM_SCENE || query > ACMMP_SURF_FROM_VISIBLE || !distance_data(f, query, q, have)) {
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "query must be one of ACMMP_SURF_FROM_*");
-    }
-    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such query result");
-    if (!f->m_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
-    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
-    if (n_tau < 0 || n_tau > ACMMP_DIST_MAX_TAU || (n_tau > 0 && !tau))
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "n_tau must be 0 to 8");
-    for (int i = 0; i < n_tau; ++i)
-        if (!finite32(tau[i]) || !(tau[i] >= 0.0f) || tau[i] > max_dist)
-            return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every tau must be finite and in [0, max_dist]");
+    const Res id = surf_source(query);
+    if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "query must be one of ACMMP_SURF_FROM_*");
+    const Cloud src = cloud(f, id);
+    const DistCloud q = src.dist();
+    if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such query result");
+    if (!f->mesh.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
+    const acmmp_status taus = check_tau_list(f, max_dist, n_tau, tau);
+    if (taus != ACMMP_OK) return taus;
     if (f->surf_force_cell != 0.0f && (!finite32(f->surf_force_cell) || !(f->surf_force_cell > 0.0f)))
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
-    if (f->m_nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
+    if (f->mesh.nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
     if (q.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 queries");
     // the frames: reference queries see the mesh under the transform, data queries share its frame
-    SurfMesh m = {DistCloud{f->m_verts, 9, f->m_nv}, f->m_faces, static_cast<unsigned>(f->m_nf)};
-    if (query == ACMMP_SURF_FROM_REFERENCE && f->xf_set) {
+    SurfMesh m = {DistCloud{f->mesh.verts, 9, f->mesh.nv}, f->mesh.faces, static_cast<unsigned>(f->mesh.nf)};
+    if (id == R_REFERENCE && f->xf_set) {
         m.v.xf = 1;
         std::memcpy(m.v.M, f->xf, sizeof(m.v.M));
     }
     F_HIP(f, hipSetDevice(f->device));
     SurfOut out;
     const acmmp_status st = surface_run(f, q, m, max_dist, n_tau, tau, out);
-    if (st != ACMMP_OK) {
-        const std::string why = f->err;
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(f->stream);
-        f->err = why;
-        return st;
-    }
-    f->surf_d2 = std::move(out.d2);
-    f->surf_nn = std::move(out.nn);
-    f->surf_n = q.n;
-    f->surf_query = query;
-    f->surf_have = true;
+    if (st != ACMMP_OK) return run_failed(f, st);
+    out.n = q.n;
+    out.source = id;
+    out.have = true;
+    f->surf = std::move(out);
     f->surf_plan[0] = static_cast<long long>(out.words[kSurfSmall]);
     f->surf_plan[1] = static_cast<long long>(out.words[kSurfLarge]);
     f->surf_plan[2] = static_cast<long long>(out.words[kSurfRegs]);
-    f->surf_plan[3] = static_cast<long long>(f->m_nf - out.valid_faces);
+    f->surf_plan[3] = static_cast<long long>(f->mesh.nf - out.valid_faces);
     f->surf_cell = static_cast<float>(out.cell);
     f->surf_stats[0] = static_cast<long long>(out.words[kDistOccupied]);
     f->surf_stats[1] = static_cast<long long>(out.words[kDistMaxList]);
@@ -1975,13 +1832,12 @@ acmmp_status acmmp_fusion_surface_distance(acmmp_fusion* f, int query, float max
 }
 
 acmmp_status acmmp_fusion_surface_results(acmmp_fusion* f, int64_t first, int64_t n, float* d2, int32_t* nearest_face) {
-    if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    if (bad_range(first, n, f->surf_n)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the surface result");
-    if (n == 0) return ACMMP_OK;
-    F_HIP(f, hipSetDevice(f->device));
-    F_HIP(f, read_range<float>(d2, f->surf_d2, static_cast<size_t>(first), static_cast<size_t>(n)));
-    F_HIP(f, read_range<int32_t>(nearest_face, f->surf_nn, static_cast<size_t>(first), static_cast<size_t>(n)));
-    return ACMMP_OK;
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->surf.n, "range beyond the surface result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(d2, f->surf.d2, a, m));
+        F_HIP(f, read_range<int32_t>(nearest_face, f->surf.nn, a, m));
+        return ACMMP_OK;
+    });
 }
 
 acmmp_status acmmp_fusion_surface_plan(acmmp_fusion* f, int small_max, int64_t* n_small, int64_t* n_large,
@@ -2130,10 +1986,8 @@ double align_step(const double D[12], const double lo[3], const double hi[3], do
     return shift;
 }
 
-// What a successful align call installs.
-struct AlignOut {
-    std::vector<int64_t> words;
-    std::vector<double> M, shift;
+// What a successful align call installs, and what it reports.
+struct AlignOut : AlignRec {
     double last[12];
     int stop = ACMMP_ALIGN_MAX_ITERATIONS;
     double cell = 0.0;
@@ -2402,8 +2256,7 @@ acmmp_status acmmp_fusion_set_cloud_transform(acmmp_fusion* f, const double M[12
     const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     std::memcpy(f->xf, M ? M : I, sizeof(f->xf));
     f->xf_set = M != nullptr;
-    distance_release(f);                              // it was measured under the previous transform
-    surface_reference_gone(f);                        // and so were the faces that reference queries saw
+    invalidate(f, R_XFORM);                           // what was measured under the previous transform
     return ACMMP_OK;
 }
 
@@ -2414,17 +2267,22 @@ acmmp_status acmmp_fusion_get_cloud_transform(const acmmp_fusion* f, double M[12
     return ACMMP_OK;
 }
 
-acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, float max_dist, int max_iterations, int stride,
-                                      double min_shift, const double init[12], double M_out[12], int* n_iterations,
-                                      int* stop_reason) {
+}  // extern "C"
+
+namespace {
+
+// Both align calls: the argument checks in the order the header lists them (a plane call has no mode), the run, the
+// records installed.
+acmmp_status align_call(acmmp_fusion* f, bool plane, int source, int mode, float max_dist, int max_iterations, int stride,
+                        double min_shift, const double init[12], double M_out[12], int* n_iterations, int* stop_reason) {
     if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    DistCloud data = {nullptr, 9, 0};
-    bool have = false;
-    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
-    if (mode != ACMMP_ALIGN_RIGID && mode != ACMMP_ALIGN_SIMILARITY)
+    const Res id = dist_source(source);
+    if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
+    if (!plane && mode != ACMMP_ALIGN_RIGID && mode != ACMMP_ALIGN_SIMILARITY)
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "mode must be ACMMP_ALIGN_RIGID or ACMMP_ALIGN_SIMILARITY");
-    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
-    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
+    const Cloud src = cloud(f, id);
+    if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
+    if (!f->ref.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
     if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
     if (max_iterations < 1 || max_iterations > 1024) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_iterations must be 1 to 1024");
     if (stride < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "stride must be at least 1");
@@ -2432,54 +2290,49 @@ acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, flo
     if (init && !finite12(init)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every entry of init must be finite");
     if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
-    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
+    const DistCloud data = src.dist(), ref = cloud(f, R_REFERENCE).dist();
     if (ref.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
     F_HIP(f, hipSetDevice(f->device));
     AlignOut out;
     const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     std::memcpy(out.last, init ? init : I, sizeof(out.last));
-    const acmmp_status st = align_run(f, data, ref, mode, max_dist, max_iterations, static_cast<unsigned long long>(stride),
-                                      min_shift, out);
-    if (st != ACMMP_OK) {
-        const std::string why = f->err;
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(f->stream);
-        f->err = why;
-        return st;
-    }
-    f->align_words = std::move(out.words);
-    f->align_M = std::move(out.M);
-    f->align_shift = std::move(out.shift);
-    f->align_source = source;
-    f->align_have = true;
-    f->align_plane = false;                           // the plane records, if any, went with the vectors above
+    const unsigned long long step = static_cast<unsigned long long>(stride);
+    const acmmp_status st = plane ? align_plane_run(f, data, ref, max_dist, max_iterations, step, min_shift, out)
+                                  : align_run(f, data, ref, mode, max_dist, max_iterations, step, min_shift, out);
+    if (st != ACMMP_OK) return run_failed(f, st);
+    out.plane = plane;                                // the other kind's records, if any, go with the record replaced
+    out.source = id;
+    out.have = true;
+    f->align = std::move(out);
     f->dist_cell = static_cast<float>(out.cell);
     for (int k = 0; k < 3; ++k) f->dist_stats[k] = static_cast<long long>(out.stats[k]);
     if (M_out) std::memcpy(M_out, out.last, sizeof(out.last));
-    if (n_iterations) *n_iterations = static_cast<int>(f->align_shift.size());
+    if (n_iterations) *n_iterations = static_cast<int>(f->align.shift.size());
     if (stop_reason) *stop_reason = out.stop;
     return ACMMP_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
 // Iterations [first, first + n) of the records of the given kind (none of the other kind's are visible).
 acmmp_status align_read(acmmp_fusion* f, bool plane, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
     if (!f || first < 0 || n < 0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "bad argument");
-    const size_t have = f->align_plane == plane ? f->align_shift.size() : 0;
-    if (bad_range(first, n, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the align records");
+    const AlignRec& r = f->align;
+    if (bad_range(first, n, r.plane == plane ? r.shift.size() : 0)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "range beyond the align records");
     const size_t a = static_cast<size_t>(first), m = static_cast<size_t>(n), nw = plane ? kAlignPlaneWords : kAlignWords;
-    if (words && m) std::memcpy(words, f->align_words.data() + nw * a, sizeof(int64_t) * nw * m);
-    if (M && m) std::memcpy(M, f->align_M.data() + 12 * a, sizeof(double) * 12 * m);
-    if (shift && m) std::memcpy(shift, f->align_shift.data() + a, sizeof(double) * m);
+    if (words && m) std::memcpy(words, r.words.data() + nw * a, sizeof(int64_t) * nw * m);
+    if (M && m) std::memcpy(M, r.M.data() + 12 * a, sizeof(double) * 12 * m);
+    if (shift && m) std::memcpy(shift, r.shift.data() + a, sizeof(double) * m);
     return ACMMP_OK;
 }
 
 }  // namespace
 
 extern "C" {
+
+acmmp_status acmmp_fusion_cloud_align(acmmp_fusion* f, int source, int mode, float max_dist, int max_iterations, int stride,
+                                      double min_shift, const double init[12], double M_out[12], int* n_iterations,
+                                      int* stop_reason) {
+    return align_call(f, false, source, mode, max_dist, max_iterations, stride, min_shift, init, M_out, n_iterations, stop_reason);
+}
 
 acmmp_status acmmp_fusion_align_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M, double* shift) {
     return align_read(f, false, first, n, words, M, shift);
@@ -2488,46 +2341,8 @@ acmmp_status acmmp_fusion_align_records(acmmp_fusion* f, int64_t first, int64_t 
 acmmp_status acmmp_fusion_cloud_align_plane(acmmp_fusion* f, int source, float max_dist, int max_iterations, int stride,
                                             double min_shift, const double init[12], double M_out[12], int* n_iterations,
                                             int* stop_reason) {
-    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
-    DistCloud data = {nullptr, 9, 0};
-    bool have = false;
-    if (!distance_data(f, source, data, have)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_*");
-    if (!have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such data result");
-    if (!f->ref_have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no reference cloud: acmmp_fusion_set_reference_cloud first");
-    if (!finite32(max_dist) || !(max_dist > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_dist must be finite and > 0");
-    if (max_iterations < 1 || max_iterations > 1024) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "max_iterations must be 1 to 1024");
-    if (stride < 1) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "stride must be at least 1");
-    if (!std::isfinite(min_shift) || min_shift < 0.0) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "min_shift must be finite and >= 0");
-    if (init && !finite12(init)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "every entry of init must be finite");
-    if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
-        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
-    const DistCloud ref = {f->ref_pts, 3, f->ref_n};
-    if (ref.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
-    F_HIP(f, hipSetDevice(f->device));
-    AlignOut out;
-    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    std::memcpy(out.last, init ? init : I, sizeof(out.last));
-    const acmmp_status st = align_plane_run(f, data, ref, max_dist, max_iterations, static_cast<unsigned long long>(stride),
-                                            min_shift, out);
-    if (st != ACMMP_OK) {
-        const std::string why = f->err;
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(f->stream);
-        f->err = why;
-        return st;
-    }
-    f->align_words = std::move(out.words);
-    f->align_M = std::move(out.M);
-    f->align_shift = std::move(out.shift);
-    f->align_source = source;
-    f->align_have = true;
-    f->align_plane = true;                            // the point records, if any, went with the vectors above
-    f->dist_cell = static_cast<float>(out.cell);
-    for (int k = 0; k < 3; ++k) f->dist_stats[k] = static_cast<long long>(out.stats[k]);
-    if (M_out) std::memcpy(M_out, out.last, sizeof(out.last));
-    if (n_iterations) *n_iterations = static_cast<int>(f->align_shift.size());
-    if (stop_reason) *stop_reason = out.stop;
-    return ACMMP_OK;
+    return align_call(f, true, source, ACMMP_ALIGN_RIGID, max_dist, max_iterations, stride, min_shift, init, M_out, n_iterations,
+                      stop_reason);
 }
 
 acmmp_status acmmp_fusion_align_plane_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M,
