@@ -25,7 +25,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["kernels.hip", "fusion_kernels.hip", "aux_kernels.hip", "capi.cpp", "comm.cpp", "fusion.cpp", "planar_prior.cpp"]
 KERNEL_TUS = 5            # kernels.hip is compiled once per ACMMP_TU value in parallel (see its header)
 HIP_CPP = {"capi.cpp", "comm.cpp", "fusion.cpp", "planar_prior.cpp"}              # host C++ that includes HIP headers
-HEADERS = ["engine.h", "detmath.h", "planar.h", "camera_dev.h", "fusion.h", "fusion_results.h", "devbuf.h"]
+HEADERS = ["engine.h", "run_plan.h", "detmath.h", "planar.h", "camera_dev.h", "fusion.h", "fusion_results.h", "devbuf.h"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", f"--offload-arch={ARCH}",
           f"-I{INCLUDE}", f"-I{CSRC}", "-Wall", "-Wno-unused-function"]
 

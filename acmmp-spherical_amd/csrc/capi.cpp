@@ -127,6 +127,7 @@ struct acmmp_ctx {
     std::vector<hipEvent_t> sev;
     hipEvent_t fork_ev = nullptr;
     std::vector<StripSlice> strips;
+    RunPlan plan;                               // the plan of the last build_kparams (run_plan.h), as `strips` is
     float ktiming[4] = {0.f, 0.f, 0.f, 0.f};
     DevBuf<unsigned long long> d_work;          // [256] k_eval_nb work counters + [256] the run's status word
     PinnedBuf<unsigned long long> h_work;       // its pinned host copy, enqueued behind the run's last kernel
@@ -136,6 +137,7 @@ struct acmmp_ctx {
     // row-band split (acmmp_band_*): the run in progress
     bool band_active = false;
     KParams band_kp{};
+    RunPlan band_plan;                          // the plan band_kp was built from
     int band_lo = 0, band_hi = 0, band_sw = 0, band_nsw = 0;
     int band_cur[2] = {0, 0};
     std::string err;
@@ -907,34 +909,6 @@ static unsigned long long colour_pixels(const acmmp_ctx* c, const KParams& kp, i
     return n;
 }
 
-// Split point of the refinement evaluation: half the views up to 4 views, one 4-view NCC
-// chunk above (r03 sweep, profiles/r03_ref_split_sweep.txt / r03_ref_split_v20.txt: at V = 10, 15 and 20
-// S = 4 beats 6 / 8 / 12 by 1-4%); 0 (no split) for one view, for colour grids too large for the 32-bit
-// queue entries, or with ACMMP_REF_SPLIT=0 in the environment (A/B switch).
-// Read at every run (one getenv per RunPatchMatch), so tests can switch it within one process.
-// interp_ref: the refinement's first part interpolates SPHERE sample coordinates (fast mode, V > 4, views
-// of the interpolation's size), which makes its views cheaper than the tail's per-sample ones: S = 8 there
-// from V = 9 up (C3 V = 15: 88.9 -> 90.4 Mpix-it/s against S = 4; S = 10 / 12 lose, and the exact mode
-// loses 5% at S = 8, profiles/r04_split_ab.txt, r04_split2_ab.txt)
-static int ref_split_point(int V, size_t Pc, bool interp_ref) {
-    const char* e_on = std::getenv("ACMMP_REF_SPLIT");
-    const char* e_at = std::getenv("ACMMP_REF_SPLIT_AT");  // ACMMP_REF_SPLIT_AT=S: fixed split (A/B)
-    const int enabled = e_on ? std::atoi(e_on) : 1;
-    const int at = e_at ? std::atoi(e_at) : 0;
-    if (!enabled || V < 2 || Pc >= (static_cast<size_t>(1) << 29)) return 0;
-    if (at > 0) return at < V ? at : 0;
-    if (interp_ref && V > 8) return 8;
-    return V <= 4 ? V / 2 : 4;
-}
-
-// Strips of a run when ACMMP_STRIPS does not say (profiles/strips_ab.txt).
-// Two strips for SPHERE views of 2 Mpixel and up (metric -4.5%, 2000x1000 -2.7% per step; four and more lose
-// again); smaller views, where a strip's launches no longer fill the chip, pinhole and more than 4 source views
-// (not measured; the fast mode's interpolating runs with V > 4 ignore the knob too, build_kparams) stay at one.
-static int default_strips(int model, int W, int H, int V) {
-    return (model == kSphere && V <= 4 && static_cast<long long>(W) * H >= 2000000LL) ? 2 : 1;
-}
-
 int acmmp_strip_plan(int rows, int want_strips, int* bounds, int* waits) {
     if (rows < 1 || !bounds) return 0;
     const int ns = strip_plan(rows, want_strips, bounds);
@@ -942,32 +916,20 @@ int acmmp_strip_plan(int rows, int want_strips, int* bounds, int* waits) {
     return ns;
 }
 
-// want_strips: the strip schedule's strip count before clamping (strip_plan); the queues a half-sweep indexes by
-// block number get one slice per strip (c->strips), and kp's own queue pointers are strip 0's.
-// The run-time gates build_kparams and the host-side size query (acmmp_keep_mask_bytes) share; the environment is read
-// at every call.  interp_geometry: the geometric part of the interpolation gate (see build_kparams).
-static bool interp_geometry(int model, int nside, int R, int W, int H) {
-    return model == kSphere && nside == 6 && 2000LL * R <= 5LL * W && 1000LL * R <= 5LL * H;
-}
-static float ref_neg_tau_of(bool interp_geom, bool fast, bool tex16, int V) {
-    float tau = -1.0f;
-    if (interp_geom && fast && tex16 && V <= 4) {
-        tau = 0x1p-35f;
-        if (const char* e = std::getenv("ACMMP_REF_NEG_TAU")) tau = std::strtof(e, nullptr);
-        if (const char* e = std::getenv("ACMMP_REF_NEG_SKIP")) if (std::atoi(e) == 0) tau = -1.0f;
-    }
-    return tau;
-}
-// ACMMP_KEEP_MASK=0 (read per run) launches the instances that recompute the test, with the same bits (A/B,
-// tests/test_gpu_keep_mask.py); without the mask there is nothing to publish.  Not in a geom run: k_eval_ref's geom
-// form would go from 80 to 81 VGPRs and from 6 waves to 5 with the word, and it and the tail must agree on who fills psum.
-static bool keep_mask_of(float ref_neg_tau, bool geom) {
-    bool keep = ref_neg_tau >= 0.0f && !geom;
-    if (const char* e = std::getenv("ACMMP_KEEP_MASK")) if (std::atoi(e) == 0) keep = false;
-    return keep;
+// The run's shape as plan_run takes it.  want_strips: the caller's strip count (band runs and hooks: 1), 0 where
+// ACMMP_STRIPS and the default decide.
+static RunShape run_shape(const acmmp_ctx* c, int want_strips) {
+    RunShape sh;
+    sh.model = c->model; sh.W = c->W; sh.H = c->H; sh.V = c->N - 1;
+    sh.patch_size = c->params.patch_size; sh.radius_increment = c->params.radius_increment;
+    sh.fast = c->math == ACMMP_MATH_FAST; sh.tex16 = c->tex16; sh.geom = c->params.geom_consistency != 0;
+    sh.want_strips = want_strips;
+    return sh;
 }
 
-static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int want_strips = 1) {
+// State checks, the plan (c->plan), the plan into KParams, then tables, slab and strip slices: the queues a half-sweep
+// indexes by block number get one slice per strip (c->strips), and kp's own rows and queue pointers are strip 0's.
+static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, const RunKnobs& knobs, int want_strips = 1) {
     const acmmp_params& p = c->params;
     if (!c->has_params) return fail(c, ACMMP_ERR_STATE, "set_params first");
     if (c->N == 0) return fail(c, ACMMP_ERR_STATE, "upload_views first");
@@ -981,60 +943,22 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "scaled_cols/rows != scaled state size");
     if (p.hierarchy && !p.upsample && !p.geom_consistency && !p.planar_prior && (c->sw != c->W || c->sh != c->H))
         return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "hierarchy reuse needs a full-size scaled state");
-    const int R = p.patch_size / 2;
-    if (R > 64) return fail(c, ACMMP_ERR_UNSUPPORTED, "patch radius > 64");
-    int nside = 0;
-    for (int i = -R; i <= R; i += p.radius_increment) ++nside;
+
+    const RunPlan plan = plan_run(run_shape(c, want_strips), knobs);
+    if (plan.status != kPlanOk) return fail(c, ACMMP_ERR_UNSUPPORTED, plan_error(plan.status));
+    c->plan = plan;
+
     kp = KParams{};
+    put_plan(kp, plan);
     kp.model = c->model;
-    kp.W = c->W; kp.H = c->H; kp.Wh = Wh_of(c); kp.N = c->N; kp.V = c->N - 1;
-    kp.R = R; kp.inc = p.radius_increment; kp.nside = nside; kp.S = nside * nside;
-    // interpolated SPHERE sample coordinates in the fast k_eval_nb: 6x6 patches whose
-    // radius spans at most 5 pixels of 2 pi / 2000 rad (patch_size 11, radius_increment 2 from 2000x1000
-    // up) -- a wider patch angle makes the interpolation's NCC error exceed 1e-4 in the tail near source
-    // poles, where the 256-pixel corner-spread fallback no longer catches it (1600x800: 3.7e-3 at a spread
-    // of 65 px; scripts/interp_feasibility.py, tests/test_interp_design.py).  patch_size 21 / increment 4
-    // also gives 6x6 samples but spans twice the angle: it projects every sample below 4000x2000.
-    kp.interp = interp_geometry(c->model, nside, R, c->W, c->H);
-    // The per-sample refinement loops' negligible-sample threshold (ncc_chunk's PNEG instances):
-    // fast SPHERE with binary16 texels, V <= 4, in k_init, k_eval_ref, k_eval_ref_tail and k_select's cache misses
-    // (without the binary16 images these run the TF = 0 instances, which have no masked form), so the cost cache holds
-    // one arithmetic from the first vector on.  A sample whose weight is at most tau x its own pixel's patch sum
-    // adds nothing to the source sums: a function of the pixel alone, so whichever kernel and wave evaluates a
-    // (pixel, plane, view) forms the same bits.  Gated by the geometry above only, before ACMMP_INTERP is applied, and by none of
-    // ACMMP_SPREAD_MAX / ACMMP_NBFIX_MAX_PC / ACMMP_NEG_*: the runs the tests compare across those knobs share
-    // one refinement.  ACMMP_REF_NEG_TAU overrides tau (tests), ACMMP_REF_NEG_SKIP=0 launches the instances
-    // without the mask; both read per run.
-    kp.ref_neg_tau = ref_neg_tau_of(kp.interp, c->math == ACMMP_MATH_FAST, c->tex16, kp.V);
-    // The kept-sample mask (KParams::keep, keep_mask_of): the drop test above is the same in every half-sweep of a
-    // run, so a masked run's k_init publishes it once per pixel, with the patch sums, and k_eval_ref and its tail
-    // read it instead of forming every weight again to test it.
-    const bool keep = keep_mask_of(kp.ref_neg_tau, p.geom_consistency != 0);
-    kp.keep = keep ? 1 : 0;
-    // ACMMP_INTERP=0 projects every sample in the fast mode too (the per-sample fast arithmetic the
-    // interpolation is gated against, tests/test_gpu_fastmath.py T2); read per run
-    if (const char* e = std::getenv("ACMMP_INTERP")) kp.interp = kp.interp && std::atoi(e) != 0;
-    // fast pinhole: each sample's source point from the per-view homogeneous affine form (ncc_chunk);
-    // ACMMP_PIN_HOMOG=0 projects it through depth and point per sample instead (A/B, tests)
-    kp.homog = 1;
-    if (const char* e = std::getenv("ACMMP_PIN_HOMOG")) kp.homog = std::atoi(e) != 0;
-    // the interpolation's corner-spread fallback threshold (ncc_chunk); ACMMP_SPREAD_MAX overrides it (tests
-    // force fallbacks with a small one, A/B without any with a huge one)
-    kp.spread_max = 256.0f;
-    if (const char* e = std::getenv("ACMMP_SPREAD_MAX")) kp.spread_max = std::strtof(e, nullptr);
-    // the interpolated loop's negligible-sample threshold (stage_neg_mask): 36 dropped terms of at
-    // most tau x the patch sum each move a source sum by 36 tau = 2^-29.8 of its scale, 1 / 57 of one binary32
-    // rounding (2^-24) of that sum.  ACMMP_NEG_TAU overrides it (tests); ACMMP_NEG_SKIP=0 (read per run) keeps
-    // every sample.  Only where k_eval_nb interpolates; the exact mode never reads it.
-    kp.neg_tau = 0x1p-35f;
-    if (const char* e = std::getenv("ACMMP_NEG_TAU")) kp.neg_tau = std::strtof(e, nullptr);
-    if (const char* e = std::getenv("ACMMP_NEG_SKIP")) if (std::atoi(e) == 0) kp.neg_tau = -1.0f;
-    kp.rows = std::min(c->H, 32 * (((c->H / 2) + 15) / 16));
-    kp.row_lo = 0; kp.row_hi = kp.rows;
+    kp.tex16 = c->tex16;
+    kp.fast = c->math == ACMMP_MATH_FAST;
+    kp.W = c->W; kp.H = c->H; kp.N = c->N; kp.V = c->N - 1;
+    kp.inc = p.radius_increment;
     kp.init_lo = 0; kp.init_hi = c->H;
     kp.merge_lo = 0; kp.merge_hi = c->H;
     for (int k = 0; k < 2; ++k) { kp.filt_lo[k] = 0; kp.filt_hi[k] = kp.rows; }
-    kp.dpitch = c->W + 2 * R;
+    kp.dpitch = c->W + 2 * kp.R;
     kp.depth_min = p.depth_min; kp.depth_max = p.depth_max;
     kp.sigma_spatial = p.sigma_spatial; kp.sigma_color = p.sigma_color;
     kp.top_k = p.top_k;
@@ -1043,72 +967,25 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
     kp.sw = c->sw; kp.sh = c->sh;
     kp.seed_lo = static_cast<uint32_t>(seed);
     kp.seed_hi = static_cast<uint32_t>(seed >> 32);
-    kp.Pc = static_cast<long long>(c->H) * kp.Wh;
-    const size_t Pc = static_cast<size_t>(kp.Pc);
+    kp.color_den = 2.0f * p.sigma_color * p.sigma_color;
+    kp.nb_views = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
+    kp.nb_count_work = 1;
 
-    if (kp.S > 64) return fail(c, ACMMP_ERR_UNSUPPORTED, "more than 64 patch samples (patch_size / radius_increment)");
+    // tables
     kp.cams = c->d_cams;
-    if (c->dirs_R != R) {
+    if (c->dirs_R != kp.R) {
         if (c->model == kSphere) {
             c->d_dirs.reset();
-            HIP_TRY(c, c->d_sph_row.alloc(static_cast<size_t>(c->H + 2 * R)));
-            HIP_TRY(c, c->d_sph_col.alloc(static_cast<size_t>(c->W + 2 * R)));
+            HIP_TRY(c, c->d_sph_row.alloc(static_cast<size_t>(c->H + 2 * kp.R)));
+            HIP_TRY(c, c->d_sph_col.alloc(static_cast<size_t>(c->W + 2 * kp.R)));
         } else {
-            HIP_TRY(c, c->d_dirs.alloc(static_cast<size_t>(c->W + 2 * R) * (c->H + 2 * R)));
+            HIP_TRY(c, c->d_dirs.alloc(static_cast<size_t>(c->W + 2 * kp.R) * (c->H + 2 * kp.R)));
         }
         HIP_TRY(c, launch_ray_tables(kp, c->d_dirs, c->d_sph_row, c->d_sph_col, c->stream));
-        c->dirs_R = R;
+        c->dirs_R = kp.R;
     }
-    kp.color_den = 2.0f * p.sigma_color * p.sigma_color;
     HIP_TRY(c, c->d_spatial.reserve(static_cast<size_t>(c->model == kSphere ? c->H : 1) * kp.S));
     HIP_TRY(c, launch_spatial_table(kp, c->d_spatial, c->stream));
-    // queue of k_eval_nb's deferred interpolation fallbacks (pixel << 8 | hypothesis << 5 | view: colour
-    // grids below 2^24 pixels), fast SPHERE with interpolated coordinates only: per region (blocks b with
-    // b % kNbFixRegions equal) room for every entry its blocks can queue, kNbPix x 8 hypotheses x the
-    // launch's views each -- so none is ever dropped (metric 193 MB, C3 656 MB)
-    kp.nb_chunk = nb_view_chunk(kp);
-    kp.nb_tile = nb_tile_order(kp);
-    // the queue's key holds the colour-grid pixel in 24 bits: a larger grid (views of 8192x4096 and up) has no
-    // queue, and then k_eval_nb does not interpolate (ncc_chunk interpolates only with somewhere to put its
-    // fallbacks).  ACMMP_NBFIX_MAX_PC lowers the limit (a test forces that branch at a small size).
-    size_t fix_max_pc = static_cast<size_t>(1) << 24;
-    if (const char* e = std::getenv("ACMMP_NBFIX_MAX_PC")) fix_max_pc = std::min<size_t>(fix_max_pc, std::strtoull(e, nullptr, 10));
-    const bool fixq = c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc < fix_max_pc;
-    if (!fixq && c->model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 && kp.interp && Pc >= fix_max_pc) kp.interp = 0;
-    // (the mask is per wave: only the 8 x 4 tile order keeps a wave's 8 pixels the same under every strip and band cut --
-    // with row runs, ACMMP_NB_TILE=0, a cut regroups them -- so no mask there)
-    if (!kp.interp || !kp.nb_tile) kp.neg_tau = -1.0f;
-    // One strip where the fast mode's refinement has two arithmetic forms for the same cost: pinhole (k_eval_ref's
-    // homogeneous sample points against the per-sample projection of k_eval_ref_tail and k_select's cache misses)
-    // and SPHERE with interpolated coordinates and V > 4 (k_eval_ref's interpolated instance against the same two).
-    // Which of a candidate's views the tail evaluates, and so which form a cached cost has, depends on the views
-    // the other lanes of its wave selected; a strip start regroups the waves, and the low bits of some costs follow
-    // (two strips run one after the other on one stream already differ from one).  A knob changes no
-    // result, so these runs ignore ACMMP_STRIPS.  Everywhere else every form of a cost has the same bits.
-    if (c->math == ACMMP_MATH_FAST && (c->model != kSphere || (kp.interp && kp.V > 4))) want_strips = 1;
-    int sb[kMaxStrips + 1];
-    const int ns = strip_plan(kp.rows, want_strips, sb);
-    // the refinement's interpolated instance (fast SPHERE, V > 4) queues its survivors' fallback views of
-    // [0, ref_split) into the same regions after k_eval_nb's queue is drained: a region's k_eval_ref blocks x
-    // kRefSlots survivors x ref_split views.  The room is the larger of the two producers' worst cases (the
-    // split can exceed the view chunk: ACMMP_REF_SPLIT_AT / ACMMP_NB_VIEW_CHUNK)
-    const int ref_split = ref_split_point(kp.V, Pc, kp.model == kSphere && c->math == ACMMP_MATH_FAST && c->tex16 &&
-                                                        kp.interp && kp.V > 4);
-    // per strip, by its own share of blocks: its launches number their blocks from 0
-    size_t ref_blocks[kMaxStrips], fix_cap[kMaxStrips], fix_total = 0, ref_total = 0;
-    for (int i = 0; i < ns; ++i) {
-        const size_t srows = static_cast<size_t>(sb[i + 1] - sb[i]);
-        const size_t nb_blocks = static_cast<size_t>(nb_block_count(static_cast<long long>(srows), kp.Wh, kp.nb_tile));
-        ref_blocks[i] = (srows * kp.Wh + kRefPix - 1) / kRefPix;
-        fix_cap[i] = !fixq ? 0 : std::max(
-            (nb_blocks + kNbFixRegions - 1) / kNbFixRegions * kNbPix * 8 * static_cast<size_t>(kp.nb_chunk),
-            (ref_blocks[i] + kNbFixRegions - 1) / kNbFixRegions * kRefSlots * static_cast<size_t>(std::max(ref_split, 0)));
-        fix_total += fix_cap[i];
-        ref_total += ref_blocks[i];
-    }
-    kp.cams = c->d_cams;
-    kp.tex16 = c->tex16;
-    kp.fast = c->math == ACMMP_MATH_FAST;
     kp.dep = c->d_dep;
     kp.dirs = c->d_dirs;
     kp.sph_row = c->d_sph_row;
@@ -1122,9 +999,15 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         kp.sel_cs[k] = c->d_sel_cs[k];
         kp.rng_cs[k] = c->d_rng_cs[k];
     }
+    if (!c->d_work) HIP_TRY(c, c->d_work.alloc(258));
+    kp.work = c->d_work;
+    kp.status = reinterpret_cast<unsigned*>(c->d_work + 256);
+    kp.dead_any = reinterpret_cast<unsigned*>(c->d_work + 257);  // zeroed with the counters before k_init
+
     // half-sweep scratch slab: the pieces of engine.h's KParams carved out of one grow-only allocation, each at
     // the next multiple of 256 bytes, in this order.  The list runs twice: without a slab it only sums the
     // sizes, with one it hands out the pieces.
+    const size_t Pc = plan.Pc;
     uint8_t* dead = nullptr;
     auto carve = [&](char* slab) -> size_t {
         size_t at = 0;
@@ -1134,7 +1017,6 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
             at = (at + sizeof(T) * count + 255) & ~static_cast<size_t>(255);
         };
         const size_t VP = static_cast<size_t>(kp.V) * Pc;
-        const size_t surv_n = std::max(5 * Pc + 256, ref_total * kRefSlots);
         piece(kp.hyp_cost, 8 * VP);
         piece(kp.nbpos, 8 * Pc);
         piece(kp.cand, 5 * Pc);
@@ -1144,63 +1026,50 @@ static acmmp_status build_kparams(acmmp_ctx* c, KParams& kp, uint64_t seed, int 
         piece(kp.cvec[0], VP);
         piece(kp.cvec[1], VP);
         piece(kp.cand_vcost, 5 * VP);
-        piece(kp.surv, surv_n);
-        piece(kp.surv_count, std::max(Pc / 51 + 2, ref_total));
-        piece(kp.psum, psum_count(Pc, keep));
-        piece(kp.nbfix, kNbFixRegions * fix_total);              // (empty without a fallback queue)
-        piece(kp.nbfix_count, static_cast<size_t>(kNbFixRegions) * ns);
-        piece(kp.surv_pre, std::max(Pc / 51 + 3, ref_total + ns));
-        piece(kp.surv_dense, surv_n);
+        piece(kp.surv, plan.surv_n);
+        piece(kp.surv_count, plan.surv_count_n);
+        piece(kp.psum, plan.psum_n);
+        piece(kp.nbfix, plan.nbfix_n);
+        piece(kp.nbfix_count, plan.nbfix_count_n);
+        piece(kp.surv_pre, plan.surv_pre_n);
+        piece(kp.surv_dense, plan.surv_n);
         piece(kp.cand_rough, 5 * Pc);
         piece(dead, 2 * Pc);                                     // kp.dead[0], kp.dead[1]
         return at;
     };
     HIP_TRY(c, c->d_scratch.reserve(carve(nullptr)));
     carve(c->d_scratch);
-    if (!fixq) kp.nbfix = nullptr;
+    if (!plan.fix_queue) kp.nbfix = nullptr;
     // SPHERE dead mask (engine.h), one byte per pixel and colour, written by k_init for the rows it initialises
-    // (they cover the half-sweeps' rows, band runs included).  ACMMP_DEAD_SKIP=0 (read per run) keeps none: every
-    // pixel then takes the long paths, with the same result (A/B, tests/test_gpu_dead_skip.py)
-    {
-        const char* e = std::getenv("ACMMP_DEAD_SKIP");
-        const bool skip = c->model == kSphere && !(e && std::atoi(e) == 0);
-        for (int k = 0; k < 2; ++k) kp.dead[k] = skip ? dead + k * Pc : nullptr;
+    // (they cover the half-sweeps' rows, band runs included)
+    for (int k = 0; k < 2; ++k) kp.dead[k] = plan.dead_skip ? dead + k * Pc : nullptr;
+    c->strips.assign(plan.ns, StripSlice{});
+    size_t ref_at = 0, fix_at = 0;
+    for (int i = 0; i < plan.ns; ++i) {
+        StripSlice& t = c->strips[i];
+        t.row_lo = plan.bounds[i]; t.row_hi = plan.bounds[i + 1];
+        t.surv = kp.surv + ref_at * kRefSlots;
+        t.surv_count = kp.surv_count + ref_at;
+        t.surv_pre = kp.surv_pre + ref_at + i;          // ref_blocks + 1 entries each
+        t.surv_dense = kp.surv_dense + ref_at * kRefSlots;
+        t.nbfix = kp.nbfix ? kp.nbfix + kNbFixRegions * fix_at : nullptr;
+        t.nbfix_count = kp.nbfix_count + kNbFixRegions * i;
+        t.nbfix_cap = static_cast<unsigned>(plan.fix_cap[i]);
+        ref_at += plan.ref_blocks[i];
+        fix_at += plan.fix_cap[i];
     }
-    kp.nbfix_cap = static_cast<unsigned>(fix_cap[0]);
-    c->strips.assign(ns, StripSlice{});
-    {
-        size_t ref_at = 0, fix_at = 0;
-        for (int i = 0; i < ns; ++i) {
-            StripSlice& t = c->strips[i];
-            t.row_lo = sb[i]; t.row_hi = sb[i + 1];
-            t.surv = kp.surv + ref_at * kRefSlots;
-            t.surv_count = kp.surv_count + ref_at;
-            t.surv_pre = kp.surv_pre + ref_at + i;          // ref_blocks + 1 entries each
-            t.surv_dense = kp.surv_dense + ref_at * kRefSlots;
-            t.nbfix = kp.nbfix ? kp.nbfix + kNbFixRegions * fix_at : nullptr;
-            t.nbfix_count = kp.nbfix_count + kNbFixRegions * i;
-            t.nbfix_cap = static_cast<unsigned>(fix_cap[i]);
-            ref_at += ref_blocks[i];
-            fix_at += fix_cap[i];
-        }
-    }
-    kp.ref_split = ref_split;
-    if (!c->d_work) HIP_TRY(c, c->d_work.alloc(258));
-    kp.work = c->d_work;
-    kp.status = reinterpret_cast<unsigned*>(c->d_work + 256);
-    kp.dead_any = reinterpret_cast<unsigned*>(c->d_work + 257);  // zeroed with the counters before k_init
-    kp.nb_views = kp.V >= 32 ? 0xFFFFFFFFu : ((1u << kp.V) - 1u);
-    kp.nb_count_work = 1;
+    put_strip(kp, c->strips[0]);
+    kp.row_lo = 0; kp.row_hi = kp.rows;                  // the whole grid: the callers cut it (strips, a band)
     return ACMMP_OK;
 }
 
 // A run's prologue, whole view or band: zeroed work counters, k_init, and buffer 1 of both colours made equal to
 // buffer 0 (rows outside the reference's checkerboard grid are never rewritten).  ev[0] .. ev[1] time it.
-static acmmp_status run_begin(acmmp_ctx* c, const KParams& kp, hipStream_t s) {
+static acmmp_status run_begin(acmmp_ctx* c, const KParams& kp, const RunPlan& plan, hipStream_t s) {
     const size_t Pc = static_cast<size_t>(kp.Pc);
     HIP_TRY(c, hipMemsetAsync(c->d_work, 0, sizeof(unsigned long long) * 258, s));
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
-    HIP_TRY(c, launch_init(kp, s));
+    HIP_TRY(c, launch_init(kp, plan, s));
     for (int k = 0; k < 2; ++k) {
         HIP_TRY(c, hipMemcpyAsync(c->d_plane_cs[k][1], c->d_plane_cs[k][0], sizeof(float4) * Pc,
                                   hipMemcpyDeviceToDevice, s));
@@ -1241,18 +1110,16 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
     if (!c) return ACMMP_ERR_INVALID_ARGUMENT;
     HIP_TRY(c, hipSetDevice(c->device));
     KParams kp;
-    // strip schedule: ACMMP_STRIPS strips over ACMMP_STRIP_STREAMS streams, read per run; they
-    // change no result (tests/test_gpu_strips.py)
-    int want_strips = default_strips(c->model, c->W, c->H, c->N - 1);
-    if (const char* e = std::getenv("ACMMP_STRIPS")) { if (std::atoi(e) > 0) want_strips = std::atoi(e); }
-    int want_streams = kMaxStripStreams;
-    if (const char* e = std::getenv("ACMMP_STRIP_STREAMS")) { if (std::atoi(e) > 0) want_streams = std::atoi(e); }
-    acmmp_status st = build_kparams(c, kp, seed, want_strips);
+    // the knobs are read per run; the strip schedule is the plan's strips over
+    // ACMMP_STRIP_STREAMS streams
+    const RunKnobs knobs = read_knobs();
+    acmmp_status st = build_kparams(c, kp, seed, knobs, 0);
     if (st != ACMMP_OK) return st;
+    const RunPlan& plan = c->plan;
     if (n_half_sweeps < 0) n_half_sweeps = 2 * c->params.max_iterations;
     hipStream_t s = c->stream;
     const int NS = static_cast<int>(c->strips.size());
-    const int NQ = std::max(1, std::min(std::min(want_streams, NS), kMaxStripStreams));
+    const int NQ = std::max(1, std::min(std::min(knobs.strip_streams, NS), kMaxStripStreams));
     hipStream_t qs[kMaxStripStreams] = {s, nullptr, nullptr, nullptr};
     for (int q = 1; q < NQ; ++q) {
         if (!c->xstream[q - 1]) HIP_TRY(c, hipStreamCreateWithFlags(&c->xstream[q - 1], hipStreamNonBlocking));
@@ -1272,11 +1139,9 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
         c->kev.push_back(e);
     }
     // per-kernel events: the k_eval_nb bucket always (the bench's roofline prices it); the other three buckets with
-    // ACMMP_KERNEL_TIMING=all in the environment (read per run) -- an event record between two kernels leaves the
-    // GPU idle ~6 us, 3 x 6 per half-sweep (0.45% of the metric's RunPatchMatch, profiles/r06_ab9_events_ab.txt)
-    const char* e_kt = std::getenv("ACMMP_KERNEL_TIMING");
-    const bool time_all = e_kt && std::strcmp(e_kt, "all") == 0;
-    if ((st = run_begin(c, kp, s)) != ACMMP_OK) return st;
+    // ACMMP_KERNEL_TIMING=all (RunKnobs::time_all)
+    const bool time_all = knobs.time_all;
+    if ((st = run_begin(c, kp, plan, s)) != ACMMP_OK) return st;
     int cur[2] = {0, 0};
     // Fork, the strips' chains and the join.  A failure partway leaves work queued on the extra streams that
     // nothing has joined to the context's stream yet: they are waited for before the error goes back, so that
@@ -1301,11 +1166,8 @@ acmmp_status acmmp_run_patchmatch_ex(acmmp_ctx* c, uint64_t seed, int n_half_swe
                     if (waits[w] >= 0 && waits[w] % NQ != i % NQ)
                         HIP_TRY(c, hipStreamWaitEvent(q, c->sev[static_cast<size_t>(sw - 1) * NS + waits[w]], 0));
                 KParams ks = kp;
-                const StripSlice& t = c->strips[i];
-                ks.row_lo = t.row_lo; ks.row_hi = t.row_hi;
-                ks.surv = t.surv; ks.surv_count = t.surv_count; ks.surv_pre = t.surv_pre; ks.surv_dense = t.surv_dense;
-                ks.nbfix = t.nbfix; ks.nbfix_count = t.nbfix_count; ks.nbfix_cap = t.nbfix_cap;
-                HIP_TRY(c, launch_propagate(ks, colour, iter, out, q, &c->kev[5 * (static_cast<size_t>(sw) * NS + i)], time_all));
+                put_strip(ks, c->strips[i]);
+                HIP_TRY(c, launch_propagate(ks, plan, colour, iter, out, q, &c->kev[5 * (static_cast<size_t>(sw) * NS + i)], time_all));
                 if (NS > 1) HIP_TRY(c, hipEventRecord(c->sev[static_cast<size_t>(sw) * NS + i], q));
             }
             cur[colour] ^= 1;
@@ -1398,15 +1260,16 @@ acmmp_status acmmp_band_begin(acmmp_ctx* c, uint64_t seed, int row0, int row1) {
         return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "a band must span at least ACMMP_BAND_HALO rows");
     HIP_TRY(c, hipSetDevice(c->device));
     KParams& kp = c->band_kp;
-    acmmp_status st = build_kparams(c, kp, seed);
+    acmmp_status st = build_kparams(c, kp, seed, read_knobs());    // one strip: kp's queues are slice 0's (put_strip)
     if (st != ACMMP_OK) return st;
+    c->band_plan = c->plan;
     const int h = ACMMP_BAND_HALO, rows = kp.rows, H = c->H;
     kp.row_lo = std::min(row0, rows); kp.row_hi = std::min(row1, rows);
     kp.init_lo = std::max(0, row0 - h); kp.init_hi = std::min(H, row1 + h);
     kp.merge_lo = std::max(0, row0 - 10); kp.merge_hi = std::min(H, row1 + 10);
     kp.filt_lo[0] = std::min(std::max(0, row0 - 5), rows); kp.filt_hi[0] = std::min(row1 + 5, rows);
     kp.filt_lo[1] = kp.row_lo; kp.filt_hi[1] = kp.row_hi;
-    if ((st = run_begin(c, kp, c->stream)) != ACMMP_OK) return st;
+    if ((st = run_begin(c, kp, c->band_plan, c->stream)) != ACMMP_OK) return st;
     c->band_lo = row0; c->band_hi = row1;
     c->band_sw = 0; c->band_nsw = 2 * c->params.max_iterations;
     c->band_cur[0] = c->band_cur[1] = 0;
@@ -1423,7 +1286,7 @@ acmmp_status acmmp_band_sweep(acmmp_ctx* c, int* colour_out) {
     const int sw = c->band_sw, colour = sw & 1, iter = sw / 2;
     int* cur = c->band_cur;
     SweepOut out{c->d_plane_cs[colour][cur[colour] ^ 1], c->d_cost_cs[colour][cur[colour] ^ 1]};
-    HIP_TRY(c, launch_propagate(kp, colour, iter, out, c->stream, nullptr));
+    HIP_TRY(c, launch_propagate(kp, c->band_plan, colour, iter, out, c->stream, nullptr));
     cur[colour] ^= 1;
     kp.plane_cs[colour] = c->d_plane_cs[colour][cur[colour]];
     kp.cost_cs[colour] = c->d_cost_cs[colour][cur[colour]];
@@ -1516,17 +1379,17 @@ acmmp_status acmmp_debug_band_keep_mask(acmmp_ctx* c, int colour, int row_a, int
 }
 
 // The bytes the kept-sample mask adds to the scratch slab of a run of the given view and settings, before the piece's
-// 256-byte rounding: build_kparams' own gates (with the environment as it is now) and piece count.  No GPU needed.
+// 256-byte rounding: the run's own plan (with the environment as it is now) and its piece count.  No GPU needed.
 long long acmmp_keep_mask_bytes(int W, int H, int model, int patch_size, int radius_increment, int fast, int tex16,
                                 int n_src, int geom) {
     if (W < 1 || H < 1 || patch_size < 1 || radius_increment < 1 || n_src < 1) return -1;
-    const int R = patch_size / 2;
-    int nside = 0;
-    for (int i = -R; i <= R; i += radius_increment) ++nside;
-    const float tau = ref_neg_tau_of(interp_geometry(model, nside, R, W, H), fast != 0, tex16 != 0, n_src);
-    const bool keep = keep_mask_of(tau, geom != 0);
-    const size_t Pc = static_cast<size_t>(H) * ((W + 1) / 2);
-    return static_cast<long long>(sizeof(float4) * (psum_count(Pc, keep) - psum_count(Pc, false)));
+    RunShape sh;
+    sh.model = model; sh.W = W; sh.H = H; sh.V = n_src;
+    sh.patch_size = patch_size; sh.radius_increment = radius_increment;
+    sh.fast = fast != 0; sh.tex16 = tex16 != 0; sh.geom = geom != 0;
+    const RunPlan plan = plan_run(sh, read_knobs());
+    if (plan.status != kPlanOk) return 0;
+    return static_cast<long long>(sizeof(float4) * (plan.psum_n - psum_count(plan.Pc, false)));
 }
 
 acmmp_status acmmp_band_set_rows(acmmp_ctx* c, int colour, int row_a, int row_b, const float* planes, const float* costs,
@@ -1645,7 +1508,7 @@ static acmmp_status debug_eval(acmmp_ctx* c, int which, int n, const int* px, co
     if (!c || !px || !py || !planes || !out || n <= 0) return fail(c, ACMMP_ERR_INVALID_ARGUMENT, "bad debug args");
     HIP_TRY(c, hipSetDevice(c->device));
     KParams kp;
-    acmmp_status st = build_kparams(c, kp, 0);
+    acmmp_status st = build_kparams(c, kp, 0, read_knobs());
     if (st != ACMMP_OK) return st;
     for (int q = 0; q < n; ++q)
         if (px[q] < 0 || py[q] < 0 || px[q] >= c->W || py[q] >= c->H)
@@ -1664,8 +1527,8 @@ static acmmp_status debug_eval(acmmp_ctx* c, int which, int n, const int* px, co
     if (e == hipSuccess) e = hipMemcpy(dy, py, sizeof(int) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dp, planes, sizeof(float4) * n * per, hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = which == 2 ? launch_debug_nb(kp, n, dx, dy, dp, dout, c->stream)
-          : which == 3 ? launch_debug_ref(kp, n, dx, dy, dp, dout, c->stream)
+        e = which == 2 ? launch_debug_nb(kp, c->plan, n, dx, dy, dp, dout, c->stream)
+          : which == 3 ? launch_debug_ref(kp, c->plan, n, dx, dy, dp, dout, c->stream)
                        : launch_debug(kp, which, n, dx, dy, dp, dout, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = d2h(out, dout, sizeof(float) * nout);

@@ -20,18 +20,9 @@
 #include <stdint.h>
 
 #include "acmmp.h"
+#include "run_plan.h"
 
 namespace acmmp {
-
-constexpr int kPinhole = 0;
-constexpr int kSphere = 11;
-constexpr int kMaxViews = 32;       // cost_vector[32], uint32 view bitmask (ACMMP.cu:522,1153)
-constexpr int kNbPix = 32;          // k_eval_nb: pixels per 256-lane block (8 lanes each)
-constexpr int kNbFixRegions = 256;  // the queue's regions, one counter each (block % regions)
-constexpr int kRefLanes = 5;        // k_eval_ref: refinement candidates (ACMMP.cu:870)
-constexpr int kRefPix = 51;         // k_eval_ref: pixels per 256-lane block (255 lanes used)
-constexpr int kRefSlots = kRefPix * kRefLanes;  // survivor slots per k_eval_ref block
-constexpr unsigned kStatusFixOverflow = 1u;   // KParams::status: k_nb_fix found a region's queue overfull
 
 struct DevCam {
     // The fields the fast-math sample loop reads come first, contiguous and 16-byte aligned, so each
@@ -183,9 +174,6 @@ struct KParams {
 };
 static_assert(sizeof(KParams) == 568, "KParams is every kernel's first argument: a size change moves the ones behind it");
 
-// The psum piece of the scratch slab (build_kparams), in float4 entries: one colour's sums, or with the kept-sample
-// mask both colours' and behind them the 2 Pc mask words (two words per entry).
-inline size_t psum_count(size_t Pc, bool keep) { return keep ? 3 * Pc : Pc; }
 // The kept-sample words of a run with kp.keep, [2][Pc] colour-major.
 __host__ __device__ inline unsigned long long* keep_words(const KParams& kp) {
     return reinterpret_cast<unsigned long long*>(kp.psum + 2 * kp.Pc);
@@ -196,11 +184,6 @@ struct SweepOut {
     float4* plane;
     float* cost;
 };
-
-// Strip schedule of a run's half-sweeps: the checkerboard rows [0, rows) cut into contiguous
-// strips, each running its own k_pick .. k_finish chain on one of a few streams.
-constexpr int kMaxStrips = 64;
-constexpr int kMaxStripStreams = 4;  // the context's stream included: the runtime's default hardware queues
 
 // The queues of one strip's launches: everything a half-sweep indexes by block number or resets per launch
 // (engine.h's KParams fields of the same names), carved per strip out of the scratch slab.
@@ -215,44 +198,44 @@ struct StripSlice {
     unsigned nbfix_cap;
 };
 
-// Strip boundaries: `want` strips clamped so that every boundary but the last is a multiple of 4 rows
-// (k_eval_nb's 8 x 4 tiles keep their shape) and every strip is at least ACMMP_BAND_HALO rows tall (24, the
-// next multiple of 4), so a half-sweep reads no strip beyond its two neighbours.  The 4-row units are dealt
-// evenly, the first strips one more; the last strip takes the rows past the last whole unit.  Returns the
-// strip count NS >= 1 and writes bounds[0 .. NS].
-inline int strip_plan(int rows, int want, int* bounds) {
-    const int units = rows / 4, per = (ACMMP_BAND_HALO + 3) / 4;
-    int ns = want < 1 ? 1 : (want > kMaxStrips ? kMaxStrips : want);
-    if (ns > units / per) ns = units / per;
-    if (ns < 1) ns = 1;
-    int at = 0;
-    for (int i = 0; i < ns; ++i) {
-        bounds[i] = 4 * at;
-        at += units / ns + (i < units % ns ? 1 : 0);
-    }
-    bounds[0] = 0;
-    bounds[ns] = rows;
-    return ns;
+// The plan-to-KParams step (run_plan.h): the fields the plan decides, as every kernel but the refinement's sees them
+// (build_kparams sets the queue pointers with put_strip).
+inline void put_plan(KParams& kp, const RunPlan& p) {
+    kp.R = p.R; kp.nside = p.nside; kp.S = p.S;
+    kp.Wh = p.Wh; kp.rows = p.rows; kp.Pc = static_cast<long long>(p.Pc);
+    kp.interp = p.interp; kp.homog = p.homog; kp.spread_max = p.spread_max;
+    kp.neg_tau = p.neg_tau; kp.ref_neg_tau = p.ref_neg_tau; kp.keep = p.keep;
+    kp.nb_chunk = p.nb_chunk; kp.nb_tile = p.nb_tile; kp.ref_split = p.ref_split;
+}
+// One strip's rows and queues.
+inline void put_strip(KParams& kp, const StripSlice& t) {
+    kp.row_lo = t.row_lo; kp.row_hi = t.row_hi;
+    kp.surv = t.surv; kp.surv_count = t.surv_count; kp.surv_pre = t.surv_pre; kp.surv_dense = t.surv_dense;
+    kp.nbfix = t.nbfix; kp.nbfix_count = t.nbfix_count; kp.nbfix_cap = t.nbfix_cap;
+}
+// What k_eval_ref, its fallbacks and its tail see: the interpolated instance leaves its rough views to the tail, so
+// without a split it does not interpolate.
+inline KParams ref_stage(const KParams& kp, const RunPlan& p) {
+    KParams r = kp;
+    r.interp = p.ref_interp;
+    if (!p.ref_fix) r.nbfix = nullptr;
+    return r;
+}
+// A test hook whose queries the queue cannot hold or key: every sample projected instead.
+inline KParams without_queue(const KParams& kp) {
+    KParams r = kp;
+    r.nbfix = nullptr;
+    return r;
 }
 
-// Strips whose half-sweep n must be complete before strip i's half-sweep n + 1 starts: i - 1, i and i + 1
-// where they exist (-1 otherwise); none with a single strip, whose one stream orders its launches.
-inline void strip_waits(int ns, int i, int waits[3]) {
-    waits[0] = (ns > 1 && i > 0) ? i - 1 : -1;
-    waits[1] = ns > 1 ? i : -1;
-    waits[2] = (ns > 1 && i + 1 < ns) ? i + 1 : -1;
-}
-
-// Grid size of a launch: ceil(a / b).
-inline int cdiv(long long a, int b) { return static_cast<int>((a + b - 1) / b); }
-
-// Host-side launchers (kernels.hip; the fusion and voxel launchers are declared in fusion.h).
+// Host-side launchers (kernels.hip; the fusion and voxel launchers are declared in fusion.h).  `plan` is the plan
+// kp was built from: it names the kernel instances.
 hipError_t launch_ray_tables(const KParams& kp, float4* dirs, float2* sph_row, float2* sph_col, hipStream_t s);
 hipError_t launch_spatial_table(const KParams& kp, float* spatial, hipStream_t s);
-hipError_t launch_init(const KParams& kp, hipStream_t s);
+hipError_t launch_init(const KParams& kp, const RunPlan& plan, hipStream_t s);
 // ev: null, or 5 events recorded around the 4 kernels of the half-sweep (per-kernel timing); all_marks false
 // records ev[0] and ev[1] only (the k_eval_nb bucket): each event record in the stream costs ~6 us of idle GPU
-hipError_t launch_propagate(const KParams& kp, int colour, int iter, SweepOut out, hipStream_t s,
+hipError_t launch_propagate(const KParams& kp, const RunPlan& plan, int colour, int iter, SweepOut out, hipStream_t s,
                             hipEvent_t* ev = nullptr, bool all_marks = true);
 hipError_t launch_post(const KParams& kp, int do_post, hipStream_t s);
 // Reference Camera -> device camera (derived constants computed as DESIGN.md §2.3 says), capi.cpp.
@@ -284,20 +267,13 @@ struct ClockStamp {
 hipError_t launch_clock_probe(const float* rnd, int iters, int blocks, ClockStamp* stamps, float* sink, hipStream_t s);
 // acmmp_device_checksum: adds the checksum of `bytes` (multiple of 4) at ptr to *out (device, pre-zeroed)
 hipError_t launch_checksum(const void* ptr, size_t bytes, unsigned long long* out, hipStream_t s);
-// k_eval_nb's source views per launch (kernels.hip, r02 view chunking)
-int nb_view_chunk(const KParams& kp);
-int nb_tile_order(const KParams& kp);
-// k_eval_nb's block count over colour-grid rows [0, rows) of width Wh: 32-pixel row runs, or 8 x 4 tiles
-inline long long nb_block_count(long long rows, long long Wh, int tile) {
-    return tile ? ((rows + 3) / 4) * ((Wh + 7) / 8) : (rows * Wh + 31) / 32;
-}
 hipError_t launch_debug(const KParams& kp, int which, int n, const int* px, const int* py, const float4* planes,
                         float* out, hipStream_t s);
 // k_eval_nb's NCC instance on n pixels x 8 planes (planes[q * 8 + h]): out[(q * 8 + h) * V + v]
-hipError_t launch_debug_nb(const KParams& kp, int n, const int* px, const int* py, const float4* planes, float* out,
+hipError_t launch_debug_nb(const KParams& kp, const RunPlan& plan, int n, const int* px, const int* py, const float4* planes, float* out,
                            hipStream_t s);
 // k_eval_ref's NCC instance (+ the tail's per-sample fallbacks) on n pixels x 5 planes: out[(q * 5 + h) * V + v]
-hipError_t launch_debug_ref(const KParams& kp, int n, const int* px, const int* py, const float4* planes, float* out,
+hipError_t launch_debug_ref(const KParams& kp, const RunPlan& plan, int n, const int* px, const int* py, const float4* planes, float* out,
                             hipStream_t s);
 // Row-pair binary16 copy of one padded view (W + 2) x (H + 2) (DevCam::img16_base layout); *inexact
 // (device int, pre-zeroed) is set when a texel is not exactly representable as a normal binary16

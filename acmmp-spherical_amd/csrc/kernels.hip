@@ -18,6 +18,7 @@
 //    lane of the wave selected (zero-weight views add exactly +0 in the reference).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "camera_dev.h"
 #include "detmath.h"
@@ -1392,7 +1393,6 @@ __device__ __forceinline__ void for_all_views_tf(const KParams& kp, int px, int 
             kp, px, py, pt, ph, wave_mask, f, fixkey);
     }
 }
-static inline int tf_of(const KParams& kp) { return kp.tex16 ? (kp.fast ? 2 : 1) : 0; }
 
 __device__ __forceinline__ float vw_get(const uint32_t (&vwp)[4], int v) {
     const uint32_t word = v < 8 ? vwp[0] : (v < 16 ? vwp[1] : (v < 24 ? vwp[2] : vwp[3]));
@@ -3190,15 +3190,6 @@ hipError_t launch_spatial_table(const KParams& kp, float* spatial, hipStream_t s
 
 #endif  // ACMMP_IN_TU(0)
 
-// View-chunk width: the per-view accumulators live in registers (6 per view).
-static inline int pick_vb(int V) { return V <= 1 ? 1 : (V <= 2 ? 2 : (V <= 4 ? 4 : 8)); }
-
-// Whether a launch defers interpolation fallbacks to the queue kp.nbfix: fast SPHERE with binary16 texels and
-// interpolated coordinates -- k_eval_nb at every V, the refinement's interpolated instance from V = 5 up.
-static inline bool uses_fix_queue(const KParams& kp, bool refinement) {
-    return kp.nbfix && kp.model == kSphere && kp.fast && kp.tex16 && kp.interp && (!refinement || kp.V > 4);
-}
-
 // Dynamic LDS of k_eval_ref and k_debug_ref: the separable staging up to 4 views per chunk on SPHERE.
 static inline size_t ref_lds_bytes(const KParams& kp) {
     return (kp.model == kSphere && pick_vb(kp.V) <= 4) ? sep_lds_bytes(kp.S, kp.nside, kRefPix)
@@ -3231,7 +3222,7 @@ static inline int ref_block_count(const KParams& kp) {
 
 #define ACMMP_DISPATCH_TF(KP, BODY)                                                     \
     do {                                                                                \
-        const int tf_ = tf_of(KP);                                                      \
+        const int tf_ = tf_of((KP).tex16 != 0, (KP).fast != 0);                         \
         if (tf_ == 2) { constexpr int TF = 2; BODY; }                                   \
         else if (tf_ == 1) { constexpr int TF = 1; BODY; }                              \
         else { constexpr int TF = 0; BODY; }                                            \
@@ -3243,31 +3234,44 @@ static inline int ref_block_count(const KParams& kp) {
 template <int M, int VBC, int TF>
 constexpr bool ref_neg_inst() { return M == kSphere && VBC <= 4 && TF == 2; }
 
-#if ACMMP_IN_TU(1)
-template <int M, int BR, int VBC, int TF>
-static void launch_init_inst(const KParams& kp, dim3 grd, dim3 blk, hipStream_t s) {
+// The plan's mask form (RunPlan::init_inst, ref_inst) as the template argument of the instance to launch:
+// f(std::integral_constant<int, PNEG>).  FULL: the kernel's form that publishes (k_init: kNegPublish) or reads
+// (k_eval_ref and its tail: kNegWord) the kept-sample word, kNegNone where it has none -- k_eval_ref's GEOM form (a
+// geom run publishes no word, keep_mask_of: the kernel would lose a wave to it) and the hook.
+template <int M, int VBC, int TF, int FULL, typename F>
+static void with_mask_inst(MaskInst inst, F f) {
+    static_assert(int(kInstTest) == int(kNegTest) && int(kInstWord) == int(kNegWord) && int(kInstPublish) == int(kNegPublish),
+                  "MaskInst names NegMode's values");
     if constexpr (ref_neg_inst<M, VBC, TF>()) {
-        if (kp.ref_neg_tau >= 0.0f) {
-            if (kp.keep) k_init<M, kInitVB, BR, VBC, TF, kNegPublish><<<grd, blk, 0, s>>>(kp);
-            else k_init<M, kInitVB, BR, VBC, TF, kNegTest><<<grd, blk, 0, s>>>(kp);
-            return;
+        if constexpr (FULL != kNegNone) {
+            if (inst == FULL) { f(std::integral_constant<int, FULL>{}); return; }
         }
+        if (inst != kInstNone) { f(std::integral_constant<int, kNegTest>{}); return; }
     }
-    k_init<M, kInitVB, BR, VBC, TF><<<grd, blk, 0, s>>>(kp);
+    f(std::integral_constant<int, kNegNone>{});
 }
 
-hipError_t launch_init(const KParams& kp, hipStream_t s) {
+#if ACMMP_IN_TU(1)
+template <int M, int BR, int VBC, int TF>
+static void launch_init_inst(const KParams& kp, MaskInst inst, dim3 grd, dim3 blk, hipStream_t s) {
+    with_mask_inst<M, VBC, TF, kNegPublish>(inst, [&](auto neg) {
+        k_init<M, kInitVB, BR, VBC, TF, decltype(neg)::value><<<grd, blk, 0, s>>>(kp);
+    });
+}
+
+hipError_t launch_init(const KParams& kp, const RunPlan& plan, hipStream_t s) {
     if (kp.init_hi <= kp.init_lo) return hipSuccess;
     dim3 blk(16, 16), grd(xcd_grid(static_cast<long long>(cdiv(kp.W, 16)) * cdiv(kp.init_hi - kp.init_lo, 16)));
     // branch order of ACMMP.cu:686-793
     const int br = (!kp.geom && !kp.hier) ? kInitRandom : kp.planar ? kInitPlanar : kp.upsample ? kInitUpsample
                                                                                                  : kInitReuse;
-    if (br == kInitRandom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitRandom, VBC, TF>(kp, grd, blk, s))));
+    const MaskInst inst = plan.init_inst;
+    if (br == kInitRandom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitRandom, VBC, TF>(kp, inst, grd, blk, s))));
     else if (br == kInitPlanar)
-        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitPlanar, VBC, TF>(kp, grd, blk, s))));
+        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitPlanar, VBC, TF>(kp, inst, grd, blk, s))));
     else if (br == kInitUpsample)
-        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitUpsample, VBC, TF>(kp, grd, blk, s))));
-    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitReuse, VBC, TF>(kp, grd, blk, s))));
+        ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitUpsample, VBC, TF>(kp, inst, grd, blk, s))));
+    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_init_inst<M, kInitReuse, VBC, TF>(kp, inst, grd, blk, s))));
     return hipGetLastError();
 }
 
@@ -3282,10 +3286,9 @@ hipError_t launch_debug(const KParams& kp, int which, int n, const int* px, cons
 
 // The half-sweep's launches, each in its own translation unit (their kernels are the bulk of the
 // template instances); launch_propagate strings them together.
-hipError_t launch_eval_nb(const KParams& kp, int colour, hipStream_t s);
-hipError_t launch_eval_nb_views(const KParams& kp, int colour, hipStream_t s);
-hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s);
-hipError_t launch_eval_ref(const KParams& kp, int colour, hipStream_t s);
+hipError_t launch_eval_nb(const KParams& kp, const RunPlan& plan, int colour, hipStream_t s);
+hipError_t launch_select(const KParams& kp, const RunPlan& plan, int colour, int iter, hipStream_t s);
+hipError_t launch_eval_ref(const KParams& kp, const RunPlan& plan, int colour, hipStream_t s);   // kp: ref_stage's
 
 // The hooks' deferred fallbacks: k_nb_fix's entry code (fix_row, fix_fold) for query pixels and planes.  LANES:
 // hypotheses per query (8: acmmp_debug_ncc_nb, k_eval_nb's layout; 5: acmmp_debug_ncc_ref, the refinement's
@@ -3319,56 +3322,28 @@ __global__ __launch_bounds__(256) void k_debug_nb_fix(const KParams kp, const in
 }
 
 #if ACMMP_IN_TU(2)
-// View-chunked k_eval_nb: one launch per chunk of 8 source views when the sources' texels outgrow the
-// 256 MB Infinity Cache, so all waves in flight sample the same few images (r02 A/B
-// profiles/r02_view_chunk_ab.txt: SPHERE V = 15 at 3200x1600 +3.7%, at 4096x2048 +6.4%; pinhole V = 10
-// at 1600x1200, 77 MB of texels, -1% -- not chunked; round 4 with the deferred fallbacks, C3: 8 views 90.2,
-// 5 89.6, one launch 89.4 Mpix-it/s, profiles/r04_chunk_ab.txt).  ACMMP_NB_VIEW_CHUNK=c overrides (c <= 0: one
-// launch over all views); read per half-sweep.
-int nb_view_chunk(const KParams& kp) {
-    const char* e = std::getenv("ACMMP_NB_VIEW_CHUNK");
-    int c = e ? std::atoi(e) : 0;
-    if (!e) {
-        // texel bytes of the sources at the reference's size (row-pair binary16 or fp32: 4 B per texel)
-        const double bytes = 4.0 * (kp.W + 2) * (kp.H + 2) * kp.V;
-        c = (kp.V > 8 && bytes > 160e6) ? 8 : 0;
-    }
-    return (c <= 0 || c >= kp.V) ? kp.V : c;
-}
-
-// k_eval_nb's block shape (KParams::nb_tile): 8 x 4 tiles of the colour grid (a block's 32 pixels then span
-// 4 rows, so their patches and source footprints overlap in the CU's L1): k_eval_nb -3% at C2 (3.17 -> 3.07 ms),
-// -2.5% at C3, neutral at the metric against 32-pixel row runs (profiles/r05_ab7_ab.txt).  ACMMP_NB_TILE=0: row runs.
-int nb_tile_order(const KParams&) {
-    const char* e = std::getenv("ACMMP_NB_TILE");
-    return e ? (std::atoi(e) != 0) : 1;
-}
-
-// Precondition: kp.nbfix_count[0 .. kNbFixRegions) is zero -- k_pick, the kernel launch_propagate runs right
-// before, empties it (the later view chunks' memsets are here).
-hipError_t launch_eval_nb(const KParams& kp0, int colour, hipStream_t s) {
-    KParams kp = kp0;
-    const bool fix = uses_fix_queue(kp, false);             // interpolation fallbacks deferred to k_nb_fix
-    if (!fix) kp.nbfix = nullptr;
-    const int chunk = kp.nb_chunk;                          // nb_view_chunk, fixed when the run's KParams were built
-    for (int v0 = 0; v0 < kp.V; v0 += chunk) {
-        const int v1 = std::min(kp.V, v0 + chunk);
-        const uint32_t hi = v1 >= 32 ? 0xFFFFFFFFu : ((1u << v1) - 1u);
-        kp.nb_views = hi & ~((1u << v0) - 1u);
-        kp.nb_count_work = v0 == 0;
-        // the queue holds one launch's entries (a region's lanes x the chunk's views): emptied before and
-        // drained after every view chunk
-        hipError_t e = hipSuccess;
-        // (k_pick empties them for the first chunk)
-        if (fix && v0 > 0 && (e = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e;
-        if ((e = launch_eval_nb_views(kp, colour, s)) != hipSuccess) return e;
-        if (fix) {
-            k_nb_fix<1><<<16 * kNbFixRegions, 256, 0, s>>>(kp, colour);   // 16 stripes per region
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
-}
+// k_eval_nb's instance for the production launch and its hook alike: BODY sees TEX, FM, NEG (the instance with the
+// negligible-sample mask, stage_neg_mask, whose words lie behind the patch in LDS) and the dynamic LDS size `lds`.
+#define ACMMP_DISPATCH_NB(KP, PLAN, BODY)                                                                       \
+    do {                                                                                                        \
+        const size_t lds_nb_ = nb_lds_bytes((KP).model, (KP).S, (KP).nside);                                    \
+        if ((PLAN).nb_masked) {                                                                                 \
+            constexpr int TEX = 1, FM = 1;                                                                      \
+            constexpr bool MASKED = true;                                                                       \
+            const size_t lds = lds_nb_ + kNbMaskBytes;                                                          \
+            ACMMP_DISPATCH((KP).model, (KP).V, BODY);                                                           \
+        } else {                                                                                                \
+            constexpr bool MASKED = false;                                                                      \
+            const size_t lds = lds_nb_;                                                                         \
+            if ((PLAN).nb_fm) {                                                                                 \
+                if ((PLAN).nb_tex) { constexpr int TEX = 1, FM = 1; ACMMP_DISPATCH((KP).model, (KP).V, BODY); } \
+                else { constexpr int TEX = 0, FM = 1; ACMMP_DISPATCH((KP).model, (KP).V, BODY); }               \
+            } else {                                                                                            \
+                if ((PLAN).nb_tex) { constexpr int TEX = 1, FM = 0; ACMMP_DISPATCH((KP).model, (KP).V, BODY); } \
+                else { constexpr int TEX = 0, FM = 0; ACMMP_DISPATCH((KP).model, (KP).V, BODY); }               \
+            }                                                                                                   \
+        }                                                                                                       \
+    } while (0)
 
 // Test hook (acmmp_debug_ncc_nb): k_eval_nb's NCC code on given queries of one pixel and 8 planes (the 8
 // neighbour hypotheses of k_eval_nb) -- the same coop_patch_nb staging and the same for_all_views_t
@@ -3397,62 +3372,58 @@ __global__ __launch_bounds__(256) void k_debug_nb(const KParams kp, int n, const
         kp, px, py, pt, ph, all, [&](int v, float c) { o[v] = c; }, fixkey);
 }
 
-hipError_t launch_debug_nb(const KParams& kp0, int n, const int* px, const int* py, const float4* planes, float* out,
-                           hipStream_t s) {
+hipError_t launch_debug_nb(const KParams& kp0, const RunPlan& plan, int n, const int* px, const int* py,
+                           const float4* planes, float* out, hipStream_t s) {
     // the hook takes k_eval_nb's path, deferred fallbacks included
-    KParams kp = kp0;
-    const bool fix = uses_fix_queue(kp, false) && n < (1 << 24);
-    if (!fix) kp.nbfix = nullptr;                           // (ncc_chunk then projects every sample)
+    const bool fix = plan.fix_queue && n < (1 << 24);
+    const KParams kp = fix ? kp0 : without_queue(kp0);      // (ncc_chunk then projects every sample)
     // the queue holds every entry: a region's blocks x 256 lanes x all V views (one launch here)
     if (fix && static_cast<long long>(cdiv(cdiv(n, kNbPix), kNbFixRegions)) * 256 * kp.V > kp.nbfix_cap)
         return hipErrorInvalidValue;
     hipError_t e0 = hipSuccess;
     if (fix && (e0 = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e0;
-    const size_t lds_nb = nb_lds_bytes(kp.model, kp.S, kp.nside);
-    const size_t lds_neg = lds_nb + kNbMaskBytes;            // the masked instance: stage_neg_mask's words behind the patch
     const dim3 grd = static_cast<unsigned>(cdiv(n, kNbPix));
-    if (kp.fast) {
-        // (the masked instance where the run skips negligible samples, else the unmasked one: ACMMP_NEG_SKIP=0)
-        if (kp.tex16 && kp.neg_tau >= 0.0f) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 1, M == kSphere><<<grd, 256, lds_neg, s>>>(kp, n, px, py, planes, out)));
-        else if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
-        else ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 0, 1><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
-    } else {
-        if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 1, 0><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
-        else ACMMP_DISPATCH(kp.model, kp.V, (k_debug_nb<M, VBC, 0, 0><<<grd, 256, lds_nb, s>>>(kp, n, px, py, planes, out)));
-    }
+    ACMMP_DISPATCH_NB(kp, plan, (k_debug_nb<M, VBC, TEX, FM, MASKED && M == kSphere><<<grd, 256, lds, s>>>(kp, n, px, py, planes, out)));
     if (fix) k_debug_nb_fix<1, kNbLanes><<<kNbFixRegions, 256, 0, s>>>(kp, px, py, planes, out);
     return hipGetLastError();
 }
 
-hipError_t launch_eval_nb_views(const KParams& kp, int colour, hipStream_t s) {
-    const size_t lds_nb = nb_lds_bytes(kp.model, kp.S, kp.nside);
-    const size_t lds_neg = lds_nb + kNbMaskBytes;            // the masked instance: stage_neg_mask's words behind the patch
+// Precondition: kp.nbfix_count[0 .. kNbFixRegions) is zero -- k_pick, the kernel launch_propagate runs right
+// before, empties it (the later view chunks' memsets are here).
+hipError_t launch_eval_nb(const KParams& kp0, const RunPlan& plan, int colour, hipStream_t s) {
+    KParams kp = kp0;                                       // (nb_views and nb_count_work differ per view chunk)
+    const bool fix = plan.fix_queue;                        // interpolation fallbacks deferred to k_nb_fix
+    const int chunk = kp.nb_chunk;                          // nb_view_chunk, fixed when the run's KParams were built
     const dim3 grd = static_cast<unsigned>(nb_block_count(kp.row_hi - kp.row_lo, kp.Wh, kp.nb_tile));
-    if (kp.fast) {
-        // the instance with the negligible-sample mask (stage_neg_mask) where the run skips such samples; without
-        // (ACMMP_NEG_SKIP=0, nothing interpolated) the instance that has no code for it
-        if (kp.tex16 && kp.neg_tau >= 0.0f) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1, M == kSphere><<<grd, 256, lds_neg, s>>>(kp, colour)));
-        else if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
-        else ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 0, 1><<<grd, 256, lds_nb, s>>>(kp, colour)));
-    } else {
-        if (kp.tex16) ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 1, 0><<<grd, 256, lds_nb, s>>>(kp, colour)));
-        else ACMMP_DISPATCH(kp.model, kp.V, (k_eval_nb<M, VBC, 0, 0><<<grd, 256, lds_nb, s>>>(kp, colour)));
+    for (int v0 = 0; v0 < kp.V; v0 += chunk) {
+        const int v1 = std::min(kp.V, v0 + chunk);
+        const uint32_t hi = v1 >= 32 ? 0xFFFFFFFFu : ((1u << v1) - 1u);
+        kp.nb_views = hi & ~((1u << v0) - 1u);
+        kp.nb_count_work = v0 == 0;
+        // the queue holds one launch's entries (a region's lanes x the chunk's views): emptied before and
+        // drained after every view chunk
+        hipError_t e = hipSuccess;
+        // (k_pick empties them for the first chunk)
+        if (fix && v0 > 0 && (e = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e;
+        ACMMP_DISPATCH_NB(kp, plan, (k_eval_nb<M, VBC, TEX, FM, MASKED && M == kSphere><<<grd, 256, lds, s>>>(kp, colour)));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (fix) {
+            k_nb_fix<1><<<16 * kNbFixRegions, 256, 0, s>>>(kp, colour);   // 16 stripes per region
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
     }
-    return hipGetLastError();
+    return hipSuccess;
 }
 #endif  // ACMMP_IN_TU(2)
 
 #if ACMMP_IN_TU(3)
-hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s) {
+hipError_t launch_select(const KParams& kp, const RunPlan& plan, int colour, int iter, hipStream_t s) {
     const long long npix = static_cast<long long>(kp.row_hi - kp.row_lo) * kp.Wh;
-    // the per-view arrays of k_select are sized to the next power of two of V: a 32-entry bound for every V
-    // above 4 kept C3's (V = 15) probabilities in 384 B of scratch per lane
-    const int vs = kp.V <= 4 ? pick_vb(kp.V) : (kp.V <= 8 ? 8 : (kp.V <= 16 ? 16 : 32));
 #define ACMMP_SELECT(MV)                                                                                              \
     do {                                                                                                              \
         if (kp.model == kSphere) {                                                                                    \
-            constexpr bool N = MV <= 4;       /* the masked per-sample loop (ref_neg_tau: fast, binary16, V <= 4) */  \
-            if (kp.ref_neg_tau >= 0.0f && N) {                                                                        \
+            constexpr bool N = MV <= 4;       /* the masked per-sample loop exists up to 4 views */                   \
+            if (plan.sel_masked && N) {                                                                               \
                 if (kp.geom) k_select<kSphere, MV, true, N><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);        \
                 else k_select<kSphere, MV, false, N><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);               \
             } else if (kp.geom) k_select<kSphere, MV, true><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);        \
@@ -3462,7 +3433,7 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
             else k_select<kPinhole, MV, false><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, iter);                     \
         }                                                                                                             \
     } while (0)
-    switch (vs) {
+    switch (plan.sel_mv) {
         case 1: ACMMP_SELECT(1); break;
         case 2: ACMMP_SELECT(2); break;
         case 4: ACMMP_SELECT(4); break;
@@ -3477,45 +3448,22 @@ hipError_t launch_select(const KParams& kp, int colour, int iter, hipStream_t s)
 
 #if ACMMP_IN_TU(4)
 template <int M, int VBC, bool GEOM, int TF>
-static void launch_ref_inst(const KParams& kp, int colour, dim3 grd, size_t lds, hipStream_t s) {
-    if constexpr (ref_neg_inst<M, VBC, TF>()) {
-        if (kp.ref_neg_tau >= 0.0f) {
-            // (a geom run publishes no word, build_kparams: this kernel's GEOM form would lose a wave to it)
-            if constexpr (!GEOM) {
-                if (kp.keep) {
-                    k_eval_ref<M, VBC, GEOM, TF, kNegWord><<<grd, 256, lds, s>>>(kp, colour);
-                    return;
-                }
-            }
-            k_eval_ref<M, VBC, GEOM, TF, kNegTest><<<grd, 256, lds, s>>>(kp, colour);
-            return;
-        }
-    }
-    k_eval_ref<M, VBC, GEOM, TF><<<grd, 256, lds, s>>>(kp, colour);
+static void launch_ref_inst(const KParams& kp, MaskInst inst, int colour, dim3 grd, size_t lds, hipStream_t s) {
+    with_mask_inst<M, VBC, TF, GEOM ? kNegNone : kNegWord>(inst, [&](auto neg) {
+        k_eval_ref<M, VBC, GEOM, TF, decltype(neg)::value><<<grd, 256, lds, s>>>(kp, colour);
+    });
 }
 template <int M, int VBC, bool GEOM, int TF>
-static void launch_tail_inst(const KParams& kp, int colour, int nref, dim3 grd, hipStream_t s) {
-    if constexpr (ref_neg_inst<M, VBC, TF>()) {
-        if (kp.ref_neg_tau >= 0.0f) {
-            if constexpr (!GEOM) {
-                if (kp.keep) {
-                    k_eval_ref_tail<M, VBC, GEOM, TF, kNegWord><<<grd, 256, 0, s>>>(kp, colour, nref);
-                    return;
-                }
-            }
-            k_eval_ref_tail<M, VBC, GEOM, TF, kNegTest><<<grd, 256, 0, s>>>(kp, colour, nref);
-            return;
-        }
-    }
-    k_eval_ref_tail<M, VBC, GEOM, TF><<<grd, 256, 0, s>>>(kp, colour, nref);
+static void launch_tail_inst(const KParams& kp, MaskInst inst, int colour, int nref, dim3 grd, hipStream_t s) {
+    with_mask_inst<M, VBC, TF, GEOM ? kNegNone : kNegWord>(inst, [&](auto neg) {
+        k_eval_ref_tail<M, VBC, GEOM, TF, decltype(neg)::value><<<grd, 256, 0, s>>>(kp, colour, nref);
+    });
 }
 
 // Precondition: kp.surv_count[0 .. ref_block_count(kp)) is zero -- k_select, the kernel launch_propagate runs
 // right before, empties it.
-hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
-    // the interpolated refinement leaves its rough views to k_eval_ref_tail: none without a split
-    KParams kp = kp0;
-    if (kp.ref_split <= 0) kp.interp = 0;
+hipError_t launch_eval_ref(const KParams& kp, const RunPlan& plan, int colour, hipStream_t s) {
+    const MaskInst inst = plan.ref_inst;
     const size_t lds_ref = ref_lds_bytes(kp);
     hipError_t e = hipSuccess;
     const int nref = ref_block_count(kp);
@@ -3523,10 +3471,10 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
     // the interpolated instance (fast SPHERE, V > 4) queues its survivors' fallback views on k_eval_nb's queue
     // (drained by then): a region's k_eval_ref blocks x 255 candidates x S views fit its room (Pc S / 51 against
     // k_eval_nb's Pc x chunk / 32, S <= chunk)
-    const bool ref_fix = uses_fix_queue(kp, true);
+    const bool ref_fix = plan.ref_fix;
     if (ref_fix && (e = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e;
-    if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, true, TF>(kp, colour, grd_ref, lds_ref, s))));
-    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, false, TF>(kp, colour, grd_ref, lds_ref, s))));
+    if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, true, TF>(kp, inst, colour, grd_ref, lds_ref, s))));
+    else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_ref_inst<M, VBC, false, TF>(kp, inst, colour, grd_ref, lds_ref, s))));
     if (ref_fix) k_nb_fix<1, true><<<16 * kNbFixRegions, 256, 0, s>>>(kp, colour);
     if (kp.ref_split > 0) {
         // the survivors' prefix over k_eval_ref blocks, then 8 x nk tail blocks (the queue's length is
@@ -3540,8 +3488,8 @@ hipError_t launch_eval_ref(const KParams& kp0, int colour, hipStream_t s) {
         k_tail_scan<<<1, 1024, 0, s>>>(kp, nref);
         k_tail_compact<<<static_cast<unsigned>(nref), 256, 0, s>>>(kp);
         const unsigned grd = 8u * static_cast<unsigned>(std::min<long long>(ACMMP_TAIL_NK, std::max<long long>(1, cdiv(static_cast<long long>(nref) * kRefSlots, 8 * 256))));
-        if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, true, TF>(kp, colour, nref, grd, s))));
-        else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, false, TF>(kp, colour, nref, grd, s))));
+        if (kp.geom) ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, true, TF>(kp, inst, colour, nref, grd, s))));
+        else ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_tail_inst<M, VBC, false, TF>(kp, inst, colour, nref, grd, s))));
     }
     return hipGetLastError();
 }
@@ -3599,41 +3547,29 @@ __global__ __launch_bounds__(256) void k_debug_ref(const KParams kp, int n, cons
     }
 }
 
-// (the masked instance where the run's refinement takes it: launch_ref_inst's rule)
-template <int M, int VBC, int TF>
-static void launch_debug_ref_inst(const KParams& kp, int n, const int* px, const int* py, const float4* planes, float* out,
-                                  dim3 grd, size_t lds, hipStream_t s) {
-    if constexpr (ref_neg_inst<M, VBC, TF>()) {
-        if (kp.ref_neg_tau >= 0.0f) {
-            k_debug_ref<M, VBC, TF, true><<<grd, 256, lds, s>>>(kp, n, px, py, planes, out);
-            return;
-        }
-    }
-    k_debug_ref<M, VBC, TF><<<grd, 256, lds, s>>>(kp, n, px, py, planes, out);
-}
-
-hipError_t launch_debug_ref(const KParams& kp0, int n, const int* px, const int* py, const float4* planes, float* out,
-                            hipStream_t s) {
-    KParams kp = kp0;
-    if (kp.ref_split <= 0) kp.interp = 0;                   // launch_eval_ref's rule
-    const size_t lds_ref = ref_lds_bytes(kp);
+hipError_t launch_debug_ref(const KParams& kp0, const RunPlan& plan, int n, const int* px, const int* py,
+                            const float4* planes, float* out, hipStream_t s) {
     const dim3 grd = static_cast<unsigned>(cdiv(n, kRefPix));
     // the interpolated instance's fallbacks on the context's queue: room for every entry (a region's blocks x
     // 255 candidates x V views), else the hook refuses
-    const bool fix = uses_fix_queue(kp, true) && n < (1 << 24);
-    if (!fix) kp.nbfix = nullptr;
+    const bool fix = plan.ref_fix && n < (1 << 24);
+    const KParams kp = fix ? ref_stage(kp0, plan) : without_queue(ref_stage(kp0, plan));
+    const size_t lds_ref = ref_lds_bytes(kp);
     if (fix && static_cast<long long>(cdiv(grd.x, kNbFixRegions)) * kRefSlots * kp.V > kp.nbfix_cap) return hipErrorInvalidValue;
     hipError_t e0 = hipSuccess;
     if (fix && (e0 = hipMemsetAsync(kp.nbfix_count, 0, sizeof(unsigned) * kNbFixRegions, s)) != hipSuccess) return e0;
-    ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (launch_debug_ref_inst<M, VBC, TF>(kp, n, px, py, planes, out, grd, lds_ref, s))));
+    // (the hook has no form that reads the word: the run's masked instance recomputes the test, with the same bits)
+    ACMMP_DISPATCH_TF(kp, ACMMP_DISPATCH(kp.model, kp.V, (with_mask_inst<M, VBC, TF, kNegNone>(plan.ref_inst, [&](auto neg) {
+        k_debug_ref<M, VBC, TF, decltype(neg)::value != kNegNone><<<grd, 256, lds_ref, s>>>(kp, n, px, py, planes, out);
+    }))));
     if (fix) k_debug_nb_fix<1, kRefLanes><<<kNbFixRegions, 256, 0, s>>>(kp, px, py, planes, out);
     return hipGetLastError();
 }
 #endif  // ACMMP_IN_TU(4)
 
 #if ACMMP_IN_TU(0)
-hipError_t launch_propagate(const KParams& kp, int colour, int iter, SweepOut out, hipStream_t s, hipEvent_t* ev,
-                            bool all_marks) {
+hipError_t launch_propagate(const KParams& kp, const RunPlan& plan, int colour, int iter, SweepOut out, hipStream_t s,
+                            hipEvent_t* ev, bool all_marks) {
     const long long npix = static_cast<long long>(kp.row_hi - kp.row_lo) * kp.Wh;
     hipError_t e = hipSuccess;
 #define ACMMP_MARK(i) if (ev && (i < 2 || all_marks) && (e = hipEventRecord(ev[i], s)) != hipSuccess) return e
@@ -3641,11 +3577,11 @@ hipError_t launch_propagate(const KParams& kp, int colour, int iter, SweepOut ou
     // roofline prices is that kernel alone
     k_pick<<<dim3(cdiv(npix, 256), 8), 256, 0, s>>>(kp, colour);
     ACMMP_MARK(0);
-    if ((e = launch_eval_nb(kp, colour, s)) != hipSuccess) return e;
+    if ((e = launch_eval_nb(kp, plan, colour, s)) != hipSuccess) return e;
     ACMMP_MARK(1);
-    if ((e = launch_select(kp, colour, iter, s)) != hipSuccess) return e;
+    if ((e = launch_select(kp, plan, colour, iter, s)) != hipSuccess) return e;
     ACMMP_MARK(2);
-    if ((e = launch_eval_ref(kp, colour, s)) != hipSuccess) return e;
+    if ((e = launch_eval_ref(ref_stage(kp, plan), plan, colour, s)) != hipSuccess) return e;
     ACMMP_MARK(3);
     if (kp.model == kSphere) k_finish<kSphere><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, out);
     else k_finish<kPinhole><<<cdiv(npix, 256), 256, 0, s>>>(kp, colour, out);

@@ -3,7 +3,8 @@
   python scripts/func_diff.py OLD.so NEW.so
 
 Every gfx950 code object of each library is extracted (llvm-objdump --offloading) and disassembled (llvm-objdump -d);
-a function's text is its instructions without addresses, encodings and branch-target symbols.  Names are demangled;
+a function's text is its instructions without addresses, encodings, branch-target symbols and the zero fill that
+follows whichever function comes last in its section.  Names are demangled;
 the last template argument of k_init, k_eval_ref and k_eval_ref_tail (PNEG) is written as a number on both sides (false
 = 0, true = 1), since it changed type from bool to int.  Prints how many functions of OLD are in NEW with the same
 text, the ones that differ or are missing, and the ones only NEW has."""
@@ -59,7 +60,7 @@ def functions(lib, tmp):
             if name and line.strip():
                 ins = line.split("//")[0].strip()
                 ins = re.sub(r"<[^>]*>", "", ins).strip()
-                if ins:
+                if ins and ins != "...":       # (objdump's mark for the zero fill behind a section's last function)
                     body.append(ins)
         if name:
             put(funcs, name, body)
