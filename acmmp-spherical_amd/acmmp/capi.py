@@ -126,6 +126,7 @@ EXPORTS = [
     "acmmp_fusion_distance_grid",
     "acmmp_fusion_surface_distance", "acmmp_fusion_surface_results", "acmmp_fusion_surface_plan",
     "acmmp_fusion_surface_grid",
+    "acmmp_fusion_mesh_sample", "acmmp_fusion_sample_points",
     "acmmp_fusion_set_cloud_transform", "acmmp_fusion_get_cloud_transform", "acmmp_fusion_cloud_align",
     "acmmp_fusion_align_records", "acmmp_fusion_cloud_align_plane", "acmmp_fusion_align_plane_records",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
@@ -277,6 +278,8 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_surface_results.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_surface_plan.argtypes = [vp, i32, vp, vp, vp, vp]
     L.acmmp_fusion_surface_grid.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.acmmp_fusion_mesh_sample.argtypes = [vp, C.c_float, C.c_uint64, vp, vp]
+    L.acmmp_fusion_sample_points.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.acmmp_fusion_set_cloud_transform.argtypes = [vp, vp]
     L.acmmp_fusion_get_cloud_transform.argtypes = [vp, vp, vp]
     L.acmmp_fusion_cloud_align.argtypes = [vp, i32, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
@@ -930,13 +933,20 @@ FUSE_UNIQUE = 1     # ACMMP_FUSE_UNIQUE
 VIS_SOURCES = {"voxel": 0, "clean": 1}     # ACMMP_VIS_FROM_VOXELS, ACMMP_VIS_FROM_CLEAN
 MESH_SOURCES = {"voxel": 0, "clean": 1, "visible": 2}     # ACMMP_MESH_FROM_VOXELS, _CLEAN, _VISIBLE
 RENDER_COUNTS = ("agree", "mesh_in_front", "mesh_behind", "mesh_only", "raw_only", "neither", "back_facing")
-DIST_SOURCES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "mesh": 4}     # ACMMP_DIST_FROM_*
+DIST_SOURCES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "mesh": 4, "samples": 6}     # ACMMP_DIST_FROM_*
 DIST_DIRECTIONS = {"data_to_ref": 0, "ref_to_data": 1}     # ACMMP_DIST_DATA_TO_REF (accuracy), _REF_TO_DATA (completeness)
 SURF_QUERIES = {"scene": 0, "voxels": 1, "clean": 2, "visible": 3, "reference": 5}     # ACMMP_SURF_FROM_*
 DIST_SUMMARY_WORDS = 268     # ACMMP_DIST_SUMMARY_WORDS: n_query, n_valid, n_matched, sum_q, within[8], hist[256]
 ALIGN_MODES = {"rigid": 0, "similarity": 1}     # ACMMP_ALIGN_RIGID, ACMMP_ALIGN_SIMILARITY
 ALIGN_STOP_REASONS = ("max_iterations", "converged", "degenerate")     # ACMMP_ALIGN_MAX_ITERATIONS, _CONVERGED, _DEGENERATE
 ALIGN_RECORD_WORDS = 32     # ACMMP_ALIGN_RECORD_WORDS: n_query, n_valid, n_matched, sum_q, n_out_of_range, N, the moments
+
+
+@dataclasses.dataclass
+class MeshSamples:
+    """What Fusion.mesh_sample returns."""
+    n_samples: int         # points of the sample result
+    n_skipped: int         # faces with a non-finite vertex, which have no samples
 
 
 @dataclasses.dataclass
@@ -1291,6 +1301,31 @@ class Fusion:
                                                  _p(t) if t.size else None), "fusion_set_mesh")
         return v.shape[0], t.shape[0]
 
+    def mesh_sample(self, spacing: float, seed: int = 0) -> MeshSamples:
+        """Samples the faces of the mesh result into an area-uniform cloud, about one point per spacing^2 of surface,
+        deterministic in (mesh, spacing, seed) bit for bit (acmmp_fusion_mesh_sample, include/acmmp.h).  The samples stay
+        on the GPU (sample_points) as the source "samples" of cloud_distance, cloud_align and cloud_align_plane until
+        the next mesh_sample or until the mesh goes.  Returns MeshSamples(n_samples, n_skipped): the points, and the
+        faces with a non-finite vertex."""
+        sp = float(np.float32(spacing))
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        out = np.zeros(2, np.int64)
+        self._check(self.L.acmmp_fusion_mesh_sample(self.h, sp, int(seed), _p(out[0:1]), _p(out[1:2])), "fusion_mesh_sample")
+        self._n_samples = int(out[0])
+        return MeshSamples(n_samples=int(out[0]), n_skipped=int(out[1]))
+
+    def sample_points(self, first: int = 0, n: int | None = None):
+        """(points (n, 9) float32 (position, normal, colour), face (n,) int32) of samples [first, first + n) of the last
+        mesh_sample (n None: to the end)."""
+        if first < 0 or (n is not None and n < 0):
+            raise ValueError("first and n must be >= 0")
+        if n is None:
+            n = max(getattr(self, "_n_samples", 0) - first, 0)
+        pts, face = host_empty((n, 9), np.float32), np.empty(n, np.int32)
+        self._check(self.L.acmmp_fusion_sample_points(self.h, first, n, _p(pts), _p(face)), "fusion_sample_points")
+        return pts, face
+
     def render_mesh(self, view=None, camera=None, rel_tol: float = 0.01):
         """Renders the mesh result into view `view`'s camera, or with view None into `camera` (one CAMERA_DTYPE record of
         the set's model): a z-buffer over all faces, exact at shared edges, the seam and the poles
@@ -1341,7 +1376,7 @@ class Fusion:
     def cloud_distance(self, source: str = "scene", direction: str = "data_to_ref", max_dist: float = 1.0,
                        thresholds=()) -> CloudDistance:
         """Nearest-neighbour distances between the resident cloud `source` ("scene", "voxels", "clean", "visible",
-        "mesh") and the reference cloud, capped at max_dist: "data_to_ref" measures every point of the data cloud
+        "mesh", "samples") and the reference cloud, capped at max_dist: "data_to_ref" measures every point of the data cloud
         against the reference (accuracy), "ref_to_data" the reverse (completeness).  Exhaustive by definition, bit for
         bit (acmmp_fusion_cloud_distance, include/acmmp.h); at most 8 thresholds, each in [0, max_dist].  The per-query
         results stay on the GPU (distance_results) until the source or the reference cloud goes."""

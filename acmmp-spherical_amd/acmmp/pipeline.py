@@ -799,7 +799,8 @@ class Pipeline:
                    eval_max_dist: float | None = None, eval_thresholds=(), eval_source: str | None = None,
                    eval_align: str | None = None, eval_align_max_dist: float | None = None,
                    eval_align_iterations: int | None = None, eval_align_stride: int | None = None,
-                   eval_align_plane_iterations: int | None = None, eval_surface: bool = False):
+                   eval_align_plane_iterations: int | None = None, eval_surface: bool = False,
+                   eval_mesh_samples: float | None = None):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -874,9 +875,18 @@ class Pipeline:
         mesh, point to triangle (acmmp_fusion_surface_distance, include/acmmp.h); eval_info and eval.json gain "surface":
         {"completeness", "fidelity", "thresholds"} (evaluate_surface), precision from the accuracy pass above, recall
         from the surface.
+
+        eval_mesh_samples (a spacing; eval_cloud and mesh_trunc are then required): after all of that, and under the
+        transform an alignment installed, the mesh is sampled on the device into an area-uniform cloud, about one point
+        per spacing^2 of surface with seed 0 (acmmp_fusion_mesh_sample, include/acmmp.h), and that cloud is measured
+        against the reference cloud in both directions; eval_info and eval.json gain "mesh_samples": {"spacing",
+        "seed", "n_samples", "n_skipped", "accuracy", "completeness", "thresholds"} (evaluate_mesh_samples): the
+        accuracy of the mesh's surface, weighted by area.  Nothing else in eval.json changes.
         """
         self.fusion_info = None
         self.eval_info = None
+        if eval_mesh_samples is not None and (eval_cloud is None or mesh_trunc is None):
+            raise ValueError("eval_mesh_samples needs eval_cloud and the mesh (mesh_trunc)")
         if eval_surface and (eval_cloud is None or mesh_trunc is None):
             raise ValueError("eval_surface needs eval_cloud and the mesh (mesh_trunc)")
         if eval_align_plane_iterations is not None and eval_align is None:
@@ -1034,6 +1044,11 @@ class Pipeline:
                         raise ValueError("the surface evaluation needs a fusion object with surface_distance (capi.Fusion)")
                     self.eval_info["surface"] = evaluate_surface(fu, written, eval_max_dist, eval_thresholds,
                                                                  self.eval_info["accuracy"])
+                if eval_mesh_samples is not None:
+                    if not hasattr(fu, "mesh_sample"):
+                        raise ValueError("the mesh-sample evaluation needs a fusion object with mesh_sample (capi.Fusion)")
+                    self.eval_info["mesh_samples"] = evaluate_mesh_samples(fu, eval_mesh_samples, eval_max_dist,
+                                                                           eval_thresholds)
                 if path:
                     with open(os.path.join(os.path.dirname(os.path.abspath(path)), "eval.json"), "w") as f:
                         json.dump(self.eval_info, f, indent=1)
@@ -1151,6 +1166,18 @@ def evaluate_surface(fu, cloud: str, max_dist: float, thresholds=(), accuracy: d
         rows.append(row)
     out["thresholds"] = rows
     return out
+
+
+def evaluate_mesh_samples(fu, spacing: float, max_dist: float, thresholds=(), seed: int = 0) -> dict:
+    """The surface of the fusion object's mesh result against its reference cloud: the mesh is sampled into an
+    area-uniform cloud (mesh_sample, about one point per spacing^2) and that cloud measured in both directions of
+    cloud_distance, under the installed transform: {"spacing", "seed", "n_samples", "n_skipped", "accuracy",
+    "completeness", "thresholds"}, the last three with evaluate_clouds' fields."""
+    s = fu.mesh_sample(spacing, seed)
+    e = evaluate_clouds(fu, "samples", max_dist, thresholds)
+    return {"spacing": float(np.float32(spacing)), "seed": int(seed), "n_samples": int(s.n_samples),
+            "n_skipped": int(s.n_skipped), "accuracy": e["accuracy"], "completeness": e["completeness"],
+            "thresholds": e["thresholds"]}
 
 
 def launcher_store():
@@ -1276,6 +1303,10 @@ def arg_parser():
     ap.add_argument("--eval-surface", action="store_true",
                     help="with --eval-cloud and a mesh: also measure the reference cloud and the written cloud against the "
                          "mesh's faces (point-to-triangle); eval.json gains \"surface\"")
+    ap.add_argument("--eval-mesh-samples", metavar="SPACING", type=float, default=None,
+                    help="with --eval-cloud and a mesh: sample the mesh's surface on the GPU, about one point per SPACING^2 of "
+                         "area, and measure the samples against the reference cloud in both directions; eval.json gains "
+                         "\"mesh_samples\"")
     return ap
 
 
@@ -1313,7 +1344,8 @@ def main(argv=None):
                               eval_thresholds=tuple(a.eval_threshold), eval_source=a.eval_source,
                               eval_align=a.eval_align, eval_align_max_dist=a.eval_align_max_dist,
                               eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride,
-                              eval_align_plane_iterations=a.eval_align_plane_iterations, eval_surface=a.eval_surface)
+                              eval_align_plane_iterations=a.eval_align_plane_iterations, eval_surface=a.eval_surface,
+                              eval_mesh_samples=a.eval_mesh_samples)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

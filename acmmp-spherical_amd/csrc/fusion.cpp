@@ -133,8 +133,15 @@ struct MeshRec {
     Res source = R_NONE;                         // stays R_NONE for a mesh that acmmp_fusion_set_mesh installed
     bool have = false;
 };
+struct SampleRec {
+    DevBuf<float> pts;                           // 9 floats per sample
+    DevBuf<int32_t> face;                        // the sample's face
+    unsigned long long n = 0, skipped = 0;       // samples held, invalid faces
+    Res source = R_MESH;
+    bool have = false;
+};
 struct RenderRec {
-    DevBuf<float> depth, normal, colour;         // 1, 3 and 3 floats per pixel
+    DevBuf<float> depth, normal, colour;        // 1, 3 and 3 floats per pixel
     DevBuf<int32_t> face;                        // the winner per pixel, -1 = none
     int W = 0, H = 0;
     Res source = R_MESH;
@@ -196,6 +203,7 @@ struct acmmp_fusion {
     CleanRec clean;                              // acmmp_fusion_voxel_clean
     VisRec visible;                              // acmmp_fusion_voxel_visibility
     MeshRec mesh;                                // acmmp_fusion_voxel_mesh, acmmp_fusion_set_mesh
+    SampleRec samples;                           // acmmp_fusion_mesh_sample
     RenderRec render;                            // acmmp_fusion_mesh_render
     RefRec ref;                                  // acmmp_fusion_set_reference_cloud
     DistRec dist, surf;                          // acmmp_fusion_cloud_distance, acmmp_fusion_surface_distance
@@ -219,7 +227,7 @@ struct acmmp_fusion {
     SegScratch seg;                              // of voxelize's compaction and of every later stage's
     DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
     DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the 3 minima (32-bit each, in 2 words)
-    DevBuf<unsigned long long> c_words, vis_words, m_words, r_words, dist_words, surf_words;   // k*Words device words each
+    DevBuf<unsigned long long> c_words, vis_words, m_words, r_words, dist_words, surf_words, smp_words;   // k*Words device words each
     std::string err;
 };
 
@@ -387,6 +395,7 @@ void invalidate(acmmp_fusion* f, Res what) {
     drop(f->clean, R_CLEAN);
     drop(f->visible, R_VISIBLE);
     drop(f->mesh, R_MESH);
+    drop(f->samples, R_SAMPLES);
     drop(f->render, R_RENDER);
     drop(f->dist, R_DIST);
     drop(f->surf, R_SURF);
@@ -419,6 +428,7 @@ Cloud cloud(const acmmp_fusion* f, Res id) {
         case R_VISIBLE: return {f->visible.have, f->visible.pts, 9, f->visible.kept, f->visible.cnt, f->visible.vox};
         case R_MESH: return {f->mesh.have, f->mesh.verts, 9, f->mesh.nv};
         case R_REFERENCE: return {f->ref.have, f->ref.pts, 3, f->ref.n};
+        case R_SAMPLES: return {f->samples.have, f->samples.pts, 9, f->samples.n};
         default: return {};
     }
 }
@@ -1359,6 +1369,77 @@ acmmp_status acmmp_fusion_set_mesh(acmmp_fusion* f, int64_t nv, const float* ver
     invalidate(f, R_MESH);
     f->mesh = std::move(out);
     return ACMMP_OK;
+}
+
+}  // extern "C"
+
+// ---- the mesh result sampled into an area-uniform cloud (include/acmmp.h; kernels: k_sample_*) ----------------
+
+namespace {
+
+// The new result of a sample call and the call's offsets (scratch).
+struct SampleOut : SampleRec {
+    DevBuf<unsigned long long> loc;                        // per face: the samples before it in its chunk of 256 faces
+    DevBuf<unsigned long long> chunk_tot, base;            // per chunk: its samples, the samples before it
+};
+
+acmmp_status sample_run(acmmp_fusion* f, double s2, unsigned long long seed, SampleOut& out) {
+    hipStream_t s = f->stream;
+    const MeshRec& m = f->mesh;
+    const unsigned nf = static_cast<unsigned>(m.nf);
+    const size_t n_chunks = (static_cast<size_t>(nf) + 255) / 256;
+    if (!f->smp_words) F_HIP(f, alloc(f->smp_words, kSampleWords));
+    F_HIP(f, alloc(out.loc, nf));
+    F_HIP(f, alloc(out.chunk_tot, n_chunks));
+    F_HIP(f, alloc(out.base, n_chunks));
+    unsigned long long h[kSampleWords] = {0};
+    F_HIP(f, hipMemsetAsync(f->smp_words, 0, sizeof(h), s));
+    F_HIP(f, launch_sample_count(m.verts, m.nv, m.faces, nf, s2, seed, out.loc, out.chunk_tot, out.base, f->smp_words, s));
+    // the first host wait: the total, to size the result
+    F_HIP(f, hipMemcpyAsync(h, f->smp_words, sizeof(h), hipMemcpyDeviceToHost, s));
+    F_HIP(f, hipStreamSynchronize(s));
+    out.n = h[kSampleTotal];
+    out.skipped = h[kSampleSkipped];
+    if (out.n > 0x7fffffffull)
+        return ffail(f, ACMMP_ERR_UNSUPPORTED, "mesh sample: " + std::to_string(out.n) + " samples, more than 2^31 - 1");
+    const size_t N = static_cast<size_t>(out.n);
+    F_HIP(f, alloc(out.pts, 9 * N));
+    F_HIP(f, alloc(out.face, N));
+    F_HIP(f, launch_sample_emit(m.verts, m.nv, m.faces, nf, seed, out.loc, out.base, out.n, out.pts, out.face, s));
+    // the second host wait: the end
+    F_HIP(f, hipStreamSynchronize(s));
+    return ACMMP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_mesh_sample(acmmp_fusion* f, float spacing, uint64_t seed, int64_t* n_samples, int64_t* n_skipped) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (!f->mesh.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
+    if (!finite32(spacing) || !(spacing > 0.0f)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "spacing must be finite and > 0");
+    if (f->mesh.nf > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 faces");
+    F_HIP(f, hipSetDevice(f->device));
+    SampleOut out;
+    const double s2 = static_cast<double>(spacing) * static_cast<double>(spacing);
+    const acmmp_status st = sample_run(f, s2, static_cast<unsigned long long>(seed), out);
+    if (st != ACMMP_OK) return run_failed(f, st);
+    out.have = true;
+    invalidate(f, R_SAMPLES);                         // what was measured on the previous samples or aligned from them
+    f->samples = std::move(out);
+    if (n_samples) *n_samples = static_cast<int64_t>(f->samples.n);
+    if (n_skipped) *n_skipped = static_cast<int64_t>(f->samples.skipped);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_sample_points(acmmp_fusion* f, int64_t first, int64_t n, float* points, int32_t* face) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->samples.n, "range beyond the sample result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<float>(points, f->samples.pts, a, m, 9));
+        F_HIP(f, read_range<int32_t>(face, f->samples.face, a, m));
+        return ACMMP_OK;
+    });
 }
 
 }  // extern "C"

@@ -334,4 +334,18 @@ hipError_t launch_surf_query(DistCloud q, DistGrid g, DistTable fine, const floa
                              unsigned n_large, DistQuery p, float* d2, int32_t* nearest, unsigned long long* words,
                              hipStream_t s);
 
+// Area-uniform samples of the mesh result (acmmp_fusion_mesh_sample, include/acmmp.h).
+// Device words of a sample call (all zero before it).
+enum { kSampleTotal = 0, kSampleSkipped = 1, kSampleWords = 2 };
+// Steps 1 to 4 in stream order, one lane per face, then one workgroup over the chunks of 256 faces: loc[f] = the samples
+// of the faces before f in its chunk, chunk_tot[c] and base[c] = the samples of chunk c and of the chunks before it
+// (ceil(nf / 256) of each), words[kSampleTotal] = N, words[kSampleSkipped] += the invalid faces.  s2 = spacing^2.
+hipError_t launch_sample_count(const float* verts, unsigned long long nv, const int32_t* faces, unsigned nf, double s2,
+                               unsigned long long seed, unsigned long long* loc, unsigned long long* chunk_tot,
+                               unsigned long long* base, unsigned long long* words, hipStream_t s);
+// Steps 5 and 6, one lane per sample: sample i < N (the host's copy of words[kSampleTotal]) to out[9 i ..] and out_face[i].
+hipError_t launch_sample_emit(const float* verts, unsigned long long nv, const int32_t* faces, unsigned nf,
+                              unsigned long long seed, const unsigned long long* loc, const unsigned long long* base,
+                              unsigned long long N, float* out, int32_t* out_face, hipStream_t s);
+
 }  // namespace acmmp

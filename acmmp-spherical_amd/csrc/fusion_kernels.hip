@@ -2578,4 +2578,213 @@ hipError_t launch_surf_query(DistCloud q, DistGrid g, DistTable fine, const floa
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ area-uniform samples of the mesh
+//
+// acmmp_fusion_mesh_sample (include/acmmp.h).  Every choice is made in 64-bit integers (the rounding of a
+// face's count, the lattice, the fold into the triangle, the weights), so that the float64 blends see exact weights; the
+// samples are an expansion of the faces (a face gives 0 .. 2^31 of them), which the ordered compaction does not cover:
+// the faces' counts are scanned in chunks of 256 (in the chunk by k_sample_count, the chunks' bases by k_sample_scan),
+// and a sample finds its face by two upper-bound searches.
+
+constexpr unsigned long long kSampleG1 = 0xC13FA9A902A6328Full, kSampleG2 = 0x91E10DA5C79E7B1Dull;   // 2^64 / p, 2^64 / p^2
+constexpr unsigned long long kSampleOne = 1ull << 53;
+
+// Step 0: splitmix64's finaliser, as vox_home has it.
+__device__ __forceinline__ unsigned long long sample_mix(unsigned long long z) {
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// The vertices of face f: v[0 .. 3) point at their 9 floats; false = an index outside the vertices.
+__device__ __forceinline__ bool sample_face(const float* __restrict__ verts, unsigned long long nv,
+                                            const int32_t* __restrict__ faces, unsigned long long f, const float* v[3]) {
+    const int32_t* t = faces + 3ull * f;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long i = static_cast<uint32_t>(t[k]);
+        ok = ok && i < nv;
+        v[k] = verts + 9ull * (i < nv ? i : 0ull);
+    }
+    return ok;
+}
+
+// Exclusive prefix of x over the 256 lanes of the workgroup in lane order, and their sum.  Every lane calls it.
+__device__ __forceinline__ unsigned long long sample_block_scan(unsigned long long x, unsigned long long& total) {
+    __shared__ unsigned long long wave_tot[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long incl = x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long y = __shfl_up(incl, d);
+        if (lane >= d) incl += y;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0ull;
+    total = 0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const unsigned long long t = wave_tot[w];
+        total += t;
+        if (w < wave) before += t;
+    }
+    return before + (incl - x);
+}
+
+// Steps 1 to 3, one lane per face: loc[f] = the samples of the faces before f in f's chunk of 256 faces, chunk_tot[c] =
+// the samples of chunk c, words[kSampleSkipped] += the invalid faces.
+__global__ __launch_bounds__(256) void k_sample_count(const float* __restrict__ verts, unsigned long long nv,
+                                                      const int32_t* __restrict__ faces, unsigned nf, double s2,
+                                                      unsigned long long seed, unsigned long long* __restrict__ loc,
+                                                      unsigned long long* __restrict__ chunk_tot,
+                                                      unsigned long long* __restrict__ words) {
+    const unsigned long long f = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    unsigned long long n = 0ull;
+    bool skipped = false;
+    if (f < nf) {
+        const float* v[3];
+        bool ok = sample_face(verts, nv, faces, f, v);
+        double P[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float x = v[k][a];
+                ok = ok && !vox_nonfinite(x);
+                P[k][a] = static_cast<double>(x);
+            }
+        }
+        skipped = !ok;
+        if (ok) {
+            const double e1x = P[1][0] - P[0][0], e1y = P[1][1] - P[0][1], e1z = P[1][2] - P[0][2];
+            const double e2x = P[2][0] - P[0][0], e2y = P[2][1] - P[0][1], e2z = P[2][2] - P[0][2];
+            const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+            const double area = 0.5 * sqrt((nx * nx + ny * ny) + nz * nz);
+            const double e = area / s2;
+            if (e >= 2147483648.0) {
+                n = 1ull << 31;
+            } else {
+                const double k = floor(e), r = e - k;
+                const unsigned long long T = static_cast<unsigned long long>(r * 9007199254740992.0);
+                const unsigned long long h = sample_mix(seed ^ sample_mix(f));
+                n = static_cast<unsigned long long>(k) + ((h >> 11) < T ? 1ull : 0ull);
+            }
+        }
+    }
+    unsigned long long total;
+    const unsigned long long before = sample_block_scan(n, total);
+    if (f < nf) loc[f] = before;
+    if (threadIdx.x == 0) chunk_tot[blockIdx.x] = total;
+    wave_count(skipped, &words[kSampleSkipped]);
+}
+
+// Step 4: base[c] = the samples of the chunks before c, words[kSampleTotal] = N.  One workgroup of 1024 lanes walks
+// the chunks in tiles of 1024 with a running carry, as k_fuse_scan does, over 64-bit counts.
+__global__ __launch_bounds__(1024) void k_sample_scan(const unsigned long long* __restrict__ chunk_tot, unsigned n_chunks,
+                                                      unsigned long long* __restrict__ base,
+                                                      unsigned long long* __restrict__ words) {
+    __shared__ unsigned long long wave_tot[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0ull;
+    for (unsigned t0 = 0; t0 < n_chunks; t0 += 1024u) {
+        const unsigned i = t0 + threadIdx.x;
+        const unsigned long long x = i < n_chunks ? chunk_tot[i] : 0ull;
+        unsigned long long incl = x;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long y = __shfl_up(incl, d);
+            if (lane >= d) incl += y;
+        }
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0ull, all = 0ull;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const unsigned long long t = wave_tot[w];
+            all += t;
+            if (w < wave) before += t;
+        }
+        if (i < n_chunks) base[i] = carry + before + (incl - x);
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) words[kSampleTotal] = carry;
+}
+
+// The last of a[0 .. n) that is <= x (the upper bound minus one), for ascending a with a[0] <= x: where several equal
+// x, the last of them, which steps over every run of items without samples.
+__device__ __forceinline__ unsigned sample_find(const unsigned long long* __restrict__ a, unsigned n, unsigned long long x) {
+    unsigned lo = 0u, hi = n;                      // a[lo - 1] <= x < a[hi]
+    while (lo < hi) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        if (a[mid] <= x) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo > 0u ? lo - 1u : 0u;
+}
+
+// Steps 5 and 6, one lane per sample i of N: its face from the offsets, its number j in the face, the lattice point, the
+// blend of the three vertices.
+__global__ __launch_bounds__(256) void k_sample_emit(const float* __restrict__ verts, unsigned long long nv,
+                                                     const int32_t* __restrict__ faces, unsigned nf, unsigned long long seed,
+                                                     const unsigned long long* __restrict__ loc,
+                                                     const unsigned long long* __restrict__ base, unsigned n_chunks,
+                                                     unsigned long long N, float* __restrict__ out, int32_t* __restrict__ out_face) {
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= N) return;
+    const unsigned c = sample_find(base, n_chunks, i);
+    const unsigned f0 = c * 256u, m = nf - f0 < 256u ? nf - f0 : 256u;
+    const unsigned long long in_chunk = i - base[c];
+    const unsigned f = f0 + sample_find(loc + f0, m, in_chunk);
+    const unsigned long long j = in_chunk - loc[f];
+    const float* v[3];
+    (void)sample_face(verts, nv, faces, f, v);
+    const unsigned long long h = sample_mix(seed ^ sample_mix(f));
+    const unsigned long long o1 = sample_mix(h), o2 = sample_mix(o1);
+    unsigned long long i1 = (o1 + j * kSampleG1) >> 11, i2 = (o2 + j * kSampleG2) >> 11;
+    if (i1 + i2 > kSampleOne) {
+        i1 = kSampleOne - i1;
+        i2 = kSampleOne - i2;
+    }
+    const unsigned long long i0 = kSampleOne - i1 - i2;
+    const double scale = 1.0 / 9007199254740992.0;
+    const double w0 = static_cast<double>(i0) * scale, w1 = static_cast<double>(i1) * scale, w2 = static_cast<double>(i2) * scale;
+    float r[9];
+    double M[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const double b = (w0 * static_cast<double>(v[0][k]) + w1 * static_cast<double>(v[1][k])) + w2 * static_cast<double>(v[2][k]);
+        if (k >= 3 && k < 6) M[k - 3] = b;
+        r[k] = static_cast<float>(b);
+    }
+    const double len = sqrt((M[0] * M[0] + M[1] * M[1]) + M[2] * M[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[3 + k] = len > 0.0 ? static_cast<float>(M[k] / len) : 0.0f;
+    float* o = out + 9ull * i;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) o[k] = r[k];
+    out_face[i] = static_cast<int32_t>(f);
+}
+
+hipError_t launch_sample_count(const float* verts, unsigned long long nv, const int32_t* faces, unsigned nf, double s2,
+                               unsigned long long seed, unsigned long long* loc, unsigned long long* chunk_tot,
+                               unsigned long long* base, unsigned long long* words, hipStream_t s) {
+    if (nf == 0) return hipSuccess;
+    const unsigned n_chunks = dist_blocks(nf);
+    k_sample_count<<<n_chunks, 256, 0, s>>>(verts, nv, faces, nf, s2, seed, loc, chunk_tot, words);
+    k_sample_scan<<<1, 1024, 0, s>>>(chunk_tot, n_chunks, base, words);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_emit(const float* verts, unsigned long long nv, const int32_t* faces, unsigned nf,
+                              unsigned long long seed, const unsigned long long* loc, const unsigned long long* base,
+                              unsigned long long N, float* out, int32_t* out_face, hipStream_t s) {
+    if (N == 0) return hipSuccess;
+    k_sample_emit<<<dist_blocks(N), 256, 0, s>>>(verts, nv, faces, nf, seed, loc, base, dist_blocks(nf), N, out, out_face);
+    return hipGetLastError();
+}
+
 }  // namespace acmmp

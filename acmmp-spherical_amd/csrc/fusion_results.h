@@ -6,18 +6,20 @@
 
 namespace acmmp {
 
-// The resident results.  R_SCENE .. R_REFERENCE are also the clouds a stage can name as its source; R_XFORM stands for
-// the cloud transform, which is no result but is replaced like one.
-enum Res { R_NONE = -1, R_SCENE, R_VOXELS, R_CLEAN, R_VISIBLE, R_MESH, R_REFERENCE, R_RENDER, R_DIST, R_SURF, R_ALIGN, R_XFORM };
+// The resident results.  R_SCENE .. R_REFERENCE and R_SAMPLES are also the clouds a stage can name as its source; R_XFORM
+// stands for the cloud transform, which is no result but is replaced like one.  R_SAMPLES comes after R_XFORM: the
+// enumerators up to R_XFORM keep their values (tests/fusion_lifetime_walk.cpp indexes its tables by them).
+enum Res { R_NONE = -1, R_SCENE, R_VOXELS, R_CLEAN, R_VISIBLE, R_MESH, R_REFERENCE, R_RENDER, R_DIST, R_SURF, R_ALIGN, R_XFORM,
+           R_SAMPLES };
 
 // The lifetime table: does the held result `r`, whose record names `src` as the cloud it was computed from, go when
 // `cause` has been replaced or discarded?  invalidate (fusion.cpp) applies it transitively, so a row names only the
 // direct cause: a mesh of the visible result goes with a voxelize because the visible result does.  src of the voxel,
-// the clean and the render result is always the scene, the voxel and the mesh result; src of a mesh that
+// the clean, the render and the sample result is always the scene, the voxel, the mesh and the mesh result; src of a mesh that
 // acmmp_fusion_set_mesh installed is R_NONE, which is never a cause.  A new stage adds its name above and its row here.
 inline bool goes_with(Res r, Res src, Res cause) {
     switch (r) {
-        case R_VOXELS: case R_CLEAN: case R_VISIBLE: case R_MESH: case R_RENDER: return cause == src;
+        case R_VOXELS: case R_CLEAN: case R_VISIBLE: case R_MESH: case R_RENDER: case R_SAMPLES: return cause == src;
         case R_DIST: return cause == src || cause == R_REFERENCE || cause == R_XFORM;
         case R_ALIGN: return cause == src || cause == R_REFERENCE;
         // with the mesh, with its query cloud, and a reference query's also when the mesh is read in another frame
@@ -38,6 +40,7 @@ inline Res dist_source(int s) {
         case ACMMP_DIST_FROM_CLEAN: return R_CLEAN;
         case ACMMP_DIST_FROM_VISIBLE: return R_VISIBLE;
         case ACMMP_DIST_FROM_MESH: return R_MESH;
+        case ACMMP_DIST_FROM_SAMPLES: return R_SAMPLES;
         default: return R_NONE;
     }
 }

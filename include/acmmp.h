@@ -592,7 +592,8 @@ acmmp_status acmmp_fusion_visibility_tallies(acmmp_fusion *f, int64_t first, int
  * acmmp_fusion_set_view, trunc not finite or <= 0, min_weight < 1, more than 2^31 - 1 vertices.  The mesh result stays
  * in HBM until the next successful mesh call replaces it or its source is replaced or discarded (as the visible
  * result's; a successful acmmp_fusion_voxel_visibility discards a mesh of the visible result);
- * acmmp_fusion_set_view does not touch it.  Any error -- an out-of-memory part-way and a full sample table
+ * acmmp_fusion_set_view does not touch it.  The render, the surface and the sample result (acmmp_fusion_mesh_sample)
+ * go with the mesh result they were computed on.  Any error -- an out-of-memory part-way and a full sample table
  * (ACMMP_ERR_HIP) included -- leaves the object as it was (the new result is built beside the previous one).
  * Device memory: 8 bytes per entry held with the clean and the visible result (the voxel index) and 8 per entry
  * while the call runs; the sample table, 32 bytes per slot with the smallest power of two >= max(54 ne, 1024) slots
@@ -687,8 +688,8 @@ acmmp_status acmmp_fusion_render_plan(acmmp_fusion *f, int small_max, int64_t *n
  *
  * acmmp_fusion_cloud_distance measures the resident data cloud `source` against the reference cloud.  The data cloud is
  * the first three floats of the scene points (ACMMP_DIST_FROM_SCENE), of the voxel result (_VOXELS), of the clean
- * result's kept voxels (_CLEAN), of the visible result's kept entries (_VISIBLE) or of the mesh vertices (_MESH), in their
- * order.  With ACMMP_DIST_DATA_TO_REF the queries are the data cloud and the targets the reference cloud (accuracy); with
+ * result's kept voxels (_CLEAN), of the visible result's kept entries (_VISIBLE), of the mesh vertices (_MESH) or of the mesh's
+ * samples (_SAMPLES, acmmp_fusion_mesh_sample), in their order.  With ACMMP_DIST_DATA_TO_REF the queries are the data cloud and the targets the reference cloud (accuracy); with
  * ACMMP_DIST_REF_TO_DATA it is the reverse (completeness).  The definition is exhaustive over the pairs, in plain IEEE
  * arithmetic with no contraction:
  *  1. Validity.  A point is valid when its three coordinates are finite.  Invalid queries are neither matched nor counted
@@ -728,6 +729,7 @@ acmmp_status acmmp_fusion_render_plan(acmmp_fusion *f, int small_max, int64_t *n
 #define ACMMP_DIST_FROM_CLEAN 2     /* the clean result's kept voxels */
 #define ACMMP_DIST_FROM_VISIBLE 3   /* the visible result's kept entries */
 #define ACMMP_DIST_FROM_MESH 4      /* the mesh result's vertices */
+#define ACMMP_DIST_FROM_SAMPLES 6   /* the sample result's points (acmmp_fusion_mesh_sample); 5 is ACMMP_SURF_FROM_REFERENCE */
 #define ACMMP_DIST_DATA_TO_REF 0    /* queries = data cloud, targets = reference cloud: accuracy */
 #define ACMMP_DIST_REF_TO_DATA 1    /* queries = reference cloud, targets = data cloud: completeness */
 #define ACMMP_DIST_MAX_TAU 8
@@ -1014,6 +1016,56 @@ acmmp_status acmmp_fusion_surface_plan(acmmp_fusion *f, int small_max, int64_t *
  * searched.  They are informational: no result depends on them. */
 acmmp_status acmmp_fusion_surface_grid(acmmp_fusion *f, float force_cell, float *cell, int64_t *cells, int64_t *max_list,
                                        int64_t *rings);
+
+/* ---- the mesh result's surface as an area-uniform cloud of samples (no reference counterpart) ----
+ * acmmp_fusion_mesh_sample turns the faces of the mesh result (acmmp_fusion_voxel_mesh, acmmp_fusion_set_mesh) into
+ * points spread over their area, about one per spacing^2: the cloud that "accuracy of the mesh" is measured on, where the
+ * vertices (ACMMP_DIST_FROM_MESH) weigh a face by its corners and not by its size.  The samples are a resident cloud,
+ * ACMMP_DIST_FROM_SAMPLES, of acmmp_fusion_cloud_distance (both directions), acmmp_fusion_cloud_align and
+ * acmmp_fusion_cloud_align_plane (they carry normals); acmmp_fusion_surface_distance does not take them.  The definition
+ * is over the faces f = 0 .. nf in their order.  All float arithmetic is IEEE float64 on inputs widened from float32, with
+ * no contraction; every choice is made in integers, all 64-bit integer arithmetic is mod 2^64, and x >> s is the logical
+ * shift.
+ *  0. Constants.  mix(z): z += 0x9e3779b97f4a7c15; z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9; z = (z ^ (z >> 27)) *
+ *     0x94d049bb133111eb; the result is z ^ (z >> 31) (splitmix64's finaliser, which the voxel table hashes with).
+ *     G1 = 0xC13FA9A902A6328F and G2 = 0x91E10DA5C79E7B1D: 2^64 / p and 2^64 / p^2 for the plastic number p (the R2
+ *     lattice), the second rounded up to odd.
+ *  1. Validity.  A face is valid when the nine position coordinates of its three vertices (A, B, C) are finite.  An
+ *     invalid face has no samples; *n_skipped counts the invalid faces.
+ *  2. Area.  E1 = B - A, E2 = C - A per component; N = (E1y*E2z - E1z*E2y, E1z*E2x - E1x*E2z, E1x*E2y - E1y*E2x);
+ *     area = 0.5 * sqrt((Nx*Nx + Ny*Ny) + Nz*Nz).  It cannot overflow for float32 inputs; a degenerate face has area 0
+ *     and is valid.
+ *  3. Count.  e = area / ((double)spacing * (double)spacing).  With e >= 2^31 the face counts n_f = 2^31.  Otherwise
+ *     k = floor(e), r = e - k, T = (uint64)(r * 9007199254740992.0), h_f = mix(seed ^ mix((uint64) f)) and
+ *     n_f = k + ((h_f >> 11) < T ? 1 : 0): the expected count is e, so faces smaller than spacing^2 are sampled in
+ *     proportion to their area and not dropped.
+ *  4. Total.  N = the 64-bit sum of n_f.  N > 2^31 - 1 is ACMMP_ERR_UNSUPPORTED (the distance calls take at most that
+ *     many targets); it is known before any output is allocated.
+ *  5. Sample j of face f, 0 <= j < n_f.  o1 = mix(h_f), o2 = mix(o1); i1 = (o1 + j*G1) >> 11, i2 = (o2 + j*G2) >> 11.
+ *     If i1 + i2 > 2^53 then i1 = 2^53 - i1 and i2 = 2^53 - i2 (the fold into the triangle, so that no weight is
+ *     negative); i0 = 2^53 - i1 - i2.  w_k = (double)i_k * 2^-53, which is exact, and w0 + w1 + w2 = 1 exactly.
+ *     Position, per component: (float)((w0*A + w1*B) + w2*C).  Normal: M = (w0*nA + w1*nB) + w2*nC per component, then
+ *     M / sqrt((Mx*Mx + My*My) + Mz*Mz) rounded to float32, zero unless that length is > 0 (step 7 of
+ *     acmmp_fusion_mesh_render).  Colour: (float)((w0*cA + w1*cB) + w2*cC) per component.
+ *  6. Order.  The samples are listed in ascending (f, j): sample offset[f] + j, offset the exclusive 64-bit prefix sum
+ *     of n_f, holds the 9 floats of a cloud point (position, normal, colour) and face = f.
+ * n_samples and n_skipped may be NULL.  ACMMP_ERR_INVALID_ARGUMENT: no mesh result (an empty one is valid and gives no
+ * samples), a spacing that is not finite and > 0.  ACMMP_ERR_UNSUPPORTED: step 4.  One sample result is resident at a
+ * time (acmmp_fusion_sample_points reads it); it is built beside the previous one, and any error -- an out-of-memory
+ * part-way included -- leaves the object as it was.  It is discarded when the mesh result is replaced or discarded (a
+ * successful acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh, and whatever discards the mesh's source), and a distance
+ * result or align records of the samples go when the samples are replaced or discarded; acmmp_fusion_set_view,
+ * acmmp_fusion_set_reference_cloud, acmmp_fusion_mesh_render and the distance, align and surface calls leave it alone.
+ * The only atomic of the device is an integer add (the skipped faces, one per wave); a sample is written by the one lane
+ * that computes it, which finds its face in the offsets by binary search.
+ * Device memory: 40 bytes per sample held with the result (36 for the point, 4 for the face); 8 bytes per face (its
+ * offset within its chunk of 256 faces, from which n_f follows) and 16 per chunk (the chunk's count and offset) while
+ * the call runs.  The host waits twice: for the total, and at the end. */
+acmmp_status acmmp_fusion_mesh_sample(acmmp_fusion *f, float spacing, uint64_t seed, int64_t *n_samples,
+                                      int64_t *n_skipped);
+/* Samples [first, first + n) of the sample result to host arrays, either of which may be NULL: points n x 9 floats,
+ * face n int32.  Ranges as acmmp_fusion_voxel_points (no sample result: every range but an empty one at 0 is refused). */
+acmmp_status acmmp_fusion_sample_points(acmmp_fusion *f, int64_t first, int64_t n, float *points, int32_t *face);
 
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's

@@ -4,7 +4,7 @@ and set_reference_cloud.  For two runs of the pipeline, for example --math exact
 
     python scripts/compare_clouds.py A.ply B.ply --max-dist 0.02 --threshold 0.005 --threshold 0.01 [--out eval.json]
                                      [--align rigid|similarity [--align-max-dist D] [--align-iterations K] [--align-stride S]
-                                      [--align-plane-iterations N]] [--surface]
+                                      [--align-plane-iterations N]] [--surface] [--mesh-samples SPACING]
 
 A is the data cloud, B the reference cloud; both are PLYs of the pipeline's layout.  With --align, A is first registered
 to B on the GPU (acmmp_fusion_cloud_align) and measured under that transform, which the output then holds under "align".
@@ -13,6 +13,9 @@ With --align-plane-iterations, up to N rigid point-to-plane iterations along A's
 With --surface, A is a mesh PLY (io.write_mesh_ply's layout): its vertices are the data cloud, and the output gains
 "surface" -- B's points and A's vertices against A's faces, point to triangle (acmmp_fusion_surface_distance), recall
 from the surface (pipeline.evaluate_surface).
+With --mesh-samples SPACING, A is a mesh PLY as well: its surface is sampled on the GPU, about one point per SPACING^2 of
+area (acmmp_fusion_mesh_sample), and the output gains "mesh_samples" -- the samples against B in both directions, the
+mesh's accuracy weighted by area (pipeline.evaluate_mesh_samples).
 Prints the figures as one JSON line (pipeline.evaluate_clouds)."""
 import argparse
 import json
@@ -28,10 +31,14 @@ from acmmp import capi, io, pipeline  # noqa: E402
 
 
 def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=None, align_max_dist=None,
-            align_iterations=30, align_stride=1, align_plane_iterations=None, a_normals=None, a_faces=None):
+            align_iterations=30, align_stride=1, align_plane_iterations=None, a_normals=None, a_faces=None,
+            surface=True, mesh_samples=None):
     """evaluate_clouds of cloud A (n, 3) against cloud B, after align_clouds when align is "rigid" or "similarity";
     align_plane_iterations: its point-to-plane stage, along a_normals (n, 3).  make: the fusion object's factory
-    (tests).  a_faces (m, 3): A is a mesh, loaded through set_mesh as well, and the result gains "surface"."""
+    (tests).  a_faces (m, 3): A is a mesh, loaded through set_mesh as well, and the result gains "surface" (unless
+    surface is False) and, with mesh_samples (a spacing), "mesh_samples"."""
+    if mesh_samples is not None and a_faces is None:
+        raise ValueError("the mesh samples need A's faces")
     if align_plane_iterations is not None and (align is None or a_normals is None):
         raise ValueError("the plane stage needs align and A's normals")
     cam = np.zeros(1, capi.CAMERA_DTYPE)
@@ -53,8 +60,10 @@ def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=No
         info = pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
         if registered is not None:
             info["align"] = registered
-        if a_faces is not None:
+        if a_faces is not None and surface:
             info["surface"] = pipeline.evaluate_surface(fu, "scene", max_dist, thresholds, info["accuracy"])
+        if mesh_samples is not None:
+            info["mesh_samples"] = pipeline.evaluate_mesh_samples(fu, mesh_samples, max_dist, thresholds)
         return info
     finally:
         if hasattr(fu, "close"):
@@ -74,17 +83,19 @@ def main(argv=None):
     ap.add_argument("--align-plane-iterations", type=int, default=None,
                     help="with --align: then at most this many point-to-plane iterations along A's normals")
     ap.add_argument("--surface", action="store_true", help="A is a mesh PLY: also measure against its faces")
+    ap.add_argument("--mesh-samples", metavar="SPACING", type=float, default=None,
+                    help="A is a mesh PLY: also sample its surface, one point per SPACING^2, and measure the samples")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if a.align_plane_iterations is not None and a.align is None:
         ap.error("--align-plane-iterations needs --align")
     normals = None
-    if a.align_plane_iterations is not None and not a.surface:
+    if a.align_plane_iterations is not None and not a.surface and a.mesh_samples is None:
         rec = io.read_ply(a.a)
         normals = np.stack([rec["nx"], rec["ny"], rec["nz"]], 1)
     faces = None
-    if a.surface:
+    if a.surface or a.mesh_samples is not None:
         mesh_rec, faces = io.read_mesh_ply(a.a)
         a_xyz = np.ascontiguousarray(np.stack([mesh_rec["x"], mesh_rec["y"], mesh_rec["z"]], 1), np.float32)
         if a.align_plane_iterations is not None:
@@ -94,7 +105,7 @@ def main(argv=None):
     info = compare(a_xyz, pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device,
                    align=a.align, align_max_dist=a.align_max_dist, align_iterations=a.align_iterations,
                    align_stride=a.align_stride, align_plane_iterations=a.align_plane_iterations, a_normals=normals,
-                   a_faces=faces)
+                   a_faces=faces, surface=a.surface, mesh_samples=a.mesh_samples)
     info.update(a=a.a, b=a.b)
     if a.out:
         with open(a.out, "w") as f:
