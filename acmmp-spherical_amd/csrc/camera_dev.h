@@ -78,14 +78,23 @@ __device__ __forceinline__ float3 world_point_ray(Cam& c, int x, int y, float de
 //   max_abs / min_abs      the builtins (general operands; never signalling NaNs, so no canonicalisation)
 //   max_abs_nt / min_abs_nt inline asm, operands never a transcendental's result (the rigid transform's fmas)
 //   max_abs_h / min_abs_h  inline asm behind an s_nop 0, for the hypot operand
+// The asm maxima are v_max3_f32 with kMaxAbsFloor as third operand (one SGPR, no VALU more than v_max_f32): their only
+// use is as the divisor of the fast SPHERE projection's atan ratio min / max, and a point ON the source camera's
+// centre or vertical axis (both operands 0) would give 0 * rcp(0) = NaN there.  With the floor the ratio is 0, the
+// angle 0, and the pixel the principal point's coordinate -- ProjectonCamera_cu's `d < 1e-6 -> (cx, cy)` and its
+// atan2f(0, 0) = 0 (ACMMP.cu:618-631) for the exact zeros.  (tz must be +0 for that: a -0 takes sphere_pixel_fast's
+// `pi - r` branch and lands half a width away.  rigid_fast's last fma cancels x + (-x), which is +0 in round to
+// nearest.)  Every other operand pair is far above the floor and keeps its bits (tests/test_gpu_rigs.py's degenerate
+// queries).
 // The asm forms keep the scheduler's round-5 order in the fast SPHERE projections: both pairs on the builtins
 // measured k_eval_nb 1.444 ms against 1.428 ms this way (profiles/r06_ab8_hazard_ab.txt).
 // scripts/hazard_scan.py checks the device assembly for (transcendental, immediate reader) pairs.
 __device__ __forceinline__ float max_abs(float a, float b) { return __builtin_fmaxf(fabsf(a), fabsf(b)); }
 __device__ __forceinline__ float min_abs(float a, float b) { return __builtin_fminf(fabsf(a), fabsf(b)); }
+constexpr float kMaxAbsFloor = 1e-30f;
 __device__ __forceinline__ float max_abs_nt(float a, float b) {
     float r;
-    asm("v_max_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "s"(kMaxAbsFloor));
     return r;
 }
 __device__ __forceinline__ float min_abs_nt(float a, float b) {
@@ -95,7 +104,7 @@ __device__ __forceinline__ float min_abs_nt(float a, float b) {
 }
 __device__ __forceinline__ float max_abs_h(float a, float b) {
     float r;
-    asm("s_nop 0\n\tv_max_f32_e64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    asm("s_nop 0\n\tv_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "s"(kMaxAbsFloor));
     return r;
 }
 __device__ __forceinline__ float min_abs_h(float a, float b) {

@@ -120,15 +120,16 @@ __device__ __forceinline__ float depth_from_plane(float4 ph, float4 d) {
 // hardware v_rsq / v_sqrt / v_rcp (<= 1 ulp) instead of the IEEE division and square-root
 // sequences, the translation folded into the rotation's fma chain, W / 2pi and H / pi folded into
 // one constant, and the asin / atan2 polynomials without their special-argument paths (a point on
-// the source camera's vertical axis, tx = tz = 0, has no defined longitude; the reference's atan2f
-// returns 0 there, this returns NaN and the sample's cost is 2.0).  Not bit-identical to the
+// the source camera's centre or vertical axis, tx = tz = 0, has a zero divisor in the atan ratio:
+// max_abs_nt / max_abs_h floor it, camera_dev.h, so the angle is 0 as the reference's atan2f(0, 0)
+// and its d < 1e-6 substitution give, not NaN).  Not bit-identical to the
 // oracle: parity is the tolerance of SURVEY.md §8c (tests/test_gpu_fastmath.py).
 
 // Chunks whose VB views are all present compile without per-view guards (one basic block per sample):
 // every pinhole chunk (+17% at C2, V = 10: its 8-view chunk) and SPHERE chunks of at most 2 views
 // (k_eval_ref's 2-view chunks at V = 15 +4.7%; SPHERE's 4-view k_eval_nb chunks lose 1-3% that way,
 // longer live ranges -- r02 A/B profiles/r02_full_chunk_ab.txt).  The fast mode has no |t| < 1e-6 test
-// per view-sample (3 VALU; r02 A/B profiles/r02_micro_ab.txt: metric +2%, C3 +1.8%).
+// per view-sample (3 VALU; r02 A/B profiles/r02_micro_ab.txt: metric +2%, C3 +1.8%): the floored divisors stand in.
 
 // atan(t) on [0, 1]: t + t^3 P(t^2), 7-term minimax, max |error| 1.1e-7 rad
 __device__ __forceinline__ float atan_core_fast(float t) {
@@ -243,9 +244,8 @@ __device__ __forceinline__ void project_fast(Cam& c, float3 P, float& ox, float&
     rigid_fast(c, P, t, tz, ft);
     if (MODEL == kSphere) {
         sphere_pixel_fast(c, t, tz, ox, oy);
-        // |t| < 1e-6 (:618-622), a sample on a source camera's centre, is not tested: such a sample
-        // projects to NaN and its view's cost is 2.0 (the NCC clamp) -- the reference's tex2D of
-        // (cx, cy) there is as meaningless, and no real geometry reaches it
+        // |t| < 1e-6 (:618-622), a sample on a source camera's centre, is not tested: at t = 0 the
+        // floored atan divisors (max_abs_nt / max_abs_h) give the angles 0, i.e. (cx, cy) as the reference
     } else {
         // K (R_rel P + b) rows 0-1; the perspective divide by its row 2
         const f32x2 o = t * splat2(__builtin_amdgcn_rcpf(tz));

@@ -161,9 +161,9 @@ def source_edge_pixels(sc, p, n, seed, margin=6):
     return xs[pick].astype(np.int32), ys[pick].astype(np.int32)
 
 
-@functools.lru_cache(maxsize=None)
-def query_sets(kind, V, tex):
-    """The four query sets of one case: {set: (px (n,), py (n,), planes (n, 8, 4) float32)}.
+def query_sets_for(sc, p, seed, n=None):
+    """The four query sets of any rig (scene, params): {set: (px (n,), py (n,), planes (n, 8, 4) float32)}, n
+    pixels per set (default PIXELS[source views]).
       interior     random pixels at least 6 pixels inside, near-surface planes;
       border       the four corners and random pixels of the 6-pixel frame, near-surface planes;
       source_edge  pinhole: the surface point projects within 6 pixels of a source's edge; SPHERE: it lands
@@ -171,10 +171,8 @@ def query_sets(kind, V, tex):
       wild         interior pixels, planes of any orientation and +-40% depth (grazing planes, depth sign
                    flips inside the patch, centres outside the source), and on the first pixels one plane
                    each that contains a sample's ray (grazing_plane)."""
-    sc, p = make_case(kind, V, tex)
-    W, H = MODELS[kind]
-    n = PIXELS[V]
-    seed = 1000 * V + (0 if kind == "pinhole" else 500) + (0 if TEXELS[tex] else 250)
+    H, W = sc.images[0].shape
+    n = PIXELS[len(sc.images) - 1] if n is None else n
     out = {}
     px, py = ni.interior_pixels(W, H, n, seed + 1)
     out["interior"] = (px, py, ni.near_surface_planes(sc, px, py, PLANES, seed + 2))
@@ -189,6 +187,13 @@ def query_sets(kind, V, tex):
         planes[q, q % 5] = grazing_plane(sc, p, int(px[q]), int(py[q]), sample, rng)
     out["wild"] = (px, py, planes)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def query_sets(kind, V, tex):
+    """query_sets_for on one case of the instance matrix."""
+    sc, p = make_case(kind, V, tex)
+    return query_sets_for(sc, p, 1000 * V + (0 if kind == "pinhole" else 500) + (0 if TEXELS[tex] else 250))
 
 
 def f64_ncc(sc, p, px, py, planes, diagnostics=False):
@@ -271,28 +276,37 @@ def flat_queries(px, py, planes):
     return np.repeat(px, k), np.repeat(py, k), planes.reshape(-1, 4)
 
 
-@functools.lru_cache(maxsize=None)
-def f64_costs(kind, V, tex, name):
-    """Float64 costs of one set, (n, 8, V), with the diagnostics -- computed once per process and left unchanged."""
-    sc, p = make_case(kind, V, tex)
-    px, py, planes = query_sets(kind, V, tex)[name]
+def f64_costs_for(sc, p, px, py, planes):
+    """Float64 costs of one set of any rig, (n, 8, V), with the diagnostics; the costs are left read-only."""
     cost, diag = f64_ncc(sc, p, *flat_queries(px, py, planes), diagnostics=True)
-    cost = cost.reshape(len(px), PLANES, V)
+    cost = cost.reshape(len(px), planes.shape[1], len(sc.images) - 1)
     cost.setflags(write=False)
     return cost, diag
 
 
-def oracle_costs(oracle_mod, kind, V, tex, name):
-    """oracle.ncc (binary32, CPU) of one set: (n, 8, V) float32."""
+@functools.lru_cache(maxsize=None)
+def f64_costs(kind, V, tex, name):
+    """f64_costs_for on one set of one case -- computed once per process and left unchanged."""
     sc, p = make_case(kind, V, tex)
-    px, py, planes = query_sets(kind, V, tex)[name]
+    return f64_costs_for(sc, p, *query_sets(kind, V, tex)[name])
+
+
+def oracle_costs_for(oracle_mod, sc, p, px, py, planes):
+    """oracle.ncc (binary32, CPU) of one set of any rig: (n, 8, V) float32."""
+    V = len(sc.images) - 1
     prob = oracle_mod.Problem(sc.images, sc.cameras, p)
-    out = np.empty((len(px), PLANES, V), np.float32)
+    out = np.empty((len(px), planes.shape[1], V), np.float32)
     for q in range(len(px)):
-        for h in range(PLANES):
+        for h in range(planes.shape[1]):
             for v in range(V):
                 out[q, h, v] = oracle_mod.ncc(prob, v + 1, int(px[q]), int(py[q]), planes[q, h])
     return out
+
+
+def oracle_costs(oracle_mod, kind, V, tex, name):
+    """oracle_costs_for on one set of one case."""
+    sc, p = make_case(kind, V, tex)
+    return oracle_costs_for(oracle_mod, sc, p, *query_sets(kind, V, tex)[name])
 
 
 def reform_initial_cost(costs, top_k):
