@@ -129,6 +129,7 @@ EXPORTS = [
     "acmmp_fusion_mesh_sample", "acmmp_fusion_sample_points",
     "acmmp_fusion_set_cloud_transform", "acmmp_fusion_get_cloud_transform", "acmmp_fusion_cloud_align",
     "acmmp_fusion_align_records", "acmmp_fusion_cloud_align_plane", "acmmp_fusion_align_plane_records",
+    "acmmp_fusion_set_region", "acmmp_fusion_get_region", "acmmp_fusion_region_classify", "acmmp_fusion_region_classes",
     "acmmp_image_cache_create", "acmmp_image_cache_destroy", "acmmp_image_cache_stats",
     "acmmp_upload_views_keyed", "acmmp_device_checksum", "acmmp_device_identity", "acmmp_clock_probe",
 ]
@@ -286,6 +287,10 @@ def load_library(path: str = LIB_PATH):
     L.acmmp_fusion_align_records.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
     L.acmmp_fusion_cloud_align_plane.argtypes = [vp, i32, C.c_float, i32, i32, C.c_double, vp, vp, vp, vp]
     L.acmmp_fusion_align_plane_records.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, vp]
+    L.acmmp_fusion_set_region.argtypes = [vp, i32, vp, i32]
+    L.acmmp_fusion_get_region.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.acmmp_fusion_region_classify.argtypes = [vp, i32, vp]
+    L.acmmp_fusion_region_classes.argtypes = [vp, C.c_int64, C.c_int64, vp]
     L.acmmp_planar_prior_host.argtypes = [vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp]
     L.acmmp_set_planar_prior_from_maps.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp]
     L.acmmp_set_planar_prior_from_state.argtypes = [vp, C.c_float, C.c_float, vp]
@@ -940,6 +945,51 @@ DIST_SUMMARY_WORDS = 268     # ACMMP_DIST_SUMMARY_WORDS: n_query, n_valid, n_mat
 ALIGN_MODES = {"rigid": 0, "similarity": 1}     # ACMMP_ALIGN_RIGID, ACMMP_ALIGN_SIMILARITY
 ALIGN_STOP_REASONS = ("max_iterations", "converged", "degenerate")     # ACMMP_ALIGN_MAX_ITERATIONS, _CONVERGED, _DEGENERATE
 ALIGN_RECORD_WORDS = 32     # ACMMP_ALIGN_RECORD_WORDS: n_query, n_valid, n_matched, sum_q, n_out_of_range, N, the moments
+REGION_SIDES = {"data": 0, "reference": 1}     # ACMMP_REGION_DATA, ACMMP_REGION_REFERENCE
+REGION_QUERIES_ONLY = 1     # ACMMP_REGION_QUERIES_ONLY
+REGION_SOURCES = dict(DIST_SOURCES, reference=SURF_QUERIES["reference"])     # what region_classify takes
+REGION_COUNTS = ("points", "invalid", "inside", "planes", "prism", "grid")     # ACMMP_REGION_COUNT_WORDS words
+REGION_CLASS_BITS = {"invalid": 1, "planes": 2, "prism": 4, "grid": 8}     # ACMMP_REGION_CLASS_*
+
+
+class RegionStruct(C.Structure):
+    """acmmp_region (include/acmmp.h)."""
+    _fields_ = [("n_planes", C.c_int32), ("n_vertices", C.c_int32), ("axis", C.c_int32), ("dims", C.c_int32 * 3),
+                ("planes", C.c_double * 32), ("axis_min", C.c_double), ("axis_max", C.c_double),
+                ("origin", C.c_double * 3), ("cell", C.c_double), ("polygon", C.c_void_p), ("bits", C.c_void_p)]
+
+
+def region_struct(region):
+    """(RegionStruct, the arrays it points into) of an io.Region-like object: planes, axis, axis_min, axis_max, polygon,
+    origin, cell, dims, bits, a part absent where its array is None.  Shapes are checked here; values by the library."""
+    st, keep = RegionStruct(), []
+    if region.planes is not None:
+        pl = np.ascontiguousarray(region.planes, np.float64).reshape(-1, 4)
+        if pl.shape[0] > 8:
+            raise ValueError("at most 8 planes")
+        st.n_planes = pl.shape[0]
+        st.planes[:pl.size] = pl.reshape(-1).tolist()
+    if region.polygon is not None:
+        poly = np.ascontiguousarray(region.polygon, np.float64).reshape(-1, 2)
+        if not 3 <= poly.shape[0] <= 256:
+            raise ValueError("the polygon has 3 to 256 vertices")
+        st.n_vertices, st.axis = poly.shape[0], int(region.axis)
+        st.axis_min, st.axis_max = float(region.axis_min), float(region.axis_max)
+        st.polygon = poly.ctypes.data
+        keep.append(poly)
+    if region.dims is not None:
+        dims = [int(x) for x in region.dims]
+        if len(dims) != 3 or not all(1 <= x <= 4096 for x in dims):
+            raise ValueError("dims are three integers in 1 .. 4096")
+        bits = np.ascontiguousarray(region.bits, np.uint8).reshape(-1)
+        if bits.size != (dims[0] * dims[1] * dims[2] + 7) // 8:
+            raise ValueError("bits must hold ceil(nx ny nz / 8) bytes")
+        st.dims[:] = dims
+        st.origin[:] = [float(x) for x in np.asarray(region.origin, np.float64).reshape(3)]
+        st.cell = float(region.cell)
+        st.bits = bits.ctypes.data
+        keep.append(bits)
+    return st, keep
 
 
 @dataclasses.dataclass
@@ -1538,6 +1588,56 @@ class Fusion:
                     "fusion_align_plane_records")
         return [AlignPlaneRecord(words=w[k].copy(), M=M[k].reshape(3, 4).copy(), shift=float(sh[k]),
                                  max_dist=float(np.float32(max_dist))) for k in range(n)]
+
+    def set_region(self, side: str, region, queries_only: bool = False):
+        """Sets the evaluation region of a side of the comparison, "data" (every data cloud, read under the transform)
+        or "reference" (acmmp_fusion_set_region, include/acmmp.h): cloud_distance, surface_distance, cloud_align and
+        cloud_align_plane then treat the side's points outside it as invalid.  region: an io.Region (io.read_region), or
+        None to clear.  queries_only: the points outside stay targets.  The region is copied and stays until it is
+        replaced; a set or clear discards the distance, surface and align results."""
+        if side not in REGION_SIDES:
+            raise ValueError('side must be "data" or "reference"')
+        flags = REGION_QUERIES_ONLY if queries_only else 0
+        if region is None:
+            self._check(self.L.acmmp_fusion_set_region(self.h, REGION_SIDES[side], None, flags), "fusion_set_region")
+            return
+        st, keep = region_struct(region)
+        self._check(self.L.acmmp_fusion_set_region(self.h, REGION_SIDES[side], C.byref(st), flags), "fusion_set_region")
+        del keep
+
+    def region(self, side: str):
+        """What is set for a side: None, or {"queries_only", "n_planes", "n_vertices", "dims"}."""
+        if side not in REGION_SIDES:
+            raise ValueError('side must be "data" or "reference"')
+        w = np.zeros(7, np.int32)
+        self._check(self.L.acmmp_fusion_get_region(self.h, REGION_SIDES[side], _p(w[0:1]), _p(w[1:2]), _p(w[2:3]),
+                                                   _p(w[3:4]), _p(w[4:7])), "fusion_get_region")
+        if not w[0]:
+            return None
+        return {"queries_only": bool(w[1] & REGION_QUERIES_ONLY), "n_planes": int(w[2]), "n_vertices": int(w[3]),
+                "dims": tuple(int(x) for x in w[4:7])}
+
+    def region_classify(self, source: str) -> dict:
+        """Classifies the resident cloud `source` (a cloud_distance source, or "reference") under the region of its side,
+        a data cloud under the transform that is set: {"points", "invalid", "inside", "planes", "prism", "grid"}, the last
+        three the points each part fails.  The class bytes stay on the GPU (region_classes)."""
+        if source not in REGION_SOURCES:
+            raise ValueError('source must be one of ' + ", ".join(REGION_SOURCES))
+        out = np.zeros(len(REGION_COUNTS), np.int64)
+        self._check(self.L.acmmp_fusion_region_classify(self.h, REGION_SOURCES[source], _p(out)), "fusion_region_classify")
+        self._region_points = int(out[0])
+        return {k: int(v) for k, v in zip(REGION_COUNTS, out)}
+
+    def region_classes(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """(n,) uint8 class bytes of points [first, first + n) of the last region_classify (n None: to the end): 0 =
+        inside, else REGION_CLASS_BITS or-ed."""
+        if first < 0 or (n is not None and n < 0):
+            raise ValueError("first and n must be >= 0")
+        if n is None:
+            n = max(getattr(self, "_region_points", 0) - first, 0)
+        cls = np.empty(n, np.uint8)
+        self._check(self.L.acmmp_fusion_region_classes(self.h, first, n, _p(cls)), "fusion_region_classes")
+        return cls
 
     def close(self):
         if self.h:

@@ -347,3 +347,70 @@ def read_mesh_ply(path: str):
     if len(data) != at + nf * _PLY_FACE.itemsize or (rec["n"] != 3).any():
         raise ValueError("not a triangle mesh of write_mesh_ply's layout")
     return verts, rec["v"].astype(np.int32)
+
+
+@dataclass
+class Region:
+    """An evaluation region (acmmp_fusion_set_region, include/acmmp.h): the intersection of the parts that are not None.
+    planes (k, 4) float64 half-spaces a x + b y + c z + d >= 0; prism: axis w, [axis_min, axis_max] along it and polygon
+    (n, 2) float64 in the other two coordinates in increasing index order; grid: origin (3,), cell, dims (nx, ny, nz) and
+    bits, ceil(nx ny nz / 8) bytes, cell (ix, iy, iz) at bit k & 7 (least significant first) of byte k >> 3 with
+    k = ix + nx (iy + ny iz)."""
+    planes: np.ndarray | None = None
+    axis: int = 0
+    axis_min: float = 0.0
+    axis_max: float = 0.0
+    polygon: np.ndarray | None = None
+    origin: np.ndarray | None = None
+    cell: float = 0.0
+    dims: tuple | None = None
+    bits: np.ndarray | None = None
+
+
+def read_region(path: str) -> Region:
+    """An evaluation region from a JSON file of either kind:
+    an Open3D SelectionPolygonVolume as Tanks and Temples ships its crop files ("class_name", "orthogonal_axis" "X", "Y"
+    or "Z", "axis_min", "axis_max", "bounding_polygon" of xyz triples, of which the two coordinates other than the axis are
+    taken, in increasing index order); or the project's own {"planes": [[a, b, c, d], ...], "prism": {"axis": 0|1|2, "min":,
+    "max":, "polygon": [[u, v], ...]}, "grid": {"origin": [x, y, z], "cell":, "dims": [nx, ny, nz], "bits": "file.bin"}},
+    every part optional, the bits file relative to the JSON.  The bits file is the grid packed eight cells to a byte, least
+    significant bit first, x fastest.  There is no .mat reader: a DTU ObsMask(ix, iy, iz) is exported in MATLAB's own
+    column-major order, ObsMask(:), which is already x fastest -- pad it with zeros to a multiple of 8 and pack each run of
+    8 cells into one byte, the first cell in bit 0; from numpy that is np.packbits(mask.ravel(order="F"),
+    bitorder="little") for mask[ix, iy, iz].  The origin is the centre of cell (0, 0, 0) (DTU: BB(1, :)) and cell the
+    grid's resolution, since a point's cell is rint((p - origin) / cell)."""
+    import json
+    with open(path) as f:
+        d = json.load(f)
+    r = Region()
+    if "class_name" in d:
+        if d["class_name"] != "SelectionPolygonVolume":
+            raise ValueError(f"{path}: class_name {d['class_name']!r} is not SelectionPolygonVolume")
+        axis = {"X": 0, "Y": 1, "Z": 2}.get(str(d["orthogonal_axis"]).upper())
+        if axis is None:
+            raise ValueError(f"{path}: orthogonal_axis must be X, Y or Z")
+        poly = np.asarray(d["bounding_polygon"], np.float64).reshape(-1, 3)
+        r.axis, r.axis_min, r.axis_max = axis, float(d["axis_min"]), float(d["axis_max"])
+        r.polygon = np.ascontiguousarray(poly[:, [k for k in range(3) if k != axis]])
+        return r
+    unknown = set(d) - {"planes", "prism", "grid"}
+    if unknown:
+        raise ValueError(f"{path}: unknown keys {sorted(unknown)}")
+    if d.get("planes"):
+        r.planes = np.ascontiguousarray(np.asarray(d["planes"], np.float64).reshape(-1, 4))
+    if "prism" in d:
+        p = d["prism"]
+        r.axis, r.axis_min, r.axis_max = int(p["axis"]), float(p["min"]), float(p["max"])
+        r.polygon = np.ascontiguousarray(np.asarray(p["polygon"], np.float64).reshape(-1, 2))
+    if "grid" in d:
+        g = d["grid"]
+        r.origin = np.asarray(g["origin"], np.float64).reshape(3)
+        r.cell = float(g["cell"])
+        r.dims = tuple(int(x) for x in g["dims"])
+        if len(r.dims) != 3 or min(r.dims) < 1:
+            raise ValueError(f"{path}: dims must be three positive integers")
+        r.bits = np.fromfile(os.path.join(os.path.dirname(os.path.abspath(path)), g["bits"]), np.uint8)
+        need = (r.dims[0] * r.dims[1] * r.dims[2] + 7) // 8
+        if r.bits.size != need:
+            raise ValueError(f"{path}: the bits file holds {r.bits.size} bytes, the grid needs {need}")
+    return r

@@ -800,7 +800,8 @@ class Pipeline:
                    eval_align: str | None = None, eval_align_max_dist: float | None = None,
                    eval_align_iterations: int | None = None, eval_align_stride: int | None = None,
                    eval_align_plane_iterations: int | None = None, eval_surface: bool = False,
-                   eval_mesh_samples: float | None = None):
+                   eval_mesh_samples: float | None = None, eval_region_data=None, eval_region_reference=None,
+                   eval_region_queries_only: bool = False):
         """Fuse every view's final depth map on this rank's GPU (rank 0 when sharded: the other ranks
         broadcast their normals to it first; depths_geom were exchanged after the last pass).
         Returns the (n, 9) points and writes ACMMP/ACMM_model_cuda_5.ply when an output folder is set.
@@ -882,11 +883,24 @@ class Pipeline:
         against the reference cloud in both directions; eval_info and eval.json gain "mesh_samples": {"spacing",
         "seed", "n_samples", "n_skipped", "accuracy", "completeness", "thresholds"} (evaluate_mesh_samples): the
         accuracy of the mesh's surface, weighted by area.  Nothing else in eval.json changes.
+
+        eval_region_data, eval_region_reference (a region file of io.read_region, or an io.Region; eval_cloud is then
+        required): the evaluation region of the measured side and of the reference side (acmmp_fusion_set_region,
+        include/acmmp.h) -- a Tanks and Temples crop volume, a DTU observation mask, planes -- in the reference cloud's
+        frame.  They are set before eval_align, so the registration runs cropped under each iteration's transform, and
+        every measurement after it counts only the points inside.  eval_region_queries_only: the measured side's points
+        outside its region still serve as targets (DTU's completeness).  eval_info and eval.json gain "region": {"data":
+        {"file", "queries_only", "counts"}, "reference": {...}} for the sides that have one, counts = region_classify
+        under the final transform.
         """
         self.fusion_info = None
         self.eval_info = None
         if eval_mesh_samples is not None and (eval_cloud is None or mesh_trunc is None):
             raise ValueError("eval_mesh_samples needs eval_cloud and the mesh (mesh_trunc)")
+        if eval_cloud is None and (eval_region_data is not None or eval_region_reference is not None or eval_region_queries_only):
+            raise ValueError("the evaluation regions need eval_cloud")
+        if eval_region_queries_only and eval_region_data is None:
+            raise ValueError("eval_region_queries_only needs eval_region_data")
         if eval_surface and (eval_cloud is None or mesh_trunc is None):
             raise ValueError("eval_surface needs eval_cloud and the mesh (mesh_trunc)")
         if eval_align_plane_iterations is not None and eval_align is None:
@@ -1025,6 +1039,13 @@ class Pipeline:
                 written = ("scene" if voxel_size is None else "visible" if visibility_tol is not None
                            else "clean" if clean else "voxels")
                 fu.set_reference_cloud(reference_xyz(eval_cloud))
+                regions = {"data": eval_region_data, "reference": eval_region_reference}
+                if any(r is not None for r in regions.values()) and not hasattr(fu, "set_region"):
+                    raise ValueError("the evaluation regions need a fusion object with set_region (capi.Fusion)")
+                for side, r in regions.items():                       # before the registration: ICP runs cropped
+                    if r is not None:
+                        fu.set_region(side, io.read_region(os.fspath(r)) if isinstance(r, (str, os.PathLike)) else r,
+                                      queries_only=eval_region_queries_only and side == "data")
                 align = None
                 if eval_align is not None:
                     if not hasattr(fu, "cloud_align"):
@@ -1039,6 +1060,13 @@ class Pipeline:
                 self.eval_info = evaluate_clouds(fu, eval_source or written, eval_max_dist, eval_thresholds)
                 if align is not None:
                     self.eval_info["align"] = align
+                if any(r is not None for r in regions.values()):
+                    clouds = {"data": eval_source or written, "reference": "reference"}
+                    self.eval_info["region"] = {
+                        side: {"file": os.fspath(r) if isinstance(r, (str, os.PathLike)) else None,
+                               "queries_only": bool(eval_region_queries_only and side == "data"),
+                               "counts": fu.region_classify(clouds[side])}
+                        for side, r in regions.items() if r is not None}
                 if eval_surface:
                     if not hasattr(fu, "surface_distance"):
                         raise ValueError("the surface evaluation needs a fusion object with surface_distance (capi.Fusion)")
@@ -1303,6 +1331,16 @@ def arg_parser():
     ap.add_argument("--eval-surface", action="store_true",
                     help="with --eval-cloud and a mesh: also measure the reference cloud and the written cloud against the "
                          "mesh's faces (point-to-triangle); eval.json gains \"surface\"")
+    ap.add_argument("--eval-region-data", metavar="FILE", default=None,
+                    help="with --eval-cloud: measure only the points of the measured cloud inside this region, given in the "
+                         "reference cloud's frame: an Open3D SelectionPolygonVolume JSON (a Tanks and Temples crop file) or "
+                         "the project's region JSON (planes, prism, bit grid); set before --eval-align, so the registration "
+                         "runs cropped; eval.json gains \"region\"")
+    ap.add_argument("--eval-region-reference", metavar="FILE", default=None,
+                    help="with --eval-cloud: the same for the reference cloud's points")
+    ap.add_argument("--eval-region-queries-only", action="store_true",
+                    help="with --eval-region-data: the measured cloud's points outside the region are not measured but "
+                         "still serve as targets of the reference points (DTU's completeness)")
     ap.add_argument("--eval-mesh-samples", metavar="SPACING", type=float, default=None,
                     help="with --eval-cloud and a mesh: sample the mesh's surface on the GPU, about one point per SPACING^2 of "
                          "area, and measure the samples against the reference cloud in both directions; eval.json gains "
@@ -1345,7 +1383,9 @@ def main(argv=None):
                               eval_align=a.eval_align, eval_align_max_dist=a.eval_align_max_dist,
                               eval_align_iterations=a.eval_align_iterations, eval_align_stride=a.eval_align_stride,
                               eval_align_plane_iterations=a.eval_align_plane_iterations, eval_surface=a.eval_surface,
-                              eval_mesh_samples=a.eval_mesh_samples)
+                              eval_mesh_samples=a.eval_mesh_samples, eval_region_data=a.eval_region_data,
+                              eval_region_reference=a.eval_region_reference,
+                              eval_region_queries_only=a.eval_region_queries_only)
         n_points = None if pts is None else int(pts.shape[0])
     dt = time.perf_counter() - t0
     line = {"rank": pipe.rank, "world": pipe.world, "views": len(pipe.my_problems()),

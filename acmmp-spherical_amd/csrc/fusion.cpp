@@ -169,6 +169,37 @@ struct AlignRec {
     Res source = R_NONE;
     bool have = false;
 };
+// The region of one side (acmmp_fusion_set_region): the caller's struct with its two arrays copied to the device.  It
+// is no result: it is replaced by a set and by nothing else.
+struct RegionSet {
+    bool set = false;
+    int flags = 0;
+    acmmp_region r = {};                         // polygon and bits NULL: the copies are below
+    DevBuf<double> poly;                         // (u, v) per vertex
+    DevBuf<uint8_t> bits;
+    RegionDev dev() const {
+        RegionDev d = {};
+        if (!set) return d;                      // no part: every valid point is inside
+        d.n_planes = r.n_planes;
+        std::memcpy(d.planes, r.planes, sizeof(d.planes));
+        d.n_vertices = r.n_vertices;
+        d.axis = r.axis;
+        d.axis_min = r.axis_min;
+        d.axis_max = r.axis_max;
+        d.poly = poly;
+        for (int a = 0; a < 3; ++a) { d.dims[a] = r.dims[a]; d.o[a] = r.origin[a]; }
+        d.cell = r.cell;
+        d.bits = bits;
+        return d;
+    }
+};
+// The class result of acmmp_fusion_region_classify: `source` is the cloud classified.
+struct RegionRec {
+    DevBuf<uint8_t> cls;                         // per point
+    unsigned long long n = 0;                    // points
+    Res source = R_NONE;
+    bool have = false;
+};
 
 }  // namespace
 
@@ -208,6 +239,9 @@ struct acmmp_fusion {
     RefRec ref;                                  // acmmp_fusion_set_reference_cloud
     DistRec dist, surf;                          // acmmp_fusion_cloud_distance, acmmp_fusion_surface_distance
     AlignRec align;                              // acmmp_fusion_cloud_align, acmmp_fusion_cloud_align_plane
+    RegionRec classes;                           // acmmp_fusion_region_classify
+    // the evaluation regions of the data and the reference side (acmmp_fusion_set_region)
+    RegionSet region[2];
     // the transform of the data cloud (acmmp_fusion_set_cloud_transform)
     bool xf_set = false;
     double xf[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
@@ -227,7 +261,7 @@ struct acmmp_fusion {
     SegScratch seg;                              // of voxelize's compaction and of every later stage's
     DevBuf<int> vis_list;                        // the view list, kVisMaxList positions
     DevBuf<unsigned long long> v_words;          // kVoxWords run words, then the 3 minima (32-bit each, in 2 words)
-    DevBuf<unsigned long long> c_words, vis_words, m_words, r_words, dist_words, surf_words, smp_words;   // k*Words device words each
+    DevBuf<unsigned long long> c_words, vis_words, m_words, r_words, dist_words, surf_words, smp_words, reg_words;   // k*Words device words each
     std::string err;
 };
 
@@ -400,6 +434,7 @@ void invalidate(acmmp_fusion* f, Res what) {
     drop(f->dist, R_DIST);
     drop(f->surf, R_SURF);
     drop(f->align, R_ALIGN);
+    drop(f->classes, R_CLASSES);
     if (what == R_SCENE) {
         f->v_tab = VoxTableBuf();
         f->v_tab_spare = VoxTableBuf();
@@ -440,6 +475,18 @@ acmmp_status run_failed(acmmp_fusion* f, acmmp_status st) {
     (void)hipStreamSynchronize(f->stream);
     f->err = why;
     return st;
+}
+
+// The pre-pass of a measuring call for one cloud: where its side's region rs applies -- it is set, and the cloud is a
+// query or the region is not ACMMP_REGION_QUERIES_ONLY -- the classes of `read_as` (the cloud as the region reads it) go
+// to buf, the call's scratch, on the stream, and c reads through them.  Otherwise c is as it was: the path without a region.
+acmmp_status region_crop(acmmp_fusion* f, const RegionSet& rs, bool as_target, const DistCloud& read_as, DevBuf<uint8_t>& buf,
+                         DistCloud& c) {
+    if (!rs.set || (as_target && (rs.flags & ACMMP_REGION_QUERIES_ONLY))) return ACMMP_OK;
+    F_HIP(f, alloc(buf, static_cast<size_t>(c.n)));
+    F_HIP(f, launch_region_classify(read_as, rs.dev(), buf, nullptr, f->stream));
+    c.cls = buf;
+    return ACMMP_OK;
 }
 
 bool finite32(float x) {
@@ -1551,6 +1598,7 @@ struct DistOut : DistRec {
     DevBuf<unsigned long long> keys, ckeys;                // scratch: the cell table and the coarse table
     DevBuf<uint32_t> start, cnt;
     DevBuf<float4> list;                                   // scratch: the cells' lists
+    DevBuf<uint8_t> qcls, tcls;                            // scratch: the classes of a cropped query and target cloud
     double cell = 0.0;
     unsigned long long words[kDistWords] = {0};
 };
@@ -1717,12 +1765,17 @@ acmmp_status acmmp_fusion_cloud_distance(acmmp_fusion* f, int source, int direct
     if (f->dist_force_cell != 0.0f && (!finite32(f->dist_force_cell) || !(f->dist_force_cell > 0.0f)))
         return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "the forced cell must be finite and > 0");
     const DistCloud ref = cloud(f, R_REFERENCE).dist();
-    const DistCloud q = direction == ACMMP_DIST_DATA_TO_REF ? data : ref;
-    const DistCloud t = direction == ACMMP_DIST_DATA_TO_REF ? ref : data;
+    const bool d2r = direction == ACMMP_DIST_DATA_TO_REF;
+    DistCloud q = d2r ? data : ref;
+    DistCloud t = d2r ? ref : data;
     if (t.n > 0x7fffffffull) return ffail(f, ACMMP_ERR_UNSUPPORTED, "more than 2^31 - 1 targets");
     F_HIP(f, hipSetDevice(f->device));
     DistOut out;
-    const acmmp_status st = distance_run(f, q, t, max_dist, n_tau, tau, out);
+    const RegionSet& qr = f->region[d2r ? ACMMP_REGION_DATA : ACMMP_REGION_REFERENCE];
+    const RegionSet& tr = f->region[d2r ? ACMMP_REGION_REFERENCE : ACMMP_REGION_DATA];
+    acmmp_status st = region_crop(f, qr, false, q, out.qcls, q);
+    if (st == ACMMP_OK) st = region_crop(f, tr, true, t, out.tcls, t);
+    if (st == ACMMP_OK) st = distance_run(f, q, t, max_dist, n_tau, tau, out);
     if (st != ACMMP_OK) return run_failed(f, st);
     out.n = q.n;
     out.source = id;
@@ -1768,6 +1821,7 @@ struct SurfOut : DistRec {
     DevBuf<unsigned long long> keys;                       // scratch: the cell table
     DevBuf<uint32_t> start, cnt;
     DevBuf<float4> list, large;                            // scratch: the cells' lists and the overflow list
+    DevBuf<uint8_t> qcls;                                  // scratch: the classes of a cropped query cloud
     double cell = 0.0;
     unsigned long long valid_faces = 0;
     unsigned long long words[kSurfWords] = {0};
@@ -1876,7 +1930,7 @@ acmmp_status acmmp_fusion_surface_distance(acmmp_fusion* f, int query, float max
     const Res id = surf_source(query);
     if (id == R_NONE) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "query must be one of ACMMP_SURF_FROM_*");
     const Cloud src = cloud(f, id);
-    const DistCloud q = src.dist();
+    DistCloud q = src.dist();
     if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such query result");
     if (!f->mesh.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no mesh result: acmmp_fusion_voxel_mesh or acmmp_fusion_set_mesh first");
     const acmmp_status taus = check_tau_list(f, max_dist, n_tau, tau);
@@ -1893,7 +1947,15 @@ acmmp_status acmmp_fusion_surface_distance(acmmp_fusion* f, int query, float max
     }
     F_HIP(f, hipSetDevice(f->device));
     SurfOut out;
-    const acmmp_status st = surface_run(f, q, m, max_dist, n_tau, tau, out);
+    // the query side's region: a data query is classified where the region lives, under the transform that is set
+    DistCloud read_as = q;
+    if (id != R_REFERENCE && f->xf_set) {
+        read_as.xf = 1;
+        std::memcpy(read_as.M, f->xf, sizeof(read_as.M));
+    }
+    acmmp_status st = region_crop(f, f->region[id == R_REFERENCE ? ACMMP_REGION_REFERENCE : ACMMP_REGION_DATA], false, read_as,
+                                  out.qcls, q);
+    if (st == ACMMP_OK) st = surface_run(f, q, m, max_dist, n_tau, tau, out);
     if (st != ACMMP_OK) return run_failed(f, st);
     out.n = q.n;
     out.source = id;
@@ -2080,8 +2142,16 @@ acmmp_status align_run(acmmp_fusion* f, DistCloud data, DistCloud ref, int mode,
     hipStream_t s = f->stream;
     DistOut scratch;
     DistIndex ix;
+    const acmmp_status rc = region_crop(f, f->region[ACMMP_REGION_REFERENCE], true, ref, scratch.tcls, ref);
+    if (rc != ACMMP_OK) return rc;
     const acmmp_status st = distance_build(f, ref, max_dist, 0, nullptr, scratch, ix);   // the one build of the call
     if (st != ACMMP_OK) return st;
+    // the data side's region follows the transform: its classes are formed again under every M_k
+    const RegionSet& dr = f->region[ACMMP_REGION_DATA];
+    if (dr.set) {
+        F_HIP(f, alloc(scratch.qcls, static_cast<size_t>(data.n)));
+        data.cls = scratch.qcls;
+    }
     out.cell = scratch.cell;
     unsigned long long* w = f->dist_words;
     unsigned long long* rec = w + kDistSummary;            // the summary's words are free in an align call
@@ -2093,6 +2163,7 @@ acmmp_status align_run(acmmp_fusion* f, DistCloud data, DistCloud ref, int mode,
     for (int k = 0; k < max_iterations; ++k) {
         unsigned long long h[kDistSummary + kAlignWords];
         F_HIP(f, hipMemsetAsync(rec, 0, sizeof(unsigned long long) * kAlignWords, s));
+        if (dr.set) F_HIP(f, launch_region_classify(data, dr.dev(), scratch.qcls, nullptr, s));
         F_HIP(f, launch_align_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, w, rec, s));
         // the iteration's host wait: the record, from which the host fits and decides whether to stop
         F_HIP(f, hipMemcpyAsync(h, w, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -2262,8 +2333,16 @@ acmmp_status align_plane_run(acmmp_fusion* f, DistCloud data, DistCloud ref, flo
     hipStream_t s = f->stream;
     DistOut scratch;
     DistIndex ix;
+    const acmmp_status rc = region_crop(f, f->region[ACMMP_REGION_REFERENCE], true, ref, scratch.tcls, ref);
+    if (rc != ACMMP_OK) return rc;
     const acmmp_status st = distance_build(f, ref, max_dist, 0, nullptr, scratch, ix);   // the one build of the call
     if (st != ACMMP_OK) return st;
+    // the data side's region follows the transform: its classes are formed again under every M_k
+    const RegionSet& dr = f->region[ACMMP_REGION_DATA];
+    if (dr.set) {
+        F_HIP(f, alloc(scratch.qcls, static_cast<size_t>(data.n)));
+        data.cls = scratch.qcls;
+    }
     out.cell = scratch.cell;
     unsigned long long* w = f->dist_words;
     unsigned long long* rec = w + kDistSummary;            // the summary's words are free in an align call
@@ -2277,6 +2356,10 @@ acmmp_status align_plane_run(acmmp_fusion* f, DistCloud data, DistCloud ref, flo
     {
         // the pivot pass: the point kernel under M_0, for the mean target only; not an iteration
         const acmmp_status ck = align_pass(f, ix, kAlignWords, h, [&] {
+            if (dr.set) {
+                const hipError_t e = launch_region_classify(data, dr.dev(), scratch.qcls, nullptr, s);
+                if (e != hipSuccess) return e;
+            }
             return launch_align_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, w, rec, s);
         });
         if (ck != ACMMP_OK) return ck;
@@ -2287,6 +2370,10 @@ acmmp_status align_plane_run(acmmp_fusion* f, DistCloud data, DistCloud ref, flo
     for (int k = 0; k < max_iterations; ++k) {
         // the iteration's host wait: the record, from which the host fits and decides whether to stop
         const acmmp_status ck = align_pass(f, ix, kAlignPlaneWords, h, [&] {
+            if (dr.set) {
+                const hipError_t e = launch_region_classify(data, dr.dev(), scratch.qcls, nullptr, s);
+                if (e != hipSuccess) return e;
+            }
             return launch_align_plane_iter(data, stride, ref, ix.g, ix.fine, ix.cg, ix.coarse, scratch.list, ix.p, kq, pivot,
                                            w, rec, s);
         });
@@ -2429,6 +2516,147 @@ acmmp_status acmmp_fusion_cloud_align_plane(acmmp_fusion* f, int source, float m
 acmmp_status acmmp_fusion_align_plane_records(acmmp_fusion* f, int64_t first, int64_t n, int64_t* words, double* M,
                                               double* shift) {
     return align_read(f, true, first, n, words, M, shift);
+}
+
+}  // extern "C"
+
+// ---- evaluation regions (include/acmmp.h; kernel: k_region_classify) ------------------------------------------
+
+namespace {
+
+bool finite_all(const double* x, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(x[i])) return false;
+    return true;
+}
+
+// The checks of acmmp_fusion_set_region on the struct, in the order the header lists them; NULL = it passes.
+const char* region_refusal(const acmmp_region& r) {
+    if (r.n_planes < 0 || r.n_planes > ACMMP_REGION_MAX_PLANES) return "n_planes must be 0 to 8";
+    if (r.n_vertices != 0 && (r.n_vertices < 3 || r.n_vertices > ACMMP_REGION_MAX_VERTICES))
+        return "n_vertices must be 0 or 3 to 256";
+    const bool grid = r.dims[0] != 0 || r.dims[1] != 0 || r.dims[2] != 0;
+    for (int a = 0; a < 3; ++a)
+        if (grid && (r.dims[a] < 1 || r.dims[a] > ACMMP_REGION_MAX_DIM)) return "every grid dimension must be 1 to 4096";
+    if (!finite_all(r.planes, 4 * r.n_planes)) return "every plane coefficient must be finite";
+    if (r.n_vertices > 0) {
+        if (r.axis < 0 || r.axis > 2) return "the prism's axis must be 0, 1 or 2";
+        if (!std::isfinite(r.axis_min) || !std::isfinite(r.axis_max)) return "axis_min and axis_max must be finite";
+        if (r.axis_min > r.axis_max) return "axis_min must not exceed axis_max";
+        if (!r.polygon) return "a NULL polygon with n_vertices > 0";
+        if (!finite_all(r.polygon, 2 * r.n_vertices)) return "every polygon coordinate must be finite";
+    }
+    if (grid) {
+        if (!finite_all(r.origin, 3) || !std::isfinite(r.cell)) return "the grid's origin and cell must be finite";
+        if (!(r.cell > 0.0)) return "the grid's cell must be > 0";
+        if (!r.bits) return "NULL bits with a grid";
+    }
+    return nullptr;
+}
+
+size_t region_grid_bytes(const acmmp_region& r) {
+    const unsigned long long cells = static_cast<unsigned long long>(r.dims[0]) * static_cast<unsigned long long>(r.dims[1]) *
+                                     static_cast<unsigned long long>(r.dims[2]);
+    return static_cast<size_t>((cells + 7ull) / 8ull);
+}
+
+}  // namespace
+
+extern "C" {
+
+acmmp_status acmmp_fusion_set_region(acmmp_fusion* f, int side, const acmmp_region* r, int flags) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    if (side != ACMMP_REGION_DATA && side != ACMMP_REGION_REFERENCE)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "side must be ACMMP_REGION_DATA or ACMMP_REGION_REFERENCE");
+    if (flags != 0 && flags != ACMMP_REGION_QUERIES_ONLY)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "flags must be 0 or ACMMP_REGION_QUERIES_ONLY");
+    // built beside the present region, installed when every copy has succeeded
+    RegionSet out;
+    if (r) {
+        if (const char* why = region_refusal(*r)) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, why);
+        F_HIP(f, hipSetDevice(f->device));
+        out.set = true;
+        out.flags = flags;
+        out.r = *r;
+        out.r.polygon = nullptr;
+        out.r.bits = nullptr;
+        if (r->n_vertices > 0) {
+            const size_t n = 2 * static_cast<size_t>(r->n_vertices);
+            F_HIP(f, alloc(out.poly, n));
+            F_HIP(f, hipMemcpy(out.poly, r->polygon, sizeof(double) * n, hipMemcpyHostToDevice));
+        }
+        if (r->dims[0] > 0) {
+            const size_t n = region_grid_bytes(*r);
+            F_HIP(f, alloc(out.bits, n));
+            F_HIP(f, hipMemcpy(out.bits, r->bits, n, hipMemcpyHostToDevice));
+        }
+    } else {
+        F_HIP(f, hipSetDevice(f->device));
+    }
+    F_HIP(f, hipStreamSynchronize(f->stream));        // nothing in flight reads the arrays that go
+    f->region[side] = std::move(out);
+    invalidate(f, R_REGION);                          // what was measured inside the previous region
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_get_region(const acmmp_fusion* f, int side, int* is_set, int* flags, int* n_planes, int* n_vertices,
+                                     int* dims) {
+    if (!f || (side != ACMMP_REGION_DATA && side != ACMMP_REGION_REFERENCE)) return ACMMP_ERR_INVALID_ARGUMENT;
+    const RegionSet& rs = f->region[side];
+    if (is_set) *is_set = rs.set ? 1 : 0;
+    if (flags) *flags = rs.flags;
+    if (n_planes) *n_planes = rs.r.n_planes;
+    if (n_vertices) *n_vertices = rs.r.n_vertices;
+    if (dims)
+        for (int a = 0; a < 3; ++a) dims[a] = rs.r.dims[a];
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_region_classify(acmmp_fusion* f, int source, int64_t* counts) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    const Res id = region_source(source);
+    if (id == R_NONE)
+        return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "source must be one of ACMMP_DIST_FROM_* or ACMMP_SURF_FROM_REFERENCE");
+    const Cloud src = cloud(f, id);
+    if (!src.have) return ffail(f, ACMMP_ERR_INVALID_ARGUMENT, "no such result");
+    DistCloud c = src.dist();
+    if (id != R_REFERENCE && f->xf_set) {
+        c.xf = 1;
+        std::memcpy(c.M, f->xf, sizeof(c.M));
+    }
+    F_HIP(f, hipSetDevice(f->device));
+    hipStream_t s = f->stream;
+    RegionRec out;
+    unsigned long long h[kRegionWords] = {0};
+    const auto run = [&]() -> acmmp_status {
+        F_HIP(f, alloc(out.cls, static_cast<size_t>(c.n)));
+        if (!f->reg_words) F_HIP(f, alloc(f->reg_words, kRegionWords));
+        F_HIP(f, hipMemsetAsync(f->reg_words, 0, sizeof(unsigned long long) * kRegionWords, s));
+        F_HIP(f, launch_region_classify(c, f->region[id == R_REFERENCE ? ACMMP_REGION_REFERENCE : ACMMP_REGION_DATA].dev(),
+                                        out.cls, f->reg_words, s));
+        // the one host wait: the counts
+        F_HIP(f, hipMemcpyAsync(h, f->reg_words, sizeof(h), hipMemcpyDeviceToHost, s));
+        F_HIP(f, hipStreamSynchronize(s));
+        return ACMMP_OK;
+    };
+    const acmmp_status st = run();
+    if (st != ACMMP_OK) return run_failed(f, st);
+    if (h[0] != c.n) return ffail(f, ACMMP_ERR_HIP, "region classify: the counts do not add up to the points");
+    out.n = c.n;
+    out.source = id;
+    out.have = true;
+    f->classes = std::move(out);
+    if (counts)
+        for (int k = 0; k < kRegionWords; ++k) counts[k] = static_cast<int64_t>(h[k]);
+    return ACMMP_OK;
+}
+
+acmmp_status acmmp_fusion_region_classes(acmmp_fusion* f, int64_t first, int64_t n, uint8_t* cls) {
+    if (!f) return ACMMP_ERR_INVALID_ARGUMENT;
+    return read_result(f, first, n, f->classes.n, "range beyond the class result", [&](size_t a, size_t m) -> acmmp_status {
+        F_HIP(f, read_range<uint8_t>(cls, f->classes.cls, a, m));
+        return ACMMP_OK;
+    });
 }
 
 }  // extern "C"

@@ -236,12 +236,15 @@ hipError_t launch_render(int model, const DevCam& cam, const float* verts, unsig
 // Nearest-neighbour distances between two clouds (acmmp_fusion_cloud_distance, include/acmmp.h).
 // A cloud for the device: point i is p[stride * i .. + 3), n points.  With xf set every point is read through the
 // row-major 3x4 transform M (acmmp_fusion_set_cloud_transform, include/acmmp.h); with xf 0 M is not looked at.
+// cls, where not NULL, holds the class byte of every point (launch_region_classify): a point whose class is not 0 reads
+// as invalid, exactly as one with a coordinate that is not finite does.  NULL is the path without a region.
 struct DistCloud {
     const float* p;
     int stride;
     unsigned long long n;
     int xf;
     double M[12];
+    const uint8_t* cls;
 };
 // A uniform grid in float64: a coordinate's cell on axis a is floor(((double)x - o[a]) * inv), clamped to [0, cmax[a]].
 // The host computes inv = 1.0 / cell and cmax from the targets' bounding box with the same two operations.
@@ -333,6 +336,26 @@ hipError_t launch_surf_lists(SurfMesh m, DistGrid g, DistTable fine, long long s
 hipError_t launch_surf_query(DistCloud q, DistGrid g, DistTable fine, const float4* list, const float4* large,
                              unsigned n_large, DistQuery p, float* d2, int32_t* nearest, unsigned long long* words,
                              hipStream_t s);
+
+// Evaluation regions (acmmp_fusion_set_region, include/acmmp.h).  A region for the device: the planes by
+// value, the polygon as n_vertices (u, v) pairs of doubles in device memory (0 = no prism), the grid's bits in device
+// memory (dims[0] = 0: no grid).
+struct RegionDev {
+    int n_planes;
+    double planes[4 * ACMMP_REGION_MAX_PLANES];
+    int n_vertices, axis;
+    double axis_min, axis_max;
+    const double* poly;
+    int dims[3];
+    double o[3], cell;
+    const uint8_t* bits;
+};
+// Device words of a classify pass (all zero before it): the counts of acmmp_fusion_region_classify, in its order.
+enum { kRegionWords = ACMMP_REGION_COUNT_WORDS };
+// One lane per point of c (read through c's stride and transform; c.cls is not looked at): cls[i] = the class byte of
+// the definition, words[0 .. kRegionWords) += the counts, one atomic per word per workgroup.  words may be NULL (the
+// pre-pass of a measuring call, which needs no counts).
+hipError_t launch_region_classify(DistCloud c, RegionDev r, uint8_t* cls, unsigned long long* words, hipStream_t s);
 
 // Area-uniform samples of the mesh result (acmmp_fusion_mesh_sample, include/acmmp.h).
 // Device words of a sample call (all zero before it).

@@ -1758,6 +1758,7 @@ __device__ __forceinline__ bool dist_load(const DistCloud& c, unsigned long long
         for (int k = 0; k < 3; ++k)
             v[k] = static_cast<float>(((c.M[4 * k] * x + c.M[4 * k + 1] * y) + c.M[4 * k + 2] * z) + c.M[4 * k + 3]);
     }
+    if (c.cls && c.cls[i]) return false;             // outside its side's region (k_region_classify): as if not finite
     return !vox_nonfinite(v[0]) && !vox_nonfinite(v[1]) && !vox_nonfinite(v[2]);
 }
 
@@ -2328,6 +2329,91 @@ hipError_t launch_align_plane_iter(DistCloud q, unsigned long long stride, DistC
     const unsigned long long nq = (q.n + stride - 1ull) / stride;
     if (nq == 0) return hipSuccess;
     k_align_plane_iter<<<dist_blocks(nq), 256, 0, s>>>(q, stride, nq, t, g, fine, cg, coarse, list, p, kq, pivot, words, rec);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ evaluation regions
+//
+// acmmp_fusion_set_region (include/acmmp.h): the class byte of every point of a cloud, one lane per point,
+// in the float64 arithmetic of the definition.  The polygon is staged once per workgroup into LDS (at most 256 x 2
+// doubles, 4 KB); the edge loop's trip count and addresses are the same for every lane, so each LDS read is a
+// broadcast.  The divide of the crossing test runs only under the lanes whose edge straddles p_v -- a wave in which no
+// lane straddles skips it -- and a horizontal edge (v_j == v_i) never straddles, so no lane divides by zero.  The counts
+// are ballots per wave, summed over the workgroup through LDS, one atomic add per word per workgroup.
+__global__ __launch_bounds__(256) void k_region_classify(const DistCloud c, const RegionDev r, uint8_t* __restrict__ cls,
+                                                         unsigned long long* __restrict__ words) {
+    __shared__ double poly[2 * ACMMP_REGION_MAX_VERTICES];
+    __shared__ unsigned part[4][kRegionWords];
+    for (int k = threadIdx.x; k < 2 * r.n_vertices; k += 256) poly[k] = r.poly[k];
+    __syncthreads();
+    const unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256 + threadIdx.x;
+    const bool here = i < c.n;
+    unsigned cl = 0u;
+    if (here) {
+        float v[3];
+        if (!dist_load(c, i, v)) {
+            cl = ACMMP_REGION_CLASS_INVALID;
+        } else {
+            const double x = static_cast<double>(v[0]), y = static_cast<double>(v[1]), z = static_cast<double>(v[2]);
+            bool fail = false;
+            for (int k = 0; k < r.n_planes; ++k) {
+                const double s = ((r.planes[4 * k] * x + r.planes[4 * k + 1] * y) + r.planes[4 * k + 2] * z) + r.planes[4 * k + 3];
+                fail = fail || !(s >= 0.0);
+            }
+            if (fail) cl |= ACMMP_REGION_CLASS_PLANES;
+            if (r.n_vertices > 0) {
+                const double pw = r.axis == 0 ? x : r.axis == 1 ? y : z;
+                const double pu = r.axis == 0 ? y : x, pv = r.axis == 2 ? y : z;
+                bool odd = false;
+                double ui = poly[2 * (r.n_vertices - 1)], vi = poly[2 * (r.n_vertices - 1) + 1];   // edge n - 1 first
+                for (int e = 0; e < r.n_vertices; ++e) {
+                    // the edge from vertex e - 1 (mod n) to vertex e: the definition's edge i = e - 1, j = e
+                    const double uj = poly[2 * e], vj = poly[2 * e + 1];
+                    if ((vi > pv) != (vj > pv)) {
+                        const double cross = (((uj - ui) * (pv - vi)) / (vj - vi)) + ui;
+                        odd = odd != (pu < cross);
+                    }
+                    ui = uj;
+                    vi = vj;
+                }
+                if (!(pw >= r.axis_min && pw <= r.axis_max && odd)) cl |= ACMMP_REGION_CLASS_PRISM;
+            }
+            if (r.dims[0] > 0) {
+                const double ix = rint((x - r.o[0]) / r.cell), iy = rint((y - r.o[1]) / r.cell), iz = rint((z - r.o[2]) / r.cell);
+                bool in = ix >= 0.0 && ix < static_cast<double>(r.dims[0]) && iy >= 0.0 && iy < static_cast<double>(r.dims[1]) &&
+                          iz >= 0.0 && iz < static_cast<double>(r.dims[2]);
+                if (in) {
+                    const unsigned long long nx = static_cast<unsigned long long>(r.dims[0]), ny = static_cast<unsigned long long>(r.dims[1]);
+                    const unsigned long long k = static_cast<unsigned long long>(ix) +
+                                                 nx * (static_cast<unsigned long long>(iy) + ny * static_cast<unsigned long long>(iz));
+                    in = (r.bits[k >> 3] >> (k & 7ull)) & 1u;
+                }
+                if (!in) cl |= ACMMP_REGION_CLASS_GRID;
+            }
+        }
+        cls[i] = static_cast<uint8_t>(cl);
+    }
+    if (!words) return;                               // a measuring call's pre-pass: no counts (uniform over the grid)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b[kRegionWords] = {__ballot(here), __ballot(here && cl == ACMMP_REGION_CLASS_INVALID),
+                                                __ballot(here && cl == 0u), __ballot((cl & ACMMP_REGION_CLASS_PLANES) != 0u),
+                                                __ballot((cl & ACMMP_REGION_CLASS_PRISM) != 0u),
+                                                __ballot((cl & ACMMP_REGION_CLASS_GRID) != 0u)};
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kRegionWords; ++k) part[wave][k] = static_cast<unsigned>(__popcll(b[k]));
+    }
+    __syncthreads();
+    if (threadIdx.x < kRegionWords) {
+        const unsigned x = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if (x) atomicAdd(&words[threadIdx.x], static_cast<unsigned long long>(x));
+    }
+}
+
+hipError_t launch_region_classify(DistCloud c, RegionDev r, uint8_t* cls, unsigned long long* words, hipStream_t s) {
+    if (c.n == 0) return hipSuccess;
+    c.cls = nullptr;
+    k_region_classify<<<dist_blocks(c.n), 256, 0, s>>>(c, r, cls, words);
     return hipGetLastError();
 }
 

@@ -9,8 +9,10 @@ namespace acmmp {
 // The resident results.  R_SCENE .. R_REFERENCE and R_SAMPLES are also the clouds a stage can name as its source; R_XFORM
 // stands for the cloud transform, which is no result but is replaced like one.  R_SAMPLES comes after R_XFORM: the
 // enumerators up to R_XFORM keep their values (tests/fusion_lifetime_walk.cpp indexes its tables by them).
+// R_CLASSES is the class result of acmmp_fusion_region_classify; R_REGION stands for the two evaluation regions, which are
+// no result but are replaced like one (a set or a clear of either side raises it as the cause).
 enum Res { R_NONE = -1, R_SCENE, R_VOXELS, R_CLEAN, R_VISIBLE, R_MESH, R_REFERENCE, R_RENDER, R_DIST, R_SURF, R_ALIGN, R_XFORM,
-           R_SAMPLES };
+           R_SAMPLES, R_CLASSES, R_REGION };
 
 // The lifetime table: does the held result `r`, whose record names `src` as the cloud it was computed from, go when
 // `cause` has been replaced or discarded?  invalidate (fusion.cpp) applies it transitively, so a row names only the
@@ -20,10 +22,12 @@ enum Res { R_NONE = -1, R_SCENE, R_VOXELS, R_CLEAN, R_VISIBLE, R_MESH, R_REFEREN
 inline bool goes_with(Res r, Res src, Res cause) {
     switch (r) {
         case R_VOXELS: case R_CLEAN: case R_VISIBLE: case R_MESH: case R_RENDER: case R_SAMPLES: return cause == src;
-        case R_DIST: return cause == src || cause == R_REFERENCE || cause == R_XFORM;
-        case R_ALIGN: return cause == src || cause == R_REFERENCE;
+        case R_DIST: return cause == src || cause == R_REFERENCE || cause == R_XFORM || cause == R_REGION;
+        case R_ALIGN: return cause == src || cause == R_REFERENCE || cause == R_REGION;
         // with the mesh, with its query cloud, and a reference query's also when the mesh is read in another frame
-        case R_SURF: return cause == R_MESH || cause == src || (cause == R_XFORM && src == R_REFERENCE);
+        case R_SURF: return cause == R_MESH || cause == src || (cause == R_XFORM && src == R_REFERENCE) || cause == R_REGION;
+        // the classes of a cloud: with the cloud, with the regions, and a data cloud's with the transform it is read under
+        case R_CLASSES: return cause == src || cause == R_REGION || (cause == R_XFORM && src != R_REFERENCE);
         default: return false;                             // the scene and the reference cloud: only replaced
     }
 }
@@ -44,6 +48,9 @@ inline Res dist_source(int s) {
         default: return R_NONE;
     }
 }
+// The clouds acmmp_fusion_region_classify takes: a data cloud by its ACMMP_DIST_FROM_* constant, the reference cloud by
+// ACMMP_SURF_FROM_REFERENCE.
+inline Res region_source(int s) { return s == ACMMP_SURF_FROM_REFERENCE ? R_REFERENCE : dist_source(s); }
 inline Res surf_source(int s) {
     switch (s) {
         case ACMMP_SURF_FROM_SCENE: return R_SCENE;

@@ -1067,6 +1067,98 @@ acmmp_status acmmp_fusion_mesh_sample(acmmp_fusion *f, float spacing, uint64_t s
  * face n int32.  Ranges as acmmp_fusion_voxel_points (no sample result: every range but an empty one at 0 is refused). */
 acmmp_status acmmp_fusion_sample_points(acmmp_fusion *f, int64_t first, int64_t n, float *points, int32_t *face);
 
+/* ---- evaluation regions: crop volumes and observation masks for the measuring calls (no reference counterpart) ----
+ * A region says which points of one side of the comparison take part in it: the data side (every ACMMP_DIST_FROM_*
+ * cloud) or the reference side (the reference cloud).  It is the intersection of up to three optional parts:
+ *   planes  n_planes in [0, 8] half-spaces (a, b, c, d) at planes[4 i .. + 4); 0 = no planes.
+ *   prism   n_vertices = 0 (no prism) or in [3, 256]; an orthogonal axis w in {0, 1, 2}, axis_min <= axis_max, and a
+ *           polygon of (u, v) pairs at polygon[2 i .. + 2) in the other two coordinates in increasing index order:
+ *           w = 0 gives (y, z), w = 1 gives (x, z), w = 2 gives (x, y) -- Open3D's SelectionPolygonVolume.
+ *   grid    dims all 0 (no grid) or each in [1, 4096]; origin o, cell c > 0 and ceil(nx ny nz / 8) bytes of bits: cell
+ *           (ix, iy, iz) is bit k & 7, least significant first, of byte k >> 3, k = ix + nx (iy + ny iz).  x runs
+ *           fastest, so a column-major MATLAB logical ObsMask(ix, iy, iz) packed in that order is a plain dump.
+ * acmmp_fusion_set_region copies the struct, the polygon and the bits (the caller's arrays may go away) and makes them
+ * the region of `side`, ACMMP_REGION_DATA or ACMMP_REGION_REFERENCE; r = NULL clears it.  flags is 0 or
+ * ACMMP_REGION_QUERIES_ONLY.  A region belongs to the object, as the cloud transform does: it lives until it is cleared
+ * or replaced and survives every replacement of a source or of the reference cloud.  A successful set or clear discards
+ * the distance result, the surface result and the align records of both kinds; it keeps the sources, the reference
+ * cloud and the transform.  ACMMP_ERR_INVALID_ARGUMENT: a side or a flag that is none of the constants, a count outside
+ * the ranges above, an axis outside {0, 1, 2}, any number of a part that is present that is not finite,
+ * axis_min > axis_max, c <= 0, a NULL array with a positive count.  Any error leaves the object as it was.
+ * acmmp_fusion_get_region reports the region of a side: *is_set, *flags, *n_planes, *n_vertices and dims[3] (zeros with
+ * none set); each output may be NULL.  Device memory: 16 bytes per vertex and the bits.
+ *
+ * The definition.  Arithmetic is IEEE float64 with no contraction on the point's float32 coordinates widened.  A data-side
+ * point is x' under the cloud transform when one is set, exactly as rule 1 of acmmp_fusion_cloud_distance reads it
+ * (float64, rounded once to float32, then widened); inside an align call it is x' under that iteration's M_k.  A
+ * reference-side point is never transformed.  Every part is evaluated for every valid point, with no short-circuit, and
+ * the result is one class byte per point:
+ *   bit 0 (ACMMP_REGION_CLASS_INVALID)  a coordinate is not finite; the other bits are then 0.
+ *   bit 1 (ACMMP_REGION_CLASS_PLANES)   a plane fails: s = ((a x + b y) + c z) + d, and the point passes when s >= 0
+ *                                       (s = -0.0 passes).
+ *   bit 2 (ACMMP_REGION_CLASS_PRISM)    the prism fails: the point passes when axis_min <= p_w <= axis_max and the crossing
+ *                                       parity is odd.  The parity starts even; for each edge i with j = (i + 1) mod n it
+ *                                       toggles when (v_i > p_v) != (v_j > p_v) and
+ *                                       p_u < (((u_j - u_i) * (p_v - v_i)) / (v_j - v_i)) + u_i.
+ *                                       This is Open3D's rule, so points on an edge or a vertex fall where its tool puts them.
+ *   bit 3 (ACMMP_REGION_CLASS_GRID)     the grid fails: i_a = rint((p_a - o_a) / c), ties to even; the point passes when
+ *                                       0 <= i_a < n_a on all three axes, compared in float64 before any conversion,
+ *                                       and the cell's bit is set.
+ * Class 0 is inside.  A part that is absent never fails, and without a region every valid point is inside.
+ *
+ * What honours it.  In acmmp_fusion_cloud_distance (both directions), acmmp_fusion_surface_distance (the query cloud's
+ * side; the mesh's faces are never cropped), acmmp_fusion_cloud_align and acmmp_fusion_cloud_align_plane a point of a
+ * side whose region is set and whose class is not 0 is treated exactly as if its coordinates were not finite (rule 1 of
+ * the distance definition): it is no valid query and does not exist as a target.  Indices, n_query, the result lengths
+ * and the nearest indices of the other points are unchanged.  With ACMMP_REGION_QUERIES_ONLY the side's points are
+ * removed as queries only and remain targets (DTU's completeness is measured to the whole reconstruction).  The data
+ * queries of a surface call are classified under the transform that is set, although the call itself reads them in the
+ * data frame; the data queries of an align call are classified again under each iteration's M_k (Tanks and Temples'
+ * cropped refinement).  The device classifies every cloud of a call once (the data side of an align call once per
+ * iteration) in a pass of its own before the search, never per pair; with no region set no pass runs and the calls are
+ * what they were.
+ *
+ * acmmp_fusion_region_classify classifies the cloud `source` -- an ACMMP_DIST_FROM_* constant, or
+ * ACMMP_SURF_FROM_REFERENCE for the reference cloud -- under the region of its side (the data side under the transform
+ * that is set), keeps the class bytes resident and returns counts[ACMMP_REGION_COUNT_WORDS]: [0] points, [1] invalid,
+ * [2] inside, and the points that fail [3] a plane, [4] the prism, [5] the grid (a point can count in several of the
+ * last three).  counts may be NULL.  ACMMP_ERR_INVALID_ARGUMENT: a source that is none of the constants, no such result.
+ * acmmp_fusion_region_classes reads classes [first, first + n); ranges as acmmp_fusion_distance_results.  One class
+ * result is resident; it is built beside the previous one and any error leaves the object as it was.  It goes when its
+ * source is replaced or discarded, when a region of either side is set or cleared, and, for a data cloud, when the
+ * transform is set or cleared; the measuring calls neither read nor write it.  Only integers are summed: the counts are
+ * reduced over the wave and the workgroup and added with one atomic per word per workgroup, so no result depends on the
+ * order of execution.  Device memory: 1 byte per point; a measuring call with a region adds 1 byte per point of each
+ * cropped cloud while it runs.  The host waits once. */
+#define ACMMP_REGION_DATA 0
+#define ACMMP_REGION_REFERENCE 1
+#define ACMMP_REGION_QUERIES_ONLY 1
+#define ACMMP_REGION_MAX_PLANES 8
+#define ACMMP_REGION_MAX_VERTICES 256
+#define ACMMP_REGION_MAX_DIM 4096
+#define ACMMP_REGION_CLASS_INVALID 1
+#define ACMMP_REGION_CLASS_PLANES 2
+#define ACMMP_REGION_CLASS_PRISM 4
+#define ACMMP_REGION_CLASS_GRID 8
+#define ACMMP_REGION_COUNT_WORDS 6
+typedef struct acmmp_region {
+    int32_t n_planes;                 /* 0 .. 8 */
+    int32_t n_vertices;               /* 0 (no prism) or 3 .. 256 */
+    int32_t axis;                     /* the prism's orthogonal axis w */
+    int32_t dims[3];                  /* nx, ny, nz: all 0 (no grid) or each 1 .. 4096 */
+    double planes[4 * ACMMP_REGION_MAX_PLANES];
+    double axis_min, axis_max;
+    double origin[3];
+    double cell;
+    const double *polygon;            /* n_vertices x (u, v) */
+    const uint8_t *bits;              /* ceil(nx ny nz / 8) bytes */
+} acmmp_region;
+acmmp_status acmmp_fusion_set_region(acmmp_fusion *f, int side, const acmmp_region *r, int flags);
+acmmp_status acmmp_fusion_get_region(const acmmp_fusion *f, int side, int *is_set, int *flags, int *n_planes,
+                                     int *n_vertices, int *dims);
+acmmp_status acmmp_fusion_region_classify(acmmp_fusion *f, int source, int64_t *counts);
+acmmp_status acmmp_fusion_region_classes(acmmp_fusion *f, int64_t first, int64_t n, uint8_t *cls);
+
 /* ---- planar-prior host side (no GPU; ACMMP.cpp:904-1011, main.cpp:113-181) ---------------
  * Host restatements of the reference's planar-prior helpers, so a caller can run ProcessProblem's
  * planar pass without OpenCV.  Delaunay ties / triangle order differ from cv::Subdiv2D

@@ -32,11 +32,14 @@ from acmmp import capi, io, pipeline  # noqa: E402
 
 def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=None, align_max_dist=None,
             align_iterations=30, align_stride=1, align_plane_iterations=None, a_normals=None, a_faces=None,
-            surface=True, mesh_samples=None):
+            surface=True, mesh_samples=None, region_a=None, region_b=None, region_queries_only=False):
     """evaluate_clouds of cloud A (n, 3) against cloud B, after align_clouds when align is "rigid" or "similarity";
     align_plane_iterations: its point-to-plane stage, along a_normals (n, 3).  make: the fusion object's factory
     (tests).  a_faces (m, 3): A is a mesh, loaded through set_mesh as well, and the result gains "surface" (unless
-    surface is False) and, with mesh_samples (a spacing), "mesh_samples"."""
+    surface is False) and, with mesh_samples (a spacing), "mesh_samples".  region_a, region_b: the evaluation regions of
+    A (the data side) and of B (the reference side), io.Region or a file of io.read_region, in B's frame; they are set
+    before the registration, region_queries_only keeps A's points outside its region as targets, and the result gains
+    "region" as eval.json does."""
     if mesh_samples is not None and a_faces is None:
         raise ValueError("the mesh samples need A's faces")
     if align_plane_iterations is not None and (align is None or a_normals is None):
@@ -53,6 +56,11 @@ def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=No
         if a_faces is not None:
             fu.set_mesh(pts, a_faces)
         fu.set_reference_cloud(b_xyz)
+        regions = {"data": region_a, "reference": region_b}
+        for side, r in regions.items():
+            if r is not None:
+                fu.set_region(side, io.read_region(os.fspath(r)) if isinstance(r, (str, os.PathLike)) else r,
+                              queries_only=region_queries_only and side == "data")
         registered = None
         if align is not None:
             registered = pipeline.align_clouds(fu, "scene", align, max_dist if align_max_dist is None else align_max_dist,
@@ -60,6 +68,11 @@ def compare(a_xyz, b_xyz, max_dist, thresholds=(), device=0, make=None, align=No
         info = pipeline.evaluate_clouds(fu, "scene", max_dist, thresholds)
         if registered is not None:
             info["align"] = registered
+        if region_a is not None or region_b is not None:
+            info["region"] = {side: {"file": os.fspath(r) if isinstance(r, (str, os.PathLike)) else None,
+                                     "queries_only": bool(region_queries_only and side == "data"),
+                                     "counts": fu.region_classify("scene" if side == "data" else "reference")}
+                              for side, r in regions.items() if r is not None}
         if a_faces is not None and surface:
             info["surface"] = pipeline.evaluate_surface(fu, "scene", max_dist, thresholds, info["accuracy"])
         if mesh_samples is not None:
@@ -85,11 +98,19 @@ def main(argv=None):
     ap.add_argument("--surface", action="store_true", help="A is a mesh PLY: also measure against its faces")
     ap.add_argument("--mesh-samples", metavar="SPACING", type=float, default=None,
                     help="A is a mesh PLY: also sample its surface, one point per SPACING^2, and measure the samples")
+    ap.add_argument("--eval-region-data", metavar="FILE", default=None,
+                    help="measure only A's points inside this region (a SelectionPolygonVolume JSON or the project's region "
+                         "JSON), given in B's frame and applied under each transform of --align")
+    ap.add_argument("--eval-region-reference", metavar="FILE", default=None, help="the same for B's points")
+    ap.add_argument("--eval-region-queries-only", action="store_true",
+                    help="with --eval-region-data: A's points outside the region still serve as targets")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if a.align_plane_iterations is not None and a.align is None:
         ap.error("--align-plane-iterations needs --align")
+    if a.eval_region_queries_only and a.eval_region_data is None:
+        ap.error("--eval-region-queries-only needs --eval-region-data")
     normals = None
     if a.align_plane_iterations is not None and not a.surface and a.mesh_samples is None:
         rec = io.read_ply(a.a)
@@ -105,7 +126,8 @@ def main(argv=None):
     info = compare(a_xyz, pipeline.reference_xyz(a.b), a.max_dist, a.threshold, a.device,
                    align=a.align, align_max_dist=a.align_max_dist, align_iterations=a.align_iterations,
                    align_stride=a.align_stride, align_plane_iterations=a.align_plane_iterations, a_normals=normals,
-                   a_faces=faces, surface=a.surface, mesh_samples=a.mesh_samples)
+                   a_faces=faces, surface=a.surface, mesh_samples=a.mesh_samples, region_a=a.eval_region_data,
+                   region_b=a.eval_region_reference, region_queries_only=a.eval_region_queries_only)
     info.update(a=a.a, b=a.b)
     if a.out:
         with open(a.out, "w") as f:
